@@ -11,6 +11,11 @@ Polak-Ribiere CG direction, Armijo backtracking line search (>= 1 trial energy
 evaluation) and the position commit.  All state is resident in HBM before the
 timed region starts.
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds
+everything else the line used to carry (reuse level 0, deterministic mode, roofline
+and per-kernel profile, the other BASELINE configurations, the 16 M-facet legs, the
+CPU baseline).  --dump-outputs DIR writes what the timed steps computed as .npy files.
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").
 """
 
@@ -58,20 +63,51 @@ def build_parser():
     ap.add_argument("--step-size", type=float, default=1e-6)
     ap.add_argument("--volume", action="store_true", help="add the volume Lagrange constraint row")
     ap.add_argument("--cpu-steps", type=int, default=-1,
-                    help="CPU oracle steps per cpu_baseline leg (0 = skip; default 6 at N=1, 2 at N>1)")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="CPU oracle steps per cpu_baseline leg of --full (0 = skip; default 6 at N=1, 2 at N>1)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline / per-kernel profile")
     ap.add_argument("--no-large", action="store_true",
-                    help="skip the 16-million-facet legs (f = 905: the size at which strong scaling over 8 GPUs means "
+                    help="--full without the 16-million-facet legs (f = 905: the size at which strong scaling over 8 GPUs means "
                          "something, and the weak-scaling size of 8 GPUs)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the secondary sections (reuse level 0, deterministic mode): for kernel traces")
+                    help="--full without the secondary sections (reuse level 0, deterministic mode, other "
+                         "configurations): for kernel traces")
     ap.add_argument("--reuse-level", type=int, default=2, choices=(0, 1, 2),
                     help="ms_stepper_params.reuse_energy0: 0 repeats every pass the reference repeats, "
                          "2 (library default) never repeats a pass whose result is already on the device")
     ap.add_argument("--deterministic", action="store_true",
                     help="fixed-order per-vertex sums (ms_set_deterministic): bitwise reproducible run to "
                          "run, slower than the default LDS-atomic accumulation")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the reuse-level-0 and deterministic legs, the "
+                         "roofline / per-kernel profile, the other BASELINE configurations, the 16 M-facet legs and "
+                         "the CPU baseline (without it a run sets up, warms up, times --steps steps and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (positions, gradient, energy, step size) "
+                         "as DIR/<name>.npy, float64, at most 64 MB in all (a fixed seeded row sample beyond that)")
     return ap
+
+
+DUMP_CAP_BYTES = 64 * 1000 * 1000
+
+
+def write_outputs(out_dir, arrays, cap_bytes=DUMP_CAP_BYTES, seed=0):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  Arrays of shape (n, ...) are per-vertex rows: when
+    all of them together pass `cap_bytes`, the same fixed, seeded sample of rows (sorted) is kept of each, so that two
+    runs with the same arguments write the same rows.  Returns {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = {k: v for k, v in arrays.items() if v.ndim >= 1 and v.shape[0] > 1}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > cap_bytes and rows:
+        n = max(v.shape[0] for v in rows.values())
+        fixed = total - sum(v.nbytes for v in rows.values())
+        per_row = sum(v.nbytes // v.shape[0] for v in rows.values())
+        keep = max(1, min(n, (cap_bytes - fixed) // max(per_row, 1)))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays.update({k: v[idx[idx < v.shape[0]]] for k, v in rows.items()})
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(v))
+    return {k: v.shape for k, v in arrays.items()}
 
 
 def weak_frequency(gpus: int, base: int = 320) -> int:
@@ -623,6 +659,17 @@ def main_single(args):
                                             "gated followers; every decision is taken once on the device and replayed by "
                                             "the host from the same doubles -- mismatches must be 0; ahead = rounds queued for a step that had not "
                                             "started yet (behind the running gradient pass), adopted = those the step took")
+    if res.get("iterations", args.steps) != args.steps:
+        print(f"[bench] the timed call ran {res['iterations']} of {args.steps} steps (converged or out of step size)",
+              file=sys.stderr)
+    if args.dump_outputs:
+        # what a caller of the timed path receives: the positions left in HBM, the gradient, the energy, the next step
+        dm0 = mesh._hip_mirror.dm
+        write_outputs(args.dump_outputs, {"positions": dm0.get_positions(), "gradient": dm0.get_gradient(),
+                                          "energy": np.array([res["energy"]]), "step_size": np.array([mz.step_size])})
+    if not args.full:
+        print(json.dumps(out))
+        return
 
     # -- the same K steps with every pass the reference repeats (reuse level 0): energy0
     #    re-evaluated, a fresh energy/factor pass after every accepted step, a full gradient
@@ -916,9 +963,15 @@ def main_sharded(args, rank, world, local_rank):
     dt = float(tmax.item())
     n_exchanges = drv.exchanges - ex0
     level = int(drv.reuse_energy0)
+    if args.dump_outputs:
+        x_dump = be.gather_positions()  # collective: every rank takes part
+        if rank == 0:
+            e_dump = float(getattr(r, "energy", getattr(r, "energy_eval", float("nan"))))
+            write_outputs(args.dump_outputs, {"positions": x_dump, "energy": np.array([e_dump]),
+                                              "step_size": np.array([step])})
     # roofline on THIS rank's shard: HIP events inside the library over a few more steps
     roofline, kernels = None, None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         try:
             n_prof = min(args.steps, 30)
             be.dm.profile_enable(True)
@@ -948,7 +1001,7 @@ def main_sharded(args, rank, world, local_rank):
     rccl_ranks = be.dm.shard_comm_ranks() if isinstance(drv, LibraryShardedStepper) else dist.get_world_size()
     cpu = None
     n_cpu = (6 if world == 1 else 2) if args.cpu_steps < 0 else args.cpu_steps
-    if n_cpu > 0:
+    if args.full and n_cpu > 0:
         x_full = be.gather_positions()  # collective: every rank takes part
         if rank == 0:
             cpu = cpu_baseline(x_full, T, ["surface", "bending"], [], [], dict(GP), step, n_cpu)
@@ -964,7 +1017,7 @@ def main_sharded(args, rank, world, local_rank):
         be.dm.close()
         for key, f in (("peer_exchange", 320), ("strong_16M_facets", LARGE_FREQ), ("strong_16M_facets_peer_exchange", LARGE_FREQ),
                        ("weak_2M_facets_per_gpu", weak_frequency(world, 320))):
-            if args.no_large and f != 320:
+            if (args.no_large or not args.full) and f != 320:
                 continue
             reuses = key.startswith("weak") and ((f == LARGE_FREQ and "strong_16M_facets" in extra) or f == 320)
             # rank 0's clock decides for everybody (a leg is a collective)

@@ -40,6 +40,10 @@ ap.add_argument("--only-guard", action="store_true", help="guard / exhausted-sea
 ap.add_argument("--only-config5", action="store_true", help="the caveolin deck of BASELINE config 5 only")
 ap.add_argument("--only-enforcer", action="store_true", help="line-search enforcer-lane trajectories only")
 ap.add_argument("--only-precondition", action="store_true", help="ConjugateGradient(precondition=True) trajectories only")
+ap.add_argument("--only-signatures", action="store_true",
+                help="parameter lists of the reference's energy-module entry points only")
+ap.add_argument("--only-ref-fortran", action="store_true",
+                help="outputs of the reference's Fortran objects (oracle/_ref, `make -C oracle ref`) only")
 args = ap.parse_args()
 
 sys.dont_write_bytecode = True
@@ -1330,8 +1334,53 @@ def gen_config5():
     print("traj_config5_deck_gd.npz E0=%.16g E_final=%.16g" % (E0, out["E_final"]), out["step_log"].tolist())
 
 
+def gen_ref_fortran_cases():
+    """The reference's own Fortran kernels, compiled in place into oracle/_ref (`make -C oracle ref`), on seeded
+    random inputs: what tests/test_oracle_golden.py holds the C restatement to where oracle/_ref is not built."""
+    from oracle import ref_fortran as rf
+
+    if not rf.available():
+        raise SystemExit("oracle/_ref not built: run `make -C oracle ref` with the reference checkout present")
+    rng = np.random.default_rng(5)
+    nv, nf = 40, 90
+    out = {"pos": rng.normal(size=(nv, 3)), "tri": rng.integers(0, nv, size=(nf, 3), dtype=np.int32),
+           "gamma": rng.random(nf) + 0.5}
+    out["surface_grad"] = np.zeros((nv, 3))
+    out["surface_E"] = np.array(rf.surface_energy_and_gradient(out["pos"], out["tri"], out["gamma"], out["surface_grad"]))
+    out["u"], out["v"] = rng.normal(size=(nf, 3)), rng.normal(size=(nf, 3))
+    out["grad_cotan_gu"], out["grad_cotan_gv"] = rf.grad_cotan_batch(out["u"], out["v"])
+    out["w"], out["field"] = rng.normal(size=(nf, 3)), rng.normal(size=(nv, 3))
+    out["beltrami"] = rf.apply_beltrami_laplacian(out["w"], out["tri"], out["field"])
+    out["tilts"] = rng.normal(size=(nv, 3))
+    for i, a in enumerate(rf.p1_triangle_divergence(out["pos"], out["tilts"], out["tri"])):
+        out[f"p1_div_{i}"] = a
+    for i, a in enumerate(rf.compute_curvature_data(out["pos"], out["tri"])):
+        out[f"curvature_{i}"] = a
+    np.savez_compressed(os.path.join(OUT, "ref_fortran_cases.npz"), **out)
+    print("ref_fortran_cases.npz E_surface=%.16g" % out["surface_E"])
+
+
+def gen_module_signatures():
+    """Parameter lists of compute_energy_and_gradient_array of the reference's energy modules, as its plugin manager
+    hands them out: the surface the package's modules must expose (tests/test_reference_mesh_adapter.py)."""
+    import inspect
+
+    out = {}
+    for name in ("surface", "bending", "volume", "tilt"):
+        fn = EnergyModuleManager([name]).get_module(name).compute_energy_and_gradient_array
+        out[name] = np.array(list(inspect.signature(fn).parameters))
+    np.savez_compressed(os.path.join(OUT, "reference_module_signatures.npz"), **out)
+    print("reference_module_signatures.npz", {k: v.tolist() for k, v in out.items()})
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
+    if "--only-signatures" in sys.argv:
+        gen_module_signatures()
+        sys.exit(0)
+    if "--only-ref-fortran" in sys.argv:
+        gen_ref_fortran_cases()
+        sys.exit(0)
     if "--only-tilt" in sys.argv:
         gen_tilt_trajectory()
         sys.exit(0)
@@ -1381,3 +1430,5 @@ if __name__ == "__main__":
     gen_enforcer_lane()
     gen_precondition()
     gen_config5()
+    gen_module_signatures()
+    gen_ref_fortran_cases()

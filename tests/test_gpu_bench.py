@@ -1,5 +1,6 @@
 """bench.py end to end on the GPU at a small size: the driver's contract (ONE JSON line on stdout, the keys it reads,
-the roofline and cpu_baseline objects) and the forced-sharded line through RCCL at world 1."""
+the roofline and cpu_baseline objects of --full), a plain run's lean line and --dump-outputs, and the forced-sharded
+line through RCCL at world 1."""
 
 import json
 import os
@@ -27,7 +28,7 @@ def _run(args, env_extra=None):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    d = _run(["--gpus", "1", "--steps", "12", "--warmup", "4", "--freq", "40", "--cpu-steps", "1"])
+    d = _run(["--gpus", "1", "--steps", "12", "--warmup", "4", "--freq", "40", "--cpu-steps", "1", "--full"])
     for k in CONTRACT_KEYS:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 4 and d["unit"] == "steps/s"
@@ -45,6 +46,28 @@ def test_single_gpu_line_has_the_contract_fields():
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0
     assert d["steps_accepted"] >= 1 and d["line_search_trials"] >= d["steps_accepted"]
     assert d["accepted_steps_per_s"] > 0 and d["evaluations_per_s"] > 0
+
+
+def test_plain_line_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes what the timed steps computed, and two
+    runs with the same arguments (fixed-order sums) write the same arrays."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--steps", "12", "--warmup", "4", "--freq", "40", "--deterministic"]
+    d = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 12 and d["warmup"] == 4 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    for k in ("roofline", "kernels", "cpu_baseline", "all_reference_passes_repeated", "deterministic_mode"):
+        assert k not in d, k
+    nv = 10 * 40 * 40 + 2
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("positions", "gradient", "energy", "step_size")}
+    assert got["positions"].shape == got["gradient"].shape == (nv, 3)
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["energy"][0] == d["energy_end"] and np.all(np.isfinite(got["gradient"]))
+    _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    for n, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")), n
 
 
 def test_forced_sharded_line_goes_through_rccl_at_world_one():

@@ -231,6 +231,40 @@ def test_bench_launcher_command_and_schema_helpers(monkeypatch):
     assert rt["accepted_steps_per_s"] == 5000.0 and rt["evaluations_per_s"] == (21 + 10) / 0.002
 
 
+def test_bench_write_outputs_caps_with_a_fixed_row_sample(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files; past the byte cap the same seeded, sorted row sample of every
+    per-vertex array, the same from call to call."""
+    import bench
+
+    rng = np.random.default_rng(3)
+    x, g = rng.normal(size=(1000, 3)), rng.normal(size=(1000, 3)).astype(np.float32)
+    shapes = bench.write_outputs(str(tmp_path / "full"), {"positions": x, "gradient": g, "energy": np.array([1.5])})
+    assert shapes == {"positions": (1000, 3), "gradient": (1000, 3), "energy": (1,)}
+    assert np.array_equal(np.load(tmp_path / "full" / "positions.npy"), x)
+    assert np.load(tmp_path / "full" / "gradient.npy").dtype == np.float64
+    cap = 8 + 100 * 48  # the scalar and 100 rows of both arrays
+    for d in ("s1", "s2"):
+        shapes = bench.write_outputs(str(tmp_path / d), {"positions": x, "gradient": g, "energy": np.array([1.5])},
+                                     cap_bytes=cap)
+        assert shapes["positions"] == shapes["gradient"] == (100, 3)
+        assert sum(os.path.getsize(tmp_path / d / f"{n}.npy") - 128 for n in shapes) <= cap
+    a, b = np.load(tmp_path / "s1" / "positions.npy"), np.load(tmp_path / "s2" / "positions.npy")
+    assert np.array_equal(a, b)
+    rows = [int(np.flatnonzero((x == r).all(axis=1))[0]) for r in a]
+    assert rows == sorted(rows) and len(set(rows)) == 100
+
+
+def test_bench_plain_and_full_options():
+    """--full is off by default; the headline-only switches only narrow --full."""
+    import bench
+
+    ap = bench.build_parser()
+    a = ap.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    a = ap.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
 def test_bench_leg_budget_and_shared_mesh(tmp_path, monkeypatch):
     """bench.py --gpus N: an extra leg starts only while its estimated cost fits MS_BENCH_BUDGET_S, and rank 0's mesh
     reaches the other ranks through files instead of every rank running the generator."""

@@ -1,7 +1,8 @@
 """Pins the CPU oracle (oracle/ms_oracle.c + oracle/minimizer_port.py) to the
 reference's own outputs (tests/golden/*.npz, made by oracle/gen_golden.py from
-the reference with its Fortran kernels enabled), and to the reference's Fortran
-kernels compiled in place (oracle/_ref) when those are present.
+the reference with its Fortran kernels enabled), and to the outputs of the
+reference's Fortran kernels compiled in place (tests/golden/ref_fortran_cases.npz;
+checked against oracle/_ref itself when those objects are present).
 
 Tolerances: 1e-12 relative (max-norm) on energies and per-array outputs -- the
 oracle differs from the reference only in summation order.
@@ -101,27 +102,40 @@ def test_analytic_anchors():
     assert abs(Eb - 8 * np.pi) / (8 * np.pi) < 2e-3
 
 
-@pytest.mark.skipif(not rf.available(), reason="oracle/_ref not built (no reference checkout here)")
-def test_c_restatement_matches_reference_fortran_objects():
-    rng = np.random.default_rng(5)
-    nv, nf = 40, 90
-    pos = rng.normal(size=(nv, 3))
-    tri = rng.integers(0, nv, size=(nf, 3), dtype=np.int32)
-    gamma = rng.random(nf) + 0.5
-    g1, g2 = np.zeros((nv, 3)), np.zeros((nv, 3))
+def _ref_fortran_outputs(g):
+    """The reference's Fortran outputs on the stored inputs: recorded (tests/golden/ref_fortran_cases.npz, made by
+    oracle/gen_golden.py --only-ref-fortran), and recomputed by oracle/_ref where those objects are built."""
+    rec = {"surface": (float(g["surface_E"]), g["surface_grad"]),
+           "grad_cotan": (g["grad_cotan_gu"], g["grad_cotan_gv"]), "beltrami": g["beltrami"],
+           "p1_div": tuple(g[f"p1_div_{i}"] for i in range(5)), "curvature": tuple(g[f"curvature_{i}"] for i in range(6))}
+    if rf.available():
+        pos, tri = g["pos"], g["tri"]
+        g2 = np.zeros_like(pos)
+        E2 = rf.surface_energy_and_gradient(pos, tri, g["gamma"], g2)
+        assert abs(E2 - rec["surface"][0]) <= 1e-14 * abs(E2) and relerr(rec["surface"][1], g2) < 1e-14
+        live = {"grad_cotan": rf.grad_cotan_batch(g["u"], g["v"]),
+                "beltrami": (rf.apply_beltrami_laplacian(g["w"], tri, g["field"]),),
+                "p1_div": rf.p1_triangle_divergence(pos, g["tilts"], tri), "curvature": rf.compute_curvature_data(pos, tri)}
+        for k, arrs in live.items():
+            want = rec[k] if isinstance(rec[k], tuple) else (rec[k],)
+            assert len(arrs) == len(want) and all(relerr(b, a) < 1e-14 for a, b in zip(arrs, want)), k
+    return rec
+
+
+def test_c_restatement_matches_reference_fortran_objects(golden):
+    g = golden("ref_fortran_cases.npz")
+    ref = _ref_fortran_outputs(g)
+    pos, tri, gamma = g["pos"], g["tri"], g["gamma"]
+    g1 = np.zeros_like(pos)
     E1 = orc.surface_energy_and_gradient(pos, tri, gamma, g1)
-    E2 = rf.surface_energy_and_gradient(pos, tri, gamma, g2)
+    E2, g2 = ref["surface"]
     assert abs(E1 - E2) <= 1e-13 * abs(E2) and relerr(g1, g2) < 1e-13
-    u, v = rng.normal(size=(nf, 3)), rng.normal(size=(nf, 3))
-    for a, b in zip(orc.grad_cotan_batch(u, v), rf.grad_cotan_batch(u, v)):
+    for a, b in zip(orc.grad_cotan_batch(g["u"], g["v"]), ref["grad_cotan"], strict=True):
         assert relerr(a, b) < 1e-13
-    w = rng.normal(size=(nf, 3))
-    fld = rng.normal(size=(nv, 3))
-    assert relerr(orc.apply_beltrami_laplacian(w, tri, fld), rf.apply_beltrami_laplacian(w, tri, fld)) < 1e-13
-    tl = rng.normal(size=(nv, 3))
-    for a, b in zip(orc.p1_triangle_divergence(pos, tl, tri), rf.p1_triangle_divergence(pos, tl, tri)):
+    assert relerr(orc.apply_beltrami_laplacian(g["w"], tri, g["field"]), ref["beltrami"]) < 1e-13
+    for a, b in zip(orc.p1_triangle_divergence(pos, g["tilts"], tri), ref["p1_div"], strict=True):
         assert relerr(a, b) < 1e-12
-    for a, b in zip(orc.compute_curvature_data(pos, tri, True), rf.compute_curvature_data(pos, tri)):
+    for a, b in zip(orc.compute_curvature_data(pos, tri, True), ref["curvature"], strict=True):
         assert relerr(a, b) < 1e-12
 
 

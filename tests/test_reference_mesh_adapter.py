@@ -1,4 +1,5 @@
-"""CPU check (runs only where the reference checkout exists, i.e. in the build container):
+"""CPU checks.  The module surface is checked against the reference's recorded parameter lists everywhere; the
+mirror test runs only where the reference checkout exists, i.e. in the build container:
 ``HipMirror`` / the plugins read the reference's OWN ``Mesh`` object through exactly the
 accessors listed in INTEGRATION.md.  The device is replaced by a recorder, so this tests
 the adapter, not the kernels (those are covered by the -m gpu suite)."""
@@ -10,8 +11,9 @@ import numpy as np
 import pytest
 
 REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "geometry")),
-                                reason="reference checkout not present (GPU box)")
+_NO_REF = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "geometry")),
+                             reason="reference checkout not present (GPU box)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 class RecorderDevice:
@@ -33,6 +35,25 @@ class RecorderDevice:
         pass
 
 
+def test_energy_modules_expose_the_reference_module_surface():
+    """Our plugin manager's modules take the reference's entry-point parameters (tests/golden/
+    reference_module_signatures.npz: the reference's own lists, made by oracle/gen_golden.py --only-signatures)."""
+    import inspect
+
+    from membrane_solver_amd.runtime.energy_manager import EnergyModuleManager
+
+    ref = np.load(os.path.join(GOLDEN, "reference_module_signatures.npz"), allow_pickle=False)
+    assert sorted(ref.files) == ["bending", "surface", "tilt", "volume"]
+    for name in ref.files:
+        ref_params = [str(p) for p in ref[name]]
+        our_params = list(inspect.signature(EnergyModuleManager([name]).get_module(name)
+                                            .compute_energy_and_gradient_array).parameters)
+        assert ref_params[:3] == our_params[:3] == ["mesh", "global_params", "param_resolver"]
+        for kw in ref_params[3:]:
+            assert kw in our_params, (name, kw)
+
+
+@_NO_REF
 def test_mirror_reads_reference_mesh(monkeypatch):
     sys.dont_write_bytecode = True
     sys.path.insert(0, REF)

@@ -4,8 +4,8 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out; T=$1
 cd $R
 if [ "$2" = "tests" ]; then python -m pytest tests -m gpu -x -q > $O/${T}_tests.log 2>&1; tail -3 $O/${T}_tests.log; fi
-python3 bench.py --cpu-steps 0 > $O/${T}_bench.json 2> $O/${T}_bench.err
-python3 bench.py --steps 20 --warmup 5 --cpu-steps 0 > $O/${T}_bench20.json 2> $O/${T}_bench20.err
+python3 bench.py --full --cpu-steps 0 > $O/${T}_bench.json 2> $O/${T}_bench.err
+python3 bench.py --full --steps 20 --warmup 5 --cpu-steps 0 > $O/${T}_bench20.json 2> $O/${T}_bench20.err
 python3 - <<PY
 import json
 for f in ["$O/${T}_bench.json","$O/${T}_bench20.json"]:

@@ -3,8 +3,8 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out; T=$1
 cd $R
-python3 bench.py --freq 640 --steps 100 --warmup 20 --cpu-steps 0 --headline-only > $O/${T}_f640.json 2> $O/${T}_f640.err
-python3 bench.py --cpu-steps 0 > $O/${T}_large.json 2> $O/${T}_large.err
+python3 bench.py --full --freq 640 --steps 100 --warmup 20 --cpu-steps 0 --headline-only > $O/${T}_f640.json 2> $O/${T}_f640.err
+python3 bench.py --full --cpu-steps 0 > $O/${T}_large.json 2> $O/${T}_large.err
 python3 - <<PY
 import json
 d=json.loads(open("$O/${T}_f640.json").read().strip().splitlines()[-1])
