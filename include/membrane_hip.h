@@ -166,6 +166,11 @@ typedef struct ms_stepper_params {
                               built from the row-normalised gradient g_i/(|g_i|+1e-8);
                               the history and the Armijo slope keep the raw gradient.
                               Unfused direction pass, unqueued trials.              */
+  int enforce_pins;        /* line_search.py:448-452 with pin_to_plane / pin_to_circle loaded
+                              (minimizer.py:1379): every trial that passed the guard runs
+                              the pin program (ms_enforce_pins) before the volume projection
+                              (if enforce_volume) and its energy.  Needs ms_set_pins;
+                              unqueued trials.                                       */
 } ms_stepper_params;
 
 typedef struct ms_step_result {
@@ -566,6 +571,39 @@ int ms_exec_stats(ms_ctx *ctx, int64_t stats[4]);
  * MS_RESIDENT=0 switches it off.  stats: {co-residency (-1 not asked, 0 no, 1 yes), launches, steps taken, steps
  * declined}.  No reference counterpart. */
 int ms_resident_stats(ms_ctx *ctx, int64_t stats[4]);
+
+/* ---- pin_to_plane / pin_to_circle (modules/constraints/pin_to_plane.py, pin_to_circle.py) -------------------------
+ * Tables built on the host by membrane_solver_amd.modules.constraints.pins.device_tables; rows are EXTERNAL rows
+ * (the order of ms_set_positions).  params: n_params x 7 doubles (normal, point / centre / slide base, radius; a
+ * slide circle's radius < 0 is the members' mean radial distance).  The enforcement program is n_stages stages in
+ * order: MS_PIN_STAGE_FIXED (per-row plane / circle projections, item_arg = op << 24 | param row, a row at most once
+ * per stage), MS_PIN_STAGE_PLANE_GROUP (slide plane through the members' centroid; item_arg 1 = a fixed member that
+ * keeps its place), MS_PIN_STAGE_CIRCLE_GROUP (slide circle).  lane: MS_PIN_LANE_PROJECT removes the rows of
+ * constraint_gradients_rows_array from every gradient (and the volume row) before the KKT multiplier is taken:
+ * n_grad per-row directions (MS_PIN_GRAD_*) and n_avg slide-circle supports whose normal components are replaced by
+ * their mean; MS_PIN_LANE_SKIP leaves the gradient untouched, volume row included -- the reference's KKT solve
+ * (runtime/constraint_projection.py:101-129, _solve_kkt_system) fails on C C^T for such row sets and returns.
+ * params == NULL clears the tables. */
+#define MS_PIN_STAGE_FIXED 0
+#define MS_PIN_STAGE_PLANE_GROUP 1
+#define MS_PIN_STAGE_CIRCLE_GROUP 2
+#define MS_PIN_OP_PLANE 0
+#define MS_PIN_OP_CIRCLE 1
+#define MS_PIN_GRAD_PLANE 0
+#define MS_PIN_GRAD_CIRCLE 1
+#define MS_PIN_GRAD_RADIAL 2
+#define MS_PIN_LANE_SKIP 0
+#define MS_PIN_LANE_PROJECT 1
+int ms_set_pins(ms_ctx *ctx, int n_params, const double *params, int n_stages, const int32_t *stage_kind,
+                const int32_t *stage_param, const int32_t *stage_off, const int32_t *item_row,
+                const int32_t *item_arg, int lane, int n_grad, const int32_t *grad_row, const int32_t *grad_kind,
+                const int32_t *grad_param, int n_avg, const int32_t *avg_param, const int32_t *avg_off,
+                const int32_t *avg_row);
+/* pin_to_plane.enforce_constraint then pin_to_circle.enforce_constraint (in the order the tables hold them) on
+ * buffer X, in place: one k_pin_enforce launch. */
+int ms_enforce_pins(ms_ctx *ctx);
+/* stats: {lane (-1 no tables, 0 skip, 1 project), k_pin_enforce launches, k_pin_grad launches, trials projected} */
+int ms_pin_stats(ms_ctx *ctx, int64_t stats[4]);
 /* Tilt relaxations of multi-tile meshes: the backtracking search (runtime/steppers/tilt_relaxation.py:326-347,
  * 380-398, 918-973, 1150-1230: up to twelve halvings of the step on E(P(t + step*src)), positions frozen) runs as
  * search passes -- one launch evaluates several step sizes of the ladder for every tilt-reading module of both

@@ -34,6 +34,7 @@ MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
 MS_STEPPER_GD, MS_STEPPER_CG = 0, 1
+MS_PIN_LANE_SKIP, MS_PIN_LANE_PROJECT = 0, 1
 
 (MS_BUF_X, MS_BUF_XT, MS_BUF_G, MS_BUF_GC, MS_BUF_D, MS_BUF_PG, MS_BUF_PD, MS_BUF_FK,
  MS_BUF_FA, MS_BUF_SCAL) = range(10)
@@ -63,7 +64,7 @@ class ms_stepper_params(ctypes.Structure):
                 ("c", ctypes.c_double), ("gamma", ctypes.c_double),
                 ("alpha_max_factor", ctypes.c_double), ("restart_interval", ctypes.c_int),
                 ("edge_fraction", ctypes.c_double), ("reuse_energy0", ctypes.c_int), ("enforce_volume", ctypes.c_int),
-                ("precondition", ctypes.c_int)]
+                ("precondition", ctypes.c_int), ("enforce_pins", ctypes.c_int)]
 
 
 class ms_tilt_relax_params(ctypes.Structure):
@@ -202,6 +203,10 @@ SIGNATURES = {
     "ms_queue_stats": (ctypes.c_int, [_P, _I64]),
     "ms_exec_stats": (ctypes.c_int, [_P, _I64]),
     "ms_resident_stats": (ctypes.c_int, [_P, _I64]),
+    "ms_set_pins": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.c_int, _I32, _I32, _I32, _I32, _I32, ctypes.c_int,
+                                   ctypes.c_int, _I32, _I32, _I32, ctypes.c_int, _I32, _I32, _I32]),
+    "ms_enforce_pins": (ctypes.c_int, [_P]),
+    "ms_pin_stats": (ctypes.c_int, [_P, _I64]),
     "ms_tsearch_stats": (ctypes.c_int, [_P, _I64]),
     "ms_exec_trace": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "ms_shard_peer_export": (ctypes.c_int, [_P, _P]),

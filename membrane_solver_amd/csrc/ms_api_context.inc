@@ -257,7 +257,7 @@ void ms_destroy(ms_ctx* c) {
                   c->tf[1].kappa, c->tf[1].c0, c->tf[1].bt_vert, c->tf[2].kappa, c->tf[2].c0, c->tf[2].bt_vert,
                   c->tf[1].disk, c->tf[1].diff, c->tf[2].disk, c->tf[2].diff, c->tf[0].va, c->tf[1].va, c->tf[2].va,
                   c->state, c->d_partials, c->d_scal, c->d_stage, c->d_bnd_rows, c->d_bnd_off,
-                  c->d_halo_rows, c->d_scal_all};
+                  c->d_halo_rows, c->d_scal_all, c->d_pins};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void* q : c->peer_opened) (void)hipIpcCloseMemHandle(q);

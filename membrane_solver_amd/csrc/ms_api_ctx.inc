@@ -342,4 +342,10 @@ struct ms_ctx {
   long relax_programs = 0;
   bool exec_on = false;      // the recorder is attached to `stream`
   bool exec_wanted = false;  // ... and is to be re-attached when profiling (which needs one launch per kernel) ends
+  // pin_to_plane / pin_to_circle (ms_set_pins): one allocation holds every table; pin_lane -1 = none set
+  void* d_pins = nullptr;
+  PinEnforceArgs pin_enf{};
+  PinGradArgs pin_grad{};
+  int pin_lane = -1;
+  long pin_enforce_launches = 0, pin_grad_launches = 0, pin_trials = 0;
 };

@@ -8,6 +8,7 @@ inline hipStream_t S(ms_ctx* c) {
   if (c->exec_on) (void)c->exec.flush();
   return c->stream;
 }
+int pin_grad_run(ms_ctx* c, bool volrow);  // (ms_api_pins.inc)
 inline int exec_flush(ms_ctx* c) {
   if (!c->exec_on) return MS_OK;
   const hipError_t e = c->exec.flush();
@@ -880,7 +881,8 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
 }
 
 int phase_direction(ms_ctx* c, int stepper, bool use_history, bool g_finalized = false) {
-  const bool use_con = (c->params.modules & MS_CON_VOLUME) != 0;
+  // (pins in the skip lane: the reference's KKT solve returned before touching g, the volume row included)
+  const bool use_con = (c->params.modules & MS_CON_VOLUME) != 0 && c->pin_lane != MS_PIN_LANE_SKIP;
   c->dir_implicit = false;
   {
   ProfScope ps(c, 2, c->cur_gate, c->cur_gate_want);
@@ -1044,7 +1046,8 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
   const uint32_t mods = c->params.modules;
   // lambda needs a global reduction first; the tilt module adds into g after K_C
   // (and a preconditioned direction -- conjugate_gradient.py:74-76 -- is the direction kernel's)
-  const bool constraint = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS)) != 0 || (stepper == MS_STEPPER_CG && c->precond);
+  const bool constraint = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS)) != 0 || (stepper == MS_STEPPER_CG && c->precond) ||
+                          c->pin_lane == MS_PIN_LANE_PROJECT;
   // K_C reads the reduced volume (already reduced when the energy pass is skipped)
   const bool penalty = skip_energy || (mods & MS_MOD_VOLUME_PENALTY) != 0;
   int rc = MS_OK;
@@ -1058,6 +1061,8 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
     return reduce_slots(c, (penalty ? 0u : energy_mask(mods)) | MASK_DIR);
   }
   rc = phase_gradient(c, mods, c->buf[MS_BUF_G], false, 0, /*reduce_now=*/false);
+  if (rc) return rc;
+  rc = pin_grad_run(c, (mods & MS_CON_VOLUME) != 0);  // (project lane only)
   if (rc) return rc;
   // (<g,gC> / <gC,gC> exist only with a row or a tilt module behind K_C)
   const uint32_t gmask = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS)) ? MASK_GRAD : 0u;

@@ -623,6 +623,8 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   // plain lane instead would be a different trajectory, silently)
   if (sp->enforce_volume)
     return fail(c, MS_ERR_STATE, "volume_projection_during_minimization (the enforcer lane of the line search) is not sharded (single GPU only)");
+  if (sp->enforce_pins || pins_set(c))
+    return fail(c, MS_ERR_STATE, "pin_to_plane / pin_to_circle are not sharded (single GPU only)");
   c->precond = false;
   memset(out, 0, sizeof(*out));
   const bool cg = sp->stepper == MS_STEPPER_CG;

@@ -641,7 +641,11 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   // <g,gC> / <gC,gC>, the direction kernel and its fold, all four behind the same decision word).
   // the enforcer lane (ms_stepper_params.enforce_volume): every trial is projected onto the target volume before its
   // energy is taken -- three more passes per trial, one trial at a time
-  const bool enforce = sp->enforce_volume != 0 && volrow && !tilt;
+  // pins (ms_stepper_params.enforce_pins): the pin program on every trial first, then the volume projection if that
+  // is on as well (constraint_manager.enforce_all runs the modules in their order; the pins are listed first)
+  const bool enforce_vol = sp->enforce_volume != 0 && volrow && !tilt;
+  const bool enforce_pin = sp->enforce_pins != 0 && pins_set(c) && !tilt;
+  const bool enforce = enforce_vol || enforce_pin;
   const bool can_chain = c->speculate && carry_mode && !tilt && !(c->params.modules & MS_MOD_VOLUME_PENALTY) && !enforce &&
                          !precond;
   // a round queued by the step before (while its gradient pass was running): the round of THIS search's first
@@ -685,7 +689,12 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
         // line_search.py:448-452: constraint_enforcer(mesh) on the trial positions, then energy_fn() there.  The
         // projection works on buffer X: the trial takes that place for its duration.
         std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
-        rc = ms_project_volume_cached(c, c->params.target_volume, 1e-12, 3, 0, nullptr, nullptr);
+        rc = MS_OK;
+        if (enforce_pin) {
+          rc = pin_enforce_run(c);
+          ++c->pin_trials;
+        }
+        if (rc == MS_OK && enforce_vol) rc = ms_project_volume_cached(c, c->params.target_volume, 1e-12, 3, 0, nullptr, nullptr);
         if (rc == MS_OK) rc = phase_energy(c, c->params.modules, false, 0.0, false, false, carry_mode);
         if (rc == MS_OK) rc = fetch(c);
         std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);  // (the projected trial is the trial buffer again)
@@ -924,6 +933,7 @@ bool resident_eligible(ms_ctx* c, const ms_minimize_params* mp) {
   if (!(mods & MS_MOD_SURFACE) || (mods & ~(MS_MOD_SURFACE | MS_CON_VOLUME | MS_TRACK_VOLUME))) return false;
   if (sp.stepper != MS_STEPPER_GD || sp.precondition || sp.enforce_volume || sp.reuse_energy0 < 2 || sp.edge_fraction > 0.0)
     return false;
+  if (pins_set(c)) return false;  // (the pin program and the project lane run outside the resident kernel)
   if (mp->relax_tilts || mp->fixed_step_mode) return false;
   if (c->resident_ok < 0) {
     c->resident_lds = resident_lds_bytes(c->cap, c->til.max_ent, c->til.max_tile_facets, false);
@@ -1059,6 +1069,8 @@ int ms_minimize(ms_ctx* c, const ms_minimize_params* mp, int n_steps, ms_minimiz
       if (ro.reason == RES_DRIFT) {  // :1478-1513, for the step just taken
         if (mp->project_on_drift) {
           int iters = 0;
+          rc = pin_enforce_run(c);  // enforce_all(context="mesh_operation"): the pins, then the volume
+          if (rc) return rc;
           rc = ms_project_volume_cached(c, mp->target_volume, 1e-12, 12, 1, &iters, nullptr);
           if (rc) return rc;
           out->volume_cache_current = 0;
@@ -1159,6 +1171,8 @@ int ms_minimize(ms_ctx* c, const ms_minimize_params* mp, int n_steps, ms_minimiz
           if (mp->project_on_drift) {
             int iters = 0;
             drop_ahead(c, /*ran=*/2);  // (the projection moves x: a round queued for the next step is void)
+            rc = pin_enforce_run(c);  // enforce_all(context="mesh_operation"): the pins, then the volume
+            if (rc) return rc;
             rc = ms_project_volume_cached(c, mp->target_volume, 1e-12, 12, 1, &iters, nullptr);
             if (rc) return rc;
             out->volume_cache_current = 0;  // enforce_constraints_after_mesh_ops bumps the mesh version

@@ -323,6 +323,37 @@ struct DirectionArgs {
   uint32_t gate_want;
   int pd_neg_pg, precond;
 };
+// pin_to_plane / pin_to_circle (ms_pins.hip): the staged enforcement program and the project lane's gradient pass
+struct PinEnforceArgs {
+  double* x;
+  const double* params;  // 7 per row: normal, point / centre / base, radius (< 0: the mean radial distance)
+  int n_stages;
+  const int32_t* stage_kind;
+  const int32_t* stage_param;
+  const int32_t* stage_off;
+  const int32_t* item_row;
+  const int32_t* item_arg;
+};
+struct PinGradArgs {
+  const double* x;
+  double* g;
+  double* gc;  // the volume row, or nullptr
+  const double* params;
+  int n_grad;
+  const int32_t* grad_row;
+  const int32_t* grad_kind;
+  const int32_t* grad_param;
+  int n_avg;
+  const int32_t* avg_param;
+  const int32_t* avg_off;
+  const int32_t* avg_row;
+  int n_touch;
+  const int32_t* touch_row;
+  double* partials;
+  int n_tiles, tile;
+};
+hipError_t launch_pin_enforce(const PinEnforceArgs& a, hipStream_t s);
+hipError_t launch_pin_grad(const PinGradArgs& a, hipStream_t s);
 struct RowDotArgs {
   int tile0, nv, T;
   const double* g;

@@ -300,16 +300,18 @@ class DeviceMesh:
     def step(self, *, stepper: int, step_size: float, tol: float = 1e-6, max_iter: int = 10,
              beta: float = 0.7, c: float = 1e-4, gamma: float = 1.5, alpha_max_factor: float = 10.0,
              restart_interval: int = 10, edge_fraction: float = 0.0,
-             reuse_energy0: int = 0, enforce_volume: int = 0, precondition: int = 0) -> StepResult:
+             reuse_energy0: int = 0, enforce_volume: int = 0, precondition: int = 0,
+             enforce_pins: int = 0) -> StepResult:
         # the parameter block and the result struct are reused between calls: at ~140 us per
         # step every microsecond of ctypes marshalling shows
         key = (stepper, max_iter, beta, c, gamma, alpha_max_factor, restart_interval, edge_fraction,
-               reuse_energy0, enforce_volume, precondition)
+               reuse_energy0, enforce_volume, precondition, enforce_pins)
         cache = self.__dict__.get("_step_cache")
         if cache is None or cache[0] != key:
             sp = L.ms_stepper_params(int(stepper), int(max_iter), float(beta), float(c), float(gamma),
                                      float(alpha_max_factor), int(restart_interval), float(edge_fraction),
-                                     int(reuse_energy0), int(enforce_volume), int(precondition))
+                                     int(reuse_energy0), int(enforce_volume), int(precondition),
+                                     int(enforce_pins))
             r = L.ms_step_result()
             cache = (key, sp, r, ctypes.byref(sp), ctypes.byref(r), L.lib().ms_step)
             self._step_cache = cache
@@ -539,6 +541,36 @@ class DeviceMesh:
         self._chk(L.lib().ms_exec_stats(self._h, v.ctypes.data_as(L._I64)), "ms_exec_stats")
         return {"active": bool(v[0]), "packs": int(v[1]), "launches_recorded": int(v[2]), "wanted": bool(v[3] & 1),
                 "relax_programs": int((v[3] >> 8) & 0xffffff), "relax_fused": int(v[3] >> 32)}
+
+    def set_pins(self, tables):
+        """Upload pin tables (modules/constraints/pins.DeviceTables; None clears them)."""
+        if tables is None:
+            self._chk(L.lib().ms_set_pins(self._h, 0, None, 0, None, None, None, None, None, 0, 0, None, None, None,
+                                          0, None, None, None), "ms_set_pins")
+            return
+
+        def i32(v):
+            return np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(-1)) if len(v) else np.zeros(1, np.int32)
+
+        prm = np.ascontiguousarray(np.asarray(tables.params, dtype=np.float64).reshape(-1, 7))
+        arrs = [i32(tables.stage_kind), i32(tables.stage_param), i32(tables.stage_off), i32(tables.item_row),
+                i32(tables.item_arg), i32(tables.grad_row), i32(tables.grad_kind), i32(tables.grad_param),
+                i32(tables.avg_param), i32(tables.avg_off), i32(tables.avg_row)]
+        p = [a.ctypes.data_as(L._I32) for a in arrs]
+        lane = L.MS_PIN_LANE_PROJECT if tables.lane == "project" else L.MS_PIN_LANE_SKIP
+        self._chk(L.lib().ms_set_pins(self._h, prm.shape[0], prm.ctypes.data_as(L._D), len(tables.stage_kind),
+                                      p[0], p[1], p[2], p[3], p[4], lane, len(tables.grad_row), p[5], p[6], p[7],
+                                      len(tables.avg_param), p[8], p[9], p[10]), "ms_set_pins")
+        self._pin_arrays = (prm, arrs)
+
+    def enforce_pins(self):
+        """pin_to_plane / pin_to_circle enforce_constraint on the device positions (ms_enforce_pins)."""
+        self._chk(L.lib().ms_enforce_pins(self._h), "ms_enforce_pins")
+
+    def pin_stats(self):
+        v = np.zeros(4, dtype=np.int64)
+        self._chk(L.lib().ms_pin_stats(self._h, v.ctypes.data_as(L._I64)), "ms_pin_stats")
+        return {"lane": int(v[0]), "enforce_launches": int(v[1]), "grad_launches": int(v[2]), "trials": int(v[3])}
 
     def resident_stats(self):
         """The resident step kernel (include/membrane_hip.h, ms_resident_stats)."""

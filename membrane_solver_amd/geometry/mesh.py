@@ -40,7 +40,7 @@ class ArrayMesh:
                  bending_modulus=None, spontaneous_curvature=None, bodies=None, tilts=None,
                  tilt_fixed=None, global_parameters=None, energy_modules=None, constraint_modules=None,
                  tilts_in=None, tilts_out=None, tilt_fixed_in=None, tilt_fixed_out=None,
-                 disk_rows_in=None, disk_rows_out=None):
+                 disk_rows_in=None, disk_rows_out=None, vertex_options=None, edges=None, edge_options=None):
         self._positions = np.array(positions, dtype=np.float64, order="C", copy=True)
         self._tri_rows = np.ascontiguousarray(tri_rows, dtype=np.int32)
         nv, nf = self._positions.shape[0], self._tri_rows.shape[0]
@@ -89,6 +89,15 @@ class ArrayMesh:
         # rows tagged for tilt_disk_target_in/out (the reference reads vertex.options["tilt_disk_target_group_*"])
         self.disk_rows_in = None if disk_rows_in is None else np.asarray(disk_rows_in).copy()
         self.disk_rows_out = None if disk_rows_out is None else np.asarray(disk_rows_out).copy()
+        # entity options the constraint modules read (the reference's vertex.options / edge.options):
+        # vertex_options {row: dict} (or a list per row), edges (ne, 2) tail/head rows, edge_options {edge: dict}
+        if vertex_options is not None and not isinstance(vertex_options, dict):
+            vertex_options = {i: o for i, o in enumerate(vertex_options) if o}
+        self.vertex_options = dict(vertex_options or {})
+        self.edge_rows = None if edges is None else np.asarray(edges, dtype=np.int64).reshape(-1, 2).copy()
+        if edge_options is not None and not isinstance(edge_options, dict):
+            edge_options = {i: o for i, o in enumerate(edge_options) if o}
+        self.edge_options = dict(edge_options or {})
         self._version = 0
         self._facet_loops_version = 0
         self._vertex_ids_version = 0

@@ -1,5 +1,7 @@
 """Constraint plugin loader (runtime/constraint_manager.py, reduced to the
-in-scope ``volume`` module) and the k == 1 dense KKT projection (:293-301)."""
+in-scope ``volume``, ``pin_to_plane`` and ``pin_to_circle`` modules) and the KKT
+projection of the gradient (:174-315): the k == 1 dense row alone, or the mixed
+dense + sparse-row solve with the pins."""
 
 from __future__ import annotations
 
@@ -7,6 +9,8 @@ import importlib
 import logging
 
 import numpy as np
+
+from ..modules.constraints import pins as _pins
 
 logger = logging.getLogger("membrane_solver")
 
@@ -35,8 +39,22 @@ class ConstraintModuleManager:
         return self.modules[name]
 
     def apply_gradient_modifications_array(self, grad_arr, mesh, global_params):
-        """Host-array variant of the k == 1 dense branch (constraint_manager.py:293-301)."""
+        """Host-array variant of constraint_manager.py:174-315 (the device path's CPU restatement)."""
         positions = mesh.positions_view()
+        if any(hasattr(m, "constraint_gradients_rows_array") for m in self.modules.values()):
+            dense, sparse = [], []
+            for module in self.modules.values():
+                fr = getattr(module, "constraint_gradients_rows_array", None)
+                if fr is not None:
+                    sparse.extend(fr(mesh, global_params, positions=positions,
+                                     index_map=mesh.vertex_index_to_row) or [])
+                    continue
+                fn = getattr(module, "constraint_gradients_array", None)
+                if fn is not None:
+                    dense.extend(fn(mesh, global_params, positions=positions,
+                                    index_map=mesh.vertex_index_to_row) or [])
+            _pins.project_gradient(grad_arr, dense, sparse)
+            return
         rows = []
         for module in self.modules.values():
             fn = getattr(module, "constraint_gradients_array", None)
@@ -67,8 +85,9 @@ class ConstraintModuleManager:
         step_projection = True if global_params is None else bool(
             global_params.get("volume_projection_during_minimization", True))
         options.pop("force_projection", None)
-        volume = self.modules.get("volume")
-        if volume is None or (during_step and not step_projection):
-            return
-        volume.enforce_constraint(mesh, force_projection=True, context=context, global_params=global_params,
-                                  **options)
+        for name, module in self.modules.items():  # in the listed order (:857-905); the pins in every context
+            if name != "volume":
+                module.enforce_constraint(mesh, context=context, global_params=global_params, **options)
+            elif not (during_step and not step_projection):
+                module.enforce_constraint(mesh, force_projection=True, context=context, global_params=global_params,
+                                          **options)

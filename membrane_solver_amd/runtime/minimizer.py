@@ -27,8 +27,11 @@ modules (``tilt``, ``bending_tilt``, ``tilt_smoothness`` and their ``_in`` /
 ``_out`` leaflet forms, ``tilt_disk_target_in/out``), ``gaussian_curvature``
 and the switched-off ``rim_slope_match_out`` as host-side constants.
 
+Constraints: ``volume`` and the pins (``pin_to_plane`` / ``pin_to_circle``: the pin program on every
+line-search trial and in every enforce context, their rows removed from the gradient in the project lane).
+
 Out of scope here (raises MembraneHipError): every other energy module,
-constraints other than ``volume``, the benchmark toggles of the leaflet modules
+constraints other than ``volume``, ``pin_to_plane`` and ``pin_to_circle``, pins with tilt modules, the benchmark toggles of the leaflet modules
 (modules/energy/leaflet_common._UNSUPPORTED_KEYS), the reference's auto
 mesh-quality repair hook.
 """
@@ -46,6 +49,7 @@ from .steppers.base import BaseStepper
 from ..geometry.mesh import mirror_for
 from ..modules.energy import leaflet_common as _lc
 from ..modules.energy._common import bending_gradient_mode, bending_model
+from ..modules.constraints import pins as _pins
 from ..modules.energy.volume import body_penalty_params
 from .steppers.base import write_back_positions
 
@@ -76,6 +80,7 @@ _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": 
                 "tilt_out": L.MS_S_ETILT_OUT, "tilt_smoothness_in": L.MS_S_ETS_IN,
                 "tilt_smoothness_out": L.MS_S_ETS_OUT, "tilt_disk_target_in": L.MS_S_EDT_IN,
                 "tilt_disk_target_out": L.MS_S_EDT_OUT}
+_PIN_MODULES = ("pin_to_plane", "pin_to_circle")
 _BEND_SCALAR = {"bending": L.MS_S_EBEND, "bending_tilt": L.MS_S_EBT, "bending_tilt_in": L.MS_S_EBT_IN,
                 "bending_tilt_out": L.MS_S_EBT_OUT}
 
@@ -173,8 +178,17 @@ class Minimizer:
         self.constraint_modules = [self.constraint_manager.get_constraint(c)
                                    for c in self.constraint_module_names]
         for name in self.constraint_module_names:
-            if name != "volume":
-                raise L.MembraneHipError(f"constraint module {name!r} is outside the HIP hot path (volume)")
+            if name not in ("volume",) + _PIN_MODULES:
+                raise L.MembraneHipError(f"constraint module {name!r} is outside the HIP hot path "
+                                         "(volume, pin_to_plane, pin_to_circle)")
+        self._pin_names = [n for n in self.constraint_module_names if n in _PIN_MODULES]
+        if self._pin_names and "volume" in self.constraint_module_names and \
+                self.constraint_module_names.index("volume") < self.constraint_module_names.index(self._pin_names[0]):
+            # enforce_all runs the modules in their listed order; the device runs the pins first
+            raise L.MembraneHipError("constraint_modules lists volume before pin_to_plane / pin_to_circle: the HIP "
+                                     "path enforces the pins first; list the pin modules before volume")
+        self._pin_key = None
+        self._pins_active = False
         self._has_enforceable_constraints = any(hasattr(m, "enforce_constraint")
                                                 for m in self.constraint_modules)
         self._configured_key = None
@@ -315,6 +329,8 @@ class Minimizer:
             mir.upload_tilts(gp)
             mir.upload_tilt_fixed()
             dm.set_tilt_smoothness(float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0))
+        if self._pin_names:
+            self._upload_pins(mir, dm, mods)
         key = (mods, model, mode, stiffness, target, id(dm))
         if key != self._configured_key:
             dm.set_params(modules=mods,
@@ -323,6 +339,25 @@ class Minimizer:
                           volume_stiffness=stiffness, target_volume=target)
             self._configured_key = key
         return mir, dm
+
+    def _upload_pins(self, mir, dm, mods):
+        """Resolve the pin tags once per mesh topology, fixed mask and row set (call refresh_modules() after
+        changing the tags or the pin parameters) and upload the device tables; an empty program (nothing tagged, or
+        only slide circles of fewer than three members, which the reference skips) clears them; the project-or-skip decision is the reference's KKT solve on C = [volume row;
+        pin rows] at the current positions (runtime/constraint_projection.py:101-129)."""
+        if mods & _TILT_BITS:
+            raise L.MembraneHipError("pin_to_plane / pin_to_circle together with tilt modules are outside the HIP "
+                                     "hot path")
+        volrow = bool(mods & L.MS_CON_VOLUME)
+        key = (mir._topo_key, id(dm), volrow, np.asarray(self.mesh.fixed_mask, dtype=bool).tobytes())
+        if key == self._pin_key:
+            return
+        X = np.asarray(self.mesh.positions_view(), dtype=np.float64)
+        dense = [_volume_gradient(self.mesh, X)] if volrow else []
+        self.pin_tables = _pins.device_tables(X, _pins.programs(self.mesh, self._pin_names), dense)
+        self._pins_active = bool(self.pin_tables.params)
+        dm.set_pins(self.pin_tables if self._pins_active else None)
+        self._pin_key = key
 
     def _target_volume(self):
         bodies = getattr(self.mesh, "bodies", None) or {}
@@ -372,15 +407,19 @@ class Minimizer:
         current mesh version has made that cache look current (ms_project_volume_cached)."""
         if not self._has_enforceable_constraints:
             return False
+        moved = False
+        if self._pins_active:  # constraint_manager.enforce_all: the pins in every context, listed before volume
+            dm.enforce_pins()
+            moved = True
         gp = self.global_params
         if context == "minimize" and not gp.get("volume_projection_during_minimization", True):
-            return False
+            return moved
         target = self._target_volume()
-        if target is None:
-            return False
+        if target is None or "volume" not in self.constraint_module_names:
+            return moved
         max_iter = 12 if context in ("finalize", "mesh_operation") else 3
         iters, _v = dm.project_volume(target, tol=1e-12, max_iter=max_iter, first_step_cached=first_step_cached)
-        moved = iters > 0
+        moved = moved or iters > 0
         if context in ("finalize", "mesh_operation") and dm.modules & _TILT_BITS:
             # minimizer.py:1186, :1224, :1506: every enforce outside the line search is followed by
             # mesh.project_tilts_to_tangent() -- the tilts must be tangent to the PROJECTED surface before the
@@ -464,7 +503,7 @@ class Minimizer:
                                          float(st.c), float(st.gamma), float(st.alpha_max_factor),
                                          int(extra.get("restart_interval", 10)), edge_fraction,
                                          int(st.reuse_energy0), int(getattr(st, "enforce_volume", 0)),
-                                         int(extra.get("precondition", 0)))
+                                         int(extra.get("precondition", 0)), int(getattr(st, "enforce_pins", 0)))
         step_mode = str(gp.get("step_size_mode", "adaptive") or "adaptive").lower()
         mp.step_size = float(self.step_size)
         mp.tol = float(self.tol)
@@ -484,10 +523,10 @@ class Minimizer:
         if rp is not None:
             mp.relax = L.ms_tilt_relax_params(1 if rp["solver"] == "cg" else 0, rp["max_iters"], rp["step_size"],
                                               rp["tol"], 1 if rp["jacobi"] else 0)
-        out, _log = dm.minimize(mp, n_steps)
+        out, log = dm.minimize(mp, n_steps, want_log=True)
         self.step_size = float(out.step_size)
         self.last_run = {"accepted": out.accepted, "trials": out.trials, "guard_rejects": out.guard_rejects,
-                         "iterations": out.iterations}
+                         "iterations": out.iterations, "step_log": log}
         return out
 
     # -- the loop -------------------------------------------------------------------
@@ -506,6 +545,7 @@ class Minimizer:
             self._has_enforceable_constraints and gp.get("volume_projection_during_minimization", True)
             and gp.get("volume_constraint_mode", "lagrange") == "lagrange" and self._target_volume() is not None
             and (dm.modules & L.MS_CON_VOLUME)))
+        self.stepper.enforce_pins = int(self._pins_active)  # (pins always have enforce_constraint)
         if n_steps <= 0:
             E, g = self.compute_energy_and_gradient_array()
             moved = self._enforce(dm, "minimize")
@@ -632,6 +672,18 @@ class Minimizer:
         grad = GradientRows(self.mesh, dm.get_gradient() if sync_mesh else dm.get_gradient) if have_grad else {}
         return finish({"energy": final_energy, "gradient": grad, "mesh": self.mesh,
                        "step_success": step_success, "iterations": n_steps, "terminated_early": False})
+
+
+def _volume_gradient(mesh, X):
+    """dV/dx of the (single, whole-mesh) body: sum over facets of cross(x_j, x_k) / 6 at corner i."""
+    tri, _ = mesh.triangle_row_cache()
+    tri = np.asarray(tri, dtype=np.int64)
+    g = np.zeros_like(X)
+    a, b, c = X[tri[:, 0]], X[tri[:, 1]], X[tri[:, 2]]
+    np.add.at(g, tri[:, 0], np.cross(b, c) / 6.0)
+    np.add.at(g, tri[:, 1], np.cross(c, a) / 6.0)
+    np.add.at(g, tri[:, 2], np.cross(a, b) / 6.0)
+    return g
 
 
 def _boundary(mesh):

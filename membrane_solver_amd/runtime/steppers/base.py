@@ -51,6 +51,8 @@ class BaseStepper(ABC):
         # set by the Minimizer: every trial is projected onto the target volume before its energy is taken
         # (line_search.py:428-487 with the volume module's enforce_constraint as the enforcer)
         self.enforce_volume = 0
+        # set by the Minimizer when pin_to_plane / pin_to_circle are loaded: every trial runs the pin program first
+        self.enforce_pins = 0
         self._dm = None
 
     @abstractmethod
@@ -69,7 +71,8 @@ class BaseStepper(ABC):
         return dm.step(stepper=self.stepper_id, step_size=step_size, tol=tol,
                        max_iter=self._max_iter_for(mesh), beta=self.beta, c=self.c, gamma=self.gamma,
                        alpha_max_factor=self.alpha_max_factor, edge_fraction=edge_fraction,
-                       reuse_energy0=self.reuse_energy0, enforce_volume=int(self.enforce_volume), **self._extra())
+                       reuse_energy0=self.reuse_energy0, enforce_volume=int(self.enforce_volume),
+                       **({"enforce_pins": 1} if self.enforce_pins else {}), **self._extra())
 
     def step(self, mesh, grad, step_size, energy_fn=None, constraint_enforcer=None,
              trial_energy_fn=None):
