@@ -68,6 +68,10 @@ extern "C" {
 /* soft disk tilt-profile target (modules/energy/tilt_disk_target_in.py:160-286, tilt_disk_target_out.py) */
 #define MS_MOD_TILT_DISK_TARGET_IN 16384u
 #define MS_MOD_TILT_DISK_TARGET_OUT 32768u
+/* soft body-area penalty E = 1/2 k (A - A0)^2 over the body's facets (modules/energy/body_area_penalty.py:100-145);
+ * k and A0 come from ms_set_area_penalty.  Its gradient k (A - A0) dA/dx is an effective surface tension on the
+ * facets that carry the body flag (geometry/facet.py:168-249: the surface term's normal and 1e-12 clamp). */
+#define MS_MOD_AREA_PENALTY 65536u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -129,7 +133,9 @@ enum ms_scalar {
   MS_S_EDT_OUT = 27,
   MS_S_DTR_IN = 28,  /* largest in-plane distance of a disk row (the default disk radius), max-reduced */
   MS_S_DTR_OUT = 29,
-  MS_NSCAL = 30
+  MS_S_AREA = 30,   /* area of the body's facets (MS_MOD_AREA_PENALTY), modules/energy/body_area_penalty.py:125-132 */
+  MS_NSCAL = 31     /* slot masks are uint32_t (1u << slot) and bit MS_NSCAL marks the partials' "ran" row: ONE slot is
+                     * left before the masks have to widen */
 };
 
 typedef struct ms_params {
@@ -219,6 +225,14 @@ int ms_set_surface_tension(ms_ctx *ctx, const double *gamma /* nf */);
 int ms_set_bending_params(ms_ctx *ctx, const double *kappa /* nv */,
                           const double *c0 /* nv */);
 int ms_set_params(ms_ctx *ctx, const ms_params *p);
+/* body_area_penalty (modules/energy/body_area_penalty.py:113-123): stiffness k = param_resolver.get(body,
+ * "area_stiffness") else the global "area_stiffness", target A0 = body.options["area_target"].  Used while
+ * MS_MOD_AREA_PENALTY is in ms_params.modules; energies[2] of the evaluation calls is then volume penalty + area
+ * penalty.  Single GPU, no tilt-family module next to it (both refused with MS_ERR_STATE). */
+int ms_set_area_penalty(ms_ctx *ctx, double stiffness, double target_area);
+/* the body's area as the last energy pass folded it (MS_S_AREA; synchronises): the module's own energy is
+ * 1/2 k (area - A0)^2 */
+int ms_get_body_area(ms_ctx *ctx, double *area);
 /* Per-vertex accumulation in the two big tile kernels (energy pass, gradient pass):
  * 0 (default) LDS atomic adds -- fastest, the floating-point summation order (hence the
  * last bits) may differ between runs; 1 staged CSR gather in a fixed order -- bitwise
@@ -335,7 +349,7 @@ int ms_get_vertex_buffer(ms_ctx *ctx, int buffer, double *out /* nv*ncomp */);
 /*
  * Minimizer.compute_energy_and_gradient_array (runtime/minimizer.py:941-992):
  * module loop, volume-constraint projection, fixed rows zeroed.  energies[4] =
- * {surface, bending, volume-penalty, tilt}.  grad may be NULL (stays on device).
+ * {surface, bending, volume-penalty + area-penalty, tilt}.  grad may be NULL (stays on device).
  */
 int ms_energy_and_gradient(ms_ctx *ctx, double energies[4], double *grad);
 /*

@@ -30,6 +30,7 @@ MS_MOD_TILT_SMOOTH = 128
 MS_MOD_TILT_IN, MS_MOD_TILT_OUT, MS_MOD_TILT_SMOOTH_IN, MS_MOD_TILT_SMOOTH_OUT = 256, 512, 1024, 2048
 MS_MOD_BENDING_TILT_IN, MS_MOD_BENDING_TILT_OUT = 4096, 8192
 MS_MOD_TILT_DISK_TARGET_IN, MS_MOD_TILT_DISK_TARGET_OUT = 16384, 32768
+MS_MOD_AREA_PENALTY = 65536
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
@@ -42,8 +43,8 @@ MS_PIN_LANE_SKIP, MS_PIN_LANE_PROJECT = 0, 1
  MS_S_GNORM2, MS_S_GDOTD, MS_S_MAXD2, MS_S_ETILT, MS_S_EBT, MS_S_TGNORM2, MS_S_TRZ, MS_S_MAXG2,
  MS_S_ETS, MS_S_ETILT_IN, MS_S_ETILT_OUT, MS_S_ETS_IN, MS_S_ETS_OUT, MS_S_TGNORM2_IN, MS_S_TGNORM2_OUT,
  MS_S_TRZ_IN, MS_S_TRZ_OUT, MS_S_EBT_IN, MS_S_EBT_OUT, MS_S_EDT_IN, MS_S_EDT_OUT, MS_S_DTR_IN,
- MS_S_DTR_OUT) = range(30)
-MS_NSCAL = 30
+ MS_S_DTR_OUT, MS_S_AREA) = range(31)
+MS_NSCAL = 31
 
 
 class MembraneHipError(RuntimeError):
@@ -129,6 +130,8 @@ SIGNATURES = {
     "ms_set_surface_tension": (ctypes.c_int, [_P, _D]),
     "ms_set_bending_params": (ctypes.c_int, [_P, _D, _D]),
     "ms_set_params": (ctypes.c_int, [_P, ctypes.POINTER(ms_params)]),
+    "ms_set_area_penalty": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_double]),
+    "ms_get_body_area": (ctypes.c_int, [_P, _D]),
     "ms_set_tilts": (ctypes.c_int, [_P, _D, ctypes.c_double]),
     "ms_get_tilts": (ctypes.c_int, [_P, _D]),
     "ms_get_tilt_gradient": (ctypes.c_int, [_P, _D]),

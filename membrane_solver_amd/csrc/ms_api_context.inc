@@ -398,6 +398,10 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
     return fail(c, MS_ERR_INVALID, "ms_set_params: bending / bending_tilt together with bending_tilt_in/out is outside the device path");
   if ((p->modules & MS_MOD_BENDING_TILT) && c->shard_count != 1)
     return fail(c, MS_ERR_STATE, "the bending_tilt module is not sharded yet (single GPU only)");
+  if ((p->modules & MS_MOD_AREA_PENALTY) && c->shard_count != 1)
+    return fail(c, MS_ERR_STATE, "the body_area_penalty module is not sharded (single GPU only)");
+  if ((p->modules & MS_MOD_AREA_PENALTY) && (p->modules & MS_ANY_TILT_MODS))
+    return fail(c, MS_ERR_STATE, "body_area_penalty together with a tilt-family module is outside the device path");
   if ((p->modules & MS_MOD_BENDING_TILT) && !c->d_bt_vert) {
     const size_t bytes = sizeof(double) * 4 * (size_t)c->til.nvp;
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_bt_vert), bytes));
@@ -407,6 +411,27 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
   c->factors_valid = false;
   c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
+  return MS_OK;
+}
+
+int ms_set_area_penalty(ms_ctx* c, double stiffness, double target_area) {
+  if (!c) return MS_ERR_INVALID;
+  if (!std::isfinite(stiffness) || !std::isfinite(target_area))
+    return fail(c, MS_ERR_INVALID, "ms_set_area_penalty: stiffness and target area must be finite");
+  c->area_stiffness = stiffness;
+  c->target_area = target_area;
+  c->carry_valid = c->grad_valid = c->maxg2_valid = false;  // (the energies and the gradient held are the old term's)
+  c->sh_carry_valid = c->sh_grad_valid = false;
+  return MS_OK;
+}
+
+int ms_get_body_area(ms_ctx* c, double* area) {
+  if (!c || !area) return fail(c, MS_ERR_INVALID, "ms_get_body_area: NULL argument");
+  if (!(c->params.modules & MS_MOD_AREA_PENALTY))
+    return fail(c, MS_ERR_STATE, "ms_get_body_area: MS_MOD_AREA_PENALTY is not in the module mask");
+  int rc = fetch(c);
+  if (rc) return rc;
+  *area = c->h_scal[MS_S_AREA];
   return MS_OK;
 }
 

@@ -213,6 +213,7 @@ struct ms_ctx {
   double* d_stage = nullptr;  // nv*3 staging in external row order
   double* last_g = nullptr;   // buffer holding the most recent finalized gradient
   ms_params params{};
+  double area_stiffness = 0.0, target_area = 0.0;  // ms_set_area_penalty (MS_MOD_AREA_PENALTY)
   bool cg_have_history = false;
   int cg_iter_count = 0;
   bool factors_valid = false;

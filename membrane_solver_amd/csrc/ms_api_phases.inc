@@ -374,7 +374,8 @@ uint32_t armijo_slots(const ms_ctx* c) {
 uint32_t energy_mask(uint32_t modules) {
   constexpr uint32_t core = (1u << MS_S_ESURF) | (1u << MS_S_VOL) | (1u << MS_S_EBEND) | (1u << MS_S_MINEDGE2) |
                             (1u << MS_S_GUARD);
-  return (modules & MS_ANY_TILT_MODS) ? MASK_ENERGY : core;
+  // (body_area_penalty and the tilt families exclude each other: ms_set_params)
+  return (modules & MS_ANY_TILT_MODS) ? MASK_ENERGY : ((modules & MS_MOD_AREA_PENALTY) ? (core | (1u << MS_S_AREA)) : core);
 }
 
 // a pinned, device-mapped mailbox of its own (stage mailboxes of the line-search queue, the side sets' boxes)
@@ -809,6 +810,8 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
   a.bending_grad_mode = c->params.bending_grad_mode;
   a.volume_stiffness = c->params.volume_stiffness;
   a.target_volume = c->params.target_volume;
+  a.area_stiffness = c->area_stiffness;
+  a.target_area = c->target_area;
   a.accumulate = accumulate ? 1 : 0;
   a.dir_mode = dir_mode;
   a.d = c->buf[MS_BUF_D];
@@ -1015,10 +1018,19 @@ int verify_decision(ms_ctx* c, uint32_t host_code, uint32_t dev_code, const char
   return fail(c, MS_ERR_STATE, msg);
 }
 
-double penalty_energy(const ms_ctx* c, double V) {
-  if (!(c->params.modules & MS_MOD_VOLUME_PENALTY)) return 0.0;
-  const double delta = V - c->params.target_volume;
-  return 0.5 * c->params.volume_stiffness * (delta * delta);
+// volume penalty (modules/energy/volume.py:94-128) + body-area penalty (modules/energy/body_area_penalty.py:136-137)
+double penalty_energy(const ms_ctx* c, double V, double A) {
+  double e = 0.0;
+  if (c->params.modules & MS_MOD_VOLUME_PENALTY) {
+    const double delta = V - c->params.target_volume;
+    e = 0.5 * c->params.volume_stiffness * (delta * delta);
+  }
+  if (c->params.modules & MS_MOD_AREA_PENALTY) {
+    const double delta = A - c->target_area;
+    const double ea = 0.5 * c->area_stiffness * delta * delta;
+    e = (c->params.modules & MS_MOD_VOLUME_PENALTY) ? e + ea : ea;
+  }
+  return e;
 }
 
 // energies from the pinned mailbox: {surface, bending, penalty, tilt}
@@ -1026,7 +1038,7 @@ void energies_from_mailbox(const ms_ctx* c, double e[4]) {
   e[0] = (c->params.modules & MS_MOD_SURFACE) ? c->h_scal[MS_S_ESURF] : 0.0;
   e[1] = (c->params.modules & MS_MOD_BENDING) ? c->h_scal[MS_S_EBEND] : 0.0;
   if (c->params.modules & MS_MOD_BENDING_TILT) e[1] += c->h_scal[MS_S_EBT];
-  e[2] = penalty_energy(c, c->h_scal[MS_S_VOL]);
+  e[2] = penalty_energy(c, c->h_scal[MS_S_VOL], c->h_scal[MS_S_AREA]);
   e[3] = (c->params.modules & MS_MOD_TILT) ? c->h_scal[MS_S_ETILT] : 0.0;
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e[3] += c->h_scal[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
@@ -1048,8 +1060,8 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
   // (and a preconditioned direction -- conjugate_gradient.py:74-76 -- is the direction kernel's)
   const bool constraint = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS)) != 0 || (stepper == MS_STEPPER_CG && c->precond) ||
                           c->pin_lane == MS_PIN_LANE_PROJECT;
-  // K_C reads the reduced volume (already reduced when the energy pass is skipped)
-  const bool penalty = skip_energy || (mods & MS_MOD_VOLUME_PENALTY) != 0;
+  // K_C reads the reduced volume / body area (already reduced when the energy pass is skipped)
+  const bool penalty = skip_energy || (mods & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) != 0;
   int rc = MS_OK;
   if (!skip_energy) rc = phase_energy(c, mods, false, 0.0, false, false, true, /*reduce_now=*/penalty);
   if (rc) return rc;

@@ -401,7 +401,7 @@ double shard_energy_of(const ms_ctx* c, const double* scal) {
   double e = 0.0;
   if (m & MS_MOD_SURFACE) e += scal[MS_S_ESURF];
   if (m & MS_MOD_BENDING) e += scal[MS_S_EBEND];
-  e += penalty_energy(c, scal[MS_S_VOL]);
+  e += penalty_energy(c, scal[MS_S_VOL], 0.0);  // (no area penalty here: ms_shard_step refuses the module)
   return e;
 }
 double shard_energy(const ms_ctx* c) { return shard_energy_of(c, c->sh_scal); }
@@ -618,6 +618,7 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   if (!c || !sp || !out) return fail(c, MS_ERR_INVALID, "ms_shard_step: NULL argument");
   const uint32_t mods = c->params.modules;
   if (mods & MS_ANY_TILT_MODS) return fail(c, MS_ERR_STATE, "the tilt modules are not sharded yet (single GPU only)");
+  if (mods & MS_MOD_AREA_PENALTY) return fail(c, MS_ERR_STATE, "the body_area_penalty module is not sharded (single GPU only)");
   if (sp->precondition) return fail(c, MS_ERR_STATE, "ConjugateGradient(precondition=True) is not sharded (single GPU only)");
   // (line_search.py:428-487: every trial projected onto the target volume -- the projection is not sharded; running the
   // plain lane instead would be a different trajectory, silently)

@@ -49,7 +49,7 @@ int ms_energy_and_raw_gradient(ms_ctx* c, double energies[4], double* grad) {
   if (c->shard_count != 1)
     return fail(c, MS_ERR_STATE, "ms_energy_and_raw_gradient: sharded contexts use the phase API");
   const uint32_t mods = c->params.modules;
-  const bool penalty = (mods & MS_MOD_VOLUME_PENALTY) != 0;  // K_C reads the reduced volume
+  const bool penalty = (mods & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) != 0;  // K_C reads the reduced volume / body area
   int rc = phase_energy(c, mods, false, 0.0, false, false, true, /*reduce_now=*/penalty);
   if (rc) return rc;
   c->grad_valid = false;  // G receives the raw gradient: no fixed-row zeroing, no KKT projection
@@ -646,7 +646,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   const bool enforce_vol = sp->enforce_volume != 0 && volrow && !tilt;
   const bool enforce_pin = sp->enforce_pins != 0 && pins_set(c) && !tilt;
   const bool enforce = enforce_vol || enforce_pin;
-  const bool can_chain = c->speculate && carry_mode && !tilt && !(c->params.modules & MS_MOD_VOLUME_PENALTY) && !enforce &&
+  const bool can_chain = c->speculate && carry_mode && !tilt && !(c->params.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) && !enforce &&
                          !precond;
   // a round queued by the step before (while its gradient pass was running): the round of THIS search's first
   // iteration if it was queued for exactly what this step has computed by itself

@@ -56,7 +56,7 @@ __device__ __forceinline__ void exec_plain_args(A& a, ExecCmdHead& h, exec_kptr 
 }
 
 // ---- one function per body ------------------------------------------------------------------------------------------
-template <bool BEND, bool GUARD, bool ATOMIC>
+template <bool BEND, bool GUARD, bool ATOMIC, bool AREA = false>
 __device__ __noinline__ MS_EXEC_FN void exec_energy(exec_kptr base_v, int off_v, double* lds) {
   const exec_kptr base = exec_uniform_ptr(base_v);
   const int off = exec_uniform(off_v);
@@ -65,11 +65,11 @@ __device__ __noinline__ MS_EXEC_FN void exec_energy(exec_kptr base_v, int off_v,
   exec_tile_args(a, h, base, off);
   for (int b = 0; b < h.grid; ++b) {
     EnergyArgs c = a;
-    energy_body<BEND, GUARD, 256, 0, ATOMIC, 0>(c, h.cap, h.max_ent, lds, b);
+    energy_body<BEND, GUARD, 256, 0, ATOMIC, 0, AREA>(c, h.cap, h.max_ent, lds, b);
     __syncthreads();
   }
 }
-template <int BENDMODE, bool VOLROW, int TT, bool ATOMIC, bool LEAN>
+template <int BENDMODE, bool VOLROW, int TT, bool ATOMIC, bool LEAN, bool AREA = false>
 __device__ __noinline__ MS_EXEC_FN void exec_gradient(exec_kptr base_v, int off_v, double* lds) {
   const exec_kptr base = exec_uniform_ptr(base_v);
   const int off = exec_uniform(off_v);
@@ -77,7 +77,7 @@ __device__ __noinline__ MS_EXEC_FN void exec_gradient(exec_kptr base_v, int off_
   ExecCmdHead h;
   exec_tile_args(a, h, base, off);
   for (int b = 0; b < h.grid; ++b) {
-    gradient_body<BENDMODE, VOLROW, TT, 0, ATOMIC, LEAN>(a, h.cap, h.max_ent, lds, b);
+    gradient_body<BENDMODE, VOLROW, TT, 0, ATOMIC, LEAN, AREA>(a, h.cap, h.max_ent, lds, b);
     __syncthreads();
   }
 }
@@ -208,21 +208,44 @@ __device__ __forceinline__ void exec_dispatch(exec_kptr base, int off, double* l
   exec_load<0>(h, base + off);
   switch (h.kind) {
     case CK_ENERGY: {
-      // inst: bit0 bending, bit1 guard, bit2 LDS-atomic vertex sums
-      switch (h.inst & 7u) {
+      // inst: bit0 bending, bit1 guard, bit2 LDS-atomic vertex sums, bit3 body area (body_area_penalty)
+      switch (h.inst & 15u) {
         case 0: exec_energy<false, false, false>(base, off, lds); break;
         case 2: exec_energy<false, true, false>(base, off, lds); break;
         case 1: exec_energy<true, false, false>(base, off, lds); break;
         case 3: exec_energy<true, true, false>(base, off, lds); break;
         case 5: exec_energy<true, false, true>(base, off, lds); break;
         case 7: exec_energy<true, true, true>(base, off, lds); break;
+        case 8: exec_energy<false, false, false, true>(base, off, lds); break;
+        case 10: exec_energy<false, true, false, true>(base, off, lds); break;
+        case 9: exec_energy<true, false, false, true>(base, off, lds); break;
+        case 11: exec_energy<true, true, false, true>(base, off, lds); break;
+        case 13: exec_energy<true, false, true, true>(base, off, lds); break;
+        case 15: exec_energy<true, true, true, true>(base, off, lds); break;
         default: break;  // (atomic without bending is never recorded)
       }
       break;
     }
     case CK_GRADIENT: {
-      // inst: bit0 lean, bit1 constraint row, bit2 LDS-atomic vertex sums, bits 4-5 bending mode
+      // inst: bit0 lean, bit1 constraint row, bit2 LDS-atomic vertex sums, bit3 body-area penalty term (never lean, never
+      // mode 3), bits 4-5 bending mode
       const uint32_t lean = h.inst & 1u, vr = (h.inst >> 1) & 1u, at = (h.inst >> 2) & 1u, mode = (h.inst >> 4) & 3u;
+      const uint32_t ar = (h.inst >> 3) & 1u;
+#define MS_EXEC_GA(M)                                                                 \
+  do {                                                                                \
+    if (vr) {                                                                         \
+      if (at) exec_gradient<M, true, 256, true, false, true>(base, off, lds);         \
+      else exec_gradient<M, true, 256, false, false, true>(base, off, lds);           \
+    } else {                                                                          \
+      if (at) exec_gradient<M, false, 256, true, false, true>(base, off, lds);        \
+      else exec_gradient<M, false, 256, false, false, true>(base, off, lds);          \
+    }                                                                                 \
+  } while (0)
+      if (ar) {
+        if (mode == 0) MS_EXEC_GA(0); else if (mode == 1) MS_EXEC_GA(1); else if (mode == 2) MS_EXEC_GA(2);
+        break;
+      }
+#undef MS_EXEC_GA
 #define MS_EXEC_G(M, TT)                                                              \
   do {                                                                                \
     if (vr) {                                                                         \

@@ -172,6 +172,7 @@ struct GradientArgs {
   uint32_t modules;
   int bending_grad_mode;
   double volume_stiffness, target_volume;
+  double area_stiffness, target_area;  // body_area_penalty: k and A0 (K_C's effective tension k (A - A0))
   int accumulate;         // add into existing g instead of overwriting
   // fused direction pass (only when no constraint row has to be projected out first)
   int dir_mode;           // 0 off, 1 d = -g (GD / CG restart), 2 per-row Polak-Ribiere with history

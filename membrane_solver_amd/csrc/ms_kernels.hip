@@ -454,7 +454,10 @@ __device__ unsigned long long g_stamps[8 * 16384];
 #endif
 // (energy_body: the kernel's code as a device function of (arguments, LDS base, block index) -- k_energy below is its
 // one-block-per-tile launch; the one-workgroup interpreter k_exec runs the same body command by command)
-template <bool BEND, bool GUARD, int TT, int CAPC, bool ATOMIC, int MULTI = 0>
+// AREA: also sum the area of the body's facets into MS_S_AREA (body_area_penalty).  A template flag, not a runtime one:
+// the accumulator and the sixth reduced value would cost existing instances registers, some of them occupancy
+// (tools/kernel_resources.py).  Only the k_energy_area instances carry it; never combined with MULTI.
+template <bool BEND, bool GUARD, int TT, int CAPC, bool ATOMIC, int MULTI = 0, bool AREA = false>
 __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_ent, double* lds, int block_id) {
   int bid = block_id;
   double* const ran_row = a.partials + (size_t)MS_P_RAN * a.m.n_tiles;  // (of the ordinary partials)
@@ -492,7 +495,7 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
   // some vertex carries VF_BOUNDARY
   double* red = stg;
   // ATOMIC: stg holds the five per-vertex accumulators K(3), A_vor, A_eff - A_vor (ds_add_f64), no CSR
-  uint16_t* vent = reinterpret_cast<uint16_t*>(stg + (BEND ? (ATOMIC ? 5 : 9) * T : 5 * 16));
+  uint16_t* vent = reinterpret_cast<uint16_t*>(stg + (BEND ? (ATOMIC ? 5 : 9) * T : 6 * 16));
   uint8_t* lfl = reinterpret_cast<uint8_t*>(vent + ((BEND && !ATOMIC) ? ((max_ent + 3) & ~3) : 0));
   const bool stage_flags = a.m.has_boundary || GUARD;
   // queued line-search stage: runs only if the decision word says so (DEC_CONTINUE: every trial before it was rejected)
@@ -621,6 +624,10 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
   double e_surf = 0.0, vol = 0.0, min_e2 = 1.0e300, guard = 0.0;
   const bool want_surf = a.modules & MS_MOD_SURFACE;
   const bool want_vol = a.modules & (MS_MOD_VOLUME_PENALTY | MS_CON_VOLUME | MS_TRACK_VOLUME);
+  // body_area_penalty (modules/energy/body_area_penalty.py:125-137): the body's area, for K_C's effective tension and the
+  // host's 1/2 k (A - A0)^2
+  constexpr bool want_area = AREA;
+  double area = 0.0;
   // vertex accumulators (BEND): K(3), A_vor, A_eff
   double aKx = 0, aKy = 0, aKz = 0, aAv = 0, aAe = 0;
   if (!(BEND && tid < t.n_owned)) cur = end = 0;
@@ -651,6 +658,8 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
         if (owner) {
           if (want_surf && A2 >= 1.0e-12) e_surf += gam * (0.5 * A2);
           if (want_vol && (tf.flags & TF_BODY)) vol += dot(cross(v1, v2), v0);
+          // geometry/facet.py:228-232: a facet below the clamp has area 0
+          if (want_area && (tf.flags & TF_BODY) && A2 >= 1.0e-12) area += 0.5 * A2;
           min_e2 = min_plain(min_e2, min_plain(l0, min_plain(l1, l2)));
           if (GUARD) {
             const V3 o0 = lds_row3(ox, tf.l0), o1 = lds_row3(ox, tf.l1), o2 = lds_row3(ox, tf.l2);
@@ -883,7 +892,12 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
 
   double* pout = a.partials + t.tile;
   const size_t pstride = (size_t)a.m.n_tiles;
-  if (GUARD || want_vol) {
+  if (want_area) {
+    const double vals[6] = {e_surf, vol, e_bend, min_e2, guard, area};
+    const int ops[6] = {0, 0, 0, 1, 2, 0};
+    const int slots[6] = {MS_S_ESURF, MS_S_VOL, MS_S_EBEND, MS_S_MINEDGE2, MS_S_GUARD, MS_S_AREA};
+    block_reduce_store<6>(vals, ops, slots, red, pout, pstride);
+  } else if (GUARD || want_vol) {
     const double vals[5] = {e_surf, vol, e_bend, min_e2, guard};
     const int ops[5] = {0, 0, 0, 1, 2};
     const int slots[5] = {MS_S_ESURF, MS_S_VOL, MS_S_EBEND, MS_S_MINEDGE2, MS_S_GUARD};
@@ -914,7 +928,7 @@ __global__ __launch_bounds__(TT ? TT : 512, (TT == 256 && BEND && !GUARD && ATOM
 static size_t u16_bytes(int T, int max_ent) { return 2 * ((size_t)((max_ent + 3) & ~3)); }
 
 size_t energy_lds_bytes(int T, int cap, int max_ent, bool bend, bool guard, bool flags, bool atomic) {
-  size_t d = 3 * (size_t)cap + (guard ? 3 * (size_t)cap : 0) + (bend ? (atomic ? 5 : 9) * (size_t)T : 5 * 16);
+  size_t d = 3 * (size_t)cap + (guard ? 3 * (size_t)cap : 0) + (bend ? (atomic ? 5 : 9) * (size_t)T : 6 * 16);
   return d * sizeof(double) + ((bend && !atomic) ? u16_bytes(T, max_ent) : 0) +
          ((flags || guard) ? (((size_t)cap + 15) / 16) * 16 : 0);
 }
@@ -926,6 +940,12 @@ static bool no_lean() {  // MS_NO_LEAN=1: A/B switch for the lean gradient insta
     v = (e && atoi(e) != 0) ? 1 : 0;
   }
   return v != 0;
+}
+
+template <bool BEND, bool GUARD, int TT, int CAPC, bool ATOMIC>
+__global__ __launch_bounds__(TT ? TT : 512, (TT == 256 && BEND && !GUARD && ATOMIC) ? MS_KA_SLOTS : 1) MS_WPE_ENERGY void k_energy_area(EnergyArgs a, int cap_rt, int max_ent) {
+  extern __shared__ double lds[];
+  energy_body<BEND, GUARD, TT, CAPC, ATOMIC, 0, true>(a, cap_rt, max_ent, lds, (int)blockIdx.x);
 }
 
 template <typename K>
@@ -961,6 +981,8 @@ hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_en
   // tile instead of twelve and half the LDS traffic, at the price of a summation order that
   // varies from run to run (ms_set_deterministic).  Without bending there are no vertex sums.
   const bool atomic = a.atomic != 0 && bend;
+  const bool area = (a.modules & MS_MOD_AREA_PENALTY) != 0;  // (the k_energy_area instances)
+  if (area && a.pair) return hipErrorInvalidValue;  // (multi-trial launches belong to the device-decided queue: never with it)
   // MS_KA_LDS_MIN=<bytes> (variant builds only): request at least this much LDS per workgroup (caps the workgroups per CU)
   static const size_t lds_min = variant_env("MS_KA_LDS_MIN") ? (size_t)atol(variant_env("MS_KA_LDS_MIN")) : 0;
   const size_t lds = std::max(lds_min, energy_lds_bytes(a.m.T, cap, max_ent, bend, guard, a.m.has_boundary != 0, atomic));
@@ -969,7 +991,7 @@ hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_en
     // one-workgroup interpreter: the T = 256 instances, one trial per launch (the context switched multi-trial launches
     // off); anything else runs as an ordinary launch behind what has been recorded
     if (fast && !a.pair)
-      return r->push(CK_ENERGY, 0, cap, max_ent, nb, (bend ? 1u : 0u) | (guard ? 2u : 0u) | (atomic ? 4u : 0u), lds, &a,
+      return r->push(CK_ENERGY, 0, cap, max_ent, nb, (bend ? 1u : 0u) | (guard ? 2u : 0u) | (atomic ? 4u : 0u) | (area ? 8u : 0u), lds, &a,
                      sizeof(a), &a.m);
     e = r->flush();
     if (e != hipSuccess) return e;
@@ -1009,7 +1031,28 @@ hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_en
 #undef MS_LAUNCH_P
     return hipGetLastError();
   }
-  if (bend && atomic) {
+  if (area) {
+#define MS_LAUNCH_EA(B, G, TT, CC, AT)                                                                  \
+  do {                                                                                                  \
+    e = ensure_lds(k_energy_area<B, G, TT, CC, AT>, lds);                                               \
+    if (e != hipSuccess) return e;                                                                      \
+    hipLaunchKernelGGL((k_energy_area<B, G, TT, CC, AT>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent); \
+  } while (0)
+#define MS_PICK_EA(B, G, AT)                               \
+  do {                                                     \
+    if (fast) MS_LAUNCH_EA(B, G, FAST_T, FAST_CAP, AT);    \
+    else MS_LAUNCH_EA(B, G, 0, 0, AT);                     \
+  } while (0)
+    if (bend && atomic) {
+      if (guard) MS_PICK_EA(true, true, true); else MS_PICK_EA(true, false, true);
+    } else if (bend) {
+      if (guard) MS_PICK_EA(true, true, false); else MS_PICK_EA(true, false, false);
+    } else {
+      if (guard) MS_PICK_EA(false, true, false); else MS_PICK_EA(false, false, false);
+    }
+#undef MS_PICK_EA
+#undef MS_LAUNCH_EA
+  } else if (bend && atomic) {
     if (guard) MS_PICK_E(true, true, true); else MS_PICK_E(true, false, true);
   } else if (bend) {
     if (guard) MS_PICK_E(true, true, false); else MS_PICK_E(true, false, false);
@@ -1073,7 +1116,7 @@ hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_en
 // LEAN: the instance of the headline loop -- uniform surface tension (no per-facet gamma registers) and no separate
 // previous-direction rows (dir_mode != 2, or pd = -pg after an implicit steepest-descent step): 8 registers fewer live
 // through the facet loop, which is what lets the kernel fit 128 VGPRs = 4 resident workgroups per CU instead of 3.
-template <int BENDMODE, bool VOLROW, int TT, int CAPC, bool ATOMIC, bool LEAN = false>
+template <int BENDMODE, bool VOLROW, int TT, int CAPC, bool ATOMIC, bool LEAN = false, bool AREA = false>
 __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt, int max_ent, double* lds, int block_id) {
   constexpr bool BEND = BENDMODE != 0;
   // BENDMODE 3: leaflet bending_tilt (bt_gradient.py:89-389): analytic back-propagation whose effective-area
@@ -1266,6 +1309,10 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
   const bool volpen = !LEAN && (a.modules & MS_MOD_VOLUME_PENALTY);  // (the lean instances have no penalty term)
   double pen_factor = 0.0;
   if (volpen) pen_factor = a.volume_stiffness * (ld_agent(a.scal + MS_S_VOL) - a.target_volume) / 6.0;
+  // body_area_penalty.py:136-143: factor * dA/dx with factor = k (A - A0) -- an effective tension on the body's facets
+  constexpr bool areapen = AREA && !LEAN;  // (a template flag for the reason given at energy_body; the k_gradient_area instances)
+  double pen_area = 0.0;
+  if (areapen) pen_area = a.area_stiffness * (ld_agent(a.scal + MS_S_AREA) - a.target_area);
 
   double gx = 0, gy = 0, gz = 0, cx = 0, cy = 0, cz = 0;
   if (tid >= t.n_owned) cur = end = 0;
@@ -1336,6 +1383,7 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
       double a01 = 0, a02 = 0, a11 = 0, a12 = 0;  // e-part of G0, G1 in the basis (e1, e2)
       V3 T0 = mk(0, 0, 0), T1 = mk(0, 0, 0);     // -L fK part of G0, G1
       if (surf && S >= 1.0e-12) R = -(0.5 * gam) * invS;  // g_k = gamma/2 (v_{k+1}-v_{k+2}) x nhat
+      if (areapen && (tf.flags & TF_BODY) && S >= 1.0e-12) R += -(0.5 * pen_area) * invS;
       if ((VOLROW || volpen) && (tf.flags & TF_BODY)) {
         const V3 w0 = cross(v1, v2), w1 = cross(v2, v0), w2 = cross(v0, v1);
         if (volpen) {
@@ -1681,6 +1729,12 @@ __global__ __launch_bounds__(TT ? TT : 512, LEAN ? (ATOMIC ? ((VOLROW && !MS_ROW
   gradient_body<BENDMODE, VOLROW, TT, CAPC, ATOMIC, LEAN>(a, cap_rt, max_ent, lds, (int)blockIdx.x);
 }
 
+template <int BENDMODE, bool VOLROW, int TT, int CAPC, bool ATOMIC>
+__global__ __launch_bounds__(TT ? TT : 512, 1) MS_WPE_GRADIENT void k_gradient_area(GradientArgs a, int cap_rt, int max_ent) {
+  extern __shared__ double lds[];
+  gradient_body<BENDMODE, VOLROW, TT, CAPC, ATOMIC, false, true>(a, cap_rt, max_ent, lds, (int)blockIdx.x);
+}
+
 size_t gradient_lds_bytes(int T, int cap, int max_ent, bool bend, bool volrow, bool atomic, bool leaf) {
   const size_t cols = atomic ? ((volrow && !MS_ROW_TWO_PASS) ? 6 : 3) : (volrow ? 18 : 9);
   size_t d = 3 * (size_t)cap + (bend ? 5 * (size_t)cap : 0) + (leaf ? 4 * (size_t)cap : 0) + cols * (size_t)T + 4 * 16;
@@ -1694,7 +1748,7 @@ bool gradient_lean_instance(const GradientArgs& a) {
   const bool bend = (a.modules & MS_MOD_BENDING) != 0;
   const bool leaf = bend && a.bt_vert != nullptr;
   return a.m.T == FAST_T && a.m.tile_facets32 != nullptr && !leaf && bend && a.bending_grad_mode != MS_GRAD_APPROX &&
-         !a.m.has_boundary && !(a.modules & MS_MOD_VOLUME_PENALTY) && !no_lean() && !a.m.no_fast;
+         !a.m.has_boundary && !(a.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) && !no_lean() && !a.m.no_fast;
 }
 
 hipError_t launch_gradient(const GradientArgs& a_in, int cap, int max_ent, hipStream_t s) {
@@ -1707,13 +1761,15 @@ hipError_t launch_gradient(const GradientArgs& a_in, int cap, int max_ent, hipSt
   const bool fast = a.m.T == FAST_T && a.m.tile_facets32 != nullptr && !a.m.no_fast;
   const bool atomic = a.atomic != 0;
   const bool leaf = bend && a.bt_vert != nullptr;
+  const bool area = (a.modules & MS_MOD_AREA_PENALTY) != 0;  // (the k_gradient_area instances)
   const size_t lds = gradient_lds_bytes(a.m.T, cap, max_ent, bend, volrow, atomic, leaf);
   hipError_t e;
   if (ExecRecorder* r = exec_find(s)) {
     const int mode_r = !bend ? 0 : (leaf ? 3 : (a.bending_grad_mode == MS_GRAD_APPROX ? 2 : 1));
+    if (area && mode_r == 3) return hipErrorInvalidValue;  // (no tilt-family module next to body_area_penalty: ms_set_params)
     if (fast || mode_r == 3)
       return r->push(CK_GRADIENT, 0, cap, max_ent, nb,
-                     (gradient_lean_instance(a) ? 1u : 0u) | (volrow ? 2u : 0u) | (atomic ? 4u : 0u) | ((uint32_t)mode_r << 4),
+                     (gradient_lean_instance(a) ? 1u : 0u) | (volrow ? 2u : 0u) | (atomic ? 4u : 0u) | (area ? 8u : 0u) | ((uint32_t)mode_r << 4),
                      lds, &a, sizeof(a), &a.m);
     e = r->flush();
     if (e != hipSuccess) return e;
@@ -1748,6 +1804,30 @@ hipError_t launch_gradient(const GradientArgs& a_in, int cap, int max_ent, hipSt
     else MS_LAUNCH_G(M, V, 0, 0, false);                          \
   } while (0)
   const int mode = !bend ? 0 : (leaf ? 3 : (a.bending_grad_mode == MS_GRAD_APPROX ? 2 : 1));
+  if (area) {
+    if (mode == 3) return hipErrorInvalidValue;  // (no tilt-family module next to body_area_penalty: ms_set_params)
+#define MS_LAUNCH_GA(M, V, TT, CC, AT)                                                                    \
+  do {                                                                                                    \
+    e = ensure_lds(k_gradient_area<M, V, TT, CC, AT>, lds);                                               \
+    if (e != hipSuccess) return e;                                                                        \
+    hipLaunchKernelGGL((k_gradient_area<M, V, TT, CC, AT>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent); \
+  } while (0)
+#define MS_PICK_GA(M, V)                                            \
+  do {                                                              \
+    if (fast && atomic) MS_LAUNCH_GA(M, V, FAST_T, FAST_CAP, true); \
+    else if (fast) MS_LAUNCH_GA(M, V, FAST_T, FAST_CAP, false);     \
+    else if (atomic) MS_LAUNCH_GA(M, V, 0, 0, true);                \
+    else MS_LAUNCH_GA(M, V, 0, 0, false);                           \
+  } while (0)
+    if (volrow) {
+      if (mode == 0) MS_PICK_GA(0, true); else if (mode == 1) MS_PICK_GA(1, true); else MS_PICK_GA(2, true);
+    } else {
+      if (mode == 0) MS_PICK_GA(0, false); else if (mode == 1) MS_PICK_GA(1, false); else MS_PICK_GA(2, false);
+    }
+#undef MS_PICK_GA
+#undef MS_LAUNCH_GA
+    return hipGetLastError();
+  }
   if (mode == 3) {  // leaflet bending_tilt: generic-size instances only (not a headline path)
     if (volrow) {
       if (atomic) MS_LAUNCH_G(3, true, 0, 0, true); else MS_LAUNCH_G(3, true, 0, 0, false);

@@ -112,6 +112,23 @@ class DeviceMesh:
                                    float(volume_stiffness), float(target_volume))
         self._chk(L.lib().ms_set_params(self._h, ctypes.byref(self._params)), "ms_set_params")
 
+    def set_area_penalty(self, stiffness: float, target_area: float):
+        """k and A0 of the body_area_penalty module (used while MS_MOD_AREA_PENALTY is in the module mask)."""
+        self._area_penalty = (float(stiffness), float(target_area))
+        self._chk(L.lib().ms_set_area_penalty(self._h, float(stiffness), float(target_area)), "ms_set_area_penalty")
+
+    def body_area(self) -> float:
+        """Area of the body's facets as the last energy pass folded it (MS_S_AREA)."""
+        a = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_get_body_area(self._h, ctypes.byref(a)), "ms_get_body_area")
+        return float(a.value)
+
+    def area_penalty_energy(self) -> float:
+        """1/2 k (A - A0)^2 of the last energy pass, the reference's expression (body_area_penalty.py:136-137)."""
+        k, a0 = getattr(self, "_area_penalty", (0.0, 0.0))
+        delta = self.body_area() - a0
+        return 0.5 * k * delta * delta
+
     @property
     def modules(self) -> int:
         return int(self._params.modules)

@@ -50,6 +50,7 @@ from ..geometry.mesh import mirror_for
 from ..modules.energy import leaflet_common as _lc
 from ..modules.energy._common import bending_gradient_mode, bending_model
 from ..modules.constraints import pins as _pins
+from ..modules.energy.body_area_penalty import body_area_params
 from ..modules.energy.volume import body_penalty_params
 from .steppers.base import write_back_positions
 
@@ -63,13 +64,14 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "bending_tilt_in": L.MS_MOD_BENDING_TILT_IN, "bending_tilt_out": L.MS_MOD_BENDING_TILT_OUT,
                 "tilt_disk_target_in": L.MS_MOD_TILT_DISK_TARGET_IN,
                 "tilt_disk_target_out": L.MS_MOD_TILT_DISK_TARGET_OUT,
+                "body_area_penalty": L.MS_MOD_AREA_PENALTY,
                 # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
                 # accepted in its switched-off state (strength 0, as in the caveolin decks)
                 "gaussian_curvature": 0, "rim_slope_match_out": 0}
 _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_tilt": 1, "tilt_smoothness": 3,
                 "tilt_in": 3, "tilt_out": 3, "tilt_smoothness_in": 3, "tilt_smoothness_out": 3,
                 "bending_tilt_in": 1, "bending_tilt_out": 1, "tilt_disk_target_in": 3, "tilt_disk_target_out": 3,
-                "gaussian_curvature": None, "rim_slope_match_out": None}
+                "body_area_penalty": 2, "gaussian_curvature": None, "rim_slope_match_out": None}
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
 _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
@@ -174,7 +176,11 @@ class Minimizer:
                 raise L.MembraneHipError(
                     f"energy module {name!r} is outside the HIP hot path (surface, bending, volume, tilt, "
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
-                    "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out)")
+                    "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
+                    "body_area_penalty)")
+        if "body_area_penalty" in self.energy_module_names and any(
+                _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
+            raise L.MembraneHipError("body_area_penalty together with tilt modules is outside the HIP hot path")
         self.constraint_modules = [self.constraint_manager.get_constraint(c)
                                    for c in self.constraint_module_names]
         for name in self.constraint_module_names:
@@ -225,10 +231,15 @@ class Minimizer:
         self._const_energy = {}
         disk_params = {}
         vol_mode = gp.get("volume_constraint_mode", "lagrange")
+        area_params = None
         for name in self.energy_module_names:
             if name == "volume":
                 if vol_mode == "penalty" and getattr(self.mesh, "bodies", None):
                     mods |= L.MS_MOD_VOLUME_PENALTY
+            elif name == "body_area_penalty":
+                area_params = body_area_params(self.mesh, gp, self.param_resolver)
+                if area_params is not None:  # body_area_penalty.py:114-123
+                    mods |= L.MS_MOD_AREA_PENALTY
             elif name == "tilt":
                 if float(gp.get("tilt_rigidity", 0.0) or 0.0) != 0.0:  # tilt.py:110-112
                     mods |= L.MS_MOD_TILT
@@ -331,8 +342,10 @@ class Minimizer:
             dm.set_tilt_smoothness(float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0))
         if self._pin_names:
             self._upload_pins(mir, dm, mods)
-        key = (mods, model, mode, stiffness, target, id(dm))
+        key = (mods, model, mode, stiffness, target, area_params, id(dm))
         if key != self._configured_key:
+            if area_params is not None:
+                dm.set_area_penalty(*area_params)
             dm.set_params(modules=mods,
                           bending_model=L.MS_BEND_HELFRICH if model == "helfrich" else L.MS_BEND_WILLMORE,
                           bending_grad_mode=L.MS_GRAD_ANALYTIC if mode == "analytic" else L.MS_GRAD_APPROX,
@@ -392,6 +405,14 @@ class Minimizer:
         out = {}
         for name in self.energy_module_names:
             out[name] = self._const_energy.get(name, 0.0) if _ENERGY_SLOT[name] is None else float(e[_ENERGY_SLOT[name]])
+        if "body_area_penalty" in out:  # energies[2] is volume penalty + area penalty: each module reports its own
+            area_e = dm.area_penalty_energy() if dm.modules & L.MS_MOD_AREA_PENALTY else 0.0
+            out["body_area_penalty"] = area_e
+            if "volume" in out and dm.modules & L.MS_MOD_AREA_PENALTY:
+                k, v0 = body_penalty_params(self.mesh, self.global_params, self.param_resolver) \
+                    if dm.modules & L.MS_MOD_VOLUME_PENALTY else (0.0, 0.0)
+                dv = float(dm.fetch_scalars()[L.MS_S_VOL]) - v0
+                out["volume"] = 0.5 * k * (dv * dv)
         for table in (_TILT_SCALAR, _BEND_SCALAR):
             sharing = [n for n in out if n in table]
             if len(sharing) > 1:  # they share one entry of the energy vector: split via the scalars
