@@ -329,3 +329,38 @@ def test_bench_headline_selection_between_the_two_sharded_drivers():
     assert not bench.headline_from_peer_leg(leg, 200, 30, 12400.0, pin="rccl")
     assert not bench.headline_from_peer_leg(None, 200, 30, 12400.0)
     assert not bench.headline_from_peer_leg({"note": "peer-to-peer exchange could not be set up on every rank"}, 200, 30, 1.0)
+
+
+def _cut_rows():
+    from resident_meshes import CUT_TABLE
+
+    return sorted(CUT_TABLE)
+
+
+@pytest.mark.parametrize("freq,k", _cut_rows())
+def test_cut_icosphere_sizes_at_the_resident_tile_edges(freq, k):
+    """The meshes test_gpu_resident_fullsize.py runs the resident step kernel on: the displaced icosphere without its
+    last k vertices has the vertex count the table says, is closed (k = 0) or has one clean hole, no edge with more
+    than two facets and no unused vertex; the tiling pass gives the table's tile count with every facet and corner
+    owned once."""
+    from membrane_solver_amd import _lib as L
+    from resident_meshes import CUT_TABLE, _cut_icosphere, edge_report
+
+    nv_want, tiles_want, last_rows = CUT_TABLE[(freq, k)]
+    P, T = _cut_icosphere(freq, k)
+    nv, nf = len(P), len(T)
+    assert P.dtype == np.float64 and T.dtype == np.int32 and P.flags["C_CONTIGUOUS"] and T.flags["C_CONTIGUOUS"]
+    assert nv == nv_want == 10 * freq * freq + 2 - k
+    assert tiles_want == (nv + 255) // 256 and last_rows == nv - 256 * (tiles_want - 1)
+    assert T.min() == 0 and T.max() == nv - 1
+    loops, max_facets_per_edge, isolated = edge_report(nv, T)
+    assert loops == (1 if k else 0)
+    assert max_facets_per_edge == 2
+    assert isolated == 0
+    st = (ctypes.c_int64 * 8)()
+    perm = np.empty(nv, np.int32)
+    assert L.lib().ms_plan_tiling(nv, nf, P.ctypes.data_as(L._D), T.ctypes.data_as(L._I32), 256, 1, st,
+                                  perm.ctypes.data_as(L._I32)) == 0
+    assert st[0] == tiles_want
+    assert st[4] == 0 and st[5] == nf and st[6] == 3 * nf
+    assert np.array_equal(np.sort(perm), np.arange(nv))
