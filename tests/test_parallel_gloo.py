@@ -15,13 +15,16 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TESTS = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from shard_cases import NEW_CASES, TILT_BITS, clamped_steps, lane_report, materialize, run_port  # noqa: E402
 
 
 class OracleShardBackend:
     def __init__(self, P, T, *, rank, world, dist, modules, kappa, c0, gamma, target_volume=0.0,
-                 volume_stiffness=0.0, fixed=None):
+                 volume_stiffness=0.0, fixed=None, is_boundary=None, body_rows=None):
         import torch
 
         from membrane_solver_amd import _lib as L
@@ -36,7 +39,8 @@ class OracleShardBackend:
         self.modules, self.target_volume, self.volume_stiffness = modules, target_volume, volume_stiffness
         self.kappa, self.c0, self.gamma = kappa, c0, gamma
         self.fixed = np.zeros(self.nv, bool) if fixed is None else fixed
-        self.isb = np.zeros(self.nv, bool)
+        self.isb = np.zeros(self.nv, bool) if is_boundary is None else np.asarray(is_boundary, bool)
+        self.body_rows = None if body_rows is None else np.asarray(body_rows, np.int32)  # facets of the volume
         z = lambda n: torch.zeros((self.nvp, n), dtype=torch.float64)  # noqa: E731
         self.buf = {L.MS_BUF_X: z(3), L.MS_BUF_XT: z(3), L.MS_BUF_G: z(3), L.MS_BUF_GC: z(3),
                     L.MS_BUF_D: z(3), L.MS_BUF_PG: z(3), L.MS_BUF_PD: z(3), L.MS_BUF_FK: z(3),
@@ -44,6 +48,7 @@ class OracleShardBackend:
         self.buf[L.MS_BUF_X][: self.nv] = torch.from_numpy(P)
         self.scal = np.zeros(L.MS_NSCAL)
         self.own_facets = np.flatnonzero((self.tri[:, 0] >= self.r0) & (self.tri[:, 0] < self.r1))
+        self.own_body = self.own_facets if body_rows is None else np.intersect1d(self.own_facets, self.body_rows)
 
     def _np(self, b):
         return self.buf[b].numpy()[: self.nv]
@@ -69,7 +74,7 @@ class OracleShardBackend:
         tri_own = self.tri[self.own_facets]
         s = self.scal
         s[L.MS_S_ESURF] = orc.surface_energy_and_gradient(X, tri_own, self.gamma[self.own_facets], None)
-        s[L.MS_S_VOL] = orc.volume(X, tri_own)
+        s[L.MS_S_VOL] = orc.volume(X, self.tri[self.own_body])
         s[L.MS_S_MINEDGE2] = mp.min_edge_length(X, tri_own) ** 2 if len(tri_own) else 1e300
         s[L.MS_S_GUARD] = 0.0
         if guard and use_direction and len(tri_own):
@@ -100,13 +105,14 @@ class OracleShardBackend:
             orc.bending_backprop(x, self.tri, self.isb, np.ascontiguousarray(fA[:, 0]),
                                  np.ascontiguousarray(fA[:, 1]), fK, g)
         if self.modules & L.MS_MOD_VOLUME_PENALTY:
-            orc.volume_gradient(x, self.tri, g, factor=self.volume_stiffness * (self.scal[L.MS_S_VOL] - self.target_volume))
+            orc.volume_gradient(x, self.tri, g, body_rows=self.body_rows,
+                                factor=self.volume_stiffness * (self.scal[L.MS_S_VOL] - self.target_volume))
         self._np(L.MS_BUF_G)[...] = g
         self._poison(L.MS_BUF_G)
         self.scal[L.MS_S_GGC] = self.scal[L.MS_S_GCGC] = 0.0
         if self.modules & L.MS_CON_VOLUME:
             gC = np.zeros_like(x)
-            orc.volume_gradient(x, self.tri, gC)
+            orc.volume_gradient(x, self.tri, gC, body_rows=self.body_rows)
             self._np(L.MS_BUF_GC)[...] = gC
             self._poison(L.MS_BUF_GC)
             sl = slice(self.r0, self.r1)
@@ -181,6 +187,10 @@ def _worker(rank, world, port, case, q):
         os.environ["MASTER_ADDR"] = "127.0.0.1"
         os.environ["MASTER_PORT"] = str(port)
         dist.init_process_group("gloo", rank=rank, world_size=world)
+        if case.startswith("table:"):
+            q.put((rank,) + _table_case(case[6:], rank, world, dist))
+            dist.destroy_process_group()
+            return
         case, level = case.split(":")
         P, T = meshgen.icosphere(5)
         P = meshgen.smooth_displace(P, 0.08)
@@ -235,6 +245,41 @@ def _worker(rank, world, port, case, q):
         q.put((rank, False, traceback.format_exc()))
 
 
+def _table_case(case_id, rank, world, dist):
+    """A case of tests/shard_cases.py: ShardedStepper on the stand-in backend (arrays passed through, no physics
+    added) against oracle.minimizer_port -- flags, step sizes, energies and positions as above, and the trials and
+    guard rejections of every step.  -> (ok, message)"""
+    if TESTS not in sys.path:
+        sys.path.insert(0, TESTS)
+    import shard_cases as sc
+
+    from membrane_solver_amd import _lib as L
+    from membrane_solver_amd.parallel import ShardedStepper
+
+    case = sc.BY_ID[case_id]
+    a = sc.materialize(case)
+    be = OracleShardBackend(a.P, a.T, rank=rank, world=world, dist=dist, modules=case.modules, kappa=a.kappa, c0=a.c0,
+                            gamma=a.gamma, target_volume=a.V0, volume_stiffness=case.stiffness, fixed=a.fixed,
+                            is_boundary=a.boundary, body_rows=a.body_rows)
+    drv = ShardedStepper(be, stepper=case.stepper, reuse_energy0=case.level, **case.params)
+    step, log, counts = case.step0, [], []
+    for _ in range(case.n_steps):
+        r = drv.step(step, tol=1e-9)
+        log.append((float(r.success), r.next_step, r.energy))
+        counts.append((int(r.trials), int(r.guard_rejects)))
+        step = r.next_step
+        if not r.success:
+            drv.reset()
+    x_final = be._np(L.MS_BUF_X).copy()
+    port = sc.run_port(case, a)
+    got, want = np.array(log), port.log
+    ok = (np.array_equal(got[:, 0], want[:, 0]) and np.allclose(got[:, 1], want[:, 1], rtol=1e-12)
+          and np.allclose(got[:, 2], want[:, 2], rtol=1e-10) and np.max(np.abs(x_final - port.x)) < 1e-9
+          and got[:, 0].sum() >= 2 and counts == list(zip(port.trials, port.guards)))
+    return bool(ok), "" if ok else repr((got.tolist(), want.tolist(), counts, port.trials, port.guards,
+                                         float(np.max(np.abs(x_final - port.x)))))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -246,12 +291,23 @@ def _free_port():
 @pytest.mark.parametrize("case", ["cg_bending_volume:0", "cg_bending_volume:2", "gd_surface_penalty:0",
                                   "gd_surface_penalty:2", "cg_bending:2"])
 def test_sharded_driver_world2_matches_single_process(case):
+    _run_ranks(case, 2)
+
+
+@pytest.mark.parametrize("case_id", [c.id for c in NEW_CASES])
+def test_sharded_driver_runs_the_shared_cases(case_id):
+    """The cases of tests/shard_cases.py at their own world size: this pins the Python driver's guard, edge_fraction,
+    GD, penalty, reuse-level-1 and open-surface lanes without a device."""
+    _run_ranks("table:" + case_id, {c.id: c.world for c in NEW_CASES}[case_id])
+
+
+def _run_ranks(case, world):
     import torch.multiprocessing as tmp
 
     ctx = tmp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, case, q)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, case, q)) for r in range(world)]
     for p in procs:
         p.start()
     results = [q.get(timeout=240) for _ in procs]
@@ -272,3 +328,39 @@ def test_fold_scalars_is_rank_ordered():
     a[:, L.MS_S_MAXD2] = [4.0, 1.0, 7.0]
     f = fold_scalars(a)
     assert f[L.MS_S_ESURF] == 6.0 and f[L.MS_S_MINEDGE2] == 2.0 and f[L.MS_S_GUARD] == 1.0 and f[L.MS_S_MAXD2] == 7.0
+
+
+@pytest.mark.parametrize("case", NEW_CASES, ids=[c.id for c in NEW_CASES])
+def test_port_anchor_takes_its_lane(case):
+    """oracle.minimizer_port alone on every shared case (the anchor of test_gpu_sharded.py, no device): the run takes
+    the lane the case is in the table for, and its counts are the ones the table's note records."""
+    a = materialize(case)
+    port = run_port(case, a)
+    ok = port.log[:, 0]
+    print(case.id, "accepted", int(ok.sum()), "trials", port.trials, "guards", port.guards)
+    assert not lane_report(case, ok, port.trials, port.guards, port.alpha, port.step_in)
+    if case.penalty:
+        e_pen = 0.5 * case.stiffness * (a.V_start - a.V0) ** 2
+        assert abs(a.V_start - a.V0) > 1e-3 * abs(a.V0) and e_pen > 0.0
+    if case.id == "row_gd_guard":
+        assert sum(port.guards) == 3 and port.guards[1] == 3
+    if case.id.startswith("open_cg"):
+        assert ok.astype(int).tolist() == [0, 0, 0, 1, 0, 1, 0, 1, 0] and port.trials == [2, 3, 4, 5, 0, 4, 0, 2, 0]
+        assert int(a.boundary.sum()) == 240 and a.P.shape[0] == 4921 and a.T.shape[0] == 9600
+    if case.id == "open_gd_nonuniform":
+        assert int(ok.sum()) == 6
+    if case.id == "edge_fraction":
+        assert 0 in clamped_steps(ok, port.trials, port.guards, port.alpha, port.step_in)
+
+
+def test_shard_backend_refuses_every_tilt_bit():
+    """HipShardBackend.configure names what is not sharded before it touches its context (the body_area_penalty bit:
+    test_area_host.py)."""
+    import types
+
+    from membrane_solver_amd import _lib as L
+    from membrane_solver_amd.parallel import HipShardBackend
+
+    for bit in TILT_BITS(L):
+        with pytest.raises(L.MembraneHipError, match="only surface / bending / volume are sharded"):
+            HipShardBackend.configure(types.SimpleNamespace(), modules=L.MS_MOD_SURFACE | bit)
