@@ -201,7 +201,7 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
   c->params.bending_grad_mode = MS_GRAD_ANALYTIC;
   c->params.volume_stiffness = 1000.0;
   c->params.target_volume = 0.0;
-  c->last_g = c->buf[MS_BUF_G];
+  c->carry.last_g = c->buf[MS_BUF_G];
   // A mesh of ONE tile: every kernel is one workgroup and a step is launches and host round trips -- record the launches
   // and run them pack by pack in one workgroup (k_exec).  MS_EXEC=0 keeps the launch-per-kernel path (A/B, tests).
   c->exec_wanted = t.n_tiles == 1 && t.T == 256 && t.own == 256 && shard_count == 1 &&
@@ -360,7 +360,7 @@ int ms_set_surface_tension(ms_ctx* c, const double* gamma) {
   for (int f = 1; f < t.nf && c->gamma_uniform; ++f) c->gamma_uniform = gamma[f] == c->gamma_const;
   if (!g.empty())
     HIPCHK(c, hipMemcpy(c->d_tf_gamma, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   return MS_OK;
 }
@@ -380,8 +380,8 @@ int ms_set_bending_params(ms_ctx* c, const double* kappa, const double* c0) {
   }
   HIPCHK(c, hipMemcpy(c->d_kappa, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_c0, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->factors_valid = false;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.factors_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   return MS_OK;
 }
@@ -408,8 +408,8 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
     HIPCHK(c, hipMemset(c->d_bt_vert, 0, bytes));
   }
   c->params = *p;
-  c->factors_valid = false;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.factors_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   return MS_OK;
 }
@@ -420,7 +420,7 @@ int ms_set_area_penalty(ms_ctx* c, double stiffness, double target_area) {
     return fail(c, MS_ERR_INVALID, "ms_set_area_penalty: stiffness and target area must be finite");
   c->area_stiffness = stiffness;
   c->target_area = target_area;
-  c->carry_valid = c->grad_valid = c->maxg2_valid = false;  // (the energies and the gradient held are the old term's)
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies and the gradient held are the old term's)
   c->sh_carry_valid = c->sh_grad_valid = false;
   return MS_OK;
 }
@@ -447,7 +447,7 @@ int ms_set_tilts(ms_ctx* c, const double* tilts, double tilt_rigidity) {
     HIPCHK(c, hipMemset(c->tf[0].grad, 0, bytes));
   }
   c->tf[0].k_tilt = tilt_rigidity;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   return ext_to_patch(c, tilts, c->tf[0].tilts, 3);
 }
@@ -560,15 +560,15 @@ int ms_set_deterministic(ms_ctx* c, int on) {
   if (!c) return MS_ERR_INVALID;
   if (c->deterministic == (on != 0)) return MS_OK;
   c->deterministic = on != 0;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
-  c->factors_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.factors_valid = false;
   return MS_OK;
 }
 
 int ms_set_tilt_smoothness(ms_ctx* c, double k_smooth) {
   if (!c) return MS_ERR_INVALID;
   c->tf[0].k_smooth = k_smooth;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   return MS_OK;
 }
 

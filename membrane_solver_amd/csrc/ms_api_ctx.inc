@@ -1,4 +1,58 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit): the context: everything a ms_ctx holds.
+// What describes the launch or fold being queued: the launchers (phase_energy, phase_gradient, phase_direction,
+// reduce_slots) read it through ms_ctx::stage(); only a StageScope changes it.  Default: an ungated single-trial launch,
+// parity 0, nothing deferred.
+struct StageCtl {
+  const uint32_t* cur_gate = nullptr;  // decision word the launches being queued test (nullptr: unconditional)
+  uint32_t cur_gate_want = 0;
+  bool cur_gate_fold_only = false;        // the gate (and the ran check) belongs to the fold, not to the energy kernel
+  bool cur_check_ran = false;          // the tile kernel in front of the fold being queued is gated by cur_gate
+  uint32_t* cur_dec = nullptr;         // the fold being queued closes a stage: its decision goes here
+  double cur_rhs[MS_MAX_TRIALS] = {0}; // ... taken against these Armijo right-hand sides (trial order)
+  const double* cur_rhs_dev = nullptr; // the fold being queued takes its right-hand sides from the device
+  uint32_t cur_extra_mask = 0;            // reduce_slots: fold these slots of the ordinary partials as well
+  int cur_go_kind = 0;                    // ... and take the GO decision first (FoldArgs::go_kind and its parameters)
+  uint32_t* cur_go = nullptr;          // the direction fold being queued may open the next round: its GO word
+  double cur_go_val[6] = {0};             // tol^2 (1+1e-9), guard bound, energy0, c, alpha_0, beta
+  int cur_parity = 0;            // which of a side set's two mailboxes the early trials of a multi-trial fold post to
+  int pair_on = 0;               // phase_energy / reduce_slots: the launch being queued evaluates this many trials
+  // the early trials of a multi-trial launch (the ones expected to fail) are evaluated for their energies only:
+  // no trial positions, no bending factors written for them (ms_step; the sharded driver needs the factor rows)
+  bool pair_lean = false;
+  double pair_alpha[MS_MAX_TRIALS] = {0};  // alphas of the early trials
+  double* pair_scal2 = nullptr;    // where a pair launch's second fold goes (nullptr: d_scal2)
+  bool multi_any_slot = false;   // reduce_slots: a multi-trial fold of ANY slot mask (the tilt search pass), not only the core energies
+  bool defer_dir = false;                 // reduce_slots: do not launch a direction fold, remember its mask
+  // phase_energy at x right behind an evaluation of the same x (ms_step's energy0 with tilt modules: only the tilts were
+  // re-projected in between): the shape kernels are not launched again -- their energies are in the mailbox, the
+  // bending_tilt records in place -- only the tilt modules' passes run and only their slots are folded
+  bool energy_tilt_only = false;
+  bool proj_at_x_in_normals = false;  // phase_energy: the normals launch also projects the leaflets' stored tilts onto x in place (ms_step)
+};
+// What the step logic carries from one evaluation to the next.  "Queue something in the state a later step will be in"
+// copies it out, changes it, queues, and copies it back whole.
+struct CarryState {
+  // steepest-descent restart on an unchanged gradient (ms_step): the direction is -G and is not written out;
+  // trial passes then read G with -alpha (bitwise the same x + alpha d).  After such a step is accepted the
+  // CG history's previous direction is -PG, which the next fused direction pass derives instead of loading.
+  bool dir_implicit = false;
+  bool pd_neg_pg = false;
+  bool kc_pending = false;       // the gradient pass queued behind a round ran for the accepted x: the next ms_step takes its result
+  int kc_parity = 0;
+  bool bt_valid = false;          // d_bt_vert describes the current x
+  double* last_g = nullptr;   // buffer holding the most recent finalized gradient
+  bool cg_have_history = false;
+  int cg_iter_count = 0;
+  bool factors_valid = false;
+  // true while the mailbox energies / min edge / volume AND the factor buffers describe the
+  // current x: set when ms_step accepts a trial that also wrote the factors, cleared by
+  // every other energy pass and by every mutator
+  bool carry_valid = false;
+  // true while buffer G holds the finalized gradient of the current x (set by ms_step's fused
+  // gradient pass, survives a failed line search, cleared together with carry_valid)
+  bool grad_valid = false;
+  bool maxg2_valid = false;  // the mailbox holds |g|^2 and max|g_i|^2 of the gradient in buffer G
+};
 struct ms_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -60,11 +114,7 @@ struct ms_ctx {
     bool any_free = true;      // some row of this field is not clamped (kept current by the flag setters)
     double* va = nullptr;      // relaxation: barycentric vertex areas of the frozen positions
   } tf[3];
-  // steepest-descent restart on an unchanged gradient (ms_step): the direction is -G and is not written out;
-  // trial passes then read G with -alpha (bitwise the same x + alpha d).  After such a step is accepted the
-  // CG history's previous direction is -PG, which the next fused direction pass derives instead of loading.
-  bool dir_implicit = false;
-  bool pd_neg_pg = false;
+  CarryState carry;
   bool precond = false;      // ms_stepper_params.precondition of the step in progress (CG only)
   // speculative line-search ladder (ms_step): when the last accepted step needed n > 1 Armijo trials, the next
   // n trials are queued at once; stage k > 0 runs only if the device-side Armijo test of stage k-1 failed
@@ -80,9 +130,7 @@ struct ms_ctx {
                                  // before it has not been read yet -- see Ahead)
   Mailbox first_mb[2];           // mailbox of a round's first launch
   Mailbox grad_mb[2];            // mailbox of the gradient pass queued behind a round
-  bool kc_pending = false;       // that pass ran for the accepted x: the next ms_step takes its result
-  int kc_parity = 0;
-  int next_parity = 0, cur_parity = 0;
+  int next_parity = 0;
   // a round queued for a step that has not started yet (queue_ahead)
   struct RoundPlanT {
     int n0 = 1, n_st = 0;
@@ -100,20 +148,13 @@ struct ms_ctx {
   int steps_left = 0;            // ... steps that follow the current one in this ms_minimize call
   bool ahead_allowed = false;    // set by ms_minimize: the caller is the library's own loop (nothing else touches the
                                  // context between two steps), and another step follows
-  // The direction fold of a round's gradient pass can be left out when the round is queued (defer_dir) and merged
+  // The direction fold of a round's gradient pass can be left out when the round is queued (StageCtl::defer_dir) and merged
   // into the first fold of the round after it: that round's energy launch then starts right behind the gradient pass
-  bool defer_dir = false;                 // reduce_slots: do not launch a direction fold, remember its mask
-  uint32_t dir_deferred_mask = 0;
+  uint32_t dir_deferred_mask = 0;         // reduce_slots' answer: the mask of the fold it left out
   bool dir_pending[2] = {false, false};   // the round's gradient pass has run (if its gate was open) without its fold
   uint32_t dir_mask[2] = {0, 0};
   uint32_t* kc_gate[2] = {nullptr, nullptr};  // decision word that pass was gated on
-  uint32_t cur_extra_mask = 0;            // reduce_slots: fold these slots of the ordinary partials as well
-  int cur_go_kind = 0;                    // ... and take the GO decision first (FoldArgs::go_kind and its parameters)
-  double cur_go_val[6] = {0};             // tol^2 (1+1e-9), guard bound, energy0, c, alpha_0, beta
-  bool cur_gate_fold_only = false;        // the gate (and the ran check) belongs to the fold, not to the energy kernel
   bool last_hist_descent = false;         // the last direction with CG history was a descent direction
-  uint32_t* cur_go = nullptr;          // the direction fold being queued may open the next round: its GO word
-  const double* cur_rhs_dev = nullptr; // the fold being queued takes its right-hand sides from the device
   long q_ahead = 0, q_adopted = 0, q_dropped = 0;
   int kc_stepper = 0;
   bool kc_use_history = false;
@@ -122,11 +163,6 @@ struct ms_ctx {
   // round being queued; the stream orders a record's readers between its writers.
   uint32_t* d_dec = nullptr;
   static constexpr int N_DEC = 16;
-  const uint32_t* cur_gate = nullptr;  // decision word the launches being queued test (nullptr: unconditional)
-  uint32_t cur_gate_want = 0;
-  uint32_t* cur_dec = nullptr;         // the fold being queued closes a stage: its decision goes here
-  double cur_rhs[MS_MAX_TRIALS] = {0}; // ... taken against these Armijo right-hand sides (trial order)
-  bool cur_check_ran = false;          // the tile kernel in front of the fold being queued is gated by cur_gate
   unsigned long long* h_err = nullptr; // pinned word a fold sets when a gated launch ran on part of its workgroups
   unsigned long long* d_h_err = nullptr;
   long queue_mismatches = 0;           // host and device decisions that differed (every one is also a hard error)
@@ -138,13 +174,7 @@ struct ms_ctx {
   bool escalate = true;          // MS_ESCALATE=0: a search that keeps rejecting stays with what the history suggests
   int pair_force = 0;            // MS_PAIR=2 / 3: pair (/ pair + a gated third trial) whenever possible, whatever
                                  // the history predicts (tests)
-  // phase_energy at x right behind an evaluation of the same x (ms_step's energy0 with tilt modules: only the tilts were
-  // re-projected in between): the shape kernels are not launched again -- their energies are in the mailbox, the
-  // bending_tilt records in place -- only the tilt modules' passes run and only their slots are folded
-  bool energy_tilt_only = false;
-  bool proj_at_x_in_normals = false;  // phase_energy: the normals launch also projects the leaflets' stored tilts onto x in place (ms_step)
   bool lbt_normals_current = false;  // phase_energy (leaflet bending_tilt): d_tn already holds the unit vertex normals of x
-  bool multi_any_slot = false;   // reduce_slots: a multi-trial fold of ANY slot mask (the tilt search pass), not only the core energies
   // tilt relaxations: the search pass (ms_tsearch.inc; MS_TSEARCH=0: one launch per module, field and trial)
   bool tenergy_enable = true;    // the tilt modules' energy-only evaluations as one launch (every context; MS_TSEARCH=0 off)
   bool tsearch_enable = true;
@@ -152,13 +182,8 @@ struct ms_ctx {
   int64_t tsearch_launches = 0, tsearch_trials = 0;
   bool tsearch_all_failed = false;   // the last search rejected its whole ladder: both of its passes are queued at once
   Mailbox tsearch_mb;                // the last trial's mailbox of the second pass queued that way
-  int pair_on = 0;               // phase_energy / reduce_slots: the launch being queued evaluates this many trials
-  // the early trials of a multi-trial launch (the ones expected to fail) are evaluated for their energies only:
-  // no trial positions, no bending factors written for them (ms_step; the sharded driver needs the factor rows)
   bool no_fast = false;          // MS_NO_FAST=1 (variant builds only)
-  bool pair_lean = false;
   bool pair_lean_enable = true;  // MS_PAIR_LEAN=0: write the first two early trials' outputs (copied back if one is accepted)
-  double pair_alpha[MS_MAX_TRIALS] = {0};  // alphas of the early trials
   static constexpr int N_SIDE = MS_MAX_TRIALS - 1;
   struct SideSet {
     double* partials = nullptr;
@@ -192,7 +217,6 @@ struct ms_ctx {
                                   // tilt_leaflet.py:101-150) instead of the relaxation's vertex-area form
   int factors_leaflet = 0;  // which leaflet's back-prop factors fK/fA hold (1 in, 2 out; 0: not a leaflet's)
   double* d_bt_vert = nullptr;    // (nvp,4) bending_tilt per-vertex record of the last energy pass
-  bool bt_valid = false;          // d_bt_vert describes the current x
   // tilt relaxation work space (positions frozen): unit vertex normals, CG direction, Jacobi M^-1
   double* d_tn = nullptr;
   std::vector<uint8_t> h_vflags;  // host copy of the vertex flag bytes (patch order)
@@ -211,15 +235,8 @@ struct ms_ctx {
   unsigned long long expected[MS_MB_WORDS] = {0};  // latest ticket that folds each slot (+ the decision entry)
   bool has_boundary = false;
   double* d_stage = nullptr;  // nv*3 staging in external row order
-  double* last_g = nullptr;   // buffer holding the most recent finalized gradient
   ms_params params{};
   double area_stiffness = 0.0, target_area = 0.0;  // ms_set_area_penalty (MS_MOD_AREA_PENALTY)
-  bool cg_have_history = false;
-  int cg_iter_count = 0;
-  bool factors_valid = false;
-  // true while the mailbox energies / min edge / volume AND the factor buffers describe the
-  // current x: set when ms_step accepts a trial that also wrote the factors, cleared by
-  // every other energy pass and by every mutator
   // shard boundary exchange: rows each rank owns that other ranks' tiles read as halo
   std::vector<int32_t> bnd_off;  // shard_count + 1
   int32_t* d_bnd_rows = nullptr;
@@ -295,16 +312,10 @@ struct ms_ctx {
   void* peer_barrier_user = nullptr;
   double sh_scal[MS_NSCAL] = {0};  // rank-ordered fold of the last exchanges
   double sh_scal2[MS_NSCAL] = {0}; // ... of a pair launch's other trial (header slots SH_ALT + slot)
-  double* pair_scal2 = nullptr;    // where a pair launch's second fold goes (nullptr: d_scal2)
   bool sh_carry_valid = false, sh_grad_valid = false;
   bool sh_maxg2_valid = false;  // the last direction exchange also carried the gradient rows and max|g_i|^2
   long sh_exchanges = 0;
-  bool carry_valid = false;
-  // true while buffer G holds the finalized gradient of the current x (set by ms_step's fused
-  // gradient pass, survives a failed line search, cleared together with carry_valid)
   bool deterministic = false;  // ms_set_deterministic: staged CSR gather instead of LDS atomics
-  bool grad_valid = false;
-  bool maxg2_valid = false;  // the mailbox holds |g|^2 and max|g_i|^2 of the gradient in buffer G
   // optional per-kernel timing (ms_profile_*)
   bool profiling = false;
   struct ProfRec {
@@ -349,4 +360,16 @@ struct ms_ctx {
   PinGradArgs pin_grad{};
   int pin_lane = -1;
   long pin_enforce_launches = 0, pin_grad_launches = 0, pin_trials = 0;
+  const StageCtl& stage() const { return stage_; }
+ private:
+  friend struct StageScope;
+  StageCtl stage_;  // (written by StageScope alone)
+};
+// installs a stage record for the launches queued in its scope; puts back the one that was there before
+struct StageScope {
+  ms_ctx* c;
+  const StageCtl prev;
+  StageScope(ms_ctx* ctx, const StageCtl& st) : c(ctx), prev(ctx->stage_) { c->stage_ = st; }
+  ~StageScope() { c->stage_ = prev; }
+  StageScope(const StageScope&) = delete;
 };

@@ -12,7 +12,7 @@ int ms_rebind_state(ms_ctx* c, void* device_base, size_t bytes) {
   HIPCHK(c, hipMemcpy(device_base, c->state, need, hipMemcpyDeviceToDevice));
   double* nb = static_cast<double*>(device_base);
   for (int b = 0; b <= MS_BUF_FA; ++b) c->buf[b] = nb + (c->buf[b] - c->state);
-  c->last_g = nb + (c->last_g - c->state);
+  c->carry.last_g = nb + (c->carry.last_g - c->state);
   if (c->own_state) HIPCHK(c, hipFree(c->state));
   c->state = nb;
   c->own_state = false;
@@ -30,7 +30,7 @@ int ms_fetch_scalars(ms_ctx* c, double* out) {
 int ms_store_scalars(ms_ctx* c, const double* in) {
   if (!c || !in) return MS_ERR_INVALID;
   for (int sl = 0; sl < MS_NSCAL; ++sl) put_mailbox(c, sl, in[sl]);
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   HIPCHK(c, hipMemcpyAsync(c->d_scal, c->h_scal, sizeof(double) * MS_NSCAL, hipMemcpyHostToDevice,
                            S(c)));

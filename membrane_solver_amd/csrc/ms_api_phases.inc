@@ -34,8 +34,8 @@ inline int zero_doubles(ms_ctx* c, double* p, size_t bytes) {
   return MS_ERR_HIP;
 }
 
-inline const double* trial_dir(const ms_ctx* c) { return c->dir_implicit ? c->buf[MS_BUF_G] : c->buf[MS_BUF_D]; }
-inline double trial_alpha(const ms_ctx* c, double alpha) { return c->dir_implicit ? -alpha : alpha; }
+inline const double* trial_dir(const ms_ctx* c) { return c->carry.dir_implicit ? c->buf[MS_BUF_G] : c->buf[MS_BUF_D]; }
+inline double trial_alpha(const ms_ctx* c, double alpha) { return c->carry.dir_implicit ? -alpha : alpha; }
 
 int fail(ms_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
@@ -417,28 +417,29 @@ int ensure_side_sets(ms_ctx* c, int n_side) {
 }
 
 int reduce_slots(ms_ctx* c, uint32_t mask) {
-  if (c->defer_dir && (mask & (1u << MS_S_GDOTD)) && c->cur_dec == nullptr) {
+  const StageCtl& st = c->stage();
+  if (st.defer_dir && (mask & (1u << MS_S_GDOTD)) && st.cur_dec == nullptr) {
     c->dir_deferred_mask = mask;  // (queue_round: the fold of the round after this one takes these slots along)
     return MS_OK;
   }
-  mask |= c->cur_extra_mask;
-  ProfScope ps(c, 3, c->cur_gate, c->cur_gate_want);
+  mask |= st.cur_extra_mask;
+  ProfScope ps(c, 3, st.cur_gate, st.cur_gate_want);
   ++c->ticket;
   if (trace_queue())
     fprintf(stderr, "[msq] fold ticket %llu mask %#x -> %s gate %p want %u dec %p trials %d\n",
-            (unsigned long long)(c->ticket), mask, box_name(c, c->h_seq), (const void*)c->cur_gate, c->cur_gate_want,
-            (const void*)c->cur_dec, (int)c->pair_on);
+            (unsigned long long)(c->ticket), mask, box_name(c, c->h_seq), (const void*)st.cur_gate, st.cur_gate_want,
+            (const void*)st.cur_dec, (int)st.pair_on);
   // a multi-trial launch has no tilt module: only the core slots carry anything (and the sharded driver parks the other
   // trial's fold in the tilt slots of the device scalars, which the full mask would overwrite)
-  const int n_multi = c->pair_on > 1 ? c->pair_on : 1;
-  if (n_multi > 1 && !c->multi_any_slot) {
+  const int n_multi = st.pair_on > 1 ? st.pair_on : 1;
+  if (n_multi > 1 && !st.multi_any_slot) {
     const uint32_t core = (1u << MS_S_ESURF) | (1u << MS_S_VOL) | (1u << MS_S_EBEND) | (1u << MS_S_MINEDGE2) |
-                          (1u << MS_S_GUARD) | c->cur_extra_mask;
+                          (1u << MS_S_GUARD) | st.cur_extra_mask;
     // (nobody is to wait for the dropped slots: an older, gated-out launch may have left a ticket there)
     for (int sl = 0; sl < MS_NSCAL; ++sl)
       if (mask & ~core & (1u << sl)) {
         c->expected[sl] = 0;
-        for (int k = 0; k + 1 < n_multi; ++k) c->side[k].mb[c->cur_parity].expected[sl] = 0;
+        for (int k = 0; k + 1 < n_multi; ++k) c->side[k].mb[st.cur_parity].expected[sl] = 0;
       }
     mask &= core;
   }
@@ -450,41 +451,41 @@ int reduce_slots(ms_ctx* c, uint32_t mask) {
   f.slot_mask = mask;
   f.ticket = c->ticket;
   f.n_sets = n_multi;
-  f.gate = c->cur_gate;
-  f.gate_want = c->cur_gate_want;
-  f.check_ran = (c->cur_gate != nullptr && c->cur_check_ran) ? 1 : 0;
-  f.dec_out = c->cur_dec;
+  f.gate = st.cur_gate;
+  f.gate_want = st.cur_gate_want;
+  f.check_ran = (st.cur_gate != nullptr && st.cur_check_ran) ? 1 : 0;
+  f.dec_out = st.cur_dec;
   f.counter = c->d_dec ? c->d_dec + (size_t)MS_DEC_STRIDE * (ms_ctx::N_DEC - 1) : nullptr;  // (the last record's line)
   f.e_mask = armijo_slots(c);
   f.host_err = c->d_h_err;
-  for (int j = 0; j < MS_MAX_TRIALS; ++j) f.rhs[j] = c->cur_rhs[j];
+  for (int j = 0; j < MS_MAX_TRIALS; ++j) f.rhs[j] = st.cur_rhs[j];
   // an energy-only early trial needs nothing but its energy slots (the head workgroup folds those); an early trial
   // with outputs of its own (MS_PAIR_LEAN=0, the sharded pair) can be accepted as it is and needs every slot
-  f.side_full = (n_multi > 1 && (!c->pair_lean || !f.dec_out)) ? 1 : 0;
+  f.side_full = (n_multi > 1 && (!st.pair_lean || !f.dec_out)) ? 1 : 0;
   for (int j = 0; j + 1 < n_multi; ++j) {
     ms_ctx::SideSet& sd = c->side[j];
     f.set[j].partials = sd.partials;
-    f.set[j].scal = (j == 0 && c->pair_scal2) ? c->pair_scal2 : sd.scal;
-    f.set[j].host_box = sd.mb[c->cur_parity].d_h_seq;
+    f.set[j].scal = (j == 0 && st.pair_scal2) ? st.pair_scal2 : sd.scal;
+    f.set[j].host_box = sd.mb[st.cur_parity].d_h_seq;
     const uint32_t posted = (f.side_full || !f.dec_out) ? mask : (mask & f.e_mask);
     for (int sl = 0; sl < MS_NSCAL; ++sl)
-      if (posted & (1u << sl)) sd.mb[c->cur_parity].expected[sl] = c->ticket;
+      if (posted & (1u << sl)) sd.mb[st.cur_parity].expected[sl] = c->ticket;
   }
   f.set[n_multi - 1].partials = c->d_partials;
   f.set[n_multi - 1].scal = c->d_scal;
   f.set[n_multi - 1].host_box = c->d_h_seq;
   for (int sl = 0; sl < MS_NSCAL; ++sl)
     if (mask & (1u << sl)) c->expected[sl] = c->ticket;
-  f.rhs_dev = c->cur_rhs_dev;
-  if (c->cur_go_kind && f.dec_out && (mask & (1u << MS_S_GDOTD))) {  // merged: direction scalars + GO + Armijo decision
-    f.go_out = c->cur_go;
-    f.go_kind = c->cur_go_kind;
-    f.go_tol2 = c->cur_go_val[0];
-    f.go_lim = c->cur_go_val[1];
-    f.go_e0 = c->cur_go_val[2];
-    f.go_c = c->cur_go_val[3];
-    f.go_alpha0 = c->cur_go_val[4];
-    f.go_beta = c->cur_go_val[5];
+  f.rhs_dev = st.cur_rhs_dev;
+  if (st.cur_go_kind && f.dec_out && (mask & (1u << MS_S_GDOTD))) {  // merged: direction scalars + GO + Armijo decision
+    f.go_out = st.cur_go;
+    f.go_kind = st.cur_go_kind;
+    f.go_tol2 = st.cur_go_val[0];
+    f.go_lim = st.cur_go_val[1];
+    f.go_e0 = st.cur_go_val[2];
+    f.go_c = st.cur_go_val[3];
+    f.go_alpha0 = st.cur_go_val[4];
+    f.go_beta = st.cur_go_val[5];
   }
   if (f.dec_out) c->expected[MS_MB_DEC] = c->ticket;
   HIPCHK(c, launch_reduce(f, c->stream));
@@ -561,7 +562,8 @@ int tilt_energy_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bo
 
 int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool write_trial,
                  bool guard, bool write_factors, bool reduce_now = true) {
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  const StageCtl& st = c->stage();
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   EnergyArgs a;
   a.m = device_mesh(c);
@@ -587,8 +589,8 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   a.fA = (bend && write_factors) ? c->buf[MS_BUF_FA] : nullptr;
   a.bt_vert = bt ? c->d_bt_vert : nullptr;
   a.bt_normals = nullptr;
-  a.gate = c->cur_gate_fold_only ? nullptr : c->cur_gate;
-  a.gate_want = c->cur_gate_want;
+  a.gate = st.cur_gate_fold_only ? nullptr : st.cur_gate;
+  a.gate_want = st.cur_gate_want;
   a.atomic = c->deterministic ? 0 : 1;
   a.pair = 0;
   for (int j = 0; j < MS_MAX_TRIALS - 1; ++j) {
@@ -596,34 +598,34 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     a.partials_side[j] = nullptr;
   }
   for (int j = 0; j < 2; ++j) a.xt_side[j] = a.fK_side[j] = a.fA_side[j] = nullptr;
-  if (c->pair_on > 1) {
+  if (st.pair_on > 1) {
     if (!use_dir || guard || !write_factors || !(modules & MS_MOD_BENDING) || bt || lbt || !c->side[0].partials)
       return fail(c, MS_ERR_STATE, "multi-trial launch: not an ordinary bending trial");
-    if (c->pair_on > MS_MAX_TRIALS || !c->side[c->pair_on - 2].partials)
+    if (st.pair_on > MS_MAX_TRIALS || !c->side[st.pair_on - 2].partials)
       return fail(c, MS_ERR_STATE, "multi-trial launch: side sets not allocated");
-    a.pair = c->pair_on;
-    for (int j = 0; j + 1 < c->pair_on; ++j) {
-      a.alpha_side[j] = trial_alpha(c, c->pair_alpha[j]);
+    a.pair = st.pair_on;
+    for (int j = 0; j + 1 < st.pair_on; ++j) {
+      a.alpha_side[j] = trial_alpha(c, st.pair_alpha[j]);
       a.partials_side[j] = c->side[j].partials;
     }
-    if (!c->pair_lean) {  // the first two early trials write their own positions / factors
+    if (!st.pair_lean) {  // the first two early trials write their own positions / factors
       double* const sx[2] = {c->xt2, c->xt3};
       double* const sk[2] = {c->fK2, c->fK3};
       double* const sa[2] = {c->fA2, c->fA3};
-      for (int j = 0; j < 2 && j + 1 < c->pair_on; ++j) {
+      for (int j = 0; j < 2 && j + 1 < st.pair_on; ++j) {
         if (!sk[j]) return fail(c, MS_ERR_STATE, "multi-trial launch: output side set not allocated");
         a.xt_side[j] = write_trial ? sx[j] : nullptr;
         a.fK_side[j] = sk[j];
         a.fA_side[j] = sa[j];
       }
-      if (c->pair_on > 3) return fail(c, MS_ERR_STATE, "multi-trial launch: only two early trials can write outputs");
+      if (st.pair_on > 3) return fail(c, MS_ERR_STATE, "multi-trial launch: only two early trials can write outputs");
     }
   }
   if (bt && !c->d_bt_vert) return fail(c, MS_ERR_STATE, "bending_tilt: ms_set_params did not allocate its buffers");
   a.partials = c->d_partials;
   a.bending_model = c->params.bending_model;
   a.modules = modules;
-  const bool tilt_only = c->energy_tilt_only && !use_dir && !write_factors && !write_trial && fused_tilt;
+  const bool tilt_only = st.energy_tilt_only && !use_dir && !write_factors && !write_trial && fused_tilt;
   if (tilt_only && !lbt) {
     // (nothing: the shape kernel's results for this x are where they were left)
   } else if (!lbt) {
@@ -671,7 +673,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
       if (!ta.tilts) return fail(c, MS_ERR_STATE, "bending_tilt_in/out active but ms_set_leaflet_tilts was never called");
       // (use_dir: the stored tilts onto the TRIAL surface, kept aside in `trial`; proj_at_x_in_normals: ms_step's
       // projection of the stored tilts onto x itself, in place)
-      for (int l = 1, k = 0; l <= 2 && (use_dir || c->proj_at_x_in_normals); ++l) {
+      for (int l = 1, k = 0; l <= 2 && (use_dir || st.proj_at_x_in_normals); ++l) {
         TiltField& f = c->tf[l];
         if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_bt | f.mod_dt))) continue;
         if (!f.tilts) return fail(c, MS_ERR_STATE, "tilt module active but its tilt field was never set (ms_set_tilts / ms_set_leaflet_tilts)");
@@ -768,9 +770,9 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     int rc = reduce_slots(c, tilt_only ? (energy_mask(modules) & ~core) : energy_mask(modules));
     if (rc) return rc;
   }
-  if (bend && write_factors) c->factors_valid = !use_dir;
+  if (bend && write_factors) c->carry.factors_valid = !use_dir;
   if (!lbt) c->factors_leaflet = 0;
-  c->bt_valid = (bt || lbt) && !use_dir;
+  c->carry.bt_valid = (bt || lbt) && !use_dir;
   return MS_OK;
 }
 
@@ -778,7 +780,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
 int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulate, int dir_mode = 0,
                    bool reduce_now = true) {
   uint32_t modules = modules_in;
-  if ((modules & (MS_MOD_BENDING | MS_MOD_BENDING_TILT | MS_LEAFLET_BT)) && !c->factors_valid)
+  if ((modules & (MS_MOD_BENDING | MS_MOD_BENDING_TILT | MS_LEAFLET_BT)) && !c->carry.factors_valid)
     return fail(c, MS_ERR_STATE, "gradient pass needs the bending factors of an energy pass at x");
   if (modules & MS_MOD_BENDING_TILT)  // k_bt finished the factors: K_C is the plain bending back-prop
     modules = (modules & ~MS_MOD_BENDING_TILT) | MS_MOD_BENDING;
@@ -817,9 +819,9 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
   a.d = c->buf[MS_BUF_D];
   a.pg = c->buf[MS_BUF_PG];
   a.pd = c->buf[MS_BUF_PD];
-  a.pd_neg_pg = (dir_mode == 2 && c->pd_neg_pg) ? 1 : 0;
-  a.gate = c->cur_gate;
-  a.gate_want = c->cur_gate_want;
+  a.pd_neg_pg = (dir_mode == 2 && c->carry.pd_neg_pg) ? 1 : 0;
+  a.gate = c->stage().cur_gate;
+  a.gate_want = c->stage().cur_gate_want;
   a.atomic = c->deterministic ? 0 : 1;
   a.bt_vert = nullptr;
   a.tilts = nullptr;
@@ -858,8 +860,8 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
     if (rc) return rc;
   }
   if (dir_mode) {
-    c->last_g = g_out;
-    c->dir_implicit = false;  // D was written
+    c->carry.last_g = g_out;
+    c->carry.dir_implicit = false;  // D was written
   }
   bool added_after = n_lbt > 0;
   for (int k = 0; k < 3 && g_out; ++k) {  // module loop: the tilt magnitude modules add their shape gradient into g
@@ -886,20 +888,21 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
 int phase_direction(ms_ctx* c, int stepper, bool use_history, bool g_finalized = false) {
   // (pins in the skip lane: the reference's KKT solve returned before touching g, the volume row included)
   const bool use_con = (c->params.modules & MS_CON_VOLUME) != 0 && c->pin_lane != MS_PIN_LANE_SKIP;
-  c->dir_implicit = false;
+  const StageCtl& st = c->stage();
+  c->carry.dir_implicit = false;
   {
-  ProfScope ps(c, 2, c->cur_gate, c->cur_gate_want);
+  ProfScope ps(c, 2, st.cur_gate, st.cur_gate_want);
   HIPCHK(c, launch_direction(c->tile0, c->tile1, c->til.nv, c->til.own, c->d_vflags, c->buf[MS_BUF_G],
                              c->buf[MS_BUF_GC], c->buf[MS_BUF_D], c->buf[MS_BUF_PG],
                              c->buf[MS_BUF_PD], c->d_scal, use_con ? 1 : 0,
                              (stepper == MS_STEPPER_CG && use_history) ? 1 : 0, c->d_partials,
-                             c->til.n_tiles, (g_finalized && !use_con) ? 0 : 1, c->stream, c->cur_gate,
-                             c->cur_gate_want,
+                             c->til.n_tiles, (g_finalized && !use_con) ? 0 : 1, c->stream, st.cur_gate,
+                             st.cur_gate_want,
                              // (the previous direction was an implicit -PG: the kernel derives it, as the fused epilogue does)
-                             (stepper == MS_STEPPER_CG && use_history && c->pd_neg_pg) ? 1 : 0,
+                             (stepper == MS_STEPPER_CG && use_history && c->carry.pd_neg_pg) ? 1 : 0,
                              (stepper == MS_STEPPER_CG && c->precond) ? 1 : 0));
   }
-  c->last_g = c->buf[MS_BUF_G];
+  c->carry.last_g = c->buf[MS_BUF_G];
   return reduce_slots(c, MASK_DIR);
 }
 

@@ -14,8 +14,8 @@ int pin_enforce_run(ms_ctx* c) {
   a.x = c->buf[MS_BUF_X];
   HIPCHK(c, launch_pin_enforce(a, c->stream));
   ++c->pin_enforce_launches;
-  c->factors_valid = false;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.factors_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   return MS_OK;
 }
 
@@ -162,7 +162,7 @@ int ms_set_pins(ms_ctx* c, int n_params, const double* params, int n_stages, con
   g.n_touch = (int)touch.size();
   g.touch_row = di + o_t;
   c->pin_lane = lane;
-  c->carry_valid = c->grad_valid = c->maxg2_valid = false;  // (G no longer describes this row set)
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (G no longer describes this row set)
   return MS_OK;
 }
 

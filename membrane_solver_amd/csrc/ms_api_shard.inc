@@ -11,7 +11,7 @@ int ms_phase_energy(ms_ctx* c, int use_direction, double alpha, int write_trial,
 
 int ms_phase_gradient(ms_ctx* c) {
   if (!c) return MS_ERR_INVALID;
-  c->grad_valid = false;  // G receives the raw (unfinalized) gradient
+  c->carry.grad_valid = false;  // G receives the raw (unfinalized) gradient
   return phase_gradient(c, c->params.modules, c->buf[MS_BUF_G], false);
 }
 
@@ -24,19 +24,19 @@ int ms_phase_direction(ms_ctx* c, int stepper, int use_history) {
 int ms_phase_accept(ms_ctx* c, int keep_history) {
   if (!c) return MS_ERR_INVALID;
   std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
-  c->factors_valid = false;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.factors_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   c->sh_maxg2_valid = false;
   if (keep_history) {
     std::swap(c->buf[MS_BUF_G], c->buf[MS_BUF_PG]);
     std::swap(c->buf[MS_BUF_D], c->buf[MS_BUF_PD]);
-    c->pd_neg_pg = c->dir_implicit;  // the accepted direction was -G = -PG from now on
-    c->last_g = c->buf[MS_BUF_PG];
-    c->cg_have_history = true;
-    ++c->cg_iter_count;
+    c->carry.pd_neg_pg = c->carry.dir_implicit;  // the accepted direction was -G = -PG from now on
+    c->carry.last_g = c->buf[MS_BUF_PG];
+    c->carry.cg_have_history = true;
+    ++c->carry.cg_iter_count;
   }
-  c->dir_implicit = false;
+  c->carry.dir_implicit = false;
   return MS_OK;
 }
 
@@ -66,14 +66,14 @@ int ms_phase_gradient_direction(ms_ctx* c, int stepper, int use_history) {
   if (!c) return MS_ERR_INVALID;
   if (c->params.modules & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS))
     return fail(c, MS_ERR_STATE, "fused gradient+direction needs no constraint row and no tilt module");
-  c->grad_valid = false;
+  c->carry.grad_valid = false;
   const int dir_mode = (stepper == MS_STEPPER_CG && use_history) ? 2 : 1;
   return phase_gradient(c, c->params.modules, c->buf[MS_BUF_G], false, dir_mode);
 }
 
 int ms_phase_set_factors_valid(ms_ctx* c, int valid) {
   if (!c) return MS_ERR_INVALID;
-  c->factors_valid = valid != 0;
+  c->carry.factors_valid = valid != 0;
   return MS_OK;
 }
 
@@ -630,7 +630,7 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   memset(out, 0, sizeof(*out));
   const bool cg = sp->stepper == MS_STEPPER_CG;
   const int restart = sp->restart_interval > 0 ? sp->restart_interval : 10;
-  const bool use_history = cg && c->cg_have_history && (c->cg_iter_count % restart != 0);
+  const bool use_history = cg && c->carry.cg_have_history && (c->carry.cg_iter_count % restart != 0);
   const bool bend = (mods & MS_MOD_BENDING) != 0;
   const bool constraint = (mods & MS_CON_VOLUME) != 0;
   const bool penalty = (mods & MS_MOD_VOLUME_PENALTY) != 0;
@@ -676,14 +676,14 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
     if (rc) return rc;
     ++c->sh_chain_adopted;
     fused = true;
-    c->last_g = c->buf[MS_BUF_G];
-    c->dir_implicit = false;
+    c->carry.last_g = c->buf[MS_BUF_G];
+    c->carry.dir_implicit = false;
     c->sh_maxg2_valid = true;  // (the fused epilogue reduced max|g_i|^2 as well, and G's boundary rows went along)
   } else if (carried && c->sh_grad_valid && !constraint && !use_history && c->sh_maxg2_valid) {
     // steepest-descent restart on an unchanged gradient: d = -g.  The last direction exchange carried the
     // finalized gradient rows as well, so G is valid on every row this rank reads and the scalars follow from
     // the ones already folded -- no kernel and, above all, no exchange
-    c->dir_implicit = true;
+    c->carry.dir_implicit = true;
     c->sh_scal[MS_S_GDOTD] = -c->sh_scal[MS_S_GNORM2];
     c->sh_scal[MS_S_MAXD2] = c->sh_scal[MS_S_MAXG2];
     implicit_restart = true;
@@ -747,12 +747,9 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   const double alpha_max = sp->alpha_max_factor * step_size;
   const int max_iter = sp->max_iter > 0 ? sp->max_iter : 10;
   // line-search history (same bookkeeping as ms_step: prediction only)
-  double min_rejected = INFINITY, a_hi = 0.0, r_lo = INFINITY;
+  double min_rejected = INFINITY, a_hi, r_lo;
   ms_ctx::LsHist& lh = c->ls[use_history ? 1 : 0];
-  for (int k = 0; k < std::min(lh.n, (int)ms_ctx::LS_HIST); ++k) {
-    a_hi = std::max(a_hi, lh.acc[k]);
-    r_lo = std::min(r_lo, lh.rej[k]);
-  }
+  ls_bounds(lh, a_hi, r_lo);
   auto remember = [&](double alpha_acc) {
     lh.acc[lh.n % ms_ctx::LS_HIST] = alpha_acc;
     lh.rej[lh.n % ms_ctx::LS_HIST] = min_rejected;
@@ -777,6 +774,23 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
     HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_sh_post), c->h_sh_post, 0));
     return MS_OK;
   };
+  // stage records: a launch gated on a decision word of the chain (nullptr: ungated) ...
+  auto gated_stage = [](const uint32_t* gate) {
+    StageCtl st;
+    st.cur_gate = gate;
+    st.cur_gate_want = DEC_ACCEPT_MAIN;
+    st.cur_check_ran = true;
+    return st;
+  };
+  // ... and the pair launch: the other trial's fold goes to the SH_ALT slots of the device scalars and travels in the
+  // exchange header (the driver waits on neither of the side set's mailboxes: parity stays 0)
+  auto pair_stage = [&](double alpha0, const uint32_t* gate) {
+    StageCtl st = gated_stage(gate);
+    st.pair_on = 2;
+    st.pair_alpha[0] = alpha0;
+    st.pair_scal2 = c->d_scal + SH_ALT;
+    return st;
+  };
   auto slab_of = [&](unsigned long long peer_ticket) {
     return c->d_peer_slab + (size_t)(peer_ticket % PEER_SLABS) * c->shard_count * c->peer_stride;
   };
@@ -796,33 +810,21 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
       lh2.rej[lh2.n % ms_ctx::LS_HIST] = rej_acc;
       ++lh2.n;
     }
-    double hi2 = 0.0, lo2 = INFINITY;
-    for (int k = 0; k < std::min(lh2.n, (int)ms_ctx::LS_HIST); ++k) {
-      hi2 = std::max(hi2, lh2.acc[k]);
-      lo2 = std::min(lo2, lh2.rej[k]);
-    }
+    double hi2, lo2;
+    ls_bounds(lh2, hi2, lo2);
     const bool pair2 = c->pair_enable && bend && max_iter >= 2 &&
                        (c->pair_force || (lh2.n >= 2 && a_next > 1.05 * hi2 && lo2 < INFINITY));
     int r2 = pair2 ? spec_prepare(c) : MS_OK;
     if (r2) return r2;
-    const bool s_implicit = c->dir_implicit, s_factors = c->factors_valid, s_bt = c->bt_valid;
-    c->dir_implicit = true;  // (after the reset: the trial passes read G with -alpha)
-    c->cur_gate = gate;
-    c->cur_gate_want = DEC_ACCEPT_MAIN;
-    c->cur_check_ran = true;
+    // (not the whole carried state: the trial pass also clears carry_valid and maxg2_valid, and the driver leaves them so)
+    const bool s_implicit = c->carry.dir_implicit, s_factors = c->carry.factors_valid, s_bt = c->carry.bt_valid;
+    c->carry.dir_implicit = true;  // (after the reset: the trial passes read G with -alpha)
     const double a0 = a_next, a1 = a_next * sp->beta;
-    if (pair2) {
-      c->pair_on = 2;
-      c->pair_alpha[0] = a0;
-      c->pair_scal2 = c->d_scal + SH_ALT;
-      r2 = phase_energy(c, mods, true, a1, false, false, true);
-      c->pair_on = 0;
-      c->pair_scal2 = nullptr;
-    } else {
-      r2 = phase_energy(c, mods, true, a0, false, false, carry_mode);
+    {
+      StageScope scope(c, pair2 ? pair_stage(a0, gate) : gated_stage(gate));
+      r2 = pair2 ? phase_energy(c, mods, true, a1, false, false, true)
+                 : phase_energy(c, mods, true, a0, false, false, carry_mode);
     }
-    c->cur_check_ran = false;
-    c->cur_gate = nullptr;
     unsigned long long tk2 = 0;
     if (r2 == MS_OK) {
       ShardDecideArgs da;
@@ -865,9 +867,9 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
       spec_new.post_ticket = c->sh_post_ticket;
       ++c->sh_spec_queued;
     }
-    c->dir_implicit = s_implicit;
-    c->factors_valid = s_factors;
-    c->bt_valid = s_bt;
+    c->carry.dir_implicit = s_implicit;
+    c->carry.factors_valid = s_factors;
+    c->carry.bt_valid = s_bt;
     return r2;
   };
   // queue a trial's exchange and, when chain: the device-side decision and what an acceptance of the MAIN trial is
@@ -924,32 +926,31 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
                                  DEC_ACCEPT_MAIN));
       // (b) the gradient + direction pass in the state the acceptance produces (CG history swapped, the trial's
       // factors valid), every change of the context undone afterwards; (c) its exchange; (d) the trial queued ahead
-      chain_next_hist = cg && ((c->cg_iter_count + 1) % restart != 0);
-      const bool s_factors = c->factors_valid, s_implicit = c->dir_implicit, s_pdneg = c->pd_neg_pg, s_grad = c->grad_valid;
-      double* const s_last_g = c->last_g;
+      chain_next_hist = next_use_history(c, cg, restart);
+      // (not the whole carried state: queue_spec's trial pass clears carry_valid and maxg2_valid, and they stay cleared)
+      const bool s_factors = c->carry.factors_valid, s_implicit = c->carry.dir_implicit, s_pdneg = c->carry.pd_neg_pg, s_grad = c->carry.grad_valid;
+      double* const s_last_g = c->carry.last_g;
       if (cg) {
         std::swap(c->buf[MS_BUF_G], c->buf[MS_BUF_PG]);
         std::swap(c->buf[MS_BUF_D], c->buf[MS_BUF_PD]);
-        c->pd_neg_pg = c->dir_implicit;
+        c->carry.pd_neg_pg = c->carry.dir_implicit;
       }
-      c->factors_valid = true;
-      c->cur_gate = gate;
-      c->cur_gate_want = DEC_ACCEPT_MAIN;
-      c->cur_check_ran = true;
-      r2 = phase_gradient(c, mods, c->buf[MS_BUF_G], false, chain_next_hist ? 2 : 1);
-      c->cur_check_ran = false;
-      c->cur_gate = nullptr;
+      c->carry.factors_valid = true;
+      {
+        StageScope scope(c, gated_stage(gate));
+        r2 = phase_gradient(c, mods, c->buf[MS_BUF_G], false, chain_next_hist ? 2 : 1);
+      }
       if (r2 == MS_OK) r2 = shard_exchange_queue(c, 2, dbuf, &chain_ticket, gate, DEC_ACCEPT_MAIN);
       if (r2 == MS_OK) r2 = queue_spec(a_main, fold_alt ? a_alt : min_rejected, gate, c->peer_ticket, c->sh_widx);
       if (cg) {
         std::swap(c->buf[MS_BUF_G], c->buf[MS_BUF_PG]);
         std::swap(c->buf[MS_BUF_D], c->buf[MS_BUF_PD]);
       }
-      c->factors_valid = s_factors;
-      c->dir_implicit = s_implicit;
-      c->pd_neg_pg = s_pdneg;
-      c->grad_valid = s_grad;
-      c->last_g = s_last_g;
+      c->carry.factors_valid = s_factors;
+      c->carry.dir_implicit = s_implicit;
+      c->carry.pd_neg_pg = s_pdneg;
+      c->carry.grad_valid = s_grad;
+      c->carry.last_g = s_last_g;
       if (r2) return r2;
       chained = true;
       ++c->sh_chained;
@@ -995,7 +996,7 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
     if (r2) return r2;
     c->sh_grad_valid = false;
     if (carry_mode) {
-      c->factors_valid = true;
+      c->carry.factors_valid = true;
       if (penalty)
         HIPCHK(c, hipMemcpyAsync(c->d_scal, c->sh_scal, sizeof(double) * MS_NSCAL, hipMemcpyHostToDevice,
                                  S(c)));
@@ -1029,12 +1030,8 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
     if (rc) return rc;
     const double alpha0 = alpha, alpha1 = alpha * sp->beta;
     if (!adopt_spec) {
-      c->pair_on = 2;
-      c->pair_alpha[0] = alpha0;
-      c->pair_scal2 = c->d_scal + SH_ALT;
+      StageScope scope(c, pair_stage(alpha0, nullptr));
       rc = phase_energy(c, mods, true, alpha1, false, false, true);
-      c->pair_on = 0;
-      c->pair_scal2 = nullptr;
       if (rc) return rc;
     }
     c->sh_carry_valid = false;

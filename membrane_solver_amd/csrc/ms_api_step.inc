@@ -1,8 +1,8 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit): energy / gradient entry points, line-search rounds, ms_step, volume projection, the resident step, ms_minimize.
 int ms_set_positions(ms_ctx* c, const double* positions) {
   if (!c || !positions) return fail(c, MS_ERR_INVALID, "ms_set_positions: NULL argument");
-  c->factors_valid = false;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.factors_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   return ext_to_patch(c, positions, c->buf[MS_BUF_X], 3);
 }
@@ -14,19 +14,19 @@ int ms_get_positions(ms_ctx* c, double* positions) {
 
 int ms_get_gradient(ms_ctx* c, double* grad) {
   if (!c || !grad) return fail(c, MS_ERR_INVALID, "ms_get_gradient: NULL argument");
-  return patch_to_ext(c, c->last_g, grad, 3);
+  return patch_to_ext(c, c->carry.last_g, grad, 3);
 }
 
 int ms_get_vertex_buffer(ms_ctx* c, int buffer, double* out) {
   if (!c || !out || buffer < 0 || buffer > MS_BUF_FA)
     return fail(c, MS_ERR_INVALID, "ms_get_vertex_buffer: bad argument");
-  if ((buffer == MS_BUF_D && c->dir_implicit) || (buffer == MS_BUF_PD && c->pd_neg_pg)) {
+  if ((buffer == MS_BUF_D && c->carry.dir_implicit) || (buffer == MS_BUF_PD && c->carry.pd_neg_pg)) {
     // the direction asked for exists only as -G / -PG: write it out
     const int src = buffer == MS_BUF_D ? MS_BUF_G : MS_BUF_PG;
     HIPCHK(c, launch_direction(c->tile0, c->tile1, c->til.nv, c->til.own, c->d_vflags, c->buf[src], c->buf[MS_BUF_GC],
                                c->buf[buffer], c->buf[MS_BUF_PG], c->buf[MS_BUF_PD], c->d_scal, 0, 0, c->d_partials,
                                c->til.n_tiles, 0, c->stream));
-    if (buffer == MS_BUF_D) c->dir_implicit = false; else c->pd_neg_pg = false;
+    if (buffer == MS_BUF_D) c->carry.dir_implicit = false; else c->carry.pd_neg_pg = false;
   }
   return patch_to_ext(c, c->buf[buffer], out, buffer == MS_BUF_FA ? 2 : 3);
 }
@@ -52,7 +52,7 @@ int ms_energy_and_raw_gradient(ms_ctx* c, double energies[4], double* grad) {
   const bool penalty = (mods & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) != 0;  // K_C reads the reduced volume / body area
   int rc = phase_energy(c, mods, false, 0.0, false, false, true, /*reduce_now=*/penalty);
   if (rc) return rc;
-  c->grad_valid = false;  // G receives the raw gradient: no fixed-row zeroing, no KKT projection
+  c->carry.grad_valid = false;  // G receives the raw gradient: no fixed-row zeroing, no KKT projection
   rc = phase_gradient(c, mods, c->buf[MS_BUF_G], false, 0, /*reduce_now=*/false);
   if (rc) return rc;
   rc = reduce_slots(c, (penalty ? 0u : energy_mask(mods)) | MASK_GRAD);
@@ -67,7 +67,7 @@ int ms_energy_and_raw_gradient(ms_ctx* c, double energies[4], double* grad) {
 int ms_energy(ms_ctx* c, double energies[4]) {
   if (!c || !energies) return fail(c, MS_ERR_INVALID, "ms_energy: NULL argument");
   if (c->shard_count != 1) return fail(c, MS_ERR_STATE, "ms_energy: sharded contexts use the phase API");
-  if (c->carry_valid) {
+  if (c->carry.carry_valid) {
     // the last accepted trial (or the pass before a failed search) evaluated exactly this x and its energies are
     // still in the mailbox: no pass, and the carried state survives for the next step
     energies_from_mailbox(c, energies);
@@ -83,9 +83,9 @@ int ms_energy(ms_ctx* c, double energies[4]) {
 
 int ms_reset_stepper(ms_ctx* c) {
   if (!c) return MS_ERR_INVALID;
-  c->cg_have_history = false;
-  c->cg_iter_count = 0;
-  c->pd_neg_pg = false;
+  c->carry.cg_have_history = false;
+  c->carry.cg_iter_count = 0;
+  c->carry.pd_neg_pg = false;
   return MS_OK;
 }
 
@@ -125,6 +125,28 @@ int spec_prepare(ms_ctx* c) {
 inline void forget(ms_ctx::Mailbox& m) {
   for (int sl = 0; sl < MS_MB_WORDS; ++sl) m.expected[sl] = 0;
 }
+// what the recent searches of a kind say about the acceptance threshold: no alpha above a_hi was accepted, and alphas
+// down to r_lo were rejected (INFINITY: nothing was rejected lately -- the step size is still growing)
+inline void ls_bounds(const ms_ctx::LsHist& lh, double& a_hi, double& r_lo) {
+  a_hi = 0.0;
+  r_lo = INFINITY;
+  for (int k = 0; k < std::min(lh.n, (int)ms_ctx::LS_HIST); ++k) {
+    a_hi = std::max(a_hi, lh.acc[k]);
+    r_lo = std::min(r_lo, lh.rej[k]);
+  }
+}
+// the trial energy a queued stage is decided on, from that stage's scalars (surface + bending: ms_step's can_chain)
+inline double stage_energy(const ms_ctx* c, const double* v) {
+  return ((c->params.modules & MS_MOD_SURFACE) ? v[MS_S_ESURF] : 0.0) +
+         ((c->params.modules & MS_MOD_BENDING) ? v[MS_S_EBEND] : 0.0);
+}
+// the energy scalars of a stage's mailbox become the context's own
+inline void adopt_scalars(ms_ctx* c, const double* v) {
+  for (int sl = 0; sl < MS_NSCAL; ++sl)
+    if (energy_mask(c->params.modules) & (1u << sl)) put_mailbox(c, sl, v[sl]);
+}
+// the gradient pass behind an acceptance computes a direction with CG history (conjugate_gradient.py:78-82)
+inline bool next_use_history(const ms_ctx* c, bool cg, int restart) { return cg && ((c->carry.cg_iter_count + 1) % restart != 0); }
 }  // namespace
 
 // ---- line-search rounds (ms_step) ------------------------------------------------------------------------------
@@ -202,35 +224,33 @@ int queue_round(ms_ctx* c, const ms_stepper_params* sp, const RoundPlan& plan, i
   const bool go_gated = merged;
   const int n0 = plan.n0, n_st = plan.n_st;
   const double* alphas = plan.alphas;
-  c->cur_parity = parity;
   int rc;
   // first launch: trials 0 .. n0-1, the early ones into the side sets, the last one into the ordinary outputs;
   // its fold decides all of them and writes decision record 0
   {
-    c->pair_on = n0 > 1 ? n0 : 0;
-    c->pair_lean = n0 > 1 && c->pair_lean_enable;
-    for (int j = 0; j + 1 < n0; ++j) c->pair_alpha[j] = alphas[j];
+    StageCtl st;
+    st.cur_parity = parity;  // (read by a multi-trial fold only: the gated stages and the gradient pass keep 0)
+    st.pair_on = n0 > 1 ? n0 : 0;
+    st.pair_lean = n0 > 1 && c->pair_lean_enable;
+    for (int j = 0; j + 1 < n0; ++j) st.pair_alpha[j] = alphas[j];
+    st.cur_gate_want = DEC_ACCEPT_MAIN;
+    st.cur_dec = dec_word(c, parity, 0);
+    for (int j = 0; j < n0; ++j) st.cur_rhs[j] = energy0 + sp->c * alphas[j] * g_dot_d;
+    if (merged) {
+      // the fold (not the energy kernel) is tied to the gradient pass in front: it checks that pass's ran count,
+      // and what it tests before it decides the trials (FoldArgs::go_kind) is what queue_ahead put into c->ahead
+      const ms_ctx::Ahead& ah = c->ahead;
+      st.cur_gate = c->kc_gate[go_src];
+      st.cur_gate_fold_only = st.cur_check_ran = true;
+      st.cur_extra_mask = c->dir_mask[go_src];
+      st.cur_go_kind = ah.go_kind;
+      st.cur_go = go_word(c, go_src);
+      const double go_val[6] = {ah.tol2p, ah.lim, ah.energy0, ah.c1, ah.alpha0, ah.beta};
+      memcpy(st.cur_go_val, go_val, sizeof(go_val));
+    }
     swap_mailbox(c, c->first_mb[parity]);
-    // merged: the fold (not the energy kernel) is tied to the gradient pass in front: it checks that pass's ran count
-    c->cur_gate = merged ? c->kc_gate[go_src] : nullptr;
-    c->cur_gate_want = DEC_ACCEPT_MAIN;
-    c->cur_gate_fold_only = merged;
-    c->cur_check_ran = merged;
-    c->cur_dec = dec_word(c, parity, 0);
-    c->cur_extra_mask = merged ? c->dir_mask[go_src] : 0u;
-    c->cur_go_kind = merged ? c->ahead.go_kind : 0;
-    c->cur_go = merged ? go_word(c, go_src) : nullptr;
-    for (int j = 0; j < n0; ++j) c->cur_rhs[j] = energy0 + sp->c * alphas[j] * g_dot_d;
+    StageScope scope(c, st);
     rc = phase_energy(c, c->params.modules, true, alphas[n0 - 1], true, false, carry_mode);
-    c->pair_on = 0;
-    c->pair_lean = false;
-    c->cur_dec = nullptr;
-    c->cur_gate = nullptr;
-    c->cur_gate_fold_only = false;
-    c->cur_check_ran = false;
-    c->cur_extra_mask = 0;
-    c->cur_go_kind = 0;
-    c->cur_go = nullptr;
     if (merged) c->dir_pending[go_src] = false;
     swap_mailbox(c, c->first_mb[parity]);
     if (rc) return rc;
@@ -238,17 +258,15 @@ int queue_round(ms_ctx* c, const ms_stepper_params* sp, const RoundPlan& plan, i
   // gated stages: stage s runs iff record s-1 says DEC_CONTINUE
   for (int s2 = 1; s2 <= n_st; ++s2) {
     swap_mailbox(c, c->spec[parity][s2 - 1]);
-    c->cur_gate = dec_word(c, parity, s2 - 1);
-    c->cur_gate_want = DEC_CONTINUE;
-    c->cur_check_ran = true;
-    c->cur_dec = dec_word(c, parity, s2);
-    c->cur_rhs[0] = energy0 + sp->c * alphas[n0 + s2 - 1] * g_dot_d;
-    c->cur_rhs_dev = go_gated ? go_rhs(c, go_src) + (n0 + s2 - 1) : nullptr;
+    StageCtl st;
+    st.cur_gate = dec_word(c, parity, s2 - 1);
+    st.cur_gate_want = DEC_CONTINUE;
+    st.cur_check_ran = true;
+    st.cur_dec = dec_word(c, parity, s2);
+    st.cur_rhs[0] = energy0 + sp->c * alphas[n0 + s2 - 1] * g_dot_d;
+    st.cur_rhs_dev = go_gated ? go_rhs(c, go_src) + (n0 + s2 - 1) : nullptr;
+    StageScope scope(c, st);
     rc = phase_energy(c, c->params.modules, true, alphas[n0 + s2 - 1], true, false, carry_mode);
-    c->cur_gate = nullptr;
-    c->cur_check_ran = false;
-    c->cur_dec = nullptr;
-    c->cur_rhs_dev = nullptr;
     swap_mailbox(c, c->spec[parity][s2 - 1]);
     if (rc) return rc;
   }
@@ -256,44 +274,37 @@ int queue_round(ms_ctx* c, const ms_stepper_params* sp, const RoundPlan& plan, i
     // the next step's gradient pass in the state an acceptance produces (x <-> xt, CG history swapped, factors of
     // the accepted trial), gated on "the accepted trial is the one in the ordinary buffers"; every change of the
     // context is undone afterwards.  Its direction fold can open the round after this one (queue_ahead).
-    const bool next_hist = cg && ((c->cg_iter_count + 1) % restart != 0);
-    const bool s_factors = c->factors_valid, s_implicit = c->dir_implicit, s_pdneg = c->pd_neg_pg;
-    const bool s_grad_valid = c->grad_valid, s_carry = c->carry_valid, s_maxg2 = c->maxg2_valid;
-    double* const s_last_g = c->last_g;
+    // (of the carried state the pass writes factors_valid, dir_implicit, pd_neg_pg, last_g and the three flags the
+    // pin project lane clears; it never runs with a tilt module, so nothing of it touches the rest)
+    const bool next_hist = next_use_history(c, cg, restart);
+    const CarryState s_carry = c->carry;
     std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
     if (cg) {
       std::swap(c->buf[MS_BUF_G], c->buf[MS_BUF_PG]);
       std::swap(c->buf[MS_BUF_D], c->buf[MS_BUF_PD]);
-      c->pd_neg_pg = c->dir_implicit;
+      c->carry.pd_neg_pg = c->carry.dir_implicit;
     }
-    c->factors_valid = true;
+    c->carry.factors_valid = true;
     swap_mailbox(c, c->grad_mb[parity]);
-    c->cur_gate = dec_word(c, parity, n_st);
-    c->cur_gate_want = DEC_ACCEPT_MAIN;
-    c->cur_check_ran = true;
+    StageCtl st;
+    st.cur_gate = dec_word(c, parity, n_st);
+    st.cur_gate_want = DEC_ACCEPT_MAIN;
+    st.cur_check_ran = true;
     // inside ms_minimize the direction fold of this pass is left to the first fold of the round after this one
-    c->defer_dir = c->ahead_allowed && sp->edge_fraction <= 0.0;
+    st.defer_dir = c->ahead_allowed && sp->edge_fraction <= 0.0;
     c->dir_deferred_mask = 0;
+    StageScope scope(c, st);
     rc = queue_energy_and_gradient(c, sp->stepper, next_hist, /*skip_energy=*/true);
-    c->dir_pending[parity] = c->defer_dir && c->dir_deferred_mask != 0;
+    c->dir_pending[parity] = st.defer_dir && c->dir_deferred_mask != 0;
     c->dir_mask[parity] = c->dir_deferred_mask;
     c->kc_gate[parity] = dec_word(c, parity, n_st);
-    c->defer_dir = false;
-    c->cur_gate = nullptr;
-    c->cur_check_ran = false;
     swap_mailbox(c, c->grad_mb[parity]);
     if (cg) {
       std::swap(c->buf[MS_BUF_G], c->buf[MS_BUF_PG]);
       std::swap(c->buf[MS_BUF_D], c->buf[MS_BUF_PD]);
     }
     std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
-    c->factors_valid = s_factors;
-    c->dir_implicit = s_implicit;
-    c->pd_neg_pg = s_pdneg;
-    c->last_g = s_last_g;
-    c->grad_valid = s_grad_valid;
-    c->carry_valid = s_carry;
-    c->maxg2_valid = s_maxg2;
+    c->carry = s_carry;
     if (rc) return rc;
   }
   return MS_OK;
@@ -304,12 +315,12 @@ int flush_dir_fold(ms_ctx* c, int parity) {
   if (!c->dir_pending[parity]) return MS_OK;
   c->dir_pending[parity] = false;
   swap_mailbox(c, c->grad_mb[parity]);
-  c->cur_gate = c->kc_gate[parity];
-  c->cur_gate_want = DEC_ACCEPT_MAIN;
-  c->cur_check_ran = true;
+  StageCtl st;
+  st.cur_gate = c->kc_gate[parity];
+  st.cur_gate_want = DEC_ACCEPT_MAIN;
+  st.cur_check_ran = true;
+  StageScope scope(c, st);
   const int rc = reduce_slots(c, c->dir_mask[parity]);
-  c->cur_gate = nullptr;
-  c->cur_check_ran = false;
   swap_mailbox(c, c->grad_mb[parity]);
   return rc;
 }
@@ -328,13 +339,13 @@ void drop_ahead(ms_ctx* c, int ran) {
   c->dir_pending[p] = false;
   c->ahead.valid = false;
   ++c->q_dropped;
-  if (ran >= 1) c->factors_valid = false;
+  if (ran >= 1) c->carry.factors_valid = false;
   if (ran >= 2) {
-    c->carry_valid = c->grad_valid = c->maxg2_valid = false;
-    c->kc_pending = false;
-    c->cg_have_history = false;
-    c->cg_iter_count = 0;
-    c->pd_neg_pg = false;
+    c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;
+    c->carry.kc_pending = false;
+    c->carry.cg_have_history = false;
+    c->carry.cg_iter_count = 0;
+    c->carry.pd_neg_pg = false;
   }
 }
 
@@ -348,8 +359,8 @@ void drop_ahead(ms_ctx* c, int ran) {
 //   kind 2: the pass computes d = -g itself (gradient descent, CG restart steps): the next step's own first round.
 int queue_ahead(ms_ctx* c, const ms_stepper_params* sp, const ms_step_result* out, double tol, bool carry_mode,
                 bool cg, int restart) {
-  if (!c->kc_pending || c->ahead.valid) return MS_OK;
-  const int src = c->kc_parity;
+  if (!c->carry.kc_pending || c->ahead.valid) return MS_OK;
+  const int src = c->carry.kc_parity;
   if (!c->dir_pending[src]) return MS_OK;  // (the pass was queued with its own direction fold)
   // kind 1: CG history, and the last direction with history was no descent direction; 3: it was one -- the next step
   // searches along the direction this pass writes; 2: the pass writes d = -g itself
@@ -359,12 +370,9 @@ int queue_ahead(ms_ctx* c, const ms_stepper_params* sp, const ms_step_result* ou
   if (c->steps_left < (kind == 1 ? 2 : 1) || !(alpha0 >= 1e-8) || sp->edge_fraction > 0.0)
     return flush_dir_fold(c, src);  // (the step it would belong to is not part of this call)
   // line-search history as the consuming step will see it (accept() has just added this search)
-  double a_hi = 0.0, r_lo = INFINITY;
+  double a_hi, r_lo;
   const ms_ctx::LsHist& lh = c->ls[kind == 3 ? 1 : 0];  // (kinds 1 and 2 search along -g)
-  for (int k = 0; k < std::min(lh.n, (int)ms_ctx::LS_HIST); ++k) {
-    a_hi = std::max(a_hi, lh.acc[k]);
-    r_lo = std::min(r_lo, lh.rej[k]);
-  }
+  ls_bounds(lh, a_hi, r_lo);
   const int max_iter = sp->max_iter > 0 ? sp->max_iter : 10;
   ms_ctx::Ahead& ah = c->ahead;
   plan_round(c, sp, alpha0, max_iter, 0, a_hi, r_lo, lh.n >= 2, lh.pred_trials, 0, ah.plan, /*ahead=*/true);
@@ -382,48 +390,25 @@ int queue_ahead(ms_ctx* c, const ms_stepper_params* sp, const ms_step_result* ou
   ah.src = src;
   ah.go = false;
   ah.go_known = false;
-  // what the round's first fold tests before it decides the trials (FoldArgs::go_kind)
+  // what the round's first fold tests before it decides the trials (FoldArgs::go_kind, with the parameters above)
   ah.go_kind = kind == 1 ? 1 : 2;
-  c->cur_go_val[0] = ah.tol2p;
-  c->cur_go_val[1] = ah.lim;
-  c->cur_go_val[2] = ah.energy0;
-  c->cur_go_val[3] = sp->c;
-  c->cur_go_val[4] = alpha0;
-  c->cur_go_val[5] = sp->beta;
   // the round itself, in the state the consuming step will be in
-  const bool s_hist = c->cg_have_history, s_implicit = c->dir_implicit, s_pdneg = c->pd_neg_pg;
-  const int s_iter = c->cg_iter_count;
-  double* const s_last_g = c->last_g;
-  const bool s_kcp = c->kc_pending;
-  const int s_kcpar = c->kc_parity;
   // (queueing a trial pass marks the carried state as gone; for a round that belongs to a later step it is not)
-  const bool s_carry = c->carry_valid, s_grad = c->grad_valid, s_maxg2 = c->maxg2_valid, s_fac = c->factors_valid,
-             s_bt = c->bt_valid;
+  const CarryState s_carry = c->carry;
   if (kind == 1) {  // (after the failed step: ms_reset_stepper, then the steepest-descent restart reads G with -alpha)
-    c->cg_have_history = false;
-    c->cg_iter_count = 0;
-    c->pd_neg_pg = false;
-    c->dir_implicit = true;
+    c->carry.cg_have_history = false;
+    c->carry.cg_iter_count = 0;
+    c->carry.pd_neg_pg = false;
+    c->carry.dir_implicit = true;
   } else {
-    c->dir_implicit = false;
+    c->carry.dir_implicit = false;
   }
   const int parity = c->next_parity;
   c->next_parity ^= 1;
   ah.parity = parity;
   // (host-side right-hand sides are not known yet: the device forms them; the consuming step replays them)
   int rc = queue_round(c, sp, ah.plan, parity, 0.0, 0.0, /*merged=*/true, src, carry_mode, cg, restart);
-  c->cg_have_history = s_hist;
-  c->cg_iter_count = s_iter;
-  c->dir_implicit = s_implicit;
-  c->pd_neg_pg = s_pdneg;
-  c->last_g = s_last_g;
-  c->kc_pending = s_kcp;
-  c->kc_parity = s_kcpar;
-  c->carry_valid = s_carry;
-  c->grad_valid = s_grad;
-  c->maxg2_valid = s_maxg2;
-  c->factors_valid = s_fac;
-  c->bt_valid = s_bt;
+  c->carry = s_carry;
   if (rc) return rc;
   ah.valid = true;
   ++c->q_ahead;
@@ -439,22 +424,22 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   const bool cg = sp->stepper == MS_STEPPER_CG;
   const int restart = sp->restart_interval > 0 ? sp->restart_interval : 10;
   // conjugate_gradient.py:78-82: steepest descent on first call and every restart
-  const bool use_history = cg && c->cg_have_history && (c->cg_iter_count % restart != 0);
+  const bool use_history = cg && c->carry.cg_have_history && (c->carry.cg_iter_count % restart != 0);
   const bool tilt = (c->params.modules & MS_ANY_TILT_MODS) != 0;
   TiltField* tfl[3];
   const int n_tf = active_fields(c, c->params.modules, tfl);
   // reuse_energy0 == 2: an accepted trial doubles as the next step's energy/factor pass
   const bool carry_mode = sp->reuse_energy0 >= 2 && !tilt;
-  if (c->ahead.valid && !c->ahead.go_known && !(c->kc_pending && carry_mode && c->carry_valid)) {
+  if (c->ahead.valid && !c->ahead.go_known && !(c->carry.kc_pending && carry_mode && c->carry.carry_valid)) {
     // a round was queued ahead, and this step will not read the direction fold that decides about it (something
     // touched the context in between): whatever it did, none of it is used
     drop_ahead(c, /*ran=*/2);
   }
   // the mailbox energies (and G, when grad_valid) describe x ...
-  const bool carried_x = carry_mode && c->carry_valid;
+  const bool carried_x = carry_mode && c->carry.carry_valid;
   // ... and so do the bending factors in fK / fA (what a gradient pass at x needs)
   const bool carried = carried_x &&
-                       (c->factors_valid || !(c->params.modules & (MS_MOD_BENDING | MS_MOD_BENDING_TILT)));
+                       (c->carry.factors_valid || !(c->params.modules & (MS_MOD_BENDING | MS_MOD_BENDING_TILT)));
   // the direction cannot ride in the gradient kernel's epilogue when a constraint row has to be projected out first
   // (lambda needs a global reduction) or when a tilt module adds its shape gradient behind K_C
   const bool volrow = (c->params.modules & MS_CON_VOLUME) != 0;
@@ -465,34 +450,34 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   int rc;
   bool restart_sd = false;
   const bool tilt_shape = (c->params.modules & MS_TILT_SHAPE_MODS) != 0;
-  if (carried_x && c->grad_valid && !tilt_shape && c->til.T <= 256 &&
-      (!volrow || (!use_history && c->maxg2_valid && !precond))) {
+  if (carried_x && c->carry.grad_valid && !tilt_shape && c->til.T <= 256 &&
+      (!volrow || (!use_history && c->carry.maxg2_valid && !precond))) {
     // x has not moved since the last gradient pass (failed search, stepper reset): only the
     // direction changes.  k_direction on the finalized g repeats the fused epilogue's
     // arithmetic and reduction order exactly.  (With a constraint row G is the projected gradient the direction
     // kernel wrote back: a steepest-descent restart reads it as it is; projecting it a second time is not on.)
-    restart_sd = !use_history && c->maxg2_valid && !precond;
+    restart_sd = !use_history && c->carry.maxg2_valid && !precond;
     if (restart_sd) {
       // steepest-descent restart: d = -g, whose scalars the gradient pass already reduced
       // (|g|^2; <g,d> = -|g|^2 and max|d_i|^2 = max|g_i|^2 exactly) -- no fold, no host round trip
       // -- and no kernel either: the trial passes read G with -alpha (dir_implicit)
-      c->dir_implicit = true;
-      c->last_g = c->buf[MS_BUF_G];
+      c->carry.dir_implicit = true;
+      c->carry.last_g = c->buf[MS_BUF_G];
       c->h_scal[MS_S_GDOTD] = -c->h_scal[MS_S_GNORM2];
       c->h_scal[MS_S_MAXD2] = c->h_scal[MS_S_MAXG2];
       rc = MS_OK;
     } else {
       rc = phase_direction(c, sp->stepper, use_history, /*g_finalized=*/true);
     }
-  } else if (c->kc_pending && carried_x && !(c->params.modules & MS_TILT_SHAPE_MODS) && c->kc_stepper == sp->stepper &&
+  } else if (c->carry.kc_pending && carried_x && !(c->params.modules & MS_TILT_SHAPE_MODS) && c->kc_stepper == sp->stepper &&
              c->kc_use_history == use_history && !precond) {
     // (a queued pass always carries the plain fused direction: a caller that switched precondition on between two
     // steps must not adopt it)
     // the gradient + direction pass of this x was queued behind the line search that accepted it (gated on the
     // acceptance) and has run: take its scalars from its mailbox
-    c->kc_pending = false;
+    c->carry.kc_pending = false;
     double vals[MS_NSCAL];
-    if (c->ahead.valid && !c->ahead.go_known && c->ahead.src == c->kc_parity) {
+    if (c->ahead.valid && !c->ahead.go_known && c->ahead.src == c->carry.kc_parity) {
       // The direction scalars of this pass arrive with the first fold of the round that was queued behind it (its
       // energy launch did not wait for them).  That fold decided first whether the round's search happens at all:
       // replay that from the scalars it was taken on (comparisons only -- the host's outcome is the device's, or
@@ -515,20 +500,20 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       // its energy launch has run in any case: without the search, the factors and the trial positions are scrap
       if (!ah.go) drop_ahead(c, /*ran=*/1);
     } else {
-      rc = flush_dir_fold(c, c->kc_parity);  // (nobody merged the direction fold: launch it now)
+      rc = flush_dir_fold(c, c->carry.kc_parity);  // (nobody merged the direction fold: launch it now)
       if (rc) return rc;
-      rc = wait_mailbox(c, c->grad_mb[c->kc_parity].h_seq, c->grad_mb[c->kc_parity].expected, vals, nullptr);
+      rc = wait_mailbox(c, c->grad_mb[c->carry.kc_parity].h_seq, c->grad_mb[c->carry.kc_parity].expected, vals, nullptr);
       if (rc) return rc;
     }
     for (int sl = 0; sl < MS_NSCAL; ++sl)
       if (MASK_DIR & (1u << sl)) put_mailbox(c, sl, vals[sl]);
-    c->last_g = c->buf[MS_BUF_G];
-    c->dir_implicit = false;
-    c->maxg2_valid = true;  // (the fused epilogue and the direction kernel both reduce max|g_i|^2)
+    c->carry.last_g = c->buf[MS_BUF_G];
+    c->carry.dir_implicit = false;
+    c->carry.maxg2_valid = true;  // (the fused epilogue and the direction kernel both reduce max|g_i|^2)
   } else {
-    c->kc_pending = false;
+    c->carry.kc_pending = false;
     rc = queue_energy_and_gradient(c, sp->stepper, use_history, carried);
-    c->maxg2_valid = true;  // the fused epilogue / the direction kernel reduced max|g_i|^2 as well
+    c->carry.maxg2_valid = true;  // the fused epilogue / the direction kernel reduced max|g_i|^2 as well
   }
   if (rc) return rc;
   if (!restart_sd) {
@@ -536,8 +521,8 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     if (rc) return rc;
   }
   // factors, mailbox energies and G now describe x (until a trial pass overwrites them)
-  c->carry_valid = carry_mode;
-  c->grad_valid = carry_mode && !tilt_shape;
+  c->carry.carry_valid = carry_mode;
+  c->carry.grad_valid = carry_mode && !tilt_shape;
   double e[4];
   energies_from_mailbox(c, e);
   const double E_eval = e[0] + e[1] + e[2] + e[3];
@@ -567,14 +552,16 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     if (rc) return rc;
   }
   if (!sp->reuse_energy0 || tilt) {
-    c->proj_at_x_in_normals = proj_in_normals;
+    StageCtl st;
+    st.proj_at_x_in_normals = proj_in_normals;
     // (reuse levels 1, 2: the surface / bending / volume terms and the bending_tilt records of THIS x were evaluated by
     // the gradient assembly above; level 0 re-runs every pass the reference re-runs)
-    c->energy_tilt_only = tilt && sp->reuse_energy0 >= 1 && c->tenergy_enable &&
-                          (c->bt_valid || !(c->params.modules & (MS_MOD_BENDING_TILT | MS_LEAFLET_BT)));
-    rc = phase_energy(c, c->params.modules, false, 0.0, false, false, false);
-    c->energy_tilt_only = false;
-    c->proj_at_x_in_normals = false;
+    st.energy_tilt_only = tilt && sp->reuse_energy0 >= 1 && c->tenergy_enable &&
+                          (c->carry.bt_valid || !(c->params.modules & (MS_MOD_BENDING_TILT | MS_LEAFLET_BT)));
+    {
+      StageScope scope(c, st);
+      rc = phase_energy(c, c->params.modules, false, 0.0, false, false, false);
+    }
     if (rc) return rc;
     rc = fetch(c);
     if (rc) return rc;
@@ -593,34 +580,29 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   const int max_iter = sp->max_iter > 0 ? sp->max_iter : 10;
   bool kc_queued = false;  // the next step's gradient pass is in the queue, gated on an acceptance
   double min_rejected = INFINITY;  // smallest alpha this search has rejected
-  // what the recent searches say about the acceptance threshold: no alpha above a_hi was accepted, and alphas
-  // down to r_lo were rejected (INFINITY: nothing was rejected lately -- the step size is still growing)
-  double a_hi = 0.0, r_lo = INFINITY;
+  double a_hi, r_lo;
   ms_ctx::LsHist& lh = c->ls[use_history ? 1 : 0];
-  for (int k = 0; k < std::min(lh.n, (int)ms_ctx::LS_HIST); ++k) {
-    a_hi = std::max(a_hi, lh.acc[k]);
-    r_lo = std::min(r_lo, lh.rej[k]);
-  }
+  ls_bounds(lh, a_hi, r_lo);
   const bool ls_warm = lh.n >= 2;
   // what an accepted trial at `alpha` does (positions, carry flags, CG history, result fields)
   auto accept = [&](double alpha_acc, double E_t) {
     std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
     // carry mode: the trial pass evaluated exactly the accepted x (it wrote those very
     // doubles to xt) with the factor outputs on -> it IS the next step's energy pass
-    c->factors_valid = carry_mode;
-    c->carry_valid = carry_mode;
-    c->grad_valid = false;
+    c->carry.factors_valid = carry_mode;
+    c->carry.carry_valid = carry_mode;
+    c->carry.grad_valid = false;
     // minimizer.py:1415 re-projects the stored tilts onto the accepted surface: that is
     // exactly the trial projection computed above
     for (int k = 0; k < n_tf; ++k) std::swap(tfl[k]->tilts, tfl[k]->trial);
-    c->bt_valid = (c->params.modules & MS_MOD_BENDING_TILT) != 0;  // the trial's record is x's now
+    c->carry.bt_valid = (c->params.modules & MS_MOD_BENDING_TILT) != 0;  // the trial's record is x's now
     if (cg) {  // conjugate_gradient.py:114-117 history on success only
       std::swap(c->buf[MS_BUF_G], c->buf[MS_BUF_PG]);
       std::swap(c->buf[MS_BUF_D], c->buf[MS_BUF_PD]);
-      c->pd_neg_pg = c->dir_implicit;  // the accepted direction was -G = -PG from now on
-      c->last_g = c->buf[MS_BUF_PG];
-      c->cg_have_history = true;
-      ++c->cg_iter_count;
+      c->carry.pd_neg_pg = c->carry.dir_implicit;  // the accepted direction was -G = -PG from now on
+      c->carry.last_g = c->buf[MS_BUF_PG];
+      c->carry.cg_have_history = true;
+      ++c->carry.cg_iter_count;
     }
     out->success = 1;
     out->alpha = alpha_acc;
@@ -633,7 +615,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     lh.acc[lh.n % ms_ctx::LS_HIST] = alpha_acc;
     lh.rej[lh.n % ms_ctx::LS_HIST] = min_rejected;
     ++lh.n;
-    c->kc_pending = kc_queued;
+    c->carry.kc_pending = kc_queued;
   };
   // the queue needs: carry mode (a trial is a complete energy pass), energies the device can add up the way the
   // host does (surface + bending only), no tilt projections between trials.  The gradient + direction pass of the
@@ -653,7 +635,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   bool adopted = false;
   if (c->ahead.valid) {
     const ms_ctx::Ahead& ah = c->ahead;
-    const bool same = ah.go && can_chain && ah.stepper == sp->stepper && ah.implicit == c->dir_implicit &&
+    const bool same = ah.go && can_chain && ah.stepper == sp->stepper && ah.implicit == c->carry.dir_implicit &&
                       ah.alpha0 == alpha && ah.energy0 == energy0 && ah.beta == sp->beta && ah.c1 == sp->c &&
                       ah.max_iter == max_iter && alpha * max_dir < safe_step_limit;
     if (same) {
@@ -667,7 +649,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   }
   int it = 0;
   bool unchained_ran = false;  // a trial went through the context's own mailbox (its scalars replaced x's there)
-  const bool s_maxg2_x = c->maxg2_valid;
+  const bool s_maxg2_x = c->carry.maxg2_valid;
   while (it < max_iter) {
     const bool safe_small = alpha * max_dir < safe_step_limit;
     kc_queued = false;  // (a gradient pass queued behind an earlier, fully rejected round found its gate closed)
@@ -699,7 +681,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
         if (rc == MS_OK) rc = fetch(c);
         std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);  // (the projected trial is the trial buffer again)
         if (rc) return rc;
-        if (carry_mode) c->factors_valid = false;  // (they belong to the trial point until it is accepted)
+        if (carry_mode) c->carry.factors_valid = false;  // (they belong to the trial point until it is accepted)
       }
       ++out->trials;
       energies_from_mailbox(c, e);
@@ -728,7 +710,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       adopted = false;
       kc_queued = true;  // (queue_round queued it with the round)
       c->kc_stepper = sp->stepper;
-      c->kc_use_history = cg && ((c->cg_iter_count + 1) % restart != 0);
+      c->kc_use_history = next_use_history(c, cg, restart);
       ++c->q_adopted;
     } else {
       plan_round(c, sp, alpha, max_iter - it, out->trials + out->guard_rejects, a_hi, r_lo, ls_warm, lh.pred_trials,
@@ -739,9 +721,9 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       if (rc) return rc;
       kc_queued = true;
       c->kc_stepper = sp->stepper;
-      c->kc_use_history = cg && ((c->cg_iter_count + 1) % restart != 0);
+      c->kc_use_history = next_use_history(c, cg, restart);
     }
-    c->kc_parity = parity;
+    c->carry.kc_parity = parity;
     const int n0 = plan.n0, n_st = plan.n_st, n_round = n0 + n_st;
     const double* const alphas = plan.alphas;
     double rhs[MS_MAX_TRIALS + ms_ctx::SPEC_STAGES];
@@ -761,8 +743,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     double E_acc = 0.0;
     for (int j = 0; j < n0 && acc < 0; ++j) {
       ++out->trials;
-      const double E_t = ((c->params.modules & MS_MOD_SURFACE) ? v[j][MS_S_ESURF] : 0.0) +
-                         ((c->params.modules & MS_MOD_BENDING) ? v[j][MS_S_EBEND] : 0.0);
+      const double E_t = stage_energy(c, v[j]);
       if (E_t <= rhs[j]) {
         acc = j;
         E_acc = E_t;
@@ -802,15 +783,13 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
         HIPCHK(c, hipMemcpyAsync(c->buf[MS_BUF_XT], sx, sizeof(double) * 3 * nvp, hipMemcpyDeviceToDevice, S(c)));
         HIPCHK(c, hipMemcpyAsync(c->buf[MS_BUF_FK], sk, sizeof(double) * 3 * nvp, hipMemcpyDeviceToDevice, S(c)));
         HIPCHK(c, hipMemcpyAsync(c->buf[MS_BUF_FA], sa, sizeof(double) * 2 * nvp, hipMemcpyDeviceToDevice, S(c)));
-        for (int sl = 0; sl < MS_NSCAL; ++sl)
-          if (energy_mask(c->params.modules) & (1u << sl)) put_mailbox(c, sl, v[acc][sl]);
+        adopt_scalars(c, v[acc]);
       }
       accept(alphas[acc], E_acc);
       return MS_OK;
     }
     if (acc == n0 - 1) {
-      for (int sl = 0; sl < MS_NSCAL; ++sl)
-        if (energy_mask(c->params.modules) & (1u << sl)) put_mailbox(c, sl, v[acc][sl]);
+      adopt_scalars(c, v[acc]);
       accept(alphas[acc], E_acc);
       if (c->ahead_allowed) {
         rc = queue_ahead(c, sp, out, tol, carry_mode, cg, restart);
@@ -826,15 +805,13 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       rc = wait_mailbox(c, c->spec[parity][s2 - 1].h_seq, c->spec[parity][s2 - 1].expected, vals, &code);
       if (rc) return rc;
       ++out->trials;
-      const double E_t = ((c->params.modules & MS_MOD_SURFACE) ? vals[MS_S_ESURF] : 0.0) +
-                         ((c->params.modules & MS_MOD_BENDING) ? vals[MS_S_EBEND] : 0.0);
+      const double E_t = stage_energy(c, vals);
       const bool ok = E_t <= rhs[n0 + s2 - 1];
       rc = verify_decision(c, ok ? DEC_ACCEPT_MAIN : DEC_CONTINUE, code, "a gated stage");
       if (rc) return rc;
       if (ok) {  // the device took the same decision from the same doubles: later stages stay out
         for (int s3 = s2; s3 < n_st; ++s3) forget(c->spec[parity][s3]);
-        for (int sl = 0; sl < MS_NSCAL; ++sl)
-          if (energy_mask(c->params.modules) & (1u << sl)) put_mailbox(c, sl, vals[sl]);
+        adopt_scalars(c, vals);
         accept(alphas[n0 + s2 - 1], E_t);
         accepted = true;
       } else {
@@ -861,10 +838,10 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   if (carry_mode && !unchained_ran) {
     // every trial was rejected and x has not moved: G and the host's scalars still describe x (the queued rounds post
     // to mailboxes of their own); only the bending factors in fK / fA and the device scalars are the last trial's
-    c->carry_valid = true;
-    c->grad_valid = !tilt_shape;
-    c->maxg2_valid = s_maxg2_x;
-    c->factors_valid = false;
+    c->carry.carry_valid = true;
+    c->carry.grad_valid = !tilt_shape;
+    c->carry.maxg2_valid = s_maxg2_x;
+    c->carry.factors_valid = false;
   }
   return MS_OK;
 }
@@ -906,8 +883,8 @@ int ms_project_volume_cached(ms_ctx* c, double target, double tol, int max_iter,
     if (std::fabs(delta) < tol) break;
     const double lam = delta / (norm2 + 1e-12);
     HIPCHK(c, launch_axpy_masked(c->til.nv, c->d_vflags, c->buf[MS_BUF_X], g, -lam, c->stream));
-    c->factors_valid = false;
-    c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+    c->carry.factors_valid = false;
+    c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   }
   if (iters_out) *iters_out = it;
   if (volume_out) *volume_out = V;
@@ -1018,9 +995,9 @@ int resident_run(ms_ctx* c, const ms_minimize_params* mp, int max_steps, double 
   }
   // x may have moved, and the launch used the G / GC / D buffers for its own (raw) rows even when it declined its first
   // step: nothing the step logic carries from earlier evaluations is valid any more
-  c->carry_valid = c->grad_valid = c->factors_valid = c->maxg2_valid = c->bt_valid = false;
-  c->kc_pending = false;
-  c->dir_implicit = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.factors_valid = c->carry.maxg2_valid = c->carry.bt_valid = false;
+  c->carry.kc_pending = false;
+  c->carry.dir_implicit = false;
   if (ro->reason == RES_TIMEOUT) return fail(c, MS_ERR_STATE, "resident step kernel: a grid barrier timed out");
   return MS_OK;
 }
@@ -1191,7 +1168,7 @@ int ms_minimize(ms_ctx* c, const ms_minimize_params* mp, int n_steps, ms_minimiz
   if (res_energy_valid) {  // (surface energy of the x the resident kernel ended at: the accepted trial's)
     out->energy_current = res_energy;
     out->energy_current_valid = 1;
-  } else if (c->carry_valid && !(c->params.modules & MS_ANY_TILT_MODS)) {
+  } else if (c->carry.carry_valid && !(c->params.modules & MS_ANY_TILT_MODS)) {
     // the mailbox energies describe the positions the loop ended at: the caller's final energy needs no pass
     double e[4];
     energies_from_mailbox(c, e);

@@ -215,16 +215,14 @@ int tsearch_queue(ms_ctx* c, TsearchArgs& a, uint32_t mask, const double* coefs,
   }
   ++c->tsearch_launches;
   c->tsearch_trials += n;
-  const int s_parity = c->cur_parity, s_pair = c->pair_on;
-  c->cur_parity = second ? 1 : 0;
-  c->pair_on = n > 1 ? n : 0;
-  c->multi_any_slot = true;
+  StageCtl st = c->stage();  // (whatever else the caller's stage says holds for this fold as well)
+  st.cur_parity = second ? 1 : 0;
+  st.pair_on = n > 1 ? n : 0;
+  st.multi_any_slot = true;
+  StageScope scope(c, st);
   if (second) swap_mailbox(c, c->tsearch_mb);
   rc = reduce_slots(c, mask);
   if (second) swap_mailbox(c, c->tsearch_mb);
-  c->multi_any_slot = false;
-  c->pair_on = s_pair;
-  c->cur_parity = s_parity;
   return rc;
 }
 // ... and taken: E[j] = the energy the reference's loop would see at trial j
@@ -243,7 +241,7 @@ int tsearch_take(ms_ctx* c, int n, bool second, double* E) {
   return rc;
 }
 int ensure_bt_record(ms_ctx* c) {
-  if (!(c->params.modules & (MS_MOD_BENDING_TILT | MS_LEAFLET_BT)) || c->bt_valid) return MS_OK;
+  if (!(c->params.modules & (MS_MOD_BENDING_TILT | MS_LEAFLET_BT)) || c->carry.bt_valid) return MS_OK;
   return phase_energy(c, c->params.modules, false, 0.0, false, false, false, /*reduce_now=*/false);
 }
 
@@ -749,8 +747,8 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     if (used) {
       if (iters_out) *iters_out = iters;
       if (evals_out) *evals_out = evals;
-      c->carry_valid = c->grad_valid = false;
-      c->factors_valid = c->factors_valid && !(mods & (MS_MOD_BENDING_TILT | MS_LEAFLET_BT));
+      c->carry.carry_valid = c->carry.grad_valid = false;
+      c->carry.factors_valid = c->carry.factors_valid && !(mods & (MS_MOD_BENDING_TILT | MS_LEAFLET_BT));
       return MS_OK;
     }
   }
@@ -797,8 +795,8 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
   if (iters_out) *iters_out = iters;
   if (evals_out) *evals_out = evals;
   // the tilt-dependent energies in the mailbox belong to whatever was evaluated last
-  c->carry_valid = c->grad_valid = false;
-  c->factors_valid = c->factors_valid && !(mods & (MS_MOD_BENDING_TILT | MS_LEAFLET_BT));
+  c->carry.carry_valid = c->carry.grad_valid = false;
+  c->carry.factors_valid = c->carry.factors_valid && !(mods & (MS_MOD_BENDING_TILT | MS_LEAFLET_BT));
   return MS_OK;
 }
 }  // namespace
@@ -870,7 +868,7 @@ int ms_set_leaflet_tilts(ms_ctx* c, int leaflet, const double* tilts, const uint
     HIPCHK(c, hipStreamSynchronize(S(c)));
     HIPCHK(c, hipMemcpy(c->d_vflags, c->h_vflags.data(), c->h_vflags.size(), hipMemcpyHostToDevice));
   }
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;
   return ext_to_patch(c, tilts, f.tilts, 3);
 }
@@ -895,8 +893,8 @@ int ms_set_leaflet_bending(ms_ctx* c, int leaflet, const double* kappa, const do
   }
   HIPCHK(c, hipMemcpy(f.kappa, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(f.c0, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->factors_valid = false;
-  c->carry_valid = c->grad_valid = c->bt_valid = c->maxg2_valid = false;
+  c->carry.factors_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   return MS_OK;
 }
 
@@ -919,7 +917,7 @@ int ms_set_leaflet_disk_target(ms_ctx* c, int leaflet, const uint8_t* disk_rows,
   HIPCHK(c, hipMemcpy(f.disk, m.data(), m.size(), hipMemcpyHostToDevice));
   f.dt = *p;
   for (int k = 0; k < 3; ++k) f.dt.normal[k] = p->normal[k] / nn;  // tilt_disk_target_in.py:73-77
-  c->carry_valid = c->grad_valid = c->maxg2_valid = false;
+  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;
   return MS_OK;
 }
 

@@ -388,7 +388,7 @@ struct ExecCmdHead {
   int32_t mode;       // template MODE of the tilt-family kernels, launch mode of the stream kernels
   int32_t cap, max_ent;
   int32_t grid;       // blocks of the ordinary launch: the body runs for block 0 .. grid-1 in turn
-  uint32_t inst;      // template instance (energy / gradient: see exec_energy_inst / exec_gradient_inst)
+  uint32_t inst;      // template instance (energy / gradient: encoded by launch_energy / launch_gradient, decoded by exec_dispatch)
   int32_t mesh;       // which DeviceMesh of the pack head the tile kernels' arguments go with
   int32_t pad;
 };

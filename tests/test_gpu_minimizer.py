@@ -848,3 +848,63 @@ def test_rounds_queued_ahead_do_not_change_the_trajectory(volume_row, monkeypatc
         assert st["mismatches"] == 0, stats
     assert stats[0]["rounds"] == 0 and stats[1]["rounds"] > 0 and stats[1]["ahead"] == 0
     assert stats[2]["ahead"] > 0 and stats[2]["adopted"] >= stats[2]["ahead"] - stats[2]["dropped"] > 0, stats
+
+
+def _small_ahead_meshes():
+    from membrane_solver_amd import meshgen
+
+    pos, tri = meshgen.icosphere(24)  # (the mesh of test_pair_launch_does_not_change_the_trajectory: 23 tiles)
+    pos = meshgen.smooth_displace(pos, 0.05)
+    pos = pos + 2.0e-3 * np.random.default_rng(3).standard_normal(pos.shape)
+    g = load_golden("mesh_ico4.npz")  # (one tile: the launches go through the one-workgroup interpreter)
+    return {"ico24": (pos, tri), "ico4": (np.ascontiguousarray(g["positions"]), np.ascontiguousarray(g["tri"]))}
+
+
+@pytest.mark.parametrize("volume_row", [False, True])
+@pytest.mark.parametrize("kind", ["gd", "cg"])
+@pytest.mark.parametrize("mesh_name", ["ico24", "ico4"])
+def test_rounds_queued_ahead_do_not_change_the_trajectory_small(mesh_name, kind, volume_row, monkeypatch):
+    """test_rounds_queued_ahead_do_not_change_the_trajectory at small size (a 23-tile and a one-tile mesh), gradient
+    descent as well as CG: ms_minimize with fixed-order sums without the line-search queue (MS_SPECULATE=0), without
+    rounds queued ahead (MS_AHEAD=0) and by default gives the same step log and positions bit for bit; no decision was
+    replayed differently; rounds were queued ahead and adopted in the default run only.  (Step size 1e-2 and 40 steps:
+    every combination queues and adopts rounds, and the 23-tile mesh and one-tile CG also drop some.)"""
+    from membrane_solver_amd import _lib as L
+    from membrane_solver_amd.device import DeviceMesh
+
+    P, T = _small_ahead_meshes()[mesh_name]
+    nv, nf = len(P), len(T)
+    v0, v1, v2 = P[T[:, 0]], P[T[:, 1]], P[T[:, 2]]
+    V0 = float(np.einsum("ij,ij->i", np.cross(v1, v2), v0).sum() / 6.0)
+    runs = []
+    for env in ({"MS_SPECULATE": "0"}, {"MS_AHEAD": "0"}, {}):
+        for k in ("MS_SPECULATE", "MS_AHEAD"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        dm = DeviceMesh(P, T)
+        dm.set_deterministic(True)
+        dm.set_surface_tension(np.ones(nf))
+        dm.set_bending_params(np.ones(nv), np.full(nv, 0.2))
+        dm.set_params(modules=L.MS_MOD_SURFACE | L.MS_MOD_BENDING | (L.MS_CON_VOLUME if volume_row else 0),
+                      target_volume=V0)
+        mp = L.ms_minimize_params()
+        mp.stepper = L.ms_stepper_params(L.MS_STEPPER_CG if kind == "cg" else L.MS_STEPPER_GD, 10, 0.7, 1e-4, 1.5,
+                                         10.0, 10, 0.0, 2)
+        mp.step_size, mp.tol = 1e-2, 1e-9
+        mp.fixed_step_mode, mp.fixed_step = 0, 1e-2
+        mp.max_zero_steps, mp.step_size_floor = 10, 1e-8
+        out, log = dm.minimize(mp, 40, want_log=True)
+        runs.append((np.array(log), dm.get_positions(), dm.queue_stats()))
+        dm.close()
+    (plain, x_plain, st_plain), (queue, x_queue, st_queue), (ahead, x_ahead, st_ahead) = runs
+    print(mesh_name, kind, volume_row, st_plain, st_queue, st_ahead)
+    assert len(plain) == 40 and plain[:, 0].sum() >= 12 and plain[:, 7].max() >= 2, \
+        "the run is meant to accept steps after backtracking"
+    assert np.array_equal(plain, queue), "the queue changed the trajectory"
+    assert np.array_equal(plain, ahead), "rounds queued ahead changed the trajectory"
+    assert np.array_equal(x_plain, x_queue) and np.array_equal(x_plain, x_ahead)
+    for st in (st_plain, st_queue, st_ahead):
+        assert st["mismatches"] == 0, (st_plain, st_queue, st_ahead)
+    assert st_plain["rounds"] == 0 and st_queue["rounds"] > 0 and st_queue["ahead"] == 0
+    assert st_ahead["ahead"] > 0 and st_ahead["adopted"] >= st_ahead["ahead"] - st_ahead["dropped"] > 0, st_ahead
