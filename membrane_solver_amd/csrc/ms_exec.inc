@@ -56,263 +56,117 @@ __device__ __forceinline__ void exec_plain_args(A& a, ExecCmdHead& h, exec_kptr 
 }
 
 // ---- one function per body ------------------------------------------------------------------------------------------
-template <bool BEND, bool GUARD, bool ATOMIC, bool AREA = false>
-__device__ __noinline__ MS_EXEC_FN void exec_energy(exec_kptr base_v, int off_v, double* lds) {
+// A record of a tile kernel: body(a, h, lds, b) for block 0 .. h.grid-1 in turn, a barrier after each.  Instantiated once
+// per body (every lambda below is a type of its own), never inlined.
+template <typename A, typename Body>
+__device__ __noinline__ MS_EXEC_FN void exec_tile(exec_kptr base_v, int off_v, double* lds, Body body) {
   const exec_kptr base = exec_uniform_ptr(base_v);
   const int off = exec_uniform(off_v);
-  EnergyArgs a;
+  A a;
   ExecCmdHead h;
   exec_tile_args(a, h, base, off);
   for (int b = 0; b < h.grid; ++b) {
-    EnergyArgs c = a;
-    energy_body<BEND, GUARD, 256, 0, ATOMIC, 0, AREA>(c, h.cap, h.max_ent, lds, b);
+    body(a, h, lds, b);
     __syncthreads();
   }
 }
-template <int BENDMODE, bool VOLROW, int TT, bool ATOMIC, bool LEAN, bool AREA = false>
-__device__ __noinline__ MS_EXEC_FN void exec_gradient(exec_kptr base_v, int off_v, double* lds) {
+// A record of a stream kernel.  EXEC_PER_BLOCK: as above; EXEC_BLOCKS: the blocks touch disjoint rows, one barrier
+// after the last; EXEC_ONCE: body(a, h, h.grid) covers the whole launch itself.
+enum ExecLoop { EXEC_PER_BLOCK, EXEC_BLOCKS, EXEC_ONCE };
+template <typename A, ExecLoop LOOP, typename Body>
+__device__ __noinline__ MS_EXEC_FN void exec_plain(exec_kptr base_v, int off_v, Body body) {
   const exec_kptr base = exec_uniform_ptr(base_v);
   const int off = exec_uniform(off_v);
-  GradientArgs a;
-  ExecCmdHead h;
-  exec_tile_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    gradient_body<BENDMODE, VOLROW, TT, 0, ATOMIC, LEAN, AREA>(a, h.cap, h.max_ent, lds, b);
-    __syncthreads();
-  }
-}
-template <int MODE>
-__device__ __noinline__ MS_EXEC_FN void exec_tilt(exec_kptr base_v, int off_v, double* lds) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  TiltArgs a;
-  ExecCmdHead h;
-  exec_tile_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    tilt_body<MODE>(a, h.cap, h.max_ent, lds, b);
-    __syncthreads();
-  }
-}
-template <int MODE>
-__device__ __noinline__ MS_EXEC_FN void exec_bt(exec_kptr base_v, int off_v, double* lds) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  BtArgs a;
-  ExecCmdHead h;
-  exec_tile_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    bt_body<MODE>(a, h.cap, h.max_ent, lds, b);
-    __syncthreads();
-  }
-}
-template <int MODE>
-__device__ __noinline__ MS_EXEC_FN void exec_ts(exec_kptr base_v, int off_v, double* lds) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  TsArgs a;
-  ExecCmdHead h;
-  exec_tile_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    ts_body<MODE>(a, h.cap, h.max_ent, lds, b);
-    __syncthreads();
-  }
-}
-template <int NF>
-__device__ __noinline__ MS_EXEC_FN void exec_tsearch(exec_kptr base_v, int off_v, double* lds) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  TsearchArgs a;
-  ExecCmdHead h;
-  exec_tile_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    tsearch_body<NF, 1>(a, h.cap, lds, b);
-    __syncthreads();
-  }
-}
-__device__ __noinline__ MS_EXEC_FN void exec_tvec(exec_kptr base_v, int off_v) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  TvecArgs a;
+  A a;
   ExecCmdHead h;
   exec_plain_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    tvec_body(a, b);
-    __syncthreads();
+  if constexpr (LOOP == EXEC_ONCE) {
+    body(a, h, h.grid);
+  } else {
+    for (int b = 0; b < h.grid; ++b) {
+      body(a, h, b);
+      if constexpr (LOOP == EXEC_PER_BLOCK) __syncthreads();
+    }
   }
-}
-__device__ __noinline__ MS_EXEC_FN void exec_disk(exec_kptr base_v, int off_v) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  DiskTargetArgs a;
-  ExecCmdHead h;
-  exec_plain_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    disk_target_body(a, h.mode, b);
-    __syncthreads();
-  }
-}
-__device__ __noinline__ MS_EXEC_FN void exec_reduce(exec_kptr base_v, int off_v) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  FoldArgs a;
-  ExecCmdHead h;
-  exec_plain_args(a, h, base, off);
-  // (one tile: every task of the fold at once, thread t = task t; ExecRecorder only exists for one-tile contexts)
-  reduce_one_tile(a, h.grid);
-  __syncthreads();
-}
-__device__ __noinline__ MS_EXEC_FN void exec_direction(exec_kptr base_v, int off_v) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  DirectionArgs a;
-  ExecCmdHead h;
-  exec_plain_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    direction_body(a, b);
-    __syncthreads();
-  }
-}
-__device__ __noinline__ MS_EXEC_FN void exec_row_dot(exec_kptr base_v, int off_v) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  RowDotArgs a;
-  ExecCmdHead h;
-  exec_plain_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) {
-    row_dot_body(a, b);
-    __syncthreads();
-  }
-}
-__device__ __noinline__ MS_EXEC_FN void exec_axpy_masked(exec_kptr base_v, int off_v) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  AxpyMaskedArgs a;
-  ExecCmdHead h;
-  exec_plain_args(a, h, base, off);
-  for (int b = 0; b < h.grid; ++b) axpy_masked_body(a, b);
-  __syncthreads();
-}
-__device__ __noinline__ MS_EXEC_FN void exec_memset(exec_kptr base_v, int off_v) {
-  const exec_kptr base = exec_uniform_ptr(base_v);
-  const int off = exec_uniform(off_v);
-  ExecMemsetArgs a;
-  ExecCmdHead h;
-  exec_plain_args(a, h, base, off);
-  for (int64_t i = threadIdx.x; i < a.n; i += blockDim.x) a.p[i] = 0.0;
-  __syncthreads();
+  if constexpr (LOOP != EXEC_PER_BLOCK) __syncthreads();
 }
 
-// one record
+// one record (ExecRecorder::push has refused an energy / gradient instance that visit_instance<true> does not have)
 __device__ __forceinline__ void exec_dispatch(exec_kptr base, int off, double* lds) {
   ExecCmdHead h;
   exec_load<0>(h, base + off);
   switch (h.kind) {
-    case CK_ENERGY: {
-      // inst: bit0 bending, bit1 guard, bit2 LDS-atomic vertex sums, bit3 body area (body_area_penalty)
-      switch (h.inst & 15u) {
-        case 0: exec_energy<false, false, false>(base, off, lds); break;
-        case 2: exec_energy<false, true, false>(base, off, lds); break;
-        case 1: exec_energy<true, false, false>(base, off, lds); break;
-        case 3: exec_energy<true, true, false>(base, off, lds); break;
-        case 5: exec_energy<true, false, true>(base, off, lds); break;
-        case 7: exec_energy<true, true, true>(base, off, lds); break;
-        case 8: exec_energy<false, false, false, true>(base, off, lds); break;
-        case 10: exec_energy<false, true, false, true>(base, off, lds); break;
-        case 9: exec_energy<true, false, false, true>(base, off, lds); break;
-        case 11: exec_energy<true, true, false, true>(base, off, lds); break;
-        case 13: exec_energy<true, false, true, true>(base, off, lds); break;
-        case 15: exec_energy<true, true, true, true>(base, off, lds); break;
-        default: break;  // (atomic without bending is never recorded)
-      }
+    case CK_ENERGY:
+      visit_instance<true>(EnergyInst::from_code(h.inst), [&](auto tag) {
+        using I = decltype(tag);
+        exec_tile<EnergyArgs>(base, off, lds, [](const EnergyArgs& a, const ExecCmdHead& h, double* lds, int b) {
+          EnergyArgs c = a;  // (energy_body changes its arguments: every block starts from the record's)
+          energy_body<I::d.bend, I::d.guard, 256, 0, I::d.atomic, 0, I::d.area>(c, h.cap, h.max_ent, lds, b);
+        });
+      });
       break;
-    }
-    case CK_GRADIENT: {
-      // inst: bit0 lean, bit1 constraint row, bit2 LDS-atomic vertex sums, bit3 body-area penalty term (never lean, never
-      // mode 3), bits 4-5 bending mode
-      const uint32_t lean = h.inst & 1u, vr = (h.inst >> 1) & 1u, at = (h.inst >> 2) & 1u, mode = (h.inst >> 4) & 3u;
-      const uint32_t ar = (h.inst >> 3) & 1u;
-#define MS_EXEC_GA(M)                                                                 \
-  do {                                                                                \
-    if (vr) {                                                                         \
-      if (at) exec_gradient<M, true, 256, true, false, true>(base, off, lds);         \
-      else exec_gradient<M, true, 256, false, false, true>(base, off, lds);           \
-    } else {                                                                          \
-      if (at) exec_gradient<M, false, 256, true, false, true>(base, off, lds);        \
-      else exec_gradient<M, false, 256, false, false, true>(base, off, lds);          \
-    }                                                                                 \
-  } while (0)
-      if (ar) {
-        if (mode == 0) MS_EXEC_GA(0); else if (mode == 1) MS_EXEC_GA(1); else if (mode == 2) MS_EXEC_GA(2);
-        break;
-      }
-#undef MS_EXEC_GA
-#define MS_EXEC_G(M, TT)                                                              \
-  do {                                                                                \
-    if (vr) {                                                                         \
-      if (at) exec_gradient<M, true, TT, true, false>(base, off, lds);                      \
-      else exec_gradient<M, true, TT, false, false>(base, off, lds);                        \
-    } else {                                                                          \
-      if (at) exec_gradient<M, false, TT, true, false>(base, off, lds);                     \
-      else exec_gradient<M, false, TT, false, false>(base, off, lds);                       \
-    }                                                                                 \
-  } while (0)
-      if (lean) {
-        if (vr) {
-          if (at) exec_gradient<1, true, 256, true, true>(base, off, lds);
-          else exec_gradient<1, true, 256, false, true>(base, off, lds);
-        } else {
-          if (at) exec_gradient<1, false, 256, true, true>(base, off, lds);
-          else exec_gradient<1, false, 256, false, true>(base, off, lds);
-        }
-      } else if (mode == 0) {
-        MS_EXEC_G(0, 256);
-      } else if (mode == 1) {
-        MS_EXEC_G(1, 256);
-      } else if (mode == 2) {
-        MS_EXEC_G(2, 256);
-      } else {
-        MS_EXEC_G(3, 0);
-      }
-#undef MS_EXEC_G
+    case CK_GRADIENT:
+      visit_instance<true>(GradientInst::from_code(h.inst), [&](auto tag) {
+        using I = decltype(tag);
+        exec_tile<GradientArgs>(base, off, lds, [](const GradientArgs& a, const ExecCmdHead& h, double* lds, int b) {
+          gradient_body<I::d.mode, I::d.volrow, I::d.fast ? 256 : 0, 0, I::d.atomic, I::d.lean, I::d.area>(a, h.cap, h.max_ent, lds, b);
+        });
+      });
       break;
-    }
     case CK_TILT:
-      switch (h.mode) {
-        case 0: exec_tilt<0>(base, off, lds); break;
-        case 1: exec_tilt<1>(base, off, lds); break;
-        case 2: exec_tilt<2>(base, off, lds); break;
-        case 3: exec_tilt<3>(base, off, lds); break;
-        case 4: exec_tilt<4>(base, off, lds); break;
-        default: exec_tilt<5>(base, off, lds); break;
-      }
+      pick_int<0, 1, 2, 3, 4, 5>(h.mode, [&](auto M) {
+        exec_tile<TiltArgs>(base, off, lds, [](const TiltArgs& a, const ExecCmdHead& h, double* lds, int b) {
+          tilt_body<decltype(M)::value>(a, h.cap, h.max_ent, lds, b);
+        });
+      });
       break;
     case CK_BT:
-      switch (h.mode) {
-        case 0: exec_bt<0>(base, off, lds); break;
-        case 1: exec_bt<1>(base, off, lds); break;
-        case 2: exec_bt<2>(base, off, lds); break;
-        default: exec_bt<3>(base, off, lds); break;
-      }
+      pick_int<0, 1, 2, 3>(h.mode, [&](auto M) {
+        exec_tile<BtArgs>(base, off, lds, [](const BtArgs& a, const ExecCmdHead& h, double* lds, int b) {
+          bt_body<decltype(M)::value>(a, h.cap, h.max_ent, lds, b);
+        });
+      });
       break;
     case CK_TS:
-      switch (h.mode) {
-        case 0: exec_ts<0>(base, off, lds); break;
-        case 1: exec_ts<1>(base, off, lds); break;
-        default: exec_ts<2>(base, off, lds); break;
-      }
+      pick_int<0, 1, 2>(h.mode, [&](auto M) {
+        exec_tile<TsArgs>(base, off, lds, [](const TsArgs& a, const ExecCmdHead& h, double* lds, int b) {
+          ts_body<decltype(M)::value>(a, h.cap, h.max_ent, lds, b);
+        });
+      });
       break;
-    case CK_TVEC: exec_tvec(base, off); break;
-    case CK_DISK: exec_disk(base, off); break;
-    case CK_REDUCE: exec_reduce(base, off); break;
-    case CK_DIRECTION: exec_direction(base, off); break;
-    case CK_ROWDOT: exec_row_dot(base, off); break;
-    case CK_AXPY_MASKED: exec_axpy_masked(base, off); break;
-    case CK_MEMSET: exec_memset(base, off); break;
     case CK_TSEARCH:
-      if (h.mode == 1) exec_tsearch<1>(base, off, lds);
-      else exec_tsearch<2>(base, off, lds);
+      pick_int<1, 2>(h.mode, [&](auto NF) {
+        exec_tile<TsearchArgs>(base, off, lds, [](const TsearchArgs& a, const ExecCmdHead& h, double* lds, int b) {
+          tsearch_body<decltype(NF)::value, 1>(a, h.cap, lds, b);
+        });
+      });
       break;
-    default: break;
+    case CK_TVEC:
+      exec_plain<TvecArgs, EXEC_PER_BLOCK>(base, off, [](const TvecArgs& a, const ExecCmdHead&, int b) { tvec_body(a, b); });
+      break;
+    case CK_DISK:
+      exec_plain<DiskTargetArgs, EXEC_PER_BLOCK>(
+          base, off, [](const DiskTargetArgs& a, const ExecCmdHead& h, int b) { disk_target_body(a, h.mode, b); });
+      break;
+    case CK_REDUCE:
+      // (one tile: every task of the fold at once, thread t = task t; ExecRecorder only exists for one-tile contexts)
+      exec_plain<FoldArgs, EXEC_ONCE>(base, off, [](const FoldArgs& a, const ExecCmdHead&, int grid) { reduce_one_tile(a, grid); });
+      break;
+    case CK_DIRECTION:
+      exec_plain<DirectionArgs, EXEC_PER_BLOCK>(base, off, [](const DirectionArgs& a, const ExecCmdHead&, int b) { direction_body(a, b); });
+      break;
+    case CK_ROWDOT:
+      exec_plain<RowDotArgs, EXEC_PER_BLOCK>(base, off, [](const RowDotArgs& a, const ExecCmdHead&, int b) { row_dot_body(a, b); });
+      break;
+    case CK_AXPY_MASKED:
+      exec_plain<AxpyMaskedArgs, EXEC_BLOCKS>(base, off, [](const AxpyMaskedArgs& a, const ExecCmdHead&, int b) { axpy_masked_body(a, b); });
+      break;
+    case CK_MEMSET:
+      exec_plain<ExecMemsetArgs, EXEC_ONCE>(base, off, [](const ExecMemsetArgs& a, const ExecCmdHead&, int) {
+        for (int64_t i = threadIdx.x; i < a.n; i += blockDim.x) a.p[i] = 0.0;
+      });
+      break;
+    default: break;  // (CK_RELAX / CK_RELAX_FUSED: k_exec runs them itself)
   }
 }
 
@@ -514,6 +368,9 @@ hipError_t ExecRecorder::push(uint16_t kind, int mode, int cap, int max_ent, int
   const size_t skip = mesh ? sizeof(DeviceMesh) : 0;
   const size_t rec = sizeof(ExecCmdHead) + ((bytes - skip + 7) & ~(size_t)7);
   if (sizeof(ExecPackHead) + rec > (size_t)EXEC_PACK_BYTES) return hipErrorInvalidValue;
+  // (an instance exec_dispatch does not have would run nothing)
+  if (kind == CK_ENERGY && !EnergyInst::from_code(inst).in_exec()) return hipErrorInvalidValue;
+  if (kind == CK_GRADIENT && !GradientInst::from_code(inst).in_exec()) return hipErrorInvalidValue;
   const size_t limit = capture ? (size_t)EXEC_PACK_BIG : (size_t)EXEC_PACK_BYTES;
   for (int attempt = 0; attempt < 2; ++attempt) {
     if (buf.empty()) {

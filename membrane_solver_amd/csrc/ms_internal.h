@@ -388,11 +388,74 @@ struct ExecCmdHead {
   int32_t mode;       // template MODE of the tilt-family kernels, launch mode of the stream kernels
   int32_t cap, max_ent;
   int32_t grid;       // blocks of the ordinary launch: the body runs for block 0 .. grid-1 in turn
-  uint32_t inst;      // template instance (energy / gradient: encoded by launch_energy / launch_gradient, decoded by exec_dispatch)
+  uint32_t inst;      // template instance (energy / gradient: EnergyInst::code() / GradientInst::code())
   int32_t mesh;       // which DeviceMesh of the pack head the tile kernels' arguments go with
   int32_t pad;
 };
 static_assert(sizeof(ExecCmdHead) == 32, "ExecCmdHead is 32 bytes");
+
+// Which template instance of the energy / gradient kernels runs.  energy_instance() / gradient_instance() choose one
+// from the arguments, visit_instance() (ms_kernels.hip) turns it into template parameters for the launchers and for
+// k_exec alike, valid() is the list of instances that are compiled, in_exec() the part of it k_exec has, and code() is
+// ExecCmdHead::inst (what ms_exec_trace reports).
+struct EnergyInst {
+  bool bend, guard, atomic, area, fast;  // fast: the T = 256 instances
+  int multi;                             // trial positions per launch: 0 (one), 2, 3 or 8
+  constexpr bool valid() const {
+    return (bend || !atomic) && (multi == 0 || ((multi == 2 || multi == 3 || multi == 8) && bend && !guard && !area));
+  }
+  constexpr bool in_exec() const { return valid() && fast && multi == 0; }
+  // bit 0 bending, bit 1 guard, bit 2 LDS-atomic vertex sums, bit 3 body area (body_area_penalty)
+  constexpr uint32_t code() const { return (bend ? 1u : 0u) | (guard ? 2u : 0u) | (atomic ? 4u : 0u) | (area ? 8u : 0u); }
+  static constexpr EnergyInst from_code(uint32_t c) {
+    return {(c & 1u) != 0, (c & 2u) != 0, (c & 4u) != 0, (c & 8u) != 0, true, c < 16u ? 0 : -1};
+  }
+  constexpr bool operator==(const EnergyInst& o) const {
+    return bend == o.bend && guard == o.guard && atomic == o.atomic && area == o.area && fast == o.fast && multi == o.multi;
+  }
+};
+struct GradientInst {
+  int mode;  // bending: 0 none, 1 analytic, 2 approx, 3 leaflet bending_tilt (generic-size instances only)
+  bool volrow, atomic, lean, area, fast;
+  constexpr bool valid() const {
+    return mode >= 0 && mode <= 3 && (!lean || (mode == 1 && fast && !area)) && (mode != 3 || (!area && !fast));
+  }
+  constexpr bool in_exec() const { return valid() && (fast || mode == 3); }
+  // bit 0 lean, bit 1 constraint row, bit 2 LDS-atomic vertex sums, bit 3 body-area penalty term, bits 4-5 bending mode
+  constexpr uint32_t code() const {
+    return (lean ? 1u : 0u) | (volrow ? 2u : 0u) | (atomic ? 4u : 0u) | (area ? 8u : 0u) | ((uint32_t)mode << 4);
+  }
+  static constexpr GradientInst from_code(uint32_t c) {
+    return {c < 64u ? (int)(c >> 4) : -1, (c & 2u) != 0, (c & 4u) != 0, (c & 1u) != 0, (c & 8u) != 0, (c >> 4) != 3u};
+  }
+  constexpr bool operator==(const GradientInst& o) const {
+    return mode == o.mode && volrow == o.volrow && atomic == o.atomic && lean == o.lean && area == o.area && fast == o.fast;
+  }
+};
+// every instance k_exec has is its own code's instance, and every code is either refused or the code of its instance
+constexpr bool inst_codes_round_trip() {
+  for (uint32_t c = 0; c < 64u; ++c) {
+    const EnergyInst e = EnergyInst::from_code(c);
+    const GradientInst g = GradientInst::from_code(c);
+    if (e.in_exec() != e.valid() || (e.in_exec() && e.code() != c)) return false;
+    if (g.in_exec() != g.valid() || (g.in_exec() && g.code() != c)) return false;
+  }
+  for (uint32_t b = 0; b < 32u; ++b)
+    for (int m = 0; m < 4; ++m) {
+      const EnergyInst e = {(b & 1u) != 0, (b & 2u) != 0, (b & 4u) != 0, (b & 8u) != 0, (b & 16u) != 0, m == 0 ? 0 : (m == 3 ? 8 : m + 1)};
+      const GradientInst g = {m, (b & 1u) != 0, (b & 2u) != 0, (b & 4u) != 0, (b & 8u) != 0, (b & 16u) != 0};
+      if (e.in_exec() && !(EnergyInst::from_code(e.code()) == e)) return false;
+      if (g.in_exec() && !(GradientInst::from_code(g.code()) == g)) return false;
+    }
+  return true;
+}
+static_assert(inst_codes_round_trip(), "EnergyInst / GradientInst: code() and from_code() are inverses on k_exec's instances");
+static_assert(EnergyInst{true, true, true, true, true, 0}.code() == 15u && EnergyInst{true, false, true, false, true, 0}.code() == 5u &&
+                  EnergyInst{false, true, false, false, true, 0}.code() == 2u && EnergyInst{true, false, false, true, true, 0}.code() == 9u,
+              "ExecCmdHead::inst of an energy record: bend 1, guard 2, atomic 4, area 8");
+static_assert(GradientInst{1, true, true, true, false, true}.code() == 0x17u && GradientInst{3, false, false, false, false, false}.code() == 0x30u &&
+                  GradientInst{1, true, false, false, true, true}.code() == 0x1au && GradientInst{2, false, false, false, false, true}.code() == 0x20u,
+              "ExecCmdHead::inst of a gradient record: lean 1, volrow 2, atomic 4, area 8, mode << 4");
 constexpr int EXEC_MESHES = 3;       // distinct DeviceMesh values per pack (plain, inner leaflet, outer leaflet)
 constexpr int EXEC_PACK_BYTES = 3968;  // kernel-argument block of one k_exec launch (HIP allows 4096)
 struct ExecPackHead {
@@ -517,7 +580,10 @@ size_t energy_lds_bytes(int T, int cap, int max_ent, bool bend, bool guard, bool
 size_t gradient_lds_bytes(int T, int cap, int max_ent, bool bend, bool volrow, bool atomic = false, bool leaf = false);
 hipError_t launch_energy(const EnergyArgs& a, bool guard, int cap, int max_ent, hipStream_t s);
 hipError_t launch_gradient(const GradientArgs& a, int cap, int max_ent, hipStream_t s);
-bool gradient_lean_instance(const GradientArgs& a);  // which k_gradient instantiation launch_gradient picks
+// which instantiation the launchers pick; !valid() for arguments they refuse (hipErrorInvalidValue)
+EnergyInst energy_instance(const EnergyArgs& a, bool guard);
+GradientInst gradient_instance(const GradientArgs& a);
+bool gradient_lean_instance(const GradientArgs& a);  // gradient_instance(a).lean
 // mode 0: energy partial (MS_S_ETILT); 1: energy + gradients; 2: project tilts to tangent
 size_t tilt_lds_bytes(int T, int cap, int max_ent, bool consistent = false, int mode = 1);
 hipError_t launch_tilt(const TiltArgs& a, int mode, int cap, int max_ent, hipStream_t s);

@@ -24,6 +24,7 @@
 #include <cstring>
 #include <ctime>
 #include <mutex>
+#include <type_traits>
 
 #include "ms_internal.h"
 
@@ -955,6 +956,31 @@ static hipError_t ensure_lds(K kernel, size_t lds) {
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
+// one launch: the LDS attribute where the request needs it, the launch, its error
+template <typename K, typename... Args>
+static hipError_t launch(K kernel, int grid, int block, size_t lds, hipStream_t s, const Args&... args) {
+  if (const hipError_t e = ensure_lds(kernel, lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, s, args...);
+  return hipGetLastError();
+}
+
+// A runtime value as a compile-time one: f(std::bool_constant<v>{}) / f(std::integral_constant<int, v>{}) for the value
+// that matches (pick_int: the last one listed also stands for anything not listed).
+template <typename F>
+__host__ __device__ __forceinline__ auto pick(bool v, F&& f) {
+  if (v) return f(std::true_type{});
+  return f(std::false_type{});
+}
+template <int V0, int... Vs, typename F>
+__host__ __device__ __forceinline__ auto pick_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) {
+    return f(std::integral_constant<int, V0>{});
+  } else {
+    if (v == V0) return f(std::integral_constant<int, V0>{});
+    return pick_int<Vs...>(v, f);
+  }
+}
+
 constexpr int FAST_T = 256;  // specialised tile size (LDS staging offsets become immediates)
 constexpr int FAST_CAP = 0;  // patch capacity stays a runtime value: a fixed 512 slots would push
                              // the gradient kernel from 3 to 2 workgroups per CU (LDS)
@@ -970,11 +996,64 @@ static int abl_ntiles() {
 #endif
 }
 
-hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_ent, hipStream_t s) {
-  EnergyArgs a = a_in;
-  if (abl_ntiles() > 0) a.tile1 = std::min(a.tile1, a.tile0 + abl_ntiles());
-  const int nb = a.tile1 - a.tile0;
-  if (nb <= 0) return hipSuccess;
+// The instance descriptors as types, and the one place that maps a runtime descriptor onto them: f(tag) runs for the
+// instance d names, the return value says whether there is one (EXEC: among those k_exec has).  Only what valid() /
+// in_exec() lists is ever instantiated.
+template <bool BEND, bool GUARD, bool ATOMIC, bool AREA, bool FAST, int MULTI>
+struct EnergyTag {
+  static constexpr EnergyInst d{BEND, GUARD, ATOMIC, AREA, FAST, MULTI};
+};
+template <int MODE, bool VOLROW, bool ATOMIC, bool LEAN, bool AREA, bool FAST>
+struct GradientTag {
+  static constexpr GradientInst d{MODE, VOLROW, ATOMIC, LEAN, AREA, FAST};
+};
+template <bool EXEC, typename I, typename F>
+__host__ __device__ __forceinline__ bool visit_tag(F&& f) {
+  if constexpr (EXEC ? I::d.in_exec() : I::d.valid()) {
+    f(I{});
+    return true;
+  } else {
+    return false;
+  }
+}
+template <bool EXEC, typename F>
+__host__ __device__ __forceinline__ bool visit_instance(const EnergyInst& d, F&& f) {
+  if (!(EXEC ? d.in_exec() : d.valid())) return false;
+  return pick(d.bend, [&](auto B) {
+    return pick(d.guard, [&](auto G) {
+      return pick(d.atomic, [&](auto AT) {
+        return pick(d.area, [&](auto AR) {
+          return pick(d.fast, [&](auto FA) {
+            return pick_int<0, 2, 3, 8>(d.multi, [&](auto NM) {
+              return visit_tag<EXEC, EnergyTag<decltype(B)::value, decltype(G)::value, decltype(AT)::value,
+                                               decltype(AR)::value, decltype(FA)::value, decltype(NM)::value>>(f);
+            });
+          });
+        });
+      });
+    });
+  });
+}
+template <bool EXEC, typename F>
+__host__ __device__ __forceinline__ bool visit_instance(const GradientInst& d, F&& f) {
+  if (!(EXEC ? d.in_exec() : d.valid())) return false;
+  return pick_int<0, 1, 2, 3>(d.mode, [&](auto M) {
+    return pick(d.volrow, [&](auto V) {
+      return pick(d.atomic, [&](auto AT) {
+        return pick(d.lean, [&](auto LE) {
+          return pick(d.area, [&](auto AR) {
+            return pick(d.fast, [&](auto FA) {
+              return visit_tag<EXEC, GradientTag<decltype(M)::value, decltype(V)::value, decltype(AT)::value,
+                                                 decltype(LE)::value, decltype(AR)::value, decltype(FA)::value>>(f);
+            });
+          });
+        });
+      });
+    });
+  });
+}
+
+EnergyInst energy_instance(const EnergyArgs& a, bool guard) {
   const bool bend = (a.modules & (MS_MOD_BENDING | MS_MOD_BENDING_TILT)) != 0;
   const bool fast = a.m.T == FAST_T && a.m.tile_facets32 != nullptr && !a.m.no_fast;  // (T = 256 instances: packed records)
   // atomic: per-vertex sums by LDS ds_add_f64 instead of the staged CSR gather -- one barrier per
@@ -982,86 +1061,39 @@ hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_en
   // varies from run to run (ms_set_deterministic).  Without bending there are no vertex sums.
   const bool atomic = a.atomic != 0 && bend;
   const bool area = (a.modules & MS_MOD_AREA_PENALTY) != 0;  // (the k_energy_area instances)
-  if (area && a.pair) return hipErrorInvalidValue;  // (multi-trial launches belong to the device-decided queue: never with it)
+  // pair launch: bending factors on, no guard (the caller checked both), never with body_area_penalty (multi-trial
+  // launches belong to the device-decided queue), 2..MS_MAX_TRIALS trials -- valid() refuses the rest
+  const int multi = !a.pair ? 0 : ((a.pair < 2 || a.pair > MS_MAX_TRIALS) ? -1 : (a.pair == 2 ? 2 : (a.pair == 3 ? 3 : 8)));
+  return {bend, guard, atomic, area, fast, multi};
+}
+
+hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_ent, hipStream_t s) {
+  EnergyArgs a = a_in;
+  if (abl_ntiles() > 0) a.tile1 = std::min(a.tile1, a.tile0 + abl_ntiles());
+  const int nb = a.tile1 - a.tile0;
+  if (nb <= 0) return hipSuccess;
+  const EnergyInst d = energy_instance(a, guard);
+  if (!d.valid()) return hipErrorInvalidValue;
   // MS_KA_LDS_MIN=<bytes> (variant builds only): request at least this much LDS per workgroup (caps the workgroups per CU)
   static const size_t lds_min = variant_env("MS_KA_LDS_MIN") ? (size_t)atol(variant_env("MS_KA_LDS_MIN")) : 0;
-  const size_t lds = std::max(lds_min, energy_lds_bytes(a.m.T, cap, max_ent, bend, guard, a.m.has_boundary != 0, atomic));
-  hipError_t e;
+  const size_t lds = std::max(lds_min, energy_lds_bytes(a.m.T, cap, max_ent, d.bend, guard, a.m.has_boundary != 0, d.atomic));
   if (ExecRecorder* r = exec_find(s)) {
     // one-workgroup interpreter: the T = 256 instances, one trial per launch (the context switched multi-trial launches
     // off); anything else runs as an ordinary launch behind what has been recorded
-    if (fast && !a.pair)
-      return r->push(CK_ENERGY, 0, cap, max_ent, nb, (bend ? 1u : 0u) | (guard ? 2u : 0u) | (atomic ? 4u : 0u) | (area ? 8u : 0u), lds, &a,
-                     sizeof(a), &a.m);
-    e = r->flush();
-    if (e != hipSuccess) return e;
+    if (d.in_exec()) return r->push(CK_ENERGY, 0, cap, max_ent, nb, d.code(), lds, &a, sizeof(a), &a.m);
+    if (const hipError_t e = r->flush(); e != hipSuccess) return e;
   }
-#define MS_LAUNCH_E(B, G, TT, CC, AT)                                                              \
-  do {                                                                                             \
-    e = ensure_lds(k_energy<B, G, TT, CC, AT>, lds);                                               \
-    if (e != hipSuccess) return e;                                                                 \
-    hipLaunchKernelGGL((k_energy<B, G, TT, CC, AT>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent); \
-  } while (0)
-#define MS_PICK_E(B, G, AT)                               \
-  do {                                                    \
-    if (fast) MS_LAUNCH_E(B, G, FAST_T, FAST_CAP, AT);    \
-    else MS_LAUNCH_E(B, G, 0, 0, AT);                     \
-  } while (0)
-  if (a.pair) {
-    // pair launch: bending factors on, no guard (the caller checked both)
-    if (!bend || guard) return hipErrorInvalidValue;
-    if (a.pair < 2 || a.pair > MS_MAX_TRIALS) return hipErrorInvalidValue;
-    const int nb2 = a.pair * NXCD * ((nb + NXCD - 1) / NXCD);
-#define MS_LAUNCH_P(TT, CC, AT, NM)                                                                          \
-  do {                                                                                                       \
-    e = ensure_lds(k_energy<true, false, TT, CC, AT, NM>, lds);                                              \
-    if (e != hipSuccess) return e;                                                                           \
-    hipLaunchKernelGGL((k_energy<true, false, TT, CC, AT, NM>), dim3(nb2), dim3(a.m.T), lds, s, a, cap, max_ent); \
-  } while (0)
-#define MS_PICK_P(NM)                                                                  \
-  do {                                                                                 \
-    if (atomic) {                                                                      \
-      if (fast) MS_LAUNCH_P(FAST_T, FAST_CAP, true, NM); else MS_LAUNCH_P(0, 0, true, NM);   \
-    } else {                                                                           \
-      if (fast) MS_LAUNCH_P(FAST_T, FAST_CAP, false, NM); else MS_LAUNCH_P(0, 0, false, NM); \
-    }                                                                                  \
-  } while (0)
-    if (a.pair == 2) MS_PICK_P(2); else if (a.pair == 3) MS_PICK_P(3); else MS_PICK_P(8);
-#undef MS_PICK_P
-#undef MS_LAUNCH_P
-    return hipGetLastError();
-  }
-  if (area) {
-#define MS_LAUNCH_EA(B, G, TT, CC, AT)                                                                  \
-  do {                                                                                                  \
-    e = ensure_lds(k_energy_area<B, G, TT, CC, AT>, lds);                                               \
-    if (e != hipSuccess) return e;                                                                      \
-    hipLaunchKernelGGL((k_energy_area<B, G, TT, CC, AT>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent); \
-  } while (0)
-#define MS_PICK_EA(B, G, AT)                               \
-  do {                                                     \
-    if (fast) MS_LAUNCH_EA(B, G, FAST_T, FAST_CAP, AT);    \
-    else MS_LAUNCH_EA(B, G, 0, 0, AT);                     \
-  } while (0)
-    if (bend && atomic) {
-      if (guard) MS_PICK_EA(true, true, true); else MS_PICK_EA(true, false, true);
-    } else if (bend) {
-      if (guard) MS_PICK_EA(true, true, false); else MS_PICK_EA(true, false, false);
-    } else {
-      if (guard) MS_PICK_EA(false, true, false); else MS_PICK_EA(false, false, false);
-    }
-#undef MS_PICK_EA
-#undef MS_LAUNCH_EA
-  } else if (bend && atomic) {
-    if (guard) MS_PICK_E(true, true, true); else MS_PICK_E(true, false, true);
-  } else if (bend) {
-    if (guard) MS_PICK_E(true, true, false); else MS_PICK_E(true, false, false);
-  } else {
-    if (guard) MS_PICK_E(false, true, false); else MS_PICK_E(false, false, false);
-  }
-#undef MS_PICK_E
-#undef MS_LAUNCH_E
-  return hipGetLastError();
+  const int grid = d.multi ? a.pair * NXCD * ((nb + NXCD - 1) / NXCD) : nb;
+  hipError_t e = hipErrorInvalidValue;
+  visit_instance<false>(d, [&](auto tag) {
+    using I = decltype(tag);
+    constexpr int TT = I::d.fast ? FAST_T : 0, CC = I::d.fast ? FAST_CAP : 0;
+    if constexpr (I::d.area)
+      e = launch(k_energy_area<I::d.bend, I::d.guard, TT, CC, I::d.atomic>, grid, a.m.T, lds, s, a, cap, max_ent);
+    else
+      e = launch(k_energy<I::d.bend, I::d.guard, TT, CC, I::d.atomic, I::d.multi>, grid, a.m.T, lds, s, a, cap, max_ent);
+  });
+  return e;
 }
 
 // ---------------------------------------------------------------------------
@@ -1744,104 +1776,42 @@ size_t gradient_lds_bytes(int T, int cap, int max_ent, bool bend, bool volrow, b
 // the lean instances (see k_gradient): analytic bending on a closed surface, uniform gamma, no penalty, no pd rows to
 // load -- without a constraint row (the headline's) or with one (no fused direction pass then: the KKT multiplier
 // needs a global reduction first)
-bool gradient_lean_instance(const GradientArgs& a) {
+GradientInst gradient_instance(const GradientArgs& a) {
   const bool bend = (a.modules & MS_MOD_BENDING) != 0;
-  const bool leaf = bend && a.bt_vert != nullptr;
-  return a.m.T == FAST_T && a.m.tile_facets32 != nullptr && !leaf && bend && a.bending_grad_mode != MS_GRAD_APPROX &&
-         !a.m.has_boundary && !(a.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) && !no_lean() && !a.m.no_fast;
+  const bool leaf = bend && a.bt_vert != nullptr;  // leaflet bending_tilt: generic-size instances only (not a headline path)
+  const int mode = !bend ? 0 : (leaf ? 3 : (a.bending_grad_mode == MS_GRAD_APPROX ? 2 : 1));
+  const bool fast = a.m.T == FAST_T && a.m.tile_facets32 != nullptr && !a.m.no_fast && !leaf;
+  const bool area = (a.modules & MS_MOD_AREA_PENALTY) != 0;  // (the k_gradient_area instances; never next to a
+                                                             //  tilt-family module, ms_set_params: valid() refuses mode 3)
+  const bool lean = fast && mode == 1 && !a.m.has_boundary && !(a.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) &&
+                    !no_lean();
+  return {mode, a.gC != nullptr && (a.modules & MS_CON_VOLUME) != 0, a.atomic != 0, lean, area, fast};
 }
+bool gradient_lean_instance(const GradientArgs& a) { return gradient_instance(a).lean; }
 
 hipError_t launch_gradient(const GradientArgs& a_in, int cap, int max_ent, hipStream_t s) {
   GradientArgs a = a_in;
   if (abl_ntiles() > 0) a.tile1 = std::min(a.tile1, a.tile0 + abl_ntiles());
   const int nb = a.tile1 - a.tile0;
   if (nb <= 0) return hipSuccess;
-  const bool bend = (a.modules & MS_MOD_BENDING) != 0;
-  const bool volrow = a.gC != nullptr && (a.modules & MS_CON_VOLUME);
-  const bool fast = a.m.T == FAST_T && a.m.tile_facets32 != nullptr && !a.m.no_fast;
-  const bool atomic = a.atomic != 0;
-  const bool leaf = bend && a.bt_vert != nullptr;
-  const bool area = (a.modules & MS_MOD_AREA_PENALTY) != 0;  // (the k_gradient_area instances)
-  const size_t lds = gradient_lds_bytes(a.m.T, cap, max_ent, bend, volrow, atomic, leaf);
-  hipError_t e;
+  const GradientInst d = gradient_instance(a);
+  if (!d.valid()) return hipErrorInvalidValue;
+  const size_t lds = gradient_lds_bytes(a.m.T, cap, max_ent, d.mode != 0, d.volrow, d.atomic, d.mode == 3);
   if (ExecRecorder* r = exec_find(s)) {
-    const int mode_r = !bend ? 0 : (leaf ? 3 : (a.bending_grad_mode == MS_GRAD_APPROX ? 2 : 1));
-    if (area && mode_r == 3) return hipErrorInvalidValue;  // (no tilt-family module next to body_area_penalty: ms_set_params)
-    if (fast || mode_r == 3)
-      return r->push(CK_GRADIENT, 0, cap, max_ent, nb,
-                     (gradient_lean_instance(a) ? 1u : 0u) | (volrow ? 2u : 0u) | (atomic ? 4u : 0u) | (area ? 8u : 0u) | ((uint32_t)mode_r << 4),
-                     lds, &a, sizeof(a), &a.m);
-    e = r->flush();
-    if (e != hipSuccess) return e;
+    if (d.in_exec()) return r->push(CK_GRADIENT, 0, cap, max_ent, nb, d.code(), lds, &a, sizeof(a), &a.m);
+    if (const hipError_t e = r->flush(); e != hipSuccess) return e;
   }
-#define MS_LAUNCH_G(M, V, TT, CC, AT)                                                                \
-  do {                                                                                               \
-    e = ensure_lds(k_gradient<M, V, TT, CC, AT>, lds);                                               \
-    if (e != hipSuccess) return e;                                                                   \
-    hipLaunchKernelGGL((k_gradient<M, V, TT, CC, AT>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent); \
-  } while (0)
-  if (gradient_lean_instance(a)) {
-#define MS_LAUNCH_LEAN(V, AT)                                                                               \
-  do {                                                                                                      \
-    e = ensure_lds(k_gradient<1, V, FAST_T, FAST_CAP, AT, true>, lds);                                      \
-    if (e != hipSuccess) return e;                                                                          \
-    hipLaunchKernelGGL((k_gradient<1, V, FAST_T, FAST_CAP, AT, true>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent); \
-  } while (0)
-    // (atomic: LDS ds_add_f64 vertex sums; otherwise the same diet with the fixed-order CSR gather, ms_set_deterministic)
-    if (volrow) {
-      if (atomic) MS_LAUNCH_LEAN(true, true); else MS_LAUNCH_LEAN(true, false);
-    } else {
-      if (atomic) MS_LAUNCH_LEAN(false, true); else MS_LAUNCH_LEAN(false, false);
-    }
-#undef MS_LAUNCH_LEAN
-    return hipGetLastError();
-  }
-#define MS_PICK_G(M, V)                                           \
-  do {                                                            \
-    if (fast && atomic) MS_LAUNCH_G(M, V, FAST_T, FAST_CAP, true); \
-    else if (fast) MS_LAUNCH_G(M, V, FAST_T, FAST_CAP, false);    \
-    else if (atomic) MS_LAUNCH_G(M, V, 0, 0, true);               \
-    else MS_LAUNCH_G(M, V, 0, 0, false);                          \
-  } while (0)
-  const int mode = !bend ? 0 : (leaf ? 3 : (a.bending_grad_mode == MS_GRAD_APPROX ? 2 : 1));
-  if (area) {
-    if (mode == 3) return hipErrorInvalidValue;  // (no tilt-family module next to body_area_penalty: ms_set_params)
-#define MS_LAUNCH_GA(M, V, TT, CC, AT)                                                                    \
-  do {                                                                                                    \
-    e = ensure_lds(k_gradient_area<M, V, TT, CC, AT>, lds);                                               \
-    if (e != hipSuccess) return e;                                                                        \
-    hipLaunchKernelGGL((k_gradient_area<M, V, TT, CC, AT>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent); \
-  } while (0)
-#define MS_PICK_GA(M, V)                                            \
-  do {                                                              \
-    if (fast && atomic) MS_LAUNCH_GA(M, V, FAST_T, FAST_CAP, true); \
-    else if (fast) MS_LAUNCH_GA(M, V, FAST_T, FAST_CAP, false);     \
-    else if (atomic) MS_LAUNCH_GA(M, V, 0, 0, true);                \
-    else MS_LAUNCH_GA(M, V, 0, 0, false);                           \
-  } while (0)
-    if (volrow) {
-      if (mode == 0) MS_PICK_GA(0, true); else if (mode == 1) MS_PICK_GA(1, true); else MS_PICK_GA(2, true);
-    } else {
-      if (mode == 0) MS_PICK_GA(0, false); else if (mode == 1) MS_PICK_GA(1, false); else MS_PICK_GA(2, false);
-    }
-#undef MS_PICK_GA
-#undef MS_LAUNCH_GA
-    return hipGetLastError();
-  }
-  if (mode == 3) {  // leaflet bending_tilt: generic-size instances only (not a headline path)
-    if (volrow) {
-      if (atomic) MS_LAUNCH_G(3, true, 0, 0, true); else MS_LAUNCH_G(3, true, 0, 0, false);
-    } else {
-      if (atomic) MS_LAUNCH_G(3, false, 0, 0, true); else MS_LAUNCH_G(3, false, 0, 0, false);
-    }
-  } else if (volrow) {
-    if (mode == 0) MS_PICK_G(0, true); else if (mode == 1) MS_PICK_G(1, true); else MS_PICK_G(2, true);
-  } else {
-    if (mode == 0) MS_PICK_G(0, false); else if (mode == 1) MS_PICK_G(1, false); else MS_PICK_G(2, false);
-  }
-#undef MS_PICK_G
-#undef MS_LAUNCH_G
-  return hipGetLastError();
+  hipError_t e = hipErrorInvalidValue;
+  // (atomic: LDS ds_add_f64 vertex sums; otherwise the fixed-order CSR gather, ms_set_deterministic)
+  visit_instance<false>(d, [&](auto tag) {
+    using I = decltype(tag);
+    constexpr int TT = I::d.fast ? FAST_T : 0, CC = I::d.fast ? FAST_CAP : 0;
+    if constexpr (I::d.area)
+      e = launch(k_gradient_area<I::d.mode, I::d.volrow, TT, CC, I::d.atomic>, nb, a.m.T, lds, s, a, cap, max_ent);
+    else
+      e = launch(k_gradient<I::d.mode, I::d.volrow, TT, CC, I::d.atomic, I::d.lean>, nb, a.m.T, lds, s, a, cap, max_ent);
+  });
+  return e;
 }
 
 // ---------------------------------------------------------------------------
@@ -2217,18 +2187,10 @@ hipError_t launch_tilt(const TiltArgs& a, int mode, int cap, int max_ent, hipStr
   const int nb = a.tile1 - a.tile0;
   if (nb <= 0) return hipSuccess;
   const size_t lds = tilt_lds_bytes(a.m.T, cap, max_ent, (mode == 0 || mode == 1) && a.consistent, mode);
-  hipError_t e;
   if (ExecRecorder* r = exec_find(s)) return r->push(CK_TILT, mode, cap, max_ent, nb, 0, lds, &a, sizeof(a), &a.m);
-#define MS_LAUNCH_T(M)                                                                  \
-  do {                                                                                  \
-    e = ensure_lds(k_tilt<M>, lds);                                                     \
-    if (e != hipSuccess) return e;                                                      \
-    hipLaunchKernelGGL((k_tilt<M>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent);    \
-  } while (0)
-  if (mode == 0) MS_LAUNCH_T(0); else if (mode == 1) MS_LAUNCH_T(1); else if (mode == 2) MS_LAUNCH_T(2);
-  else if (mode == 3) MS_LAUNCH_T(3); else if (mode == 4) MS_LAUNCH_T(4); else MS_LAUNCH_T(5);
-#undef MS_LAUNCH_T
-  return hipGetLastError();
+  return pick_int<0, 1, 2, 3, 4, 5>(mode, [&](auto M) {
+    return launch(k_tilt<decltype(M)::value>, nb, a.m.T, lds, s, a, cap, max_ent);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -2484,17 +2446,10 @@ hipError_t launch_bt(const BtArgs& a, int mode, int cap, int max_ent, hipStream_
   const int nb = a.tile1 - a.tile0;
   if (nb <= 0) return hipSuccess;
   const size_t lds = bt_lds_bytes(a.m.T, cap, max_ent, mode);
-  hipError_t e;
   if (ExecRecorder* r = exec_find(s)) return r->push(CK_BT, mode, cap, max_ent, nb, 0, lds, &a, sizeof(a), &a.m);
-#define MS_LAUNCH_B(M)                                                                      \
-  do {                                                                                      \
-    e = ensure_lds(k_bt<M>, lds);                                                           \
-    if (e != hipSuccess) return e;                                                          \
-    hipLaunchKernelGGL((k_bt<M>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent);          \
-  } while (0)
-  if (mode == 0) MS_LAUNCH_B(0); else if (mode == 1) MS_LAUNCH_B(1); else if (mode == 2) MS_LAUNCH_B(2); else MS_LAUNCH_B(3);
-#undef MS_LAUNCH_B
-  return hipGetLastError();
+  return pick_int<0, 1, 2, 3>(mode, [&](auto M) {
+    return launch(k_bt<decltype(M)::value>, nb, a.m.T, lds, s, a, cap, max_ent);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -2661,17 +2616,10 @@ hipError_t launch_ts(const TsArgs& a, int mode, int cap, int max_ent, hipStream_
   const int nb = a.tile1 - a.tile0;
   if (nb <= 0) return hipSuccess;
   const size_t lds = ts_lds_bytes(a.m.T, cap, max_ent);
-  hipError_t e;
   if (ExecRecorder* r = exec_find(s)) return r->push(CK_TS, mode, cap, max_ent, nb, 0, lds, &a, sizeof(a), &a.m);
-#define MS_LAUNCH_S(M)                                                                      \
-  do {                                                                                      \
-    e = ensure_lds(k_tsmooth<M>, lds);                                                      \
-    if (e != hipSuccess) return e;                                                          \
-    hipLaunchKernelGGL((k_tsmooth<M>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent);     \
-  } while (0)
-  if (mode == 0) MS_LAUNCH_S(0); else if (mode == 1) MS_LAUNCH_S(1); else MS_LAUNCH_S(2);
-#undef MS_LAUNCH_S
-  return hipGetLastError();
+  return pick_int<0, 1, 2>(mode, [&](auto M) {
+    return launch(k_tsmooth<decltype(M)::value>, nb, a.m.T, lds, s, a, cap, max_ent);
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -286,20 +286,11 @@ hipError_t launch_tsearch(const TsearchArgs& a, int cap, hipStream_t s) {
     return r->push(CK_TSEARCH, a.n_fields, cap, 0, nb, 0, lds, &a, sizeof(a), &a.m);
   }
   const int nt = a.n_trials <= 1 ? 1 : (a.n_trials <= 2 ? 2 : (a.n_trials <= 4 ? 4 : 8));
-  hipError_t e;
-#define MS_LAUNCH_TS(NF, NT)                                                               \
-  do {                                                                                     \
-    e = ensure_lds(k_tsearch<NF, NT>, lds);                                                \
-    if (e != hipSuccess) return e;                                                         \
-    hipLaunchKernelGGL((k_tsearch<NF, NT>), dim3(nb), dim3(a.m.T), lds, s, a, cap);        \
-  } while (0)
-  if (a.n_fields == 1) {
-    if (nt == 1) MS_LAUNCH_TS(1, 1); else if (nt == 2) MS_LAUNCH_TS(1, 2); else if (nt == 4) MS_LAUNCH_TS(1, 4); else MS_LAUNCH_TS(1, 8);
-  } else {
-    if (nt == 1) MS_LAUNCH_TS(2, 1); else if (nt == 2) MS_LAUNCH_TS(2, 2); else if (nt == 4) MS_LAUNCH_TS(2, 4); else MS_LAUNCH_TS(2, 8);
-  }
-#undef MS_LAUNCH_TS
-  return hipGetLastError();
+  return pick_int<1, 2>(a.n_fields, [&](auto NF) {
+    return pick_int<1, 2, 4, 8>(nt, [&](auto NT) {
+      return launch(k_tsearch<decltype(NF)::value, decltype(NT)::value>, nb, a.m.T, lds, s, a, cap);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -666,18 +657,9 @@ hipError_t launch_tgrad(const TgradArgs& a, int cap, int max_ent, bool combine, 
   bool need_a3 = false;
   for (int k = 0; k < a.n_fields; ++k) need_a3 = need_a3 || a.f[k].tilt_form == 1;
   const size_t lds = tgrad_lds_bytes(a.m.T, cap, max_ent, a.n_fields, combine, need_a3);
-  hipError_t e;
-#define MS_LAUNCH_TG(NF, CB)                                                                   \
-  do {                                                                                         \
-    e = ensure_lds(k_tgrad<NF, CB>, lds);                                                      \
-    if (e != hipSuccess) return e;                                                             \
-    hipLaunchKernelGGL((k_tgrad<NF, CB>), dim3(nb), dim3(a.m.T), lds, s, a, cap, max_ent);     \
-  } while (0)
-  if (a.n_fields == 1) {
-    if (combine) MS_LAUNCH_TG(1, true); else MS_LAUNCH_TG(1, false);
-  } else {
-    if (combine) MS_LAUNCH_TG(2, true); else MS_LAUNCH_TG(2, false);
-  }
-#undef MS_LAUNCH_TG
-  return hipGetLastError();
+  return pick_int<1, 2>(a.n_fields, [&](auto NF) {
+    return pick(combine, [&](auto CB) {
+      return launch(k_tgrad<decltype(NF)::value, decltype(CB)::value>, nb, a.m.T, lds, s, a, cap, max_ent);
+    });
+  });
 }

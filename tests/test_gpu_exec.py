@@ -131,6 +131,117 @@ def test_multi_tile_meshes_keep_the_launch_per_kernel_path():
     dm.close()
 
 
+# The template instance of every energy / gradient record as ms_exec_trace reports it (ExecCmdHead::inst), written
+# out from the documented layout, not from what the library prints:
+#   energy:   1 bending | 2 guard | 4 LDS-atomic vertex sums | 8 body area
+#   gradient: 1 lean | 2 constraint row | 4 LDS-atomic vertex sums | 8 body-area term | bending mode << 4
+#             (mode 1 analytic, 2 approx, 3 leaflet bending_tilt)
+# (mesh, modules, fixed-order sums, {energy inst}, {gradient inst}); modules: S surface, B bending (analytic), X bending
+# (approx), V volume row, A body_area_penalty, G a guarded trial energy pass behind the evaluation.  "leaflet": a
+# bending_tilt_in/out trajectory through the minimizer (only its gradient records are listed).
+INSTANCES = {
+    "surface": ("ico4", "S", True, {0}, {0}),
+    "surface_guard": ("ico4", "SG", True, {0, 2}, {0}),
+    "surface_volrow": ("ico4", "SV", True, {0}, {2}),
+    "bending_lean": ("ico4", "SB", True, {1}, {0x11}),
+    "bending_lean_atomic": ("ico4", "SB", False, {5}, {0x15}),
+    "bending_guard": ("ico4", "SBG", True, {1, 3}, {0x11}),
+    "bending_guard_atomic": ("ico4", "SBG", False, {5, 7}, {0x15}),
+    "bending_volrow": ("ico4", "SBV", True, {1}, {0x13}),
+    "bending_volrow_atomic": ("ico4", "SBV", False, {5}, {0x17}),
+    "bending_approx": ("ico4", "X", True, {1}, {0x20}),
+    "bending_approx_volrow_atomic": ("ico4", "XV", False, {5}, {0x26}),
+    "bending_open_disk": ("disk5", "SB", True, {1}, {0x10}),
+    "bending_open_disk_atomic": ("disk5", "SB", False, {5}, {0x14}),
+    "surface_open_disk_volrow": ("disk5", "SV", True, {0}, {2}),
+    "area": ("ico4", "SA", True, {8}, {0x08}),
+    "area_guard": ("ico4", "SAG", True, {8, 10}, {0x08}),
+    "area_bending": ("ico4", "SBA", True, {9}, {0x18}),
+    "area_bending_atomic": ("ico4", "SBA", False, {13}, {0x1c}),
+    "area_bending_volrow": ("ico4", "SBAV", True, {9}, {0x1a}),
+    "area_approx_volrow_atomic": ("disk5", "XAV", False, {13}, {0x2e}),
+    "leaflet": ("traj_disk5_gd_btl_backtrack.npz", "leaflet", True, None, {0x30}),
+}
+
+
+def _trace_insts(dm):
+    """-> ({energy inst}, {gradient inst}) of the records run since the trace was switched on (reading it clears it)"""
+    rows = dm.exec_trace(True)
+    return tuple({r["inst"] for r in rows if r["kind"] == kind} for kind in ("energy", "gradient"))
+
+
+def _run_instance(mesh, mods):
+    """-> (arrays to compare, {energy inst}, {gradient inst}) of one evaluation in a fresh context"""
+    from membrane_solver_amd import _lib as L
+    from membrane_solver_amd.device import DeviceMesh
+
+    if mods == "leaflet":
+        from test_gpu_leaflet import _leaflet_minimizer
+
+        g = load_golden(mesh)
+        m, mz, _log = _leaflet_minimizer(g, "gd", observe=False)
+        _mir, dm = mz._device()
+        dm.exec_trace(True)
+        res = mz.minimize(int(g["n_steps"]))
+        out = [np.array([res["energy"]]), m.positions_view().copy(), m.tilts_in_view().copy(), m.tilts_out_view().copy()]
+        return out, None, _trace_insts(dm)[1], dm.exec_stats()
+    g = load_golden(f"mesh_{mesh}.npz")
+    nv = g["positions"].shape[0]
+    dm = DeviceMesh(g["positions"], g["tri"], boundary=g["is_boundary"])
+    dm.set_surface_tension(g["gamma"])
+    dm.set_bending_params(g["kappa"], np.full(nv, 0.3))
+    dm.set_area_penalty(2.0, 0.9 * float(g["E_surface"]))
+    bits = {"S": L.MS_MOD_SURFACE, "B": L.MS_MOD_BENDING, "X": L.MS_MOD_BENDING, "V": L.MS_CON_VOLUME,
+            "A": L.MS_MOD_AREA_PENALTY, "G": 0}
+    modules = 0
+    for ch in mods:
+        modules |= bits[ch]
+    dm.set_params(modules=modules, bending_grad_mode=L.MS_GRAD_APPROX if "X" in mods else L.MS_GRAD_ANALYTIC,
+                  target_volume=float(g["volume"]))
+    dm.exec_trace(True)
+    e, grad = dm.energy_and_gradient()
+    out = [e, grad]
+    if "V" in mods:
+        out.append(dm.get_vertex_buffer(L.MS_BUF_GC))
+    if "G" in mods:
+        dm.phase_energy(use_direction=True, alpha=1e-3, guard=True)
+        sc = dm.fetch_scalars()
+        out.append(np.array([sc[k] for k in (L.MS_S_ESURF, L.MS_S_VOL, L.MS_S_EBEND, L.MS_S_MINEDGE2, L.MS_S_GUARD)]))
+    stats = dm.exec_stats()
+    e_inst, g_inst = _trace_insts(dm)
+    dm.close()
+    return out, e_inst, g_inst, stats
+
+
+@pytest.mark.parametrize("name", sorted(INSTANCES))
+def test_every_interpreter_instance_runs_and_reports_its_documented_inst(name, request, monkeypatch):
+    """Each energy / gradient instance k_exec has, on the smallest meshes that reach it: the interpreter's results are
+    the launch-per-kernel path's (bit for bit with fixed-order sums; to the summation-order tolerances of
+    test_gpu_kernels.py with LDS atomics), and the trace names exactly the instances the row's modules select."""
+    mesh, mods, fixed_order, e_inst, g_inst = INSTANCES[name]
+    if fixed_order:
+        request.getfixturevalue("deterministic")
+    else:
+        monkeypatch.delenv("MS_DETERMINISTIC", raising=False)
+    monkeypatch.setenv("MS_EXEC", "0")
+    ref, e0, g0, st0 = _run_instance(mesh, mods)
+    assert not st0["active"] and st0["packs"] == 0 and not e0 and not g0
+    monkeypatch.setenv("MS_EXEC", "1")
+    got, e1, g1, st1 = _run_instance(mesh, mods)
+    assert st1["active"] and st1["packs"] > 0
+    assert len(got) == len(ref)
+    for k, (a, b) in enumerate(zip(got, ref)):
+        if fixed_order:
+            assert np.array_equal(a, b), k
+        elif a.ndim == 1:  # energies, folded scalars: each to 1e-12 relative
+            assert np.all(np.abs(a - b) <= 1e-12 * np.abs(b)), k
+        else:  # vertex rows: 1e-10 relative, max-norm
+            assert np.abs(a - b).max() <= 1e-10 * np.abs(b).max(), k
+    if e_inst is not None:
+        assert e1 == e_inst
+    assert g1 == g_inst
+
+
 @pytest.mark.parametrize("fname", ["traj_config5_deck_gd.npz", "traj_disk6_cg_disktarget_coupled_gd.npz",
                                    "traj_ico4_cg_btl_coupled_gd.npz", "traj_ico4_gd_leaflet_nested_cg.npz",
                                    "traj_disk5_gd_btl_backtrack.npz"])
