@@ -568,6 +568,14 @@ int ms_profile_read(ms_ctx *ctx, double total_ms[MS_PROF_KINDS],
  * host replays it from the same doubles), [5] rounds queued for a step that had not started yet (behind the running
  * gradient pass; ms_minimize only), [6] those the step adopted, [7] those dropped. */
 int ms_queue_stats(ms_ctx *ctx, int64_t stats[8]);
+/* The fused gradient + direction pass of ms_step (CG history, no constraint row, single context) does not store the
+ * direction when the last direction with history was no descent direction: the step is expected to fail without a
+ * trial (conjugate_gradient.py:78-96 then line_search.py:325-328) and the stepper to restart along -g, so nobody
+ * reads it.  Only the store is left out: the scalars, the step log and every result stay bit for bit what they were.
+ * When the direction is wanted after all -- <g,d> < 0, ms_get_vertex_buffer(MS_BUF_D), the phase API -- the direction
+ * kernel writes it from the stored gradient and history first.  *skipped: steps whose gradient pass left the store out;
+ * *materialized: directions written out afterwards.  Since ms_create.  (MS_BUF_D after ms_reset_stepper is unspecified until the next step.) */
+int ms_direction_stats(ms_ctx *ctx, int64_t *skipped, int64_t *materialized);
 /* One-tile meshes (every mesh the reference's own benchmarks and decks use: <= 256 vertices): the library records its
  * kernel launches and runs them pack by pack in ONE workgroup (k_exec) instead of launching each -- same device code,
  * same results bit for bit, a few launches per step instead of dozens.  MS_EXEC=0 in the environment switches it off.

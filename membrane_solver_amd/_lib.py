@@ -204,6 +204,7 @@ SIGNATURES = {
     "ms_profile_enable": (ctypes.c_int, [_P, ctypes.c_int]),
     "ms_profile_read": (ctypes.c_int, [_P, _D, _I64]),
     "ms_queue_stats": (ctypes.c_int, [_P, _I64]),
+    "ms_direction_stats": (ctypes.c_int, [_P, _I64, _I64]),
     "ms_exec_stats": (ctypes.c_int, [_P, _I64]),
     "ms_resident_stats": (ctypes.c_int, [_P, _I64]),
     "ms_set_pins": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.c_int, _I32, _I32, _I32, _I32, _I32, ctypes.c_int,

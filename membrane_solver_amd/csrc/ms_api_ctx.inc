@@ -36,6 +36,10 @@ struct CarryState {
   // trial passes then read G with -alpha (bitwise the same x + alpha d).  After such a step is accepted the
   // CG history's previous direction is -PG, which the next fused direction pass derives instead of loading.
   bool dir_implicit = false;
+  // the last fused direction pass (CG history) formed its rows for the scalars only and did not store them: the host
+  // expected <g,d> >= 0, after which nobody reads D.  Whoever does want D first has k_direction write it from the
+  // stored G / PG / PD (materialize_direction); a stepper reset or a new gradient pass clears the flag.
+  bool dir_unwritten = false;
   bool pd_neg_pg = false;
   bool kc_pending = false;       // the gradient pass queued behind a round ran for the accepted x: the next ms_step takes its result
   int kc_parity = 0;
@@ -158,6 +162,10 @@ struct ms_ctx {
   long q_ahead = 0, q_adopted = 0, q_dropped = 0;
   int kc_stepper = 0;
   bool kc_use_history = false;
+  // the gradient pass queued with the round of that parity did not store D (CarryState::dir_unwritten as that pass left
+  // it: the queueing code restores the carried state, the step that adopts the pass takes the flag from here)
+  bool kc_dir_unwritten[2] = {false, false};
+  long dir_skipped = 0, dir_materialized = 0;  // ms_direction_stats
   // Decision records (ms_internal.h DEC_*): one 128-byte line each, written by the head workgroup of the fold that
   // closes a line-search stage, read by every kernel queued behind that stage.  Record k belongs to stage k of the
   // round being queued; the stream orders a record's readers between its writers.

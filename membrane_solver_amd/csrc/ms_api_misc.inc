@@ -90,6 +90,13 @@ int ms_queue_stats(ms_ctx* c, int64_t stats[8]) {
   return MS_OK;
 }
 
+int ms_direction_stats(ms_ctx* c, int64_t* skipped, int64_t* materialized) {
+  if (!c || !skipped || !materialized) return MS_ERR_INVALID;
+  *skipped = c->dir_skipped;
+  *materialized = c->dir_materialized;
+  return MS_OK;
+}
+
 int ms_resident_stats(ms_ctx* c, int64_t stats[4]) {
   if (!c || !stats) return MS_ERR_INVALID;
   stats[0] = c->resident_ok;

@@ -777,8 +777,9 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
 }
 
 // dir_mode: 0 = plain gradient pass (+ <g,gC> partials); 1/2 = fused direction (GD / CG history)
+// may_skip_d: the caller reads D only after it has seen the direction scalars (ms_step) -- the pass may leave D unstored
 int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulate, int dir_mode = 0,
-                   bool reduce_now = true) {
+                   bool reduce_now = true, bool may_skip_d = false) {
   uint32_t modules = modules_in;
   if ((modules & (MS_MOD_BENDING | MS_MOD_BENDING_TILT | MS_LEAFLET_BT)) && !c->carry.factors_valid)
     return fail(c, MS_ERR_STATE, "gradient pass needs the bending factors of an energy pass at x");
@@ -816,7 +817,14 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
   a.target_area = c->target_area;
   a.accumulate = accumulate ? 1 : 0;
   a.dir_mode = dir_mode;
-  a.d = c->buf[MS_BUF_D];
+  // A direction with CG history right after one that was no descent direction is, in the steady state of the headline
+  // workload, none either: the step fails without a trial and the stepper restarts along -g, so nobody reads D.  Such
+  // a pass forms its rows for the scalars only (24 nv bytes less to store); ms_step and the buffer getter write D out
+  // with k_direction in the rare case it is wanted after all (materialize_direction).  Only on the fused-epilogue lane
+  // of a single context: no constraint row, no tilt shape module, no preconditioned direction.
+  const bool skip_d = may_skip_d && dir_mode == 2 && c->shard_count == 1 && !c->last_hist_descent && !c->precond &&
+                      !(modules & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS)) && c->pin_lane != MS_PIN_LANE_PROJECT;
+  a.d = skip_d ? nullptr : c->buf[MS_BUF_D];
   a.pg = c->buf[MS_BUF_PG];
   a.pd = c->buf[MS_BUF_PD];
   a.pd_neg_pg = (dir_mode == 2 && c->carry.pd_neg_pg) ? 1 : 0;
@@ -861,7 +869,8 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
   }
   if (dir_mode) {
     c->carry.last_g = g_out;
-    c->carry.dir_implicit = false;  // D was written
+    c->carry.dir_implicit = false;  // D was written ...
+    c->carry.dir_unwritten = skip_d;  // ... or is k_direction's to write from G / PG / PD
   }
   bool added_after = n_lbt > 0;
   for (int k = 0; k < 3 && g_out; ++k) {  // module loop: the tilt magnitude modules add their shape gradient into g
@@ -890,6 +899,7 @@ int phase_direction(ms_ctx* c, int stepper, bool use_history, bool g_finalized =
   const bool use_con = (c->params.modules & MS_CON_VOLUME) != 0 && c->pin_lane != MS_PIN_LANE_SKIP;
   const StageCtl& st = c->stage();
   c->carry.dir_implicit = false;
+  c->carry.dir_unwritten = false;
   {
   ProfScope ps(c, 2, st.cur_gate, st.cur_gate_want);
   HIPCHK(c, launch_direction(c->tile0, c->tile1, c->til.nv, c->til.own, c->d_vflags, c->buf[MS_BUF_G],
@@ -905,6 +915,22 @@ int phase_direction(ms_ctx* c, int stepper, bool use_history, bool g_finalized =
   c->carry.last_g = c->buf[MS_BUF_G];
   return reduce_slots(c, MASK_DIR);
 }
+
+// The last fused direction pass left D unstored (CarryState::dir_unwritten) and somebody wants the rows after all:
+// k_direction on the finalized G, with the history that pass had, repeats the epilogue's arithmetic row for row.  No
+// fold: the pass's scalars are the host's already (the partials this launch writes are the same sums again).
+// `flag` is the carried one, or the one of a pass still queued behind an acceptance (ms_ctx::kc_dir_unwritten).
+int materialize_direction(ms_ctx* c, bool& flag) {
+  if (!flag) return MS_OK;
+  HIPCHK(c, launch_direction(c->tile0, c->tile1, c->til.nv, c->til.own, c->d_vflags, c->buf[MS_BUF_G], c->buf[MS_BUF_GC],
+                             c->buf[MS_BUF_D], c->buf[MS_BUF_PG], c->buf[MS_BUF_PD], c->d_scal, 0, /*cg_history=*/1,
+                             c->d_partials, c->til.n_tiles, /*write_g=*/0, c->stream, nullptr, 0,
+                             c->carry.pd_neg_pg ? 1 : 0, 0));
+  flag = false;
+  ++c->dir_materialized;
+  return MS_OK;
+}
+int materialize_direction(ms_ctx* c) { return materialize_direction(c, c->carry.dir_unwritten); }
 
 // host-side write of a slot (a stage mailbox's result moved into the main one): both the host copy and the value
 // word, so a later take_mailbox() keeps it
@@ -1071,7 +1097,7 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
   if (!constraint) {
     // no row to project out: the direction pass rides in K_C's epilogue, one reduce for all
     const int dir_mode = (stepper == MS_STEPPER_CG && use_history) ? 2 : 1;
-    rc = phase_gradient(c, mods, c->buf[MS_BUF_G], false, dir_mode, /*reduce_now=*/false);
+    rc = phase_gradient(c, mods, c->buf[MS_BUF_G], false, dir_mode, /*reduce_now=*/false, /*may_skip_d=*/true);
     if (rc) return rc;
     return reduce_slots(c, (penalty ? 0u : energy_mask(mods)) | MASK_DIR);
   }

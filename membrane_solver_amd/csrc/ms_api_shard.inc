@@ -5,6 +5,8 @@ int ms_phase_energy(ms_ctx* c, int use_direction, double alpha, int write_trial,
   if (!c) return MS_ERR_INVALID;
   if ((c->params.modules & MS_ANY_TILT_MODS) && c->shard_count != 1)
     return fail(c, MS_ERR_STATE, "the tilt module is not sharded yet (single GPU only)");
+  if (use_direction)  // (an ms_step before this call may have left D to be written on demand)
+    if (int rc = materialize_direction(c)) return rc;
   return phase_energy(c, c->params.modules, use_direction != 0, alpha, write_trial != 0, guard != 0,
                       write_bending_factors != 0);
 }
@@ -23,6 +25,7 @@ int ms_phase_direction(ms_ctx* c, int stepper, int use_history) {
 
 int ms_phase_accept(ms_ctx* c, int keep_history) {
   if (!c) return MS_ERR_INVALID;
+  if (int rc = materialize_direction(c)) return rc;  // (D becomes PD below: never unwritten)
   std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
   c->carry.factors_valid = false;
   c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
@@ -42,6 +45,7 @@ int ms_phase_accept(ms_ctx* c, int keep_history) {
 
 int ms_phase_commit_trial(ms_ctx* c, double alpha, int keep_history) {
   if (!c) return MS_ERR_INVALID;
+  if (int rc = materialize_direction(c)) return rc;
   if (c->shard_count > 1) {
     // x <- x + alpha d in place on the rows this rank reads: its own rows and the halo rows
     // of its tiles (d is valid there after the boundary exchange); same expression as the

@@ -20,7 +20,13 @@ int ms_get_gradient(ms_ctx* c, double* grad) {
 int ms_get_vertex_buffer(ms_ctx* c, int buffer, double* out) {
   if (!c || !out || buffer < 0 || buffer > MS_BUF_FA)
     return fail(c, MS_ERR_INVALID, "ms_get_vertex_buffer: bad argument");
-  if ((buffer == MS_BUF_D && c->carry.dir_implicit) || (buffer == MS_BUF_PD && c->carry.pd_neg_pg)) {
+  if (buffer == MS_BUF_D && c->carry.kc_pending) {
+    // the gradient pass queued behind the accepted trial has run: D is that pass's direction (the carried flags still
+    // describe the step before it) -- stored by the pass, or left to k_direction
+    if (int rc = materialize_direction(c, c->kc_dir_unwritten[c->carry.kc_parity])) return rc;
+  } else if (buffer == MS_BUF_D && c->carry.dir_unwritten) {
+    if (int rc = materialize_direction(c)) return rc;
+  } else if ((buffer == MS_BUF_D && c->carry.dir_implicit) || (buffer == MS_BUF_PD && c->carry.pd_neg_pg)) {
     // the direction asked for exists only as -G / -PG: write it out
     const int src = buffer == MS_BUF_D ? MS_BUF_G : MS_BUF_PG;
     HIPCHK(c, launch_direction(c->tile0, c->tile1, c->til.nv, c->til.own, c->d_vflags, c->buf[src], c->buf[MS_BUF_GC],
@@ -83,9 +89,13 @@ int ms_energy(ms_ctx* c, double energies[4]) {
 
 int ms_reset_stepper(ms_ctx* c) {
   if (!c) return MS_ERR_INVALID;
+  // (a pass still queued behind an acceptance has its history until here: D of that pass, if anybody asks later)
+  if (c->carry.kc_pending)
+    if (int rc = materialize_direction(c, c->kc_dir_unwritten[c->carry.kc_parity])) return rc;
   c->carry.cg_have_history = false;
   c->carry.cg_iter_count = 0;
   c->carry.pd_neg_pg = false;
+  c->carry.dir_unwritten = false;  // (its history is gone: the direction nobody stored is nobody's any more)
   return MS_OK;
 }
 
@@ -295,6 +305,7 @@ int queue_round(ms_ctx* c, const ms_stepper_params* sp, const RoundPlan& plan, i
     c->dir_deferred_mask = 0;
     StageScope scope(c, st);
     rc = queue_energy_and_gradient(c, sp->stepper, next_hist, /*skip_energy=*/true);
+    c->kc_dir_unwritten[parity] = c->carry.dir_unwritten;  // (the carried copy goes with the restore below)
     c->dir_pending[parity] = st.defer_dir && c->dir_deferred_mask != 0;
     c->dir_mask[parity] = c->dir_deferred_mask;
     c->kc_gate[parity] = dec_word(c, parity, n_st);
@@ -346,6 +357,7 @@ void drop_ahead(ms_ctx* c, int ran) {
     c->carry.cg_have_history = false;
     c->carry.cg_iter_count = 0;
     c->carry.pd_neg_pg = false;
+    c->carry.dir_unwritten = false;
   }
 }
 
@@ -365,6 +377,9 @@ int queue_ahead(ms_ctx* c, const ms_stepper_params* sp, const ms_step_result* ou
   // kind 1: CG history, and the last direction with history was no descent direction; 3: it was one -- the next step
   // searches along the direction this pass writes; 2: the pass writes d = -g itself
   const int kind = c->kc_use_history ? (c->last_hist_descent ? 3 : 1) : 2;
+  // (kind 3 searches along the D of a pass that was queued before last_hist_descent turned true and did not store it:
+  // that round waits for its step, which writes D out first)
+  if (kind == 3 && c->kc_dir_unwritten[src]) return flush_dir_fold(c, src);
   const double alpha0 = out->next_step;
   const double me2 = c->h_scal[MS_S_MINEDGE2];
   if (c->steps_left < (kind == 1 ? 2 : 1) || !(alpha0 >= 1e-8) || sp->edge_fraction > 0.0)
@@ -403,6 +418,7 @@ int queue_ahead(ms_ctx* c, const ms_stepper_params* sp, const ms_step_result* ou
   } else {
     c->carry.dir_implicit = false;
   }
+  c->carry.dir_unwritten = false;  // (kinds 1, 2: D is not read; kind 3: the pass stored it)
   const int parity = c->next_parity;
   c->next_parity ^= 1;
   ah.parity = parity;
@@ -462,6 +478,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       // (|g|^2; <g,d> = -|g|^2 and max|d_i|^2 = max|g_i|^2 exactly) -- no fold, no host round trip
       // -- and no kernel either: the trial passes read G with -alpha (dir_implicit)
       c->carry.dir_implicit = true;
+      c->carry.dir_unwritten = false;
       c->carry.last_g = c->buf[MS_BUF_G];
       c->h_scal[MS_S_GDOTD] = -c->h_scal[MS_S_GNORM2];
       c->h_scal[MS_S_MAXD2] = c->h_scal[MS_S_MAXG2];
@@ -509,6 +526,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       if (MASK_DIR & (1u << sl)) put_mailbox(c, sl, vals[sl]);
     c->carry.last_g = c->buf[MS_BUF_G];
     c->carry.dir_implicit = false;
+    c->carry.dir_unwritten = c->kc_dir_unwritten[c->carry.kc_parity];  // (as the queued pass left D)
     c->carry.maxg2_valid = true;  // (the fused epilogue and the direction kernel both reduce max|g_i|^2)
   } else {
     c->carry.kc_pending = false;
@@ -520,6 +538,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     rc = fetch(c);
     if (rc) return rc;
   }
+  if (c->carry.dir_unwritten) ++c->dir_skipped;  // (this step's gradient pass, queued or direct, left D to k_direction)
   // factors, mailbox energies and G now describe x (until a trial pass overwrites them)
   c->carry.carry_valid = carry_mode;
   c->carry.grad_valid = carry_mode && !tilt_shape;
@@ -573,6 +592,10 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   out->energy = energy0;
   const double safe_step_limit = min_edge > 0.0 ? 0.3 * min_edge : INFINITY;
   if (g_dot_d >= 0.0) return MS_OK;  // :325-328 non-descent: (False, step_size, energy0)
+  // a descent direction after all, and the gradient pass did not store it (it expected the line above to return):
+  // k_direction writes it from G / PG / PD before the first trial launch reads D
+  rc = materialize_direction(c);
+  if (rc) return rc;
   double alpha = step_size;
   if (sp->edge_fraction > 0.0 && min_edge > 0.0 && max_dir > 0.0)
     alpha = std::min(alpha, sp->edge_fraction * min_edge / max_dir);
@@ -998,6 +1021,7 @@ int resident_run(ms_ctx* c, const ms_minimize_params* mp, int max_steps, double 
   c->carry.carry_valid = c->carry.grad_valid = c->carry.factors_valid = c->carry.maxg2_valid = c->carry.bt_valid = false;
   c->carry.kc_pending = false;
   c->carry.dir_implicit = false;
+  c->carry.dir_unwritten = false;
   if (ro->reason == RES_TIMEOUT) return fail(c, MS_ERR_STATE, "resident step kernel: a grid barrier timed out");
   return MS_OK;
 }

@@ -1253,7 +1253,7 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
     uint8_t hfl = 0;
     if (has_h) {
       const size_t g = 3 * (size_t)hv;
-      hfl = a.m.vflags[hv];
+      if (!LEAN) hfl = a.m.vflags[hv];  // (halo flags feed the boundary test only, which the lean instance has not)
       hx0 = a.x[g];
       hx1 = a.x[g + 1];
       hx2 = a.x[g + 2];
@@ -1297,7 +1297,7 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
     }
     if (has_h) {
       const int s = t.n_owned + tid;
-      lfl[s] = hfl;
+      if (!LEAN) lfl[s] = hfl;
       lds_put3(px, s, hx0, hx1, hx2);
       if (BEND) {
         lds_put3(fk, s, hk0, hk1, hk2);
@@ -1318,7 +1318,7 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
     for (int h = tid + T; h < t.nh; h += T) {  // halo longer than the workgroup (small tiles)
       const int v = a.m.halo_ids[t.h0 + h];
       const int s = t.n_owned + h;
-      lfl[s] = a.m.vflags[v];
+      if (!LEAN) lfl[s] = a.m.vflags[v];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         px[3 * s + c] = a.x[3 * (size_t)v + c];
@@ -1706,9 +1706,13 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
         a.g[o] = gi.x;
         a.g[o + 1] = gi.y;
         a.g[o + 2] = gi.z;
-        a.d[o] = di.x;
-        a.d[o + 1] = di.y;
-        a.d[o + 2] = di.z;
+        // (d == nullptr, uniform over the launch: the host expects this direction to be no descent direction and
+        // wants its scalars only; k_direction on the stored g reproduces the rows if it turns out to be one)
+        if (a.d != nullptr) {
+          a.d[o] = di.x;
+          a.d[o + 1] = di.y;
+          a.d[o + 2] = di.z;
+        }
       }
       gn2 = dot_pinned(gi, gi);
       gdd = dot_pinned(gi, di);

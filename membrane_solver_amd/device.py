@@ -552,6 +552,13 @@ class DeviceMesh:
                 "side_accepts": int(v[3]), "mismatches": int(v[4]), "ahead": int(v[5]), "adopted": int(v[6]),
                 "dropped": int(v[7])}
 
+    def direction_stats(self):
+        """Fused direction passes that left D unstored, and directions written out afterwards (ms_direction_stats)."""
+        v = np.zeros(2, dtype=np.int64)
+        self._chk(L.lib().ms_direction_stats(self._h, v[0:1].ctypes.data_as(L._I64), v[1:2].ctypes.data_as(L._I64)),
+                  "ms_direction_stats")
+        return {"skipped": int(v[0]), "materialized": int(v[1])}
+
     def exec_stats(self):
         """One-workgroup interpreter of one-tile meshes (include/membrane_hip.h, ms_exec_stats)."""
         v = np.zeros(4, dtype=np.int64)
