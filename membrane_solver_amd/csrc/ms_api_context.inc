@@ -216,10 +216,6 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
     c->exec_fused = !(getenv("MS_EXEC_FUSED") != nullptr && atoi(getenv("MS_EXEC_FUSED")) == 0);
   }
   c->shard_chain_enable = !(getenv("MS_SHARD_CHAIN") != nullptr && atoi(getenv("MS_SHARD_CHAIN")) == 0);
-  // (off by default: measured at world 1 it pays for itself in the steady two-trial pattern -- 126 against 153 us per
-  // step pair -- and loses it again on every rejected trial, whose ten gated-out launches cost more than the host
-  // round trip they replace: 12.6 against 12.7 k steps/s over the bench's 200 steps, gpurun_out/r4i)
-  c->shard_spec_enable = getenv("MS_SHARD_AHEAD") != nullptr && atoi(getenv("MS_SHARD_AHEAD")) != 0;
   // tilt relaxations of multi-tile meshes: the backtracking search as multi-trial passes (MS_TSEARCH=0: one launch per
   // module, field and trial, the form the one-tile interpreter records)
   c->tenergy_enable = shard_count == 1 && !(getenv("MS_TSEARCH") != nullptr && atoi(getenv("MS_TSEARCH")) == 0);
@@ -263,7 +259,6 @@ void ms_destroy(ms_ctx* c) {
   for (void* q : c->peer_opened) (void)hipIpcCloseMemHandle(q);
   if (c->d_peer_slab) (void)hipFree(c->d_peer_slab);
   if (c->d_peer_flag) (void)hipFree(c->d_peer_flag);
-  if (c->peer_aux) (void)hipStreamDestroy(c->peer_aux);
   if (c->d_peer_flagtab) (void)hipFree(c->d_peer_flagtab);
   if (c->d_peer_arrived) (void)hipFree(c->d_peer_arrived);
   if (c->comm) shard_comm_destroy(c->comm);
@@ -282,7 +277,6 @@ void ms_destroy(ms_ctx* c) {
     }
   }
   if (c->d_sh_dec) (void)hipFree(c->d_sh_dec);
-  if (c->d_sh_keep) (void)hipFree(c->d_sh_keep);
   if (c->h_sh_post) (void)hipHostFree(c->h_sh_post);
   free(c->tsearch_mb.h_scal);
   if (c->tsearch_mb.h_seq) (void)hipHostFree(c->tsearch_mb.h_seq);

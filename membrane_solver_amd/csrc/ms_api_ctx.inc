@@ -260,13 +260,12 @@ struct ms_ctx {
   void* allgather_user = nullptr;
   double* d_xsend = nullptr;
   double* d_xrecv = nullptr;
-  // ms_shard_step, peer-to-peer transport: the Armijo decision of a trial is ALSO taken on the device (k_shard_decide,
+  // ms_shard_step, peer-to-peer transport: the Armijo decision of a trial is ALSO taken on the device (shard_decide,
   // from the headers in the slab), and the commit, the gradient + direction pass of the accepted point and its exchange
   // are queued behind it, gated on "the main trial was accepted" -- the host replays the decision, and the next step
   // takes the pass's results instead of queueing it (MS_SHARD_CHAIN=0: every decision on the host first)
   bool shard_chain_enable = true;
   uint32_t* d_sh_dec = nullptr;
-  double* d_sh_keep = nullptr;     // 2 x {energy, min edge^2} of the last decided main trials (k_shard_decide keep_out)
   unsigned long long* h_sh_post = nullptr;
   unsigned long long* d_h_sh_post = nullptr;
   unsigned long long sh_post_ticket = 0;
@@ -277,21 +276,8 @@ struct ms_ctx {
     unsigned long long xticket = 0;
   } sh_chain;
   int64_t sh_chained = 0, sh_chain_ran = 0, sh_chain_adopted = 0, sh_chain_dropped = 0;
-  // ... and behind the chain, the FIRST TRIAL of the search two steps on: in the CG steady state the pass the chain
-  // queues computes a direction with history that is no descent direction, that step fails without a trial, the
-  // stepper is reset and the step after it searches along -g from the step size known now.  Its energy launch and
-  // exchange are queued behind the chain (same gate); k_shard_decide (go_kind 1) tests from the direction exchange's
-  // headers whether that search happens and forms its right-hand sides; the step it belongs to adopts it.
-  struct ShardSpec {
-    bool valid = false, pair = false;
-    double alpha0 = 0.0, alpha1 = 0.0, c1 = 0.0, beta = 0.0, tol = 0.0;
-    int stepper = 0, widx = 0;
-    unsigned long long tk = 0, post_ticket = 0;
-  } sh_spec;
-  bool shard_spec_enable = false;  // MS_SHARD_AHEAD=1 on (see ms_create)
   int sh_widx = 0;                 // decision word / post pair in use (two of each, in turn)
   unsigned long long sh_post_expect[2] = {0, 0};
-  int64_t sh_spec_queued = 0, sh_spec_adopted = 0, sh_spec_dropped = 0;
   double* h_scal_all = nullptr;    // pinned + mapped, 2 (exchange parity) x shard_count x MS_NSCAL
   double* d_h_scal_all = nullptr;
   unsigned long long* h_xseq = nullptr;
@@ -308,14 +294,8 @@ struct ms_ctx {
   bool peer_on = false;
   int peer_mem_kind = -1;                   // 0 uncached, 1 fine-grained, 2 plain hipMalloc (peer_alloc)
   unsigned long long peer_ticket = 0;
-  // MS_PEER_WAIT=stream: the flag words are raised and awaited by stream memory operations (hipStreamWriteValue64 behind
-  // the pack kernel, hipStreamWaitValue64 in front of the unpack kernel) instead of a flag kernel and a waiting wave:
-  // nothing of this rank occupies the GPU while it waits for a peer.  The wait itself has no bound -- the host's poll
-  // has (2 s), and releases the words itself before it reports the error.
   PeerFlags* d_peer_flagtab = nullptr;      // [2]: per exchange parity, the peers' flag rows (read by the pack kernel)
   unsigned int* d_peer_arrived = nullptr;   // 16 block counters of the pack kernel
-  bool peer_stream_ops = false;
-  hipStream_t peer_aux = nullptr;           // (the release after a timeout goes through a stream of its own)
   ms_barrier_fn peer_barrier = nullptr;     // contexts of one process: host-side wait instead of the waiting wave
   void* peer_barrier_user = nullptr;
   double sh_scal[MS_NSCAL] = {0};  // rank-ordered fold of the last exchanges

@@ -228,8 +228,8 @@ constexpr uint32_t SH_DIR = (1u << MS_S_GNORM2) | (1u << MS_S_GDOTD) | (1u << MS
 // rank-ordered fold go to c->sh_scal (push: also to the device scalars).
 // queue half of an exchange: pack (+ flags), transport, unpack.  gate != nullptr (peer-to-peer transport with in-kernel
 // flags only): the kernels run iff *gate == gate_want -- a word every rank derives from the same doubles
-// (k_shard_decide), so the exchange is skipped by all ranks or by none.  *ticket_out = the exchange's ticket for
-// shard_exchange_take.
+// (shard_decide), so the exchange is skipped by all ranks or by none.  decide != nullptr: the exchange's unpack kernel
+// takes a trial's decision (never of a gated exchange).  *ticket_out = the exchange's ticket for shard_exchange_take.
 int shard_exchange_queue(ms_ctx* c, int n, const int* ids, unsigned long long* ticket_out, const uint32_t* gate = nullptr,
                          uint32_t gate_want = 0, const ShardDecideArgs* decide = nullptr) {
   double* p[4];
@@ -257,30 +257,18 @@ int shard_exchange_queue(ms_ctx* c, int n, const int* ids, unsigned long long* t
       dst[r] = c->peer_slabs[(size_t)r] + ((size_t)par * W + (size_t)me) * c->peer_stride;
       flg[r] = c->peer_flags[(size_t)r] + (size_t)par * 16;
     }
-    const bool stream_ops = c->peer_stream_ops && !c->peer_barrier;
-    // (the pack kernel's last block per peer raises the flag word itself; with stream memory operations the words are
-    // written behind the kernel instead)
-    const bool fused_flags = !stream_ops && c->d_peer_flagtab != nullptr;
+    // (the pack kernel's last block per peer raises the flag word itself)
+    const bool fused_flags = c->d_peer_flagtab != nullptr;
     if (gate != nullptr && (!fused_flags || c->peer_barrier))
       return fail(c, MS_ERR_STATE, "peer exchange: a gated exchange needs the in-kernel flag words");
+    if (gate != nullptr && decide != nullptr)
+      return fail(c, MS_ERR_STATE, "peer exchange: a gated exchange cannot carry a trial's decision");
     HIPCHK(c, launch_pack_peers(c->d_bnd_rows + c->bnd_off[(size_t)me],
                                 c->bnd_off[(size_t)me + 1] - c->bnd_off[(size_t)me], p, nc, n, c->d_scal, dst, W,
                                 c->stream, fused_flags ? c->d_peer_flagtab + par : nullptr, c->d_peer_arrived, me,
                                 c->peer_ticket, gate, gate_want));
-    if (stream_ops) {
-      // (the pack kernel's stores are system-scope write-through and complete before the kernel does: the value
-      // written behind it in stream order is the release)
-      for (int r = 0; r < W; ++r) HIPCHK(c, hipStreamWriteValue64(S(c), flg[r] + me, c->peer_ticket, 0));
-    } else if (!fused_flags) {
-      HIPCHK(c, launch_flag_peers(flg, me, W, c->peer_ticket, c->stream));
-    }
+    if (!fused_flags) HIPCHK(c, launch_flag_peers(flg, me, W, c->peer_ticket, c->stream));
     const unsigned long long* wait_flags = c->d_peer_flag + (size_t)par * 16;
-    if (stream_ops) {
-      for (int r = 0; r < W; ++r)
-        HIPCHK(c, hipStreamWaitValue64(S(c), const_cast<unsigned long long*>(wait_flags) + r, c->peer_ticket,
-                                       hipStreamWaitValueGte, ~0ull));
-      wait_flags = nullptr;  // (the unpack kernel starts when every word has arrived)
-    }
     if (c->peer_barrier) {  // (contexts of one process wait on the host: see ms_shard_peer_set_barrier)
       HIPCHK(c, hipStreamSynchronize(S(c)));
       if (c->peer_barrier(c->peer_barrier_user) != 0) return fail(c, MS_ERR_STATE, "peer exchange: the caller's barrier failed");
@@ -324,29 +312,11 @@ int shard_exchange_take(ms_ctx* c, unsigned long long ticket, uint32_t slots, bo
   const double* const heads = c->h_scal_all + hx * MS_NSCAL * (size_t)W;
   const unsigned long long* const seq = c->h_xseq + hx * (size_t)W;
   bool seen = false;
-  const bool watchdog = c->peer_on && c->peer_stream_ops && !c->peer_barrier;
-  struct timespec w0;
-  if (watchdog) clock_gettime(CLOCK_MONOTONIC, &w0);
   for (long spin = 0; spin < 20000000L; ++spin) {
     seen = true;
     for (int r = 0; r < W && seen; ++r) seen = __atomic_load_n(seq + r, __ATOMIC_ACQUIRE) >= ticket;
     if (seen) break;
     __builtin_ia32_pause();
-    if (watchdog && (spin & 0xfff) == 0xfff) {
-      struct timespec w1;
-      clock_gettime(CLOCK_MONOTONIC, &w1);
-      if ((double)(w1.tv_sec - w0.tv_sec) + 1e-9 * (double)(w1.tv_nsec - w0.tv_nsec) > 2.0) {
-        // a peer's word has not arrived: the stream sits in an unbounded wait.  Release it (this rank's own words,
-        // through another stream), let the queue drain, report.
-        const int par = (int)(c->peer_ticket % PEER_SLABS);
-        if (!c->peer_aux) HIPCHK(c, hipStreamCreateWithFlags(&c->peer_aux, hipStreamNonBlocking));
-        for (int r = 0; r < W; ++r)
-          HIPCHK(c, hipStreamWriteValue64(c->peer_aux, c->d_peer_flag + (size_t)par * 16 + r, c->peer_ticket, 0));
-        HIPCHK(c, hipStreamSynchronize(c->peer_aux));
-        HIPCHK(c, hipStreamSynchronize(S(c)));
-        return fail(c, MS_ERR_STATE, "peer exchange: a peer's flag word did not arrive within 2 s (stream wait released by the host)");
-      }
-    }
   }
   if (!seen) HIPCHK(c, hipStreamSynchronize(S(c)));
   if (c->peer_on && c->h_err && (__atomic_load_n(c->h_err + 1, __ATOMIC_ACQUIRE) >> 62) == 1) {
@@ -558,14 +528,6 @@ int ms_shard_peer_open(ms_ctx* c, const void* handles_all) {
   rc = peer_flag_table(c);
   if (rc) return rc;
   c->peer_on = true;
-  if (const char* e = getenv("MS_PEER_WAIT")) {
-    if (strcmp(e, "stream") == 0) {
-      int can = 0;
-      HIPCHK(c, hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device));
-      if (!can) return fail(c, MS_ERR_STATE, "MS_PEER_WAIT=stream: the device has no stream wait-value operations");
-      c->peer_stream_ops = true;
-    }
-  }
   return MS_OK;
 }
 
@@ -602,10 +564,7 @@ int ms_shard_chain_stats(const ms_ctx* c, int64_t stats[8]) {
   stats[1] = c->sh_chain_ran;
   stats[2] = c->sh_chain_adopted;
   stats[3] = c->sh_chain_dropped;
-  stats[4] = c->sh_spec_queued;
-  stats[5] = c->sh_spec_adopted;
-  stats[6] = c->sh_spec_dropped;
-  stats[7] = 0;
+  stats[4] = stats[5] = stats[6] = stats[7] = 0;  // reserved
   return MS_OK;
 }
 
@@ -645,10 +604,6 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   bool carried = carry_mode && c->sh_carry_valid;
   int rc;
   bool implicit_restart = false, fused = false;
-  // a first trial queued ahead (ms_ctx::ShardSpec): this step keeps it alive only by failing on a history direction
-  // that is no descent direction (then the NEXT step may adopt it); every other way out drops it
-  const ms_ctx::ShardSpec spec = c->sh_spec;
-  c->sh_spec.valid = false;
   // the gradient + direction pass of this x and its exchange were queued behind the decision that accepted it
   bool adopt = false;
   if (c->sh_chain.valid) {
@@ -661,11 +616,6 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
       rc = shard_exchange_take(c, c->sh_chain.xticket, 0u, false);
       if (rc) return rc;
       ++c->sh_chain_dropped;
-      if (spec.valid) {  // (the trial queued behind it has overwritten the bending factors of x)
-        carried = false;
-        c->sh_carry_valid = false;
-        ++c->sh_spec_dropped;
-      }
     }
   }
   if (!carried) {
@@ -741,10 +691,7 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   const double min_edge = c->til.nf > 0 ? std::sqrt(c->sh_scal[MS_S_MINEDGE2]) : 0.0;
   out->energy = energy0;
   const double safe_limit = min_edge > 0.0 ? 0.3 * min_edge : INFINITY;
-  if (g_dot_d >= 0.0) {
-    if (spec.valid && adopt) c->sh_spec = spec;  // (what the trial queued ahead was queued for: the next step's to take)
-    return MS_OK;
-  }
+  if (g_dot_d >= 0.0) return MS_OK;
   double alpha = step_size;
   if (sp->edge_fraction > 0.0 && min_edge > 0.0 && max_dir > 0.0)
     alpha = std::min(alpha, sp->edge_fraction * min_edge / max_dir);
@@ -760,19 +707,16 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
     ++lh.n;
   };
   // ---- the chain behind a trial's exchange (see ms_ctx::shard_chain_enable) ---------------------------------------------
-  const bool chain_ok = c->shard_chain_enable && c->peer_on && !c->peer_barrier && !c->peer_stream_ops &&
+  const bool chain_ok = c->shard_chain_enable && c->peer_on && !c->peer_barrier &&
                         c->d_peer_flagtab != nullptr && carry_mode && !constraint && !penalty && sp->edge_fraction <= 0.0;
   bool chained = false;            // the exchange in flight has the chain behind it
   unsigned long long chain_ticket = 0;
   bool chain_next_hist = false;
-  ms_ctx::ShardSpec spec_new;      // the trial queued ahead behind this exchange's chain (valid: queued)
   const int pbufs[4] = {MS_BUF_FK, MS_BUF_FA, SH_BUF_FK2, SH_BUF_FA2};
   auto chain_buffers = [&]() -> int {
     if (c->d_sh_dec) return MS_OK;
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_sh_dec), sizeof(uint32_t) * MS_DEC_STRIDE * 2));
     HIPCHK(c, hipMemset(c->d_sh_dec, 0, sizeof(uint32_t) * MS_DEC_STRIDE * 2));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_sh_keep), sizeof(double) * 4));
-    HIPCHK(c, hipMemset(c->d_sh_keep, 0, sizeof(double) * 4));
     HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_sh_post), sizeof(unsigned long long) * 4, hipHostMallocMapped));
     for (int k = 0; k < 4; ++k) c->h_sh_post[k] = 0;
     HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_sh_post), c->h_sh_post, 0));
@@ -788,8 +732,8 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   };
   // ... and the pair launch: the other trial's fold goes to the SH_ALT slots of the device scalars and travels in the
   // exchange header (the driver waits on neither of the side set's mailboxes: parity stays 0)
-  auto pair_stage = [&](double alpha0, const uint32_t* gate) {
-    StageCtl st = gated_stage(gate);
+  auto pair_stage = [&](double alpha0) {
+    StageCtl st = gated_stage(nullptr);
     st.pair_on = 2;
     st.pair_alpha[0] = alpha0;
     st.pair_scal2 = c->d_scal + SH_ALT;
@@ -798,129 +742,36 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   auto slab_of = [&](unsigned long long peer_ticket) {
     return c->d_peer_slab + (size_t)(peer_ticket % PEER_SLABS) * c->shard_count * c->peer_stride;
   };
-  // The first trial of the search TWO steps on, queued behind the chain (ms_ctx::ShardSpec): the context is in the
-  // state the acceptance produces (CG buffers swapped); the step in between is expected to fail on its history
-  // direction, the stepper to be reset, and the step after it to search along -G from `a_next`.
-  auto queue_spec = [&](double a_acc, double rej_acc, const uint32_t* gate, unsigned long long pt_dir, int widx_chain) -> int {
-    const int widx_spec = widx_chain ^ 1;
-    spec_new.valid = false;
-    if (!c->shard_spec_enable || !cg || !chain_next_hist || c->steps_left < 2) return MS_OK;
-    const double a_next = std::min(a_acc * sp->gamma, alpha_max);
-    if (!(a_next * sp->beta >= 1e-8)) return MS_OK;
-    // the restart searches' history as that step will see it (accepted() adds this search to ITS kind's history)
-    ms_ctx::LsHist lh2 = c->ls[0];
-    if (&lh == &c->ls[0]) {
-      lh2.acc[lh2.n % ms_ctx::LS_HIST] = a_acc;
-      lh2.rej[lh2.n % ms_ctx::LS_HIST] = rej_acc;
-      ++lh2.n;
-    }
-    double hi2, lo2;
-    ls_bounds(lh2, hi2, lo2);
-    const bool pair2 = c->pair_enable && bend && max_iter >= 2 &&
-                       (c->pair_force || (lh2.n >= 2 && a_next > 1.05 * hi2 && lo2 < INFINITY));
-    int r2 = pair2 ? spec_prepare(c) : MS_OK;
-    if (r2) return r2;
-    // (not the whole carried state: the trial pass also clears carry_valid and maxg2_valid, and the driver leaves them so)
-    const bool s_implicit = c->carry.dir_implicit, s_factors = c->carry.factors_valid, s_bt = c->carry.bt_valid;
-    c->carry.dir_implicit = true;  // (after the reset: the trial passes read G with -alpha)
-    const double a0 = a_next, a1 = a_next * sp->beta;
-    {
-      StageScope scope(c, pair2 ? pair_stage(a0, gate) : gated_stage(gate));
-      r2 = pair2 ? phase_energy(c, mods, true, a1, false, false, true)
-                 : phase_energy(c, mods, true, a0, false, false, carry_mode);
-    }
-    unsigned long long tk2 = 0;
-    if (r2 == MS_OK) {
-      ShardDecideArgs da;
-      da.recv = slab_of(c->peer_ticket + 1);  // (the exchange queued below)
-      da.stride = c->peer_stride;
-      da.world = c->shard_count;
-      da.has_alt = pair2 ? 1 : 0;
-      da.alt_off = SH_ALT;
-      da.slot_a = (mods & MS_MOD_SURFACE) ? (int)MS_S_ESURF : -1;
-      da.slot_b = bend ? (int)MS_S_EBEND : -1;
-      da.rhs_alt = da.rhs_main = 0.0;  // (formed on the device)
-      da.dec_out = c->d_sh_dec + (size_t)MS_DEC_STRIDE * widx_spec;
-      da.post = c->d_h_sh_post + 2 * widx_spec;
-      da.ticket = ++c->sh_post_ticket;
-      da.gate = gate;
-      da.gate_want = DEC_ACCEPT_MAIN;
-      da.go_kind = 1;
-      da.keep_in = c->d_sh_keep + 2 * widx_chain;
-      da.keep_out = c->d_sh_keep + 2 * widx_spec;
-      da.recv_dir = slab_of(pt_dir);
-      da.tol = tol;
-      da.c1 = sp->c;
-      da.alpha_main = pair2 ? a1 : a0;
-      da.alpha_alt = a0;
-      da.has_faces = c->til.nf > 0 ? 1 : 0;
-      c->sh_post_expect[widx_spec] = da.ticket;
-      r2 = shard_exchange_queue(c, pair2 ? 4 : n_fb, pair2 ? pbufs : fbufs, &tk2, gate, DEC_ACCEPT_MAIN, &da);
-    }
-    if (r2 == MS_OK) {
-      spec_new.valid = true;
-      spec_new.pair = pair2;
-      spec_new.alpha0 = a0;
-      spec_new.alpha1 = a1;
-      spec_new.c1 = sp->c;
-      spec_new.beta = sp->beta;
-      spec_new.tol = tol;
-      spec_new.stepper = sp->stepper;
-      spec_new.widx = widx_spec;
-      spec_new.tk = tk2;
-      spec_new.post_ticket = c->sh_post_ticket;
-      ++c->sh_spec_queued;
-    }
-    c->carry.dir_implicit = s_implicit;
-    c->carry.factors_valid = s_factors;
-    c->carry.bt_valid = s_bt;
-    return r2;
-  };
   // queue a trial's exchange and, when chain: the device-side decision and what an acceptance of the MAIN trial is
-  // followed by; then take the exchange's headers.  adopt_spec: the trial, its exchange and its decision were queued
-  // ahead (spec): only the chain behind them is queued now.
-  auto trial_exchange = [&](int nb, const int* bufs, bool fold_alt, double a_main, double a_alt, bool chain,
-                            bool adopt_spec) -> int {
-    unsigned long long tk = adopt_spec ? spec.tk : 0;
+  // followed by; then take the exchange's headers.
+  auto trial_exchange = [&](int nb, const int* bufs, bool fold_alt, double a_main, double a_alt, bool chain) -> int {
+    unsigned long long tk = 0;
     int r2 = MS_OK;
     chained = false;
-    spec_new.valid = false;
     if (!chain) {
-      r2 = adopt_spec ? MS_OK : shard_exchange_queue(c, nb, bufs, &tk);
+      r2 = shard_exchange_queue(c, nb, bufs, &tk);
       if (r2) return r2;
     }
     if (chain) {
       r2 = chain_buffers();
       if (r2) return r2;
-      if (adopt_spec) {
-        c->sh_widx = spec.widx;
-      } else {
-        c->sh_widx ^= 1;
-        ShardDecideArgs da;
-        da.recv = slab_of(c->peer_ticket + 1);  // (the exchange queued below; its unpack kernel takes the decision)
-        da.stride = c->peer_stride;
-        da.world = c->shard_count;
-        da.has_alt = fold_alt ? 1 : 0;
-        da.alt_off = SH_ALT;
-        da.slot_a = (mods & MS_MOD_SURFACE) ? (int)MS_S_ESURF : -1;
-        da.slot_b = bend ? (int)MS_S_EBEND : -1;
-        da.rhs_alt = energy0 + sp->c * a_alt * g_dot_d;
-        da.rhs_main = energy0 + sp->c * a_main * g_dot_d;
-        da.dec_out = c->d_sh_dec + (size_t)MS_DEC_STRIDE * c->sh_widx;
-        da.post = c->d_h_sh_post + 2 * c->sh_widx;
-        da.ticket = ++c->sh_post_ticket;
-        da.gate = nullptr;
-        da.gate_want = 0;
-        da.go_kind = 0;
-        da.keep_in = nullptr;
-        da.keep_out = c->d_sh_keep + 2 * c->sh_widx;
-        da.recv_dir = nullptr;
-        da.tol = da.c1 = da.alpha_main = da.alpha_alt = 0.0;
-        da.has_faces = 0;
-        c->sh_post_expect[c->sh_widx] = da.ticket;
-        r2 = shard_exchange_queue(c, nb, bufs, &tk, nullptr, 0, &da);
-        if (r2) return r2;
-      }
+      c->sh_widx ^= 1;
+      ShardDecideArgs da;
+      da.recv = slab_of(c->peer_ticket + 1);  // (the exchange queued below; its unpack kernel takes the decision)
+      da.stride = c->peer_stride;
+      da.world = c->shard_count;
+      da.has_alt = fold_alt ? 1 : 0;
+      da.alt_off = SH_ALT;
+      da.slot_a = (mods & MS_MOD_SURFACE) ? (int)MS_S_ESURF : -1;
+      da.slot_b = bend ? (int)MS_S_EBEND : -1;
+      da.rhs_alt = energy0 + sp->c * a_alt * g_dot_d;
+      da.rhs_main = energy0 + sp->c * a_main * g_dot_d;
+      da.dec_out = c->d_sh_dec + (size_t)MS_DEC_STRIDE * c->sh_widx;
+      da.post = c->d_h_sh_post + 2 * c->sh_widx;
+      da.ticket = ++c->sh_post_ticket;
+      c->sh_post_expect[c->sh_widx] = da.ticket;
+      r2 = shard_exchange_queue(c, nb, bufs, &tk, nullptr, 0, &da);
+      if (r2) return r2;
       const uint32_t* gate = c->d_sh_dec + (size_t)MS_DEC_STRIDE * c->sh_widx;
       // (a) the commit: x <- x + alpha d on the rows this rank reads (ms_phase_commit_trial's launch)
       const Tiling& t = c->til;
@@ -929,11 +780,11 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
                                  c->d_vflags, c->buf[MS_BUF_X], trial_dir(c), trial_alpha(c, a_main), c->stream, gate,
                                  DEC_ACCEPT_MAIN));
       // (b) the gradient + direction pass in the state the acceptance produces (CG history swapped, the trial's
-      // factors valid), every change of the context undone afterwards; (c) its exchange; (d) the trial queued ahead
+      // factors valid), every change of the context undone afterwards; (c) its exchange
+      // (of the carried state the pass writes last_g, dir_implicit and dir_unwritten -- false before and after: no
+      // sharded pass leaves D unstored -- and the exchange nothing, so the record is copied out and back whole)
       chain_next_hist = next_use_history(c, cg, restart);
-      // (not the whole carried state: queue_spec's trial pass clears carry_valid and maxg2_valid, and they stay cleared)
-      const bool s_factors = c->carry.factors_valid, s_implicit = c->carry.dir_implicit, s_pdneg = c->carry.pd_neg_pg, s_grad = c->carry.grad_valid;
-      double* const s_last_g = c->carry.last_g;
+      const CarryState s_carry = c->carry;
       if (cg) {
         std::swap(c->buf[MS_BUF_G], c->buf[MS_BUF_PG]);
         std::swap(c->buf[MS_BUF_D], c->buf[MS_BUF_PD]);
@@ -945,16 +796,11 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
         r2 = phase_gradient(c, mods, c->buf[MS_BUF_G], false, chain_next_hist ? 2 : 1);
       }
       if (r2 == MS_OK) r2 = shard_exchange_queue(c, 2, dbuf, &chain_ticket, gate, DEC_ACCEPT_MAIN);
-      if (r2 == MS_OK) r2 = queue_spec(a_main, fold_alt ? a_alt : min_rejected, gate, c->peer_ticket, c->sh_widx);
       if (cg) {
         std::swap(c->buf[MS_BUF_G], c->buf[MS_BUF_PG]);
         std::swap(c->buf[MS_BUF_D], c->buf[MS_BUF_PD]);
       }
-      c->carry.factors_valid = s_factors;
-      c->carry.dir_implicit = s_implicit;
-      c->carry.pd_neg_pg = s_pdneg;
-      c->carry.grad_valid = s_grad;
-      c->carry.last_g = s_last_g;
+      c->carry = s_carry;
       if (r2) return r2;
       chained = true;
       ++c->sh_chained;
@@ -979,7 +825,7 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
       if ((bits ^ __atomic_load_n(&box[1], __ATOMIC_ACQUIRE)) != want)
         return fail(c, MS_ERR_STATE, "sharded step: the device-side decision of a trial never arrived");
     }
-    return verify_decision(c, host_code, (uint32_t)bits, "a sharded trial (k_shard_decide)");
+    return verify_decision(c, host_code, (uint32_t)bits, "a sharded trial (shard_decide)");
   };
   auto accepted = [&](double alpha_acc, double E_t) -> int {
     int r2;
@@ -993,7 +839,6 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
       c->sh_chain.use_history = chain_next_hist;
       c->sh_chain.xticket = chain_ticket;
       ++c->sh_chain_ran;
-      c->sh_spec = spec_new;  // (valid: a first trial was queued ahead behind this chain)
     } else {
       r2 = ms_phase_commit_trial(c, alpha_acc, cg ? 1 : 0);
     }
@@ -1020,27 +865,17 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   const bool pair = c->pair_enable && carry_mode && bend && !penalty && max_iter >= 2 &&
                     alpha * max_dir < safe_limit && alpha * sp->beta >= 1e-8 &&
                     (c->pair_force || (lh.n >= 2 && alpha > 1.05 * a_hi && r_lo < INFINITY));
-  // the first trial of this search (its launch, exchange and device-side decision) was queued ahead, behind the chain
-  // of the step before last: take it if it was queued for exactly what this step has arrived at
-  bool adopt_spec = false;
-  if (spec.valid) {
-    adopt_spec = implicit_restart && chain_ok && spec.stepper == sp->stepper && spec.alpha0 == alpha && spec.pair == pair &&
-                 spec.c1 == sp->c && spec.beta == sp->beta && spec.tol == tol && alpha * max_dir < safe_limit;
-    if (adopt_spec) ++c->sh_spec_adopted;
-    else ++c->sh_spec_dropped;  // (its kernels ran for nothing; this step's own trial launch overwrites what they wrote)
-  }
   if (pair) {
     rc = spec_prepare(c);
     if (rc) return rc;
     const double alpha0 = alpha, alpha1 = alpha * sp->beta;
-    if (!adopt_spec) {
-      StageScope scope(c, pair_stage(alpha0, nullptr));
+    {
+      StageScope scope(c, pair_stage(alpha0));
       rc = phase_energy(c, mods, true, alpha1, false, false, true);
       if (rc) return rc;
     }
     c->sh_carry_valid = false;
-    rc = trial_exchange(4, pbufs, /*fold_alt=*/true, alpha1, alpha0, chain_ok, adopt_spec);
-    adopt_spec = false;
+    rc = trial_exchange(4, pbufs, /*fold_alt=*/true, alpha1, alpha0, chain_ok);
     if (rc) return rc;
     ++out->trials;
     const double E0 = shard_energy_of(c, c->sh_scal2);
@@ -1071,14 +906,10 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   }
   for (int it = it0; it < max_iter; ++it) {
     const bool safe_small = alpha * max_dir < safe_limit;
-    const bool ad = adopt_spec && it == 0;  // (queued ahead for exactly this trial)
-    adopt_spec = false;
-    if (!ad) {
-      rc = phase_energy(c, mods, true, alpha, false, !safe_small, carry_mode);
-      if (rc) return rc;
-    }
+    rc = phase_energy(c, mods, true, alpha, false, !safe_small, carry_mode);
+    if (rc) return rc;
     if (carry_mode) c->sh_carry_valid = false;  // the factor buffers now belong to the trial point
-    rc = trial_exchange(carry_mode ? n_fb : 0, fbufs, false, alpha, 0.0, chain_ok && safe_small, ad);
+    rc = trial_exchange(carry_mode ? n_fb : 0, fbufs, false, alpha, 0.0, chain_ok && safe_small);
     if (rc) return rc;
     if (chained) {
       rc = verify_chain(shard_energy(c) <= energy0 + sp->c * alpha * g_dot_d ? DEC_ACCEPT_MAIN : DEC_CONTINUE);

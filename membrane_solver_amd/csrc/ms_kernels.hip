@@ -375,9 +375,6 @@ __device__ __forceinline__ TileCtx tile_ctx(const DeviceMesh& m, int tile) {
 #ifndef MS_KA_SLOTS
 #define MS_KA_SLOTS 5  // workgroups per CU the headline k_energy instances are compiled for
 #endif
-#ifndef MS_ROW_TWO_PASS
-#define MS_ROW_TWO_PASS 0
-#endif
 #ifndef MS_LEAN_SLOTS
 #define MS_LEAN_SLOTS 5  // workgroups per CU the lean k_gradient instance is compiled for (<= 96 VGPRs)
 #endif
@@ -1165,11 +1162,7 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
   double* tl = kp + (LEAF ? cap : 0);         // LEAF: tilts
   double* stg = tl + (LEAF ? 3 * cap : 0);
   // ATOMIC: stg holds the per-vertex accumulators (ds_add_f64) instead of per-corner columns
-  // MS_ROW_TWO_PASS (A/B build): the constraint row's gC through the SAME three accumulator columns in a second sweep
-  // over the facets (cross products of the staged positions only) instead of three columns of its own -- five
-  // workgroups per CU instead of four
-  constexpr bool ROW2 = MS_ROW_TWO_PASS != 0 && VOLROW && ATOMIC;
-  constexpr int NACC = (VOLROW && !ROW2) ? 6 : 3;  // ATOMIC: gradient (and constraint-row) accumulator columns
+  constexpr int NACC = VOLROW ? 6 : 3;  // ATOMIC: gradient (and constraint-row) accumulator columns
   double* red = stg + (ATOMIC ? NACC : (VOLROW ? 18 : 9)) * T;
   uint16_t* vent = reinterpret_cast<uint16_t*>(red + 4 * 16);
   uint8_t* lfl = reinterpret_cast<uint8_t*>(vent + (ATOMIC ? 0 : ((max_ent + 3) & ~3)));
@@ -1423,7 +1416,7 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
           G1 = G1 + pen_factor * w1;
           G2 = G2 + pen_factor * w2;
         }
-        if (VOLROW && ATOMIC && !ROW2) {
+        if (VOLROW && ATOMIC) {
           const double s6 = 1.0 / 6.0;
           const int no = t.n_owned;
           double* c = stg + 3 * T;
@@ -1646,34 +1639,10 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
 #endif
       gy = stg[T + tid];
       gz = stg[2 * T + tid];
-      if (VOLROW && !ROW2) {
+      if (VOLROW) {
         cx = stg[3 * T + tid];
         cy = stg[4 * T + tid];
         cz = stg[5 * T + tid];
-      }
-    }
-    if (ROW2) {
-      __syncthreads();  // (every owner has read its gradient row)
-      if (tid < T) stg[tid] = stg[T + tid] = stg[2 * T + tid] = 0.0;
-      __syncthreads();
-      const double s6 = 1.0 / 6.0;
-      const int no = t.n_owned;
-      for (int c0f = t.f0; c0f < t.f1; c0f += T) {
-        const int p = c0f + tid;
-        if (p >= t.f1) continue;
-        const TileFacet tf = facet_unpack<PACKED>(facet_load<PACKED>(a.m, (size_t)p));
-        if (!(tf.flags & TF_BODY)) continue;
-        const V3 v0 = lds_row3(px, tf.l0), v1 = lds_row3(px, tf.l1), v2 = lds_row3(px, tf.l2);
-        const V3 w0 = cross(v1, v2), w1 = cross(v2, v0), w2 = cross(v0, v1);
-        if (tf.l0 < no) { atomicAdd(&stg[tf.l0], s6 * w0.x); atomicAdd(&stg[T + tf.l0], s6 * w0.y); atomicAdd(&stg[2 * T + tf.l0], s6 * w0.z); }
-        if (tf.l1 < no) { atomicAdd(&stg[tf.l1], s6 * w1.x); atomicAdd(&stg[T + tf.l1], s6 * w1.y); atomicAdd(&stg[2 * T + tf.l1], s6 * w1.z); }
-        if (tf.l2 < no) { atomicAdd(&stg[tf.l2], s6 * w2.x); atomicAdd(&stg[T + tf.l2], s6 * w2.y); atomicAdd(&stg[2 * T + tf.l2], s6 * w2.z); }
-      }
-      __syncthreads();
-      if (tid < t.n_owned) {
-        cx = stg[tid];
-        cy = stg[T + tid];
-        cz = stg[2 * T + tid];
       }
     }
   }
@@ -1760,7 +1729,7 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
 }
 
 template <int BENDMODE, bool VOLROW, int TT, int CAPC, bool ATOMIC, bool LEAN = false>
-__global__ __launch_bounds__(TT ? TT : 512, LEAN ? (ATOMIC ? ((VOLROW && !MS_ROW_TWO_PASS) ? 4 : MS_LEAN_SLOTS) : 3) : 1) MS_WPE_GRADIENT void k_gradient(GradientArgs a, int cap_rt, int max_ent) {
+__global__ __launch_bounds__(TT ? TT : 512, LEAN ? (ATOMIC ? (VOLROW ? 4 : MS_LEAN_SLOTS) : 3) : 1) MS_WPE_GRADIENT void k_gradient(GradientArgs a, int cap_rt, int max_ent) {
   extern __shared__ double lds[];
   gradient_body<BENDMODE, VOLROW, TT, CAPC, ATOMIC, LEAN>(a, cap_rt, max_ent, lds, (int)blockIdx.x);
 }
@@ -1772,7 +1741,7 @@ __global__ __launch_bounds__(TT ? TT : 512, 1) MS_WPE_GRADIENT void k_gradient_a
 }
 
 size_t gradient_lds_bytes(int T, int cap, int max_ent, bool bend, bool volrow, bool atomic, bool leaf) {
-  const size_t cols = atomic ? ((volrow && !MS_ROW_TWO_PASS) ? 6 : 3) : (volrow ? 18 : 9);
+  const size_t cols = atomic ? (volrow ? 6 : 3) : (volrow ? 18 : 9);
   size_t d = 3 * (size_t)cap + (bend ? 5 * (size_t)cap : 0) + (leaf ? 4 * (size_t)cap : 0) + cols * (size_t)T + 4 * 16;
   return d * sizeof(double) + (atomic ? 0 : u16_bytes(T, max_ent)) + (((size_t)cap + 15) / 16) * 16;
 }
@@ -3393,44 +3362,12 @@ __device__ void shard_decide(const ShardDecideArgs& a) {
     return e;
   };
   uint32_t code = DEC_CONTINUE;
-  double rhs_alt = a.rhs_alt, rhs_main = a.rhs_main;
-  if (a.gate != nullptr && ld_agent(a.gate) != a.gate_want) {
-    code = DEC_STOP;  // (the trial this launch would decide never ran)
-  } else if (a.go_kind != 0) {
-    // a trial queued AHEAD of its step (ms_shard_step: the search of the restart after a history direction that is no
-    // descent direction): does that search happen at all, and its right-hand sides -- the host's expressions
-    const double e0 = ld_agent(a.keep_in), me2 = ld_agent(a.keep_in + 1);
-    double gn2 = 0.0, gdd = 0.0;
-    for (int r = 0; r < a.world; ++r) gn2 += ld(a.recv_dir + (size_t)r * a.stride + MS_S_GNORM2);
-    for (int r = 0; r < a.world; ++r) gdd += ld(a.recv_dir + (size_t)r * a.stride + MS_S_GDOTD);
-    double mg2 = ld(a.recv_dir + MS_S_MAXG2);
-    for (int r = 1; r < a.world; ++r) mg2 = fmax(mg2, ld(a.recv_dir + (size_t)r * a.stride + MS_S_MAXG2));
-    const double min_edge = a.has_faces ? sqrt(me2) : 0.0;
-    const double safe = min_edge > 0.0 ? __dmul_rn(0.3, min_edge) : INFINITY;
-    const double first = a.has_alt ? a.alpha_alt : a.alpha_main;
-    const bool go = gdd >= 0.0 && !(sqrt(gn2) < a.tol) && __dmul_rn(first, sqrt(mg2)) < safe;
-    if (!go) code = DEC_STOP;
-    const double slope = -gn2;
-    rhs_alt = __dadd_rn(e0, __dmul_rn(__dmul_rn(a.c1, a.alpha_alt), slope));
-    rhs_main = __dadd_rn(e0, __dmul_rn(__dmul_rn(a.c1, a.alpha_main), slope));
-  }
   for (int t = a.has_alt ? 0 : 1; t < 2 && code == DEC_CONTINUE; ++t) {
     const double e = energy_of(a.recv, t == 0 ? a.alt_off : 0);
-    if (e <= (t == 0 ? rhs_alt : rhs_main)) code = t == 0 ? DEC_ACCEPT_SIDE : DEC_ACCEPT_MAIN;
-  }
-  if (a.keep_out != nullptr && code != DEC_STOP) {
-    // what a trial queued ahead behind THIS trial's chain needs of it, kept outside the slab (which a fast peer may be
-    // writing the exchange three tickets on into by then): the main trial's energy and min edge^2, the host's folds
-    st_agent(a.keep_out, energy_of(a.recv, 0));
-    double m2 = ld(a.recv + MS_S_MINEDGE2);
-    for (int r = 1; r < a.world; ++r) m2 = fmin(m2, ld(a.recv + (size_t)r * a.stride + MS_S_MINEDGE2));
-    st_agent(a.keep_out + 1, m2);
+    if (e <= (t == 0 ? a.rhs_alt : a.rhs_main)) code = t == 0 ? DEC_ACCEPT_SIDE : DEC_ACCEPT_MAIN;
   }
   st_agent(a.dec_out, code);
   if (a.post != nullptr) post_entry(a.post, 0, (unsigned long long)code, a.ticket);
-}
-__global__ void k_shard_decide(ShardDecideArgs a) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) shard_decide(a);
 }
 // grid (ceil(max_rows/256), world); recv = world x stride doubles
 template <bool REMOTE>
@@ -3440,11 +3377,7 @@ __global__ void k_unpack_boundary(const int32_t* rows_all, const int32_t* row_of
                                   const unsigned long long* wait_flags, unsigned long long wait_ticket,
                                   unsigned long long* host_err, const uint32_t* gate, uint32_t gate_want,
                                   int has_decide, ShardDecideArgs dec, unsigned int* dec_arrived) {
-  if (gate != nullptr && ld_agent(gate) != gate_want) {
-    // (the decision this exchange would have fed: the trial never ran)
-    if (has_decide && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) shard_decide(dec);
-    return;
-  }
+  if (gate != nullptr && ld_agent(gate) != gate_want) return;  // (a gated exchange feeds no decision)
   const int r = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const double* src = recv + (size_t)r * stride;
@@ -3582,12 +3515,6 @@ hipError_t launch_flag_peers(unsigned long long* const* peer_flags, int me, int 
 __global__ void k_post_seq(unsigned long long* host_seq, unsigned long long ticket) {
   __threadfence_system();
   *reinterpret_cast<volatile unsigned long long*>(host_seq) = ticket;
-}
-
-hipError_t launch_shard_decide(const ShardDecideArgs& a, hipStream_t s) {
-  if (hipError_t es_ = exec_sync(s); es_ != hipSuccess) return es_;  // (not recorded: runs behind what was)
-  hipLaunchKernelGGL(k_shard_decide, dim3(1), dim3(64), 0, s, a);
-  return hipGetLastError();
 }
 
 __global__ void k_gate_probe(const uint32_t* gate, uint32_t want, uint32_t* out) {

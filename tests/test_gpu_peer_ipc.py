@@ -43,8 +43,7 @@ for _ in range(12):
     step = r.next_step
     if not r.success:
         drv.reset()
-# ... and the same loop inside the library (ms_minimize over ms_shard_step): there the first trial of the search two
-# steps on is queued behind the chain as well
+# ... and the same loop inside the library (ms_minimize over ms_shard_step)
 o = drv.run(24, step, tol=1e-9)
 run = (int(o.accepted), int(o.trials), float(o.step_size), float(o.energy_eval), float(o.grad_norm))
 torch.cuda.synchronize()
@@ -55,15 +54,12 @@ dist.destroy_process_group()
 """
 
 
-@pytest.mark.parametrize("wait", ["kernel", "kernel-ahead", "kernel-host-decisions", "stream"])
+@pytest.mark.parametrize("wait", ["kernel", "kernel-host-decisions"])
 def test_two_processes_exchange_through_ipc_mapped_slabs(wait):
     """wait "kernel": flag words raised by the pack kernel + bounded in-kernel wait (the default) -- and with them the
     device-side trial decisions: the commit, the gradient + direction pass and its exchange run behind the decision
-    word on both ranks, the next step adopts them; "kernel-ahead": MS_SHARD_AHEAD=1 on top -- the first trial of the search
-    two steps on is queued behind the chain, with a device-side test whether that search happens, and adopted by its step;
-    "kernel-host-decisions": the same transport with MS_SHARD_CHAIN=0;
-    "stream": MS_PEER_WAIT=stream, the flag words raised and awaited by hipStreamWriteValue64 / hipStreamWaitValue64 on
-    the IPC-mapped words (host decisions)."""
+    word on both ranks, the next step adopts them;
+    "kernel-host-decisions": the same transport with MS_SHARD_CHAIN=0."""
     from membrane_solver_amd import _lib as L
     from membrane_solver_amd import meshgen
     from membrane_solver_amd.device import DeviceMesh
@@ -75,13 +71,7 @@ def test_two_processes_exchange_through_ipc_mapped_slabs(wait):
     for rank in range(2):
         env = dict(os.environ, MS_ROOT=ROOT, RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
-        env.pop("MS_PEER_WAIT", None)
         env.pop("MS_SHARD_CHAIN", None)
-        env.pop("MS_SHARD_AHEAD", None)
-        if wait == "kernel-ahead":
-            env["MS_SHARD_AHEAD"] = "1"
-        if wait == "stream":
-            env["MS_PEER_WAIT"] = "stream"
         if wait == "kernel-host-decisions":
             env["MS_SHARD_CHAIN"] = "0"
         procs.append(subprocess.Popen([sys.executable, "-c", RANK_SCRIPT], env=env, stdout=subprocess.PIPE,
@@ -137,13 +127,9 @@ def test_two_processes_exchange_through_ipc_mapped_slabs(wait):
         assert np.allclose(o["run"][2:4], ref_run[2:4], rtol=1e-12) and np.isclose(o["run"][4], ref_run[4], rtol=1e-9)
     assert outs[0]["exchanges"] == outs[1]["exchanges"]
     assert outs[0]["chain"] == outs[1]["chain"]
-    if wait in ("kernel", "kernel-ahead"):
+    if wait == "kernel":
         ch = outs[0]["chain"]
         assert ch["ran"] >= 2 and ch["adopted"] >= 1 and ch["queued"] >= ch["ran"], ch
-        if wait == "kernel-ahead":
-            assert ch["ahead_queued"] >= 1 and ch["ahead_adopted"] >= 1, ch
-            assert ch["ahead_adopted"] + ch["ahead_dropped"] <= ch["ahead_queued"], ch
-        else:
-            assert ch["ahead_queued"] == 0
+        assert set(ch) == {"queued", "ran", "adopted", "dropped"}
     else:
         assert outs[0]["chain"]["queued"] == 0
