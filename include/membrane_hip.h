@@ -72,6 +72,10 @@ extern "C" {
  * k and A0 come from ms_set_area_penalty.  Its gradient k (A - A0) dA/dx is an effective surface tension on the
  * facets that carry the body flag (geometry/facet.py:168-249: the surface term's normal and 1e-12 clamp). */
 #define MS_MOD_AREA_PENALTY 65536u
+/* line tension E = sum gamma |e| over the tagged edges (modules/energy/line_tension.py:103-140); the edges and their
+ * gamma come from ms_set_line_tension.  Its energy is added into the surface slot (MS_S_ESURF, energies[0]) behind the
+ * energy pass, its gradient into G behind the gradient pass: two extra launches, no reduction slot of its own. */
+#define MS_MOD_LINE_TENSION 131072u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -233,6 +237,29 @@ int ms_set_area_penalty(ms_ctx *ctx, double stiffness, double target_area);
 /* the body's area as the last energy pass folded it (MS_S_AREA; synchronises): the module's own energy is
  * 1/2 k (area - A0)^2 */
 int ms_get_body_area(ms_ctx *ctx, double *area);
+/* line_tension (modules/energy/line_tension.py:24-34 selects the edges, :117-123 their gamma: the edge's own
+ * "line_tension" option or else the global parameter; an edge whose gamma is 0 is skipped): n_edges tagged edges as
+ * EXTERNAL rows (the order of ms_set_positions) in ascending edge order, gamma per edge.  Every row is validated
+ * (MS_ERR_INVALID when one is out of range or a gamma is not finite).  tail == NULL clears the tables.  Used while
+ * MS_MOD_LINE_TENSION is in ms_params.modules (with no tables the module contributes nothing); energies[0] of the
+ * evaluation calls is then surface + line tension.  An edge shorter than 1e-15 contributes nothing (:133-134).  The
+ * module takes the penalties' lane of ms_step: one trial per launch, every Armijo decision the host's, no rounds queued
+ * ahead, no resident steps; under the one-workgroup interpreter its two kernels are not recorded (they flush it first).
+ * Single GPU, no tilt-family module next to it (both refused with MS_ERR_STATE). */
+int ms_set_line_tension(ms_ctx *ctx, int n_edges, const int32_t *tail, const int32_t *head, const double *gamma);
+/* the module's own energy as the last energy pass summed it (line_tension.py:136; synchronises); 0 without tables */
+int ms_get_line_energy(ms_ctx *ctx, double *energy);
+/* stats: {k_line_energy launches, k_line_grad launches, and -- from HIP events around the launches made while
+ * ms_profile_enable was on -- their summed microseconds, k_line_energy then k_line_grad}; reading resets the event
+ * sums (synchronises).  No reference counterpart. */
+int ms_line_stats(ms_ctx *ctx, double stats[4]);
+/* Host only, no context: the tables ms_set_line_tension uploads, built by the same code from external rows and a row
+ * permutation iperm (external row -> library row): counts = {edges kept, touched rows}; the edge table (e_tail,
+ * e_head, e_gamma: n_edges entries at most) and the vertex -> edge CSR (vrow: 2 n_edges at most, off: one more,
+ * other / csr_gamma: 2 n_edges).  No reference counterpart. */
+int ms_line_tables_host(int nv, const int32_t *iperm, int n_edges, const int32_t *tail, const int32_t *head,
+                        const double *gamma, int32_t counts[2], int32_t *e_tail, int32_t *e_head, double *e_gamma,
+                        int32_t *vrow, int32_t *off, int32_t *other, double *csr_gamma);
 /* Per-vertex accumulation in the two big tile kernels (energy pass, gradient pass):
  * 0 (default) LDS atomic adds -- fastest, the floating-point summation order (hence the
  * last bits) may differ between runs; 1 staged CSR gather in a fixed order -- bitwise
@@ -349,7 +376,7 @@ int ms_get_vertex_buffer(ms_ctx *ctx, int buffer, double *out /* nv*ncomp */);
 /*
  * Minimizer.compute_energy_and_gradient_array (runtime/minimizer.py:941-992):
  * module loop, volume-constraint projection, fixed rows zeroed.  energies[4] =
- * {surface, bending, volume-penalty + area-penalty, tilt}.  grad may be NULL (stays on device).
+ * {surface + line tension, bending, volume-penalty + area-penalty, tilt}.  grad may be NULL (stays on device).
  */
 int ms_energy_and_gradient(ms_ctx *ctx, double energies[4], double *grad);
 /*

@@ -348,6 +348,13 @@ struct ms_ctx {
   PinGradArgs pin_grad{};
   int pin_lane = -1;
   long pin_enforce_launches = 0, pin_grad_launches = 0, pin_trials = 0;
+  // line_tension (ms_set_line_tension): one allocation holds every table, the per-workgroup sums and the module's energy
+  void* d_line = nullptr;
+  LineEnergyArgs line_en{};
+  LineGradArgs line_gr{};
+  bool line_set = false;
+  long line_launches[2] = {0, 0};  // k_line_energy, k_line_grad
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> line_prof[2];  // event brackets while profiling (ms_line_stats)
   const StageCtl& stage() const { return stage_; }
  private:
   friend struct StageScope;

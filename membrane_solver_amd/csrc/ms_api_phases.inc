@@ -9,6 +9,8 @@ inline hipStream_t S(ms_ctx* c) {
   return c->stream;
 }
 int pin_grad_run(ms_ctx* c, bool volrow);  // (ms_api_pins.inc)
+int line_energy_run(ms_ctx* c, bool use_dir, double alpha);  // (ms_api_line.inc)
+int line_grad_run(ms_ctx* c, double* g, bool volrow);
 inline int exec_flush(ms_ctx* c) {
   if (!c->exec_on) return MS_OK;
   const hipError_t e = c->exec.flush();
@@ -622,6 +624,9 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     }
   }
   if (bt && !c->d_bt_vert) return fail(c, MS_ERR_STATE, "bending_tilt: ms_set_params did not allocate its buffers");
+  // line_tension takes the penalties' lane: one trial per launch, every Armijo decision the host's
+  if ((modules & MS_MOD_LINE_TENSION) && (st.pair_on > 1 || st.cur_gate != nullptr || lbt))
+    return fail(c, MS_ERR_STATE, "line_tension: the energy pass was queued on the device-decided lane");
   a.partials = c->d_partials;
   a.bending_model = c->params.bending_model;
   a.modules = modules;
@@ -718,6 +723,11 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
       if (write_factors) c->factors_leaflet = l;
     }
   }
+  // line_tension: gamma |e| of the tagged edges added into the MS_S_ESURF partials the launch above has just written
+  // (k_energy stores that slot's partial for every tile of the range whatever the module mask -- 0.0 without
+  // MS_MOD_SURFACE -- so the cell is defined before the add); the fold below then carries surface + line energy
+  if (modules & MS_MOD_LINE_TENSION)
+    if (int rc_l = line_energy_run(c, use_dir, alpha)) return rc_l;
   if (modules & MS_TILT_MODS) {
     int rc = MS_OK;
     const double* tilts = c->tf[0].tilts;
@@ -837,6 +847,14 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
   if (n_lbt == 0) {
     ProfScope ps(c, gradient_lean_instance(a) ? 9 : 1, a.gate, a.gate_want);
     HIPCHK(c, launch_gradient(a, c->cap, c->til.max_ent, c->stream));
+  }
+  // line_tension: its rows added into the G that K_C has just written (before pin_grad_run projects the full gradient),
+  // and the <g,gC> partials corrected by the change.  The direction scalars of K_C's fused epilogue would predate the
+  // addition: the callers take the separate direction pass (queue_energy_and_gradient)
+  if ((modules_in & MS_MOD_LINE_TENSION) && g_out) {
+    if (dir_mode || a.gate != nullptr)
+      return fail(c, MS_ERR_STATE, "line_tension cannot use the fused direction pass or a gated gradient pass");
+    if (int rc_l = line_grad_run(c, g_out, a.gC != nullptr)) return rc_l;
   }
   for (int k = 0; k < n_lbt; ++k) {
     TiltField& f = c->tf[lbt_order[k]];
@@ -1064,7 +1082,8 @@ double penalty_energy(const ms_ctx* c, double V, double A) {
 
 // energies from the pinned mailbox: {surface, bending, penalty, tilt}
 void energies_from_mailbox(const ms_ctx* c, double e[4]) {
-  e[0] = (c->params.modules & MS_MOD_SURFACE) ? c->h_scal[MS_S_ESURF] : 0.0;
+  // (line_tension's energy rides in the surface slot: k_line_energy adds it into that slot's partials)
+  e[0] = (c->params.modules & (MS_MOD_SURFACE | MS_MOD_LINE_TENSION)) ? c->h_scal[MS_S_ESURF] : 0.0;
   e[1] = (c->params.modules & MS_MOD_BENDING) ? c->h_scal[MS_S_EBEND] : 0.0;
   if (c->params.modules & MS_MOD_BENDING_TILT) e[1] += c->h_scal[MS_S_EBT];
   e[2] = penalty_energy(c, c->h_scal[MS_S_VOL], c->h_scal[MS_S_AREA]);
@@ -1087,8 +1106,9 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
   const uint32_t mods = c->params.modules;
   // lambda needs a global reduction first; the tilt module adds into g after K_C
   // (and a preconditioned direction -- conjugate_gradient.py:74-76 -- is the direction kernel's)
-  const bool constraint = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS)) != 0 || (stepper == MS_STEPPER_CG && c->precond) ||
-                          c->pin_lane == MS_PIN_LANE_PROJECT;
+  // (line_tension adds into g after K_C as well: |g|^2, <g,d> and max|g_i|^2 are taken over the completed G)
+  const bool constraint = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS | MS_MOD_LINE_TENSION)) != 0 ||
+                          (stepper == MS_STEPPER_CG && c->precond) || c->pin_lane == MS_PIN_LANE_PROJECT;
   // K_C reads the reduced volume / body area (already reduced when the energy pass is skipped)
   const bool penalty = skip_energy || (mods & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) != 0;
   int rc = MS_OK;

@@ -355,6 +355,39 @@ struct PinGradArgs {
 };
 hipError_t launch_pin_enforce(const PinEnforceArgs& a, hipStream_t s);
 hipError_t launch_pin_grad(const PinGradArgs& a, hipStream_t s);
+// line_tension (ms_line.hip): E = sum gamma |x_h - x_t| over the tagged edges, added into the MS_S_ESURF partials behind
+// the energy pass, and its gradient added into G behind the gradient pass.  Rows are the library's (til.iperm applied).
+struct LineEnergyArgs {
+  const double* x;
+  const double* d;        // trial direction or nullptr, alpha: exactly what EnergyArgs hands k_energy
+  double alpha;
+  const uint8_t* vflags;  // (a fixed row does not move in a trial)
+  int n_edges;
+  const int32_t* tail;    // edge table, ascending edge order, gamma != 0 only
+  const int32_t* head;
+  const double* gamma;
+  double* partials;       // the energy pass's: workgroup w adds into [MS_S_ESURF * n_tiles + tile0 + w]
+  int n_tiles, tile0;
+  int grid;               // workgroups of the launch: min(tiles, ceil(n_edges / 256))
+  double* wg_sums;        // [grid] per-workgroup sums ...
+  uint32_t* done;         // ... counted here; the workgroup that arrives last adds them up in index order ...
+  double* energy;         // ... into the module's own energy (ms_get_line_energy)
+};
+struct LineGradArgs {
+  const double* x;
+  double* g;
+  const double* gc;       // the volume row K_C wrote, or nullptr
+  int n_touch;
+  const int32_t* vrow;    // touched rows, ascending
+  const int32_t* off;     // n_touch + 1: CSR over the rows' tagged edges, ascending edge order
+  const int32_t* other;   // the other end's row
+  const double* gamma;
+  double* partials;       // the gradient pass's: workgroup w adds sum dg_v . gC_v into [MS_S_GGC * n_tiles + tile0 + w]
+  int n_tiles, tile0;
+  int grid;
+};
+hipError_t launch_line_energy(const LineEnergyArgs& a, hipStream_t s);
+hipError_t launch_line_grad(const LineGradArgs& a, hipStream_t s);
 struct RowDotArgs {
   int tile0, nv, T;
   const double* g;

@@ -129,6 +129,37 @@ class DeviceMesh:
         delta = self.body_area() - a0
         return 0.5 * k * delta * delta
 
+    def set_line_tension(self, tail=None, head=None, gamma=None):
+        """Tagged edges of the line_tension module as external rows with their gamma, in ascending edge order (used
+        while MS_MOD_LINE_TENSION is in the module mask); no arguments clear the tables."""
+        if tail is None:
+            self._chk(L.lib().ms_set_line_tension(self._h, 0, None, None, None), "ms_set_line_tension")
+            return
+        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
+        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
+        g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
+        if not (len(t) == len(h) == len(g)):
+            raise ValueError("set_line_tension: tail, head and gamma must have the same length")
+        n = len(t)
+        if n == 0:  # (a non-NULL pointer: tables that hold no edge)
+            t = h = np.zeros(1, np.int32)
+            g = np.zeros(1)
+        self._chk(L.lib().ms_set_line_tension(self._h, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32), _pd(g)),
+                  "ms_set_line_tension")
+
+    def line_energy(self) -> float:
+        """The line_tension module's own energy as the last energy pass summed it (ms_get_line_energy)."""
+        e = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_get_line_energy(self._h, ctypes.byref(e)), "ms_get_line_energy")
+        return float(e.value)
+
+    def line_stats(self):
+        """Launch counts of the two line_tension kernels and their event-timed microseconds (ms_line_stats)."""
+        v = np.zeros(4)
+        self._chk(L.lib().ms_line_stats(self._h, _pd(v)), "ms_line_stats")
+        return {"energy_launches": int(v[0]), "grad_launches": int(v[1]), "energy_us": float(v[2]),
+                "grad_us": float(v[3])}
+
     @property
     def modules(self) -> int:
         return int(self._params.modules)

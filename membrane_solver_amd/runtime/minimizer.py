@@ -51,6 +51,7 @@ from ..modules.energy import leaflet_common as _lc
 from ..modules.energy._common import bending_gradient_mode, bending_model
 from ..modules.constraints import pins as _pins
 from ..modules.energy.body_area_penalty import body_area_params
+from ..modules.energy import line_tension as _line
 from ..modules.energy.volume import body_penalty_params
 from .steppers.base import write_back_positions
 
@@ -64,14 +65,14 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "bending_tilt_in": L.MS_MOD_BENDING_TILT_IN, "bending_tilt_out": L.MS_MOD_BENDING_TILT_OUT,
                 "tilt_disk_target_in": L.MS_MOD_TILT_DISK_TARGET_IN,
                 "tilt_disk_target_out": L.MS_MOD_TILT_DISK_TARGET_OUT,
-                "body_area_penalty": L.MS_MOD_AREA_PENALTY,
+                "body_area_penalty": L.MS_MOD_AREA_PENALTY, "line_tension": L.MS_MOD_LINE_TENSION,
                 # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
                 # accepted in its switched-off state (strength 0, as in the caveolin decks)
                 "gaussian_curvature": 0, "rim_slope_match_out": 0}
 _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_tilt": 1, "tilt_smoothness": 3,
                 "tilt_in": 3, "tilt_out": 3, "tilt_smoothness_in": 3, "tilt_smoothness_out": 3,
                 "bending_tilt_in": 1, "bending_tilt_out": 1, "tilt_disk_target_in": 3, "tilt_disk_target_out": 3,
-                "body_area_penalty": 2, "gaussian_curvature": None, "rim_slope_match_out": None}
+                "body_area_penalty": 2, "line_tension": 0, "gaussian_curvature": None, "rim_slope_match_out": None}
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
 _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
@@ -172,15 +173,23 @@ class Minimizer:
         for name, mod in zip(self.energy_module_names, self.energy_modules):
             if not hasattr(mod, "compute_energy_and_gradient_array"):
                 raise TypeError(f"energy module {name!r} lacks compute_energy_and_gradient_array")
-            if name not in _ENERGY_BITS:
+            # line_tension on a mesh built without edges stays refused: nothing could be tagged, and the deck would
+            # run with a line energy of zero
+            no_edges = name == "line_tension" and not _line.has_edge_table(self.mesh)
+            if name not in _ENERGY_BITS or no_edges:
+                where = " on a mesh without an edge table (ArrayMesh(edges=, edge_options=))" if no_edges else ""
                 raise L.MembraneHipError(
-                    f"energy module {name!r} is outside the HIP hot path (surface, bending, volume, tilt, "
+                    f"energy module {name!r}{where} is outside the HIP hot path (surface, bending, volume, tilt, "
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
                     "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
-                    "body_area_penalty)")
+                    "body_area_penalty, line_tension)")
         if "body_area_penalty" in self.energy_module_names and any(
                 _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
             raise L.MembraneHipError("body_area_penalty together with tilt modules is outside the HIP hot path")
+        if "line_tension" in self.energy_module_names and any(
+                _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
+            raise L.MembraneHipError("line_tension together with tilt modules is outside the HIP hot path")
+        self._line_key = None
         self.constraint_modules = [self.constraint_manager.get_constraint(c)
                                    for c in self.constraint_module_names]
         for name in self.constraint_module_names:
@@ -240,6 +249,9 @@ class Minimizer:
                 area_params = body_area_params(self.mesh, gp, self.param_resolver)
                 if area_params is not None:  # body_area_penalty.py:114-123
                     mods |= L.MS_MOD_AREA_PENALTY
+            elif name == "line_tension":
+                if self._upload_line(mir, dm):  # line_tension.py:113-115: nothing tagged, nothing charged
+                    mods |= L.MS_MOD_LINE_TENSION
             elif name == "tilt":
                 if float(gp.get("tilt_rigidity", 0.0) or 0.0) != 0.0:  # tilt.py:110-112
                     mods |= L.MS_MOD_TILT
@@ -296,6 +308,11 @@ class Minimizer:
                 "bending_gradient_mode=approx with modules listed AFTER bending_tilt on an open mesh is "
                 "not on the fused device path (bending_tilt.py:297-299 zeroes boundary rows of what was "
                 "accumulated so far); list bending_tilt last")
+        if mode == "approx" and (mods & L.MS_MOD_LINE_TENSION) and np.any(_boundary(self.mesh)):
+            # (bending.py:165-166 / bending_tilt.py:297-299 zero the boundary rows of what the modules listed before
+            # them accumulated; the device adds the line-tension rows behind the whole gradient pass)
+            raise L.MembraneHipError("line_tension with bending_gradient_mode=approx on an open mesh is outside the "
+                                     "HIP hot path")
         if mode == "approx" and (mods & L.MS_MOD_BENDING):
             order = self.energy_module_names
             if order.index("bending") != len(order) - 1 and np.any(_boundary(self.mesh)):
@@ -342,7 +359,7 @@ class Minimizer:
             dm.set_tilt_smoothness(float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0))
         if self._pin_names:
             self._upload_pins(mir, dm, mods)
-        key = (mods, model, mode, stiffness, target, area_params, id(dm))
+        key = (mods, model, mode, stiffness, target, area_params, self._line_key, id(dm))
         if key != self._configured_key:
             if area_params is not None:
                 dm.set_area_penalty(*area_params)
@@ -352,6 +369,15 @@ class Minimizer:
                           volume_stiffness=stiffness, target_volume=target)
             self._configured_key = key
         return mir, dm
+
+    def _upload_line(self, mir, dm) -> bool:
+        """Resolve the tagged edges and their gamma (modules/energy/line_tension.py) once per mesh topology and
+        parameter value (call refresh_modules() after changing the tags) and upload the device tables; True when
+        some edge is charged.  A re-tiled mesh is a new context: its tables start empty."""
+        key = (mir._topo_key, id(dm), float(self.global_params.get("line_tension", 0.0) or 0.0))
+        if self._line_key is None or self._line_key[:3] != key:
+            self._line_key = key + (_line.upload(self.mesh, self.global_params, dm),)
+        return self._line_key[3]
 
     def _upload_pins(self, mir, dm, mods):
         """Resolve the pin tags once per mesh topology, fixed mask and row set (call refresh_modules() after
@@ -413,6 +439,11 @@ class Minimizer:
                     if dm.modules & L.MS_MOD_VOLUME_PENALTY else (0.0, 0.0)
                 dv = float(dm.fetch_scalars()[L.MS_S_VOL]) - v0
                 out["volume"] = 0.5 * k * (dv * dv)
+        if "line_tension" in out:  # energies[0] is surface + line tension: each module reports its own
+            line_e = dm.line_energy() if dm.modules & L.MS_MOD_LINE_TENSION else 0.0
+            out["line_tension"] = line_e
+            if "surface" in out:
+                out["surface"] = float(e[0]) - line_e if dm.modules & L.MS_MOD_SURFACE else 0.0
         for table in (_TILT_SCALAR, _BEND_SCALAR):
             sharing = [n for n in out if n in table]
             if len(sharing) > 1:  # they share one entry of the energy vector: split via the scalars
