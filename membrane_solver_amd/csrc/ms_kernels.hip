@@ -78,13 +78,24 @@ __device__ __forceinline__ double dpp_move(double fill, double v) {
   const int hi = __builtin_amdgcn_update_dpp((int)(fi >> 32), (int)(vi >> 32), CTRL, ROW_MASK, 0xf, false);
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
+// The row shifts of a SUM need no identity moved into the destination first: with bound_ctrl a lane without a source
+// reads zeros, the sum's identity, so the shifted value is bit for bit the filled one (two moves fewer per step).
+template <int CTRL>
+__device__ __forceinline__ double dpp_move_zero(double v) {
+  const long long vi = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_mov_dpp((int)vi, CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp((int)(vi >> 32), CTRL, 0xf, 0xf, true);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
 template <int OP>  // 0 sum, 1 min, 2 max
 __device__ __forceinline__ double wave_reduce(double v) {
   const double id = OP == 0 ? 0.0 : (OP == 1 ? 1.0e300 : -1.0e300);
-#define MS_RED_STEP(CTRL, MASK)                                         \
-  {                                                                     \
-    const double t = dpp_move<CTRL, MASK>(id, v);                       \
-    v = OP == 0 ? v + t : (OP == 1 ? fmin(v, t) : fmax(v, t));          \
+#define MS_RED_STEP(CTRL, MASK)                                                                            \
+  {                                                                                                        \
+    double t;                                                                                              \
+    if constexpr (OP == 0 && (CTRL & 0x1f0) == 0x110) t = dpp_move_zero<CTRL>(v); /* row_shr */            \
+    else t = dpp_move<CTRL, MASK>(id, v);                                                                  \
+    v = OP == 0 ? v + t : (OP == 1 ? fmin(v, t) : fmax(v, t));                                             \
   }
   MS_RED_STEP(0x111, 0xf)  // row_shr:1
   MS_RED_STEP(0x112, 0xf)  // row_shr:2
@@ -151,6 +162,40 @@ __device__ __forceinline__ void block_reduce_store(const double (&v)[NV], const 
     if (AGENT) st_agent(out + (size_t)slot * stride, r);
     else out[(size_t)slot * stride] = r;
   }
+}
+
+// The staged form of the default-mode (LDS-atomic) headline instances, 256-thread workgroups only: every thread parks
+// value k in cell [k][tid] of NV LDS columns of 256 doubles, and after ONE barrier wave k alone folds column k -- lane l
+// takes rows l, l+64, l+128, l+192 in that order, then one DPP tree -- and its lane 0 stores out[slots[k] * stride].
+// A workgroup runs NV trees instead of 4 NV, and three of the four waves leave right after the barrier.  The order is
+// fixed by (k, tid) alone and nothing is atomic: equal inputs give equal bits.  -DMS_REDUCE_STAGED=0 keeps
+// block_reduce_store in those instances too (A/B).  `col` must be free of readers when the first thread gets here;
+// nothing may write it before the workgroup's next barrier.
+#ifndef MS_REDUCE_STAGED
+#define MS_REDUCE_STAGED 1
+#endif
+template <int NV>
+__device__ __forceinline__ void block_reduce_store_staged(const double (&v)[NV], const int (&ops)[NV],
+                                                          const int (&slots)[NV], double* col,
+                                                          double* out, size_t stride) {
+  static_assert(NV <= 4, "one wave per value");
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (a scalar: the selection below is a scalar branch)
+#pragma unroll
+  for (int k = 0; k < NV; ++k) col[k * 256 + threadIdx.x] = v[k];
+  __syncthreads();
+  // (selected with constant indices: each branch instantiates the one tree of its op)
+#pragma unroll
+  for (int q = 0; q < NV; ++q)
+    if (q == w) {
+      const double* c = col + q * 256 + lane;
+      const double x0 = c[0], x1 = c[64], x2 = c[128], x3 = c[192];
+      double r;
+      if (ops[q] == 0) r = wave_sum(((x0 + x1) + x2) + x3);
+      else if (ops[q] == 1) r = wave_min(fmin(fmin(fmin(x0, x1), x2), x3));
+      else r = wave_max(fmax(fmax(fmax(x0, x1), x2), x3));
+      if (lane == 0) out[(size_t)slots[q] * stride] = r;
+    }
 }
 
 // mixed-Voronoi corner areas with the reference's sequential-overwrite obtuse
@@ -905,7 +950,14 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
     const double vals[3] = {e_surf, e_bend, min_e2};
     const int ops[3] = {0, 0, 1};
     const int slots[3] = {MS_S_ESURF, MS_S_EBEND, MS_S_MINEDGE2};
-    block_reduce_store<3>(vals, ops, slots, red, pout, pstride);
+    // The default-mode headline instances fold one value per wave out of the first three accumulator columns of stg:
+    // every owner read its five sums before the "red aliases stg" barrier above, and what runs between that barrier
+    // and here -- the rare vertex-normal path (px and global memory) and the factor stores -- touches no column of
+    // stg (the flag bytes lie behind the fifth).
+    if constexpr (MS_REDUCE_STAGED && ATOMIC && BEND && !GUARD && !AREA && TT == 256)
+      block_reduce_store_staged<3>(vals, ops, slots, stg, pout, pstride);
+    else
+      block_reduce_store<3>(vals, ops, slots, red, pout, pstride);
     if (tid == 0) {
       pout[MS_S_VOL * pstride] = 0.0;
       pout[MS_S_GUARD * pstride] = 0.0;
@@ -1715,7 +1767,16 @@ __device__ __forceinline__ void gradient_body(const GradientArgs& a, int cap_rt,
     const double vals[4] = {gn2, gdd, md2, mg2};
     const int ops[4] = {0, 0, 2, 2};
     const int slots[4] = {MS_S_GNORM2, MS_S_GDOTD, MS_S_MAXD2, MS_S_MAXG2};
-    block_reduce_store<4>(vals, ops, slots, red, a.partials + t.tile, (size_t)a.m.n_tiles);
+    // The default-mode lean instance folds one value per wave out of four adjacent columns that end where the
+    // accumulators end: the top 256 doubles of fa (allocated 2 cap >= 258 -- a 256-thread tile owns at least 129 rows
+    // -- of which the lean instance stages cap and reads them in the facet loop only) and the three gradient
+    // accumulators of stg.  No barrier beyond the helper's own: the barrier behind the facet loop has ended every read
+    // of fa and every atomic, and since then the only reader of an accumulator cell [c][tid] is thread tid itself,
+    // which is also the only thread to overwrite it.
+    if constexpr (MS_REDUCE_STAGED && ATOMIC && LEAN && !VOLROW && TT == 256)
+      block_reduce_store_staged<4>(vals, ops, slots, stg - 256, a.partials + t.tile, (size_t)a.m.n_tiles);
+    else
+      block_reduce_store<4>(vals, ops, slots, red, a.partials + t.tile, (size_t)a.m.n_tiles);
   } else {
     const double vals[2] = {ggc, gcgc};
     const int ops[2] = {0, 0};
