@@ -76,6 +76,11 @@ extern "C" {
  * gamma come from ms_set_line_tension.  Its energy is added into the surface slot (MS_S_ESURF, energies[0]) behind the
  * energy pass, its gradient into G behind the gradient pass: two extra launches, no reduction slot of its own. */
 #define MS_MOD_LINE_TENSION 131072u
+/* edge length penalty E = sum 0.5 k (|e| - L0)^2 over the edges that carry a target length
+ * (modules/energy/edge_length_penalty.py:35-69); the edges, their L0 and k come from ms_set_edge_length_penalty.  Like
+ * line tension its energy is added into the surface slot (MS_S_ESURF, energies[0]) behind the energy pass, its gradient
+ * into G behind the gradient pass, each behind line tension's launch when both are on: no reduction slot of its own. */
+#define MS_MOD_EDGE_LENGTH_PENALTY 262144u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -260,6 +265,32 @@ int ms_line_stats(ms_ctx *ctx, double stats[4]);
 int ms_line_tables_host(int nv, const int32_t *iperm, int n_edges, const int32_t *tail, const int32_t *head,
                         const double *gamma, int32_t counts[2], int32_t *e_tail, int32_t *e_head, double *e_gamma,
                         int32_t *vrow, int32_t *off, int32_t *other, double *csr_gamma);
+/* edge_length_penalty (modules/energy/edge_length_penalty.py:16-22 selects the edges, :40-42 keeps those whose
+ * "target_length" is not None, :35 reads k from the global "edge_stiffness" alone, default 100): n_edges charged edges as
+ * EXTERNAL rows (the order of ms_set_positions) in ascending edge order, the target length per edge (0 is a target like
+ * any other), one stiffness k.  Every row is validated (MS_ERR_INVALID when one is out of range, or a target or k is not
+ * finite).  tail == NULL clears the tables; k == 0 leaves tables that hold no edge.  Used while
+ * MS_MOD_EDGE_LENGTH_PENALTY is in ms_params.modules (with no tables the module contributes nothing); energies[0] of the
+ * evaluation calls is then surface + line tension + edge length penalty.  An edge shorter than 1e-15 contributes nothing
+ * (:54-55).  The module takes line_tension's lane of ms_step: one trial per launch, every Armijo decision the host's, no
+ * rounds queued ahead, no resident steps; under the one-workgroup interpreter its two kernels are not recorded (they
+ * flush it first).  Single GPU, no tilt-family module next to it (both refused with MS_ERR_STATE). */
+int ms_set_edge_length_penalty(ms_ctx *ctx, int n_edges, const int32_t *tail, const int32_t *head,
+                               const double *target_length, double k);
+/* the module's own energy as the last energy pass summed it (edge_length_penalty.py:58; synchronises); 0 without tables */
+int ms_get_edge_penalty_energy(ms_ctx *ctx, double *energy);
+/* stats: {k_edgepen_energy launches, k_edgepen_grad launches, and -- from HIP events around the launches made while
+ * ms_profile_enable was on -- their summed microseconds, k_edgepen_energy then k_edgepen_grad}; reading resets the event
+ * sums (synchronises).  No reference counterpart. */
+int ms_edge_penalty_stats(ms_ctx *ctx, double stats[4]);
+/* Host only, no context: the tables ms_set_edge_length_penalty uploads, built by the code behind ms_line_tables_host
+ * with the target length carried as a second column: counts = {edges kept, touched rows}; the edge table (e_tail, e_head,
+ * e_l0: n_edges entries at most) and the vertex -> edge CSR (vrow: 2 n_edges at most, off: one more, other / csr_l0:
+ * 2 n_edges).  No reference counterpart. */
+int ms_edge_penalty_tables_host(int nv, const int32_t *iperm, int n_edges, const int32_t *tail, const int32_t *head,
+                                const double *target_length, double k, int32_t counts[2], int32_t *e_tail,
+                                int32_t *e_head, double *e_l0, int32_t *vrow, int32_t *off, int32_t *other,
+                                double *csr_l0);
 /* Per-vertex accumulation in the two big tile kernels (energy pass, gradient pass):
  * 0 (default) LDS atomic adds -- fastest, the floating-point summation order (hence the
  * last bits) may differ between runs; 1 staged CSR gather in a fixed order -- bitwise
@@ -376,7 +407,8 @@ int ms_get_vertex_buffer(ms_ctx *ctx, int buffer, double *out /* nv*ncomp */);
 /*
  * Minimizer.compute_energy_and_gradient_array (runtime/minimizer.py:941-992):
  * module loop, volume-constraint projection, fixed rows zeroed.  energies[4] =
- * {surface + line tension, bending, volume-penalty + area-penalty, tilt}.  grad may be NULL (stays on device).
+ * {surface + line tension + edge length penalty, bending, volume-penalty + area-penalty, tilt}.  grad may be NULL
+ * (stays on device).
  */
 int ms_energy_and_gradient(ms_ctx *ctx, double energies[4], double *grad);
 /*

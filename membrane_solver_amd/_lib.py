@@ -32,6 +32,7 @@ MS_MOD_BENDING_TILT_IN, MS_MOD_BENDING_TILT_OUT = 4096, 8192
 MS_MOD_TILT_DISK_TARGET_IN, MS_MOD_TILT_DISK_TARGET_OUT = 16384, 32768
 MS_MOD_AREA_PENALTY = 65536
 MS_MOD_LINE_TENSION = 131072
+MS_MOD_EDGE_LENGTH_PENALTY = 262144
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
@@ -138,6 +139,11 @@ SIGNATURES = {
     "ms_line_stats": (ctypes.c_int, [_P, _D]),
     "ms_line_tables_host": (ctypes.c_int, [ctypes.c_int, _I32, ctypes.c_int, _I32, _I32, _D, _I32, _I32, _I32, _D, _I32,
                                           _I32, _I32, _D]),
+    "ms_set_edge_length_penalty": (ctypes.c_int, [_P, ctypes.c_int, _I32, _I32, _D, ctypes.c_double]),
+    "ms_get_edge_penalty_energy": (ctypes.c_int, [_P, _D]),
+    "ms_edge_penalty_stats": (ctypes.c_int, [_P, _D]),
+    "ms_edge_penalty_tables_host": (ctypes.c_int, [ctypes.c_int, _I32, ctypes.c_int, _I32, _I32, _D, ctypes.c_double, _I32,
+                                                  _I32, _I32, _D, _I32, _I32, _I32, _D]),
     "ms_set_tilts": (ctypes.c_int, [_P, _D, ctypes.c_double]),
     "ms_get_tilts": (ctypes.c_int, [_P, _D]),
     "ms_get_tilt_gradient": (ctypes.c_int, [_P, _D]),
@@ -243,8 +249,8 @@ _lib = None
 
 def build(force: bool = False, fp_contract: str | None = None) -> str:
     """Compile libmembrane_hip.so for gfx950 with hipcc (csrc/Makefile)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("ms_kernels.hip", "ms_pins.hip", "ms_line.hip", "ms_api.cpp",
-                                             "ms_tiles.cpp", "ms_internal.h", "Makefile")]
+    srcs = [os.path.join(_CSRC, f) for f in ("ms_kernels.hip", "ms_pins.hip", "ms_line.hip", "ms_edgepen.hip",
+                                             "ms_api.cpp", "ms_tiles.cpp", "ms_internal.h", "Makefile")]
     srcs.append(os.path.join(_PKG, "..", "include", "membrane_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

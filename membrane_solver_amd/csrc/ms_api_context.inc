@@ -253,14 +253,15 @@ void ms_destroy(ms_ctx* c) {
                   c->tf[1].kappa, c->tf[1].c0, c->tf[1].bt_vert, c->tf[2].kappa, c->tf[2].c0, c->tf[2].bt_vert,
                   c->tf[1].disk, c->tf[1].diff, c->tf[2].disk, c->tf[2].diff, c->tf[0].va, c->tf[1].va, c->tf[2].va,
                   c->state, c->d_partials, c->d_scal, c->d_stage, c->d_bnd_rows, c->d_bnd_off,
-                  c->d_halo_rows, c->d_scal_all, c->d_pins, c->d_line};
+                  c->d_halo_rows, c->d_scal_all, c->d_pins, c->d_line, c->d_edgepen};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
-  for (auto& evs : c->line_prof)
-    for (auto& ev : evs) {
-      (void)hipEventDestroy(ev.first);
-      (void)hipEventDestroy(ev.second);
-    }
+  for (auto* prof : {c->line_prof, c->edgepen_prof})
+    for (int w = 0; w < 2; ++w)
+      for (auto& ev : prof[w]) {
+        (void)hipEventDestroy(ev.first);
+        (void)hipEventDestroy(ev.second);
+      }
   for (void* q : c->peer_opened) (void)hipIpcCloseMemHandle(q);
   if (c->d_peer_slab) (void)hipFree(c->d_peer_slab);
   if (c->d_peer_flag) (void)hipFree(c->d_peer_flag);
@@ -405,6 +406,10 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
     return fail(c, MS_ERR_STATE, "the line_tension module is not sharded (single GPU only)");
   if ((p->modules & MS_MOD_LINE_TENSION) && (p->modules & MS_ANY_TILT_MODS))
     return fail(c, MS_ERR_STATE, "line_tension together with a tilt-family module is outside the device path");
+  if ((p->modules & MS_MOD_EDGE_LENGTH_PENALTY) && c->shard_count != 1)
+    return fail(c, MS_ERR_STATE, "the edge_length_penalty module is not sharded (single GPU only)");
+  if ((p->modules & MS_MOD_EDGE_LENGTH_PENALTY) && (p->modules & MS_ANY_TILT_MODS))
+    return fail(c, MS_ERR_STATE, "edge_length_penalty together with a tilt-family module is outside the device path");
   if ((p->modules & MS_MOD_BENDING_TILT) && !c->d_bt_vert) {
     const size_t bytes = sizeof(double) * 4 * (size_t)c->til.nvp;
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_bt_vert), bytes));

@@ -355,6 +355,13 @@ struct ms_ctx {
   bool line_set = false;
   long line_launches[2] = {0, 0};  // k_line_energy, k_line_grad
   std::vector<std::pair<hipEvent_t, hipEvent_t>> line_prof[2];  // event brackets while profiling (ms_line_stats)
+  // edge_length_penalty (ms_set_edge_length_penalty): the same, for its two kernels
+  void* d_edgepen = nullptr;
+  EdgePenEnergyArgs edgepen_en{};
+  EdgePenGradArgs edgepen_gr{};
+  bool edgepen_set = false;
+  long edgepen_launches[2] = {0, 0};  // k_edgepen_energy, k_edgepen_grad
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> edgepen_prof[2];  // (ms_edge_penalty_stats)
   const StageCtl& stage() const { return stage_; }
  private:
   friend struct StageScope;

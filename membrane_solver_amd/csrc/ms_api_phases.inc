@@ -11,6 +11,8 @@ inline hipStream_t S(ms_ctx* c) {
 int pin_grad_run(ms_ctx* c, bool volrow);  // (ms_api_pins.inc)
 int line_energy_run(ms_ctx* c, bool use_dir, double alpha);  // (ms_api_line.inc)
 int line_grad_run(ms_ctx* c, double* g, bool volrow);
+int edgepen_energy_run(ms_ctx* c, bool use_dir, double alpha);  // (ms_api_edgepen.inc)
+int edgepen_grad_run(ms_ctx* c, double* g, bool volrow);
 inline int exec_flush(ms_ctx* c) {
   if (!c->exec_on) return MS_OK;
   const hipError_t e = c->exec.flush();
@@ -150,6 +152,9 @@ constexpr uint32_t MS_LEAFLET_BT = MS_MOD_BENDING_TILT_IN | MS_MOD_BENDING_TILT_
 constexpr uint32_t MS_LEAFLET_DT = MS_MOD_TILT_DISK_TARGET_IN | MS_MOD_TILT_DISK_TARGET_OUT;
 constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT;
 constexpr uint32_t MS_ANY_TILT_MODS = MS_TILT_MODS | MS_LEAFLET_MODS;
+// the edge modules: energy added into the MS_S_ESURF partials behind the energy pass, gradient into G behind K_C; they
+// share one lane of the step (one trial per launch, every Armijo decision the host's, the separate direction pass)
+constexpr uint32_t MS_EDGE_MODS = MS_MOD_LINE_TENSION | MS_MOD_EDGE_LENGTH_PENALTY;
 // modules whose shape gradient is added into g by a pass after K_C (so the direction cannot be fused)
 constexpr uint32_t MS_TILT_SHAPE_MODS = MS_MOD_TILT | MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT;
 using TiltField = ms_ctx::TiltField;
@@ -624,9 +629,11 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     }
   }
   if (bt && !c->d_bt_vert) return fail(c, MS_ERR_STATE, "bending_tilt: ms_set_params did not allocate its buffers");
-  // line_tension takes the penalties' lane: one trial per launch, every Armijo decision the host's
-  if ((modules & MS_MOD_LINE_TENSION) && (st.pair_on > 1 || st.cur_gate != nullptr || lbt))
-    return fail(c, MS_ERR_STATE, "line_tension: the energy pass was queued on the device-decided lane");
+  // the edge modules take the penalties' lane: one trial per launch, every Armijo decision the host's
+  if ((modules & MS_EDGE_MODS) && (st.pair_on > 1 || st.cur_gate != nullptr || lbt))
+    return fail(c, MS_ERR_STATE, (modules & MS_MOD_LINE_TENSION)
+                                     ? "line_tension: the energy pass was queued on the device-decided lane"
+                                     : "edge_length_penalty: the energy pass was queued on the device-decided lane");
   a.partials = c->d_partials;
   a.bending_model = c->params.bending_model;
   a.modules = modules;
@@ -728,6 +735,9 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   // MS_MOD_SURFACE -- so the cell is defined before the add); the fold below then carries surface + line energy
   if (modules & MS_MOD_LINE_TENSION)
     if (int rc_l = line_energy_run(c, use_dir, alpha)) return rc_l;
+  // edge_length_penalty: 0.5 k (|e| - L0)^2 into the same cells, behind k_line_energy: the order of the two adds is fixed
+  if (modules & MS_MOD_EDGE_LENGTH_PENALTY)
+    if (int rc_p = edgepen_energy_run(c, use_dir, alpha)) return rc_p;
   if (modules & MS_TILT_MODS) {
     int rc = MS_OK;
     const double* tilts = c->tf[0].tilts;
@@ -851,10 +861,16 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
   // line_tension: its rows added into the G that K_C has just written (before pin_grad_run projects the full gradient),
   // and the <g,gC> partials corrected by the change.  The direction scalars of K_C's fused epilogue would predate the
   // addition: the callers take the separate direction pass (queue_energy_and_gradient)
-  if ((modules_in & MS_MOD_LINE_TENSION) && g_out) {
+  if ((modules_in & MS_EDGE_MODS) && g_out) {
     if (dir_mode || a.gate != nullptr)
-      return fail(c, MS_ERR_STATE, "line_tension cannot use the fused direction pass or a gated gradient pass");
-    if (int rc_l = line_grad_run(c, g_out, a.gC != nullptr)) return rc_l;
+      return fail(c, MS_ERR_STATE, (modules_in & MS_MOD_LINE_TENSION)
+                                       ? "line_tension cannot use the fused direction pass or a gated gradient pass"
+                                       : "edge_length_penalty cannot use the fused direction pass or a gated gradient pass");
+    if (modules_in & MS_MOD_LINE_TENSION)
+      if (int rc_l = line_grad_run(c, g_out, a.gC != nullptr)) return rc_l;
+    // (behind k_line_grad: both add into the same rows of G and the same <g,gC> cells, in this order)
+    if (modules_in & MS_MOD_EDGE_LENGTH_PENALTY)
+      if (int rc_p = edgepen_grad_run(c, g_out, a.gC != nullptr)) return rc_p;
   }
   for (int k = 0; k < n_lbt; ++k) {
     TiltField& f = c->tf[lbt_order[k]];
@@ -1082,8 +1098,8 @@ double penalty_energy(const ms_ctx* c, double V, double A) {
 
 // energies from the pinned mailbox: {surface, bending, penalty, tilt}
 void energies_from_mailbox(const ms_ctx* c, double e[4]) {
-  // (line_tension's energy rides in the surface slot: k_line_energy adds it into that slot's partials)
-  e[0] = (c->params.modules & (MS_MOD_SURFACE | MS_MOD_LINE_TENSION)) ? c->h_scal[MS_S_ESURF] : 0.0;
+  // (the edge modules' energies ride in the surface slot: their energy kernels add into that slot's partials)
+  e[0] = (c->params.modules & (MS_MOD_SURFACE | MS_EDGE_MODS)) ? c->h_scal[MS_S_ESURF] : 0.0;
   e[1] = (c->params.modules & MS_MOD_BENDING) ? c->h_scal[MS_S_EBEND] : 0.0;
   if (c->params.modules & MS_MOD_BENDING_TILT) e[1] += c->h_scal[MS_S_EBT];
   e[2] = penalty_energy(c, c->h_scal[MS_S_VOL], c->h_scal[MS_S_AREA]);
@@ -1106,8 +1122,8 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
   const uint32_t mods = c->params.modules;
   // lambda needs a global reduction first; the tilt module adds into g after K_C
   // (and a preconditioned direction -- conjugate_gradient.py:74-76 -- is the direction kernel's)
-  // (line_tension adds into g after K_C as well: |g|^2, <g,d> and max|g_i|^2 are taken over the completed G)
-  const bool constraint = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS | MS_MOD_LINE_TENSION)) != 0 ||
+  // (the edge modules add into g after K_C as well: |g|^2, <g,d> and max|g_i|^2 are taken over the completed G)
+  const bool constraint = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS | MS_EDGE_MODS)) != 0 ||
                           (stepper == MS_STEPPER_CG && c->precond) || c->pin_lane == MS_PIN_LANE_PROJECT;
   // K_C reads the reduced volume / body area (already reduced when the energy pass is skipped)
   const bool penalty = skip_energy || (mods & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) != 0;

@@ -532,8 +532,8 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     c->carry.kc_pending = false;
     rc = queue_energy_and_gradient(c, sp->stepper, use_history, carried);
     c->carry.maxg2_valid = true;  // the fused epilogue / the direction kernel reduced max|g_i|^2 as well
-    // (line_tension: never the kernel-free steepest-descent restart -- the direction kernel runs again on the completed G)
-    if (c->params.modules & MS_MOD_LINE_TENSION) c->carry.maxg2_valid = false;
+    // (the edge modules: never the kernel-free steepest-descent restart -- the direction kernel runs again on the completed G)
+    if (c->params.modules & MS_EDGE_MODS) c->carry.maxg2_valid = false;
   }
   if (rc) return rc;
   if (!restart_sd) {
@@ -654,7 +654,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   const bool enforce_pin = sp->enforce_pins != 0 && pins_set(c) && !tilt;
   const bool enforce = enforce_vol || enforce_pin;
   const bool can_chain = c->speculate && carry_mode && !tilt &&
-                         !(c->params.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY | MS_MOD_LINE_TENSION)) && !enforce && !precond;
+                         !(c->params.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY | MS_EDGE_MODS)) && !enforce && !precond;
   // a round queued by the step before (while its gradient pass was running): the round of THIS search's first
   // iteration if it was queued for exactly what this step has computed by itself
   bool adopted = false;

@@ -160,6 +160,40 @@ class DeviceMesh:
         return {"energy_launches": int(v[0]), "grad_launches": int(v[1]), "energy_us": float(v[2]),
                 "grad_us": float(v[3])}
 
+    def set_edge_length_penalty(self, tail=None, head=None, target_length=None, k=100.0):
+        """Charged edges of the edge_length_penalty module as external rows with their target lengths, in ascending
+        edge order, and the one stiffness k (used while MS_MOD_EDGE_LENGTH_PENALTY is in the module mask); no
+        arguments clear the tables."""
+        if tail is None:
+            self._chk(L.lib().ms_set_edge_length_penalty(self._h, 0, None, None, None, 0.0), "ms_set_edge_length_penalty")
+            return
+        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
+        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
+        l0 = np.ascontiguousarray(np.asarray(target_length, dtype=np.float64).reshape(-1))
+        if not (len(t) == len(h) == len(l0)):
+            raise ValueError("set_edge_length_penalty: tail, head and target_length must have the same length")
+        n = len(t)
+        if n == 0:  # (a non-NULL pointer: tables that hold no edge)
+            t = h = np.zeros(1, np.int32)
+            l0 = np.zeros(1)
+        self._chk(L.lib().ms_set_edge_length_penalty(self._h, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32),
+                                                     _pd(l0), float(k)), "ms_set_edge_length_penalty")
+
+    def edge_penalty_energy(self) -> float:
+        """The edge_length_penalty module's own energy as the last energy pass summed it
+        (ms_get_edge_penalty_energy)."""
+        e = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_get_edge_penalty_energy(self._h, ctypes.byref(e)), "ms_get_edge_penalty_energy")
+        return float(e.value)
+
+    def edge_penalty_stats(self):
+        """Launch counts of the two edge_length_penalty kernels and their event-timed microseconds
+        (ms_edge_penalty_stats)."""
+        v = np.zeros(4)
+        self._chk(L.lib().ms_edge_penalty_stats(self._h, _pd(v)), "ms_edge_penalty_stats")
+        return {"energy_launches": int(v[0]), "grad_launches": int(v[1]), "energy_us": float(v[2]),
+                "grad_us": float(v[3])}
+
     @property
     def modules(self) -> int:
         return int(self._params.modules)

@@ -51,6 +51,7 @@ from ..modules.energy import leaflet_common as _lc
 from ..modules.energy._common import bending_gradient_mode, bending_model
 from ..modules.constraints import pins as _pins
 from ..modules.energy.body_area_penalty import body_area_params
+from ..modules.energy import edge_length_penalty as _edgepen
 from ..modules.energy import line_tension as _line
 from ..modules.energy.volume import body_penalty_params
 from .steppers.base import write_back_positions
@@ -66,13 +67,15 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "tilt_disk_target_in": L.MS_MOD_TILT_DISK_TARGET_IN,
                 "tilt_disk_target_out": L.MS_MOD_TILT_DISK_TARGET_OUT,
                 "body_area_penalty": L.MS_MOD_AREA_PENALTY, "line_tension": L.MS_MOD_LINE_TENSION,
+                "edge_length_penalty": L.MS_MOD_EDGE_LENGTH_PENALTY,
                 # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
                 # accepted in its switched-off state (strength 0, as in the caveolin decks)
                 "gaussian_curvature": 0, "rim_slope_match_out": 0}
 _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_tilt": 1, "tilt_smoothness": 3,
                 "tilt_in": 3, "tilt_out": 3, "tilt_smoothness_in": 3, "tilt_smoothness_out": 3,
                 "bending_tilt_in": 1, "bending_tilt_out": 1, "tilt_disk_target_in": 3, "tilt_disk_target_out": 3,
-                "body_area_penalty": 2, "line_tension": 0, "gaussian_curvature": None, "rim_slope_match_out": None}
+                "body_area_penalty": 2, "line_tension": 0, "edge_length_penalty": 0, "gaussian_curvature": None, "rim_slope_match_out": None}
+_EDGE_MODULES = ("line_tension", "edge_length_penalty")  # they share the lane behind the energy and the gradient pass
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
 _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
@@ -173,23 +176,25 @@ class Minimizer:
         for name, mod in zip(self.energy_module_names, self.energy_modules):
             if not hasattr(mod, "compute_energy_and_gradient_array"):
                 raise TypeError(f"energy module {name!r} lacks compute_energy_and_gradient_array")
-            # line_tension on a mesh built without edges stays refused: nothing could be tagged, and the deck would
-            # run with a line energy of zero
-            no_edges = name == "line_tension" and not _line.has_edge_table(self.mesh)
+            # an edge module on a mesh built without edges stays refused: nothing could be tagged or given a target,
+            # and the deck would run with that module's energy at zero
+            no_edges = name in _EDGE_MODULES and not _line.has_edge_table(self.mesh)
             if name not in _ENERGY_BITS or no_edges:
                 where = " on a mesh without an edge table (ArrayMesh(edges=, edge_options=))" if no_edges else ""
                 raise L.MembraneHipError(
                     f"energy module {name!r}{where} is outside the HIP hot path (surface, bending, volume, tilt, "
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
                     "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
-                    "body_area_penalty, line_tension)")
+                    "body_area_penalty, line_tension, edge_length_penalty)")
         if "body_area_penalty" in self.energy_module_names and any(
                 _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
             raise L.MembraneHipError("body_area_penalty together with tilt modules is outside the HIP hot path")
-        if "line_tension" in self.energy_module_names and any(
-                _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
-            raise L.MembraneHipError("line_tension together with tilt modules is outside the HIP hot path")
+        for edge_mod in _EDGE_MODULES:
+            if edge_mod in self.energy_module_names and any(
+                    _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
+                raise L.MembraneHipError(f"{edge_mod} together with tilt modules is outside the HIP hot path")
         self._line_key = None
+        self._edgepen_key = None
         self.constraint_modules = [self.constraint_manager.get_constraint(c)
                                    for c in self.constraint_module_names]
         for name in self.constraint_module_names:
@@ -252,6 +257,9 @@ class Minimizer:
             elif name == "line_tension":
                 if self._upload_line(mir, dm):  # line_tension.py:113-115: nothing tagged, nothing charged
                     mods |= L.MS_MOD_LINE_TENSION
+            elif name == "edge_length_penalty":
+                if self._upload_edge_penalty(mir, dm):  # nothing charged, or k == 0 (the reference adds zeros)
+                    mods |= L.MS_MOD_EDGE_LENGTH_PENALTY
             elif name == "tilt":
                 if float(gp.get("tilt_rigidity", 0.0) or 0.0) != 0.0:  # tilt.py:110-112
                     mods |= L.MS_MOD_TILT
@@ -308,11 +316,12 @@ class Minimizer:
                 "bending_gradient_mode=approx with modules listed AFTER bending_tilt on an open mesh is "
                 "not on the fused device path (bending_tilt.py:297-299 zeroes boundary rows of what was "
                 "accumulated so far); list bending_tilt last")
-        if mode == "approx" and (mods & L.MS_MOD_LINE_TENSION) and np.any(_boundary(self.mesh)):
-            # (bending.py:165-166 / bending_tilt.py:297-299 zero the boundary rows of what the modules listed before
-            # them accumulated; the device adds the line-tension rows behind the whole gradient pass)
-            raise L.MembraneHipError("line_tension with bending_gradient_mode=approx on an open mesh is outside the "
-                                     "HIP hot path")
+        for edge_mod in _EDGE_MODULES:
+            if mode == "approx" and (mods & _ENERGY_BITS[edge_mod]) and np.any(_boundary(self.mesh)):
+                # (bending.py:165-166 / bending_tilt.py:297-299 zero the boundary rows of what the modules listed before
+                # them accumulated; the device adds the edge modules' rows behind the whole gradient pass)
+                raise L.MembraneHipError(f"{edge_mod} with bending_gradient_mode=approx on an open mesh is outside the "
+                                         "HIP hot path")
         if mode == "approx" and (mods & L.MS_MOD_BENDING):
             order = self.energy_module_names
             if order.index("bending") != len(order) - 1 and np.any(_boundary(self.mesh)):
@@ -359,7 +368,7 @@ class Minimizer:
             dm.set_tilt_smoothness(float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0))
         if self._pin_names:
             self._upload_pins(mir, dm, mods)
-        key = (mods, model, mode, stiffness, target, area_params, self._line_key, id(dm))
+        key = (mods, model, mode, stiffness, target, area_params, self._line_key, self._edgepen_key, id(dm))
         if key != self._configured_key:
             if area_params is not None:
                 dm.set_area_penalty(*area_params)
@@ -378,6 +387,16 @@ class Minimizer:
         if self._line_key is None or self._line_key[:3] != key:
             self._line_key = key + (_line.upload(self.mesh, self.global_params, dm),)
         return self._line_key[3]
+
+    def _upload_edge_penalty(self, mir, dm) -> bool:
+        """Resolve the charged edges and their targets (modules/energy/edge_length_penalty.py) once per mesh topology,
+        edge_stiffness and set of targets (they are hashed: the "fix edges" command rewrites them in place) and
+        upload the device tables; True when some edge is charged with k != 0."""
+        tail, head, target, num = _edgepen.charged_edges(self.mesh, self.global_params)
+        key = (mir._topo_key, id(dm), _edgepen.stiffness(self.global_params), num.tobytes(), target.tobytes())
+        if self._edgepen_key is None or self._edgepen_key[:5] != key:
+            self._edgepen_key = key + (_edgepen.upload(self.mesh, self.global_params, dm, (tail, head, target, num)),)
+        return self._edgepen_key[5]
 
     def _upload_pins(self, mir, dm, mods):
         """Resolve the pin tags once per mesh topology, fixed mask and row set (call refresh_modules() after
@@ -439,11 +458,16 @@ class Minimizer:
                     if dm.modules & L.MS_MOD_VOLUME_PENALTY else (0.0, 0.0)
                 dv = float(dm.fetch_scalars()[L.MS_S_VOL]) - v0
                 out["volume"] = 0.5 * k * (dv * dv)
-        if "line_tension" in out:  # energies[0] is surface + line tension: each module reports its own
+        if any(n in out for n in _EDGE_MODULES):
+            # energies[0] is surface + line tension + edge length penalty: each module reports its own
             line_e = dm.line_energy() if dm.modules & L.MS_MOD_LINE_TENSION else 0.0
-            out["line_tension"] = line_e
+            pen_e = dm.edge_penalty_energy() if dm.modules & L.MS_MOD_EDGE_LENGTH_PENALTY else 0.0
+            if "line_tension" in out:
+                out["line_tension"] = line_e
+            if "edge_length_penalty" in out:
+                out["edge_length_penalty"] = pen_e
             if "surface" in out:
-                out["surface"] = float(e[0]) - line_e if dm.modules & L.MS_MOD_SURFACE else 0.0
+                out["surface"] = float(e[0]) - line_e - pen_e if dm.modules & L.MS_MOD_SURFACE else 0.0
         for table in (_TILT_SCALAR, _BEND_SCALAR):
             sharing = [n for n in out if n in table]
             if len(sharing) > 1:  # they share one entry of the energy vector: split via the scalars
