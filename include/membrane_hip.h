@@ -81,6 +81,12 @@ extern "C" {
  * line tension its energy is added into the surface slot (MS_S_ESURF, energies[0]) behind the energy pass, its gradient
  * into G behind the gradient pass, each behind line tension's launch when both are on: no reduction slot of its own. */
 #define MS_MOD_EDGE_LENGTH_PENALTY 262144u
+/* soft contact term on an inclusion rim E = -sum gamma L 1/2 (t_tail + t_head) . r_hat over the rim edges
+ * (modules/energy/tilt_rim_source_in.py:371-451, tilt_rim_source_out.py); the edges, their gamma and the circle's
+ * frame come from ms_set_leaflet_rim_source.  Tilt gradient only.  Its sums are added into the leaflet's tilt-magnitude
+ * slot (MS_S_ETILT_IN / MS_S_ETILT_OUT, energies[3]) behind the pass that writes it: no reduction slot of its own. */
+#define MS_MOD_TILT_RIM_SOURCE_IN 524288u
+#define MS_MOD_TILT_RIM_SOURCE_OUT 1048576u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -366,6 +372,33 @@ typedef struct ms_disk_target_params {
 } ms_disk_target_params;
 int ms_set_leaflet_disk_target(ms_ctx *ctx, int leaflet, const uint8_t *disk_rows /* nv or NULL */,
                                const ms_disk_target_params *params);
+/* tilt_rim_source_in / _out: per rim edge mid = 1/2 (p0 + p1), r = (mid - c) - ((mid - c) . n) n, r_hat = r / |r| when
+ * |r| > 1e-12 and 0 otherwise, L = |p1 - p0|; E = -sum gamma L 1/2 (t_tail + t_head) . r_hat, tilt gradient
+ * -1/2 gamma L r_hat at both ends, no shape gradient.  follow == 0: c is `center`; follow != 0 (a rim row resolves
+ * pin_to_circle_mode to fit): c is the mean of the rim rows of x -- taken when an evaluation at x runs and reused by
+ * the line-search trials that follow it (tilt_rim_source_in.py:318 reads the mesh, not the trial positions); ms_step
+ * with an enforcer on the line search then fails with MS_ERR_STATE.  tail / head are external rows; an edge with
+ * gamma == 0 still makes its ends rim rows (they count in the mean).  Every row is validated, gamma / center / normal
+ * must be finite and the normal non-zero (it is normalised here).  tail == NULL clears the tables.  Takes effect when
+ * MS_MOD_TILT_RIM_SOURCE_IN / _OUT is in ms_params.modules.  Single context only. */
+typedef struct ms_rim_source_params {
+  double center[3];  /* tilt_rim_source_center (fixed frame) */
+  double normal[3];  /* pin_to_circle_normal of the first rim row that carries one, else (0,0,1) */
+  int follow;
+} ms_rim_source_params;
+int ms_set_leaflet_rim_source(ms_ctx *ctx, int leaflet, int n_edges, const int32_t *tail, const int32_t *head,
+                              const double *gamma, const ms_rim_source_params *params);
+/* the module's own energy at the last evaluation (its sums are also part of energies[3]) */
+int ms_get_leaflet_rim_source_energy(ms_ctx *ctx, int leaflet, double *energy);
+/* launches so far: {k_rim_frame, k_rim_coef, k_rim_apply} */
+int ms_leaflet_rim_source_stats(ms_ctx *ctx, int leaflet, double stats[3]);
+/* Host only, no context: the row -> rim edge CSR ms_set_leaflet_rim_source uploads, built by the same code from
+ * external rows and a row permutation (iperm: external -> library row).  counts = {edges, rim rows}; vrow holds
+ * counts[1] rows (ascending), off counts[1] + 1 offsets, other / csr_gamma 2 * counts[0] entries (room for
+ * 2 * n_edges each, and n_edges * 2 + 1 for vrow / off + 1). */
+int ms_rim_source_tables_host(int nv, const int32_t *iperm, int n_edges, const int32_t *tail, const int32_t *head,
+                              const double *gamma, int32_t counts[2], int32_t *vrow, int32_t *off, int32_t *other,
+                              double *csr_gamma);
 /* per-vertex (kappa, c0) of bending_tilt_in / bending_tilt_out (modules/energy/bt_params.py:225-318:
  * bending_modulus_in|out else bending_modulus; spontaneous_curvature_in|out else the global one) */
 int ms_set_leaflet_bending(ms_ctx *ctx, int leaflet, const double *kappa /* nv */, const double *c0 /* nv */);

@@ -33,6 +33,7 @@ MS_MOD_TILT_DISK_TARGET_IN, MS_MOD_TILT_DISK_TARGET_OUT = 16384, 32768
 MS_MOD_AREA_PENALTY = 65536
 MS_MOD_LINE_TENSION = 131072
 MS_MOD_EDGE_LENGTH_PENALTY = 262144
+MS_MOD_TILT_RIM_SOURCE_IN, MS_MOD_TILT_RIM_SOURCE_OUT = 524288, 1048576
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
@@ -78,6 +79,10 @@ class ms_tilt_relax_params(ctypes.Structure):
 class ms_leaflet_params(ctypes.Structure):
     _fields_ = [("tilt_modulus", ctypes.c_double), ("tilt_mass_consistent", ctypes.c_int),
                 ("smoothness", ctypes.c_double), ("precond_smoothness", ctypes.c_double)]
+
+
+class ms_rim_source_params(ctypes.Structure):
+    _fields_ = [("center", ctypes.c_double * 3), ("normal", ctypes.c_double * 3), ("follow", ctypes.c_int)]
 
 
 class ms_disk_target_params(ctypes.Structure):
@@ -162,6 +167,12 @@ SIGNATURES = {
     "ms_set_leaflet_bending": (ctypes.c_int, [_P, ctypes.c_int, _D, _D]),
     "ms_set_leaflet_disk_target": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8),
                                                   ctypes.POINTER(ms_disk_target_params)]),
+    "ms_set_leaflet_rim_source": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _I32, _I32, _D,
+                                                 ctypes.POINTER(ms_rim_source_params)]),
+    "ms_get_leaflet_rim_source_energy": (ctypes.c_int, [_P, ctypes.c_int, _D]),
+    "ms_leaflet_rim_source_stats": (ctypes.c_int, [_P, ctypes.c_int, _D]),
+    "ms_rim_source_tables_host": (ctypes.c_int, [ctypes.c_int, _I32, ctypes.c_int, _I32, _I32, _D, _I32, _I32, _I32,
+                                                 _I32, _D]),
     "ms_leaflet_tilt_energy_and_gradient": (ctypes.c_int, [_P, _D, _D, _D]),
     "ms_leaflet_tilt_energy_and_gradient_ex": (ctypes.c_int, [_P, ctypes.c_int, _D, _D, _D]),
     "ms_relax_leaflet_tilts": (ctypes.c_int, [_P, ctypes.POINTER(ms_tilt_relax_params),

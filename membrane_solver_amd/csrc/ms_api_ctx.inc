@@ -115,7 +115,19 @@ struct ms_ctx {
     ms_disk_target_params dt = {};
     uint32_t mod_dt = 0;
     int s_edt = 0, s_dtr = 0;
-    bool any_free = true;      // some row of this field is not clamped (kept current by the flag setters)
+    // rim source (tilt_rim_source_in/out, ms_set_leaflet_rim_source): one allocation holds the CSR, the coefficients,
+    // the follow mode's center, the per-workgroup sums and the module's energy
+    uint32_t mod_rs = 0;
+    void* d_rim = nullptr;
+    RimArgs rs{};
+    bool rs_set = false;
+    bool rs_follow = false;
+    bool rs_coef_valid = false;    // rs.coef holds c of the frozen surface of a running relaxation
+    double* rs_center = nullptr;   // (inside d_rim)
+    long rs_launches[3] = {0, 0, 0};  // k_rim_frame, k_rim_coef, k_rim_apply
+    // every module bit that reads this leaflet field
+    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs; }
+    bool any_free = true;     // some row of this field is not clamped (kept current by the flag setters)
     double* va = nullptr;      // relaxation: barycentric vertex areas of the frozen positions
   } tf[3];
   CarryState carry;

@@ -13,6 +13,8 @@ int line_energy_run(ms_ctx* c, bool use_dir, double alpha);  // (ms_api_line.inc
 int line_grad_run(ms_ctx* c, double* g, bool volrow);
 int edgepen_energy_run(ms_ctx* c, bool use_dir, double alpha);  // (ms_api_edgepen.inc)
 int edgepen_grad_run(ms_ctx* c, double* g, bool volrow);
+// tilt_rim_source_in/out: c . t of the rim rows at x (+ alpha d) into the field's tilt-magnitude partials (ms_api_rim.inc)
+int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const double* tilts, bool gradient);
 inline int exec_flush(ms_ctx* c) {
   if (!c->exec_on) return MS_OK;
   const hipError_t e = c->exec.flush();
@@ -150,7 +152,10 @@ constexpr uint32_t MASK_ENERGY = (1u << MS_S_ESURF) | (1u << MS_S_VOL) | (1u << 
 constexpr uint32_t MS_TILT_MODS = MS_MOD_TILT | MS_MOD_BENDING_TILT | MS_MOD_TILT_SMOOTH;  // modules reading the single tilt field
 constexpr uint32_t MS_LEAFLET_BT = MS_MOD_BENDING_TILT_IN | MS_MOD_BENDING_TILT_OUT;
 constexpr uint32_t MS_LEAFLET_DT = MS_MOD_TILT_DISK_TARGET_IN | MS_MOD_TILT_DISK_TARGET_OUT;
-constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT;
+// the rim sources: no slot of their own (MS_NSCAL is full) -- their sums ride in the leaflet's tilt-magnitude slot -- and no
+// shape gradient, so they are not in MS_TILT_SHAPE_MODS
+constexpr uint32_t MS_LEAFLET_RS = MS_MOD_TILT_RIM_SOURCE_IN | MS_MOD_TILT_RIM_SOURCE_OUT;
+constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS;
 constexpr uint32_t MS_ANY_TILT_MODS = MS_TILT_MODS | MS_LEAFLET_MODS;
 // the edge modules: energy added into the MS_S_ESURF partials behind the energy pass, gradient into G behind K_C; they
 // share one lane of the step (one trial per launch, every Armijo decision the host's, the separate direction pass)
@@ -165,7 +170,7 @@ int active_fields(ms_ctx* c, uint32_t mods, TiltField* out[3]) {
   int n = 0;
   for (int k = 0; k < 3; ++k) {
     TiltField& f = c->tf[k];
-    const uint32_t reads = k == 0 ? MS_TILT_MODS : (f.mod_tilt | f.mod_smooth | f.mod_bt | f.mod_dt);
+    const uint32_t reads = k == 0 ? MS_TILT_MODS : f.mods();
     if (mods & reads) out[n++] = &f;
   }
   return n;
@@ -687,7 +692,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
       // projection of the stored tilts onto x itself, in place)
       for (int l = 1, k = 0; l <= 2 && (use_dir || st.proj_at_x_in_normals); ++l) {
         TiltField& f = c->tf[l];
-        if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_bt | f.mod_dt))) continue;
+        if (!(modules & f.mods())) continue;
         if (!f.tilts) return fail(c, MS_ERR_STATE, "tilt module active but its tilt field was never set (ms_set_tilts / ms_set_leaflet_tilts)");
         ta.fld_in[k] = f.tilts;
         ta.fld_out[k] = use_dir ? f.trial : f.tilts;
@@ -762,7 +767,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   }
   for (int l = 1; l <= 2 && (modules & MS_LEAFLET_MODS); ++l) {  // leaflet fields, same protocol
     TiltField& f = c->tf[l];
-    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt))) continue;
+    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs))) continue;
     int rc = MS_OK;
     const double* tilts = f.tilts;
     if (use_dir) {
@@ -783,6 +788,13 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     int rc = tilt_energy_pass(c, modules, use_dir, alpha, &used, /*dry=*/false, /*skip_bt=*/fused_rest);
     if (rc) return rc;
     if (!used) return fail(c, MS_ERR_STATE, "tilt energy pass: planned but not launched");
+  }
+  // tilt_rim_source_in/out: c . t of the rim rows added into the leaflet's tilt-magnitude partials, behind whichever pass
+  // above wrote them (k_tilt, or the one launch of tilt_energy_pass); on a trial, with the tilts projected onto it
+  for (int l = 1; l <= 2 && (modules & MS_LEAFLET_RS); ++l) {
+    TiltField& f = c->tf[l];
+    if (!(modules & f.mod_rs)) continue;
+    if (int rc_r = rim_pass(c, f, use_dir, alpha, use_dir ? f.trial : f.tilts, false)) return rc_r;
   }
   if (reduce_now) {
     constexpr uint32_t core = (1u << MS_S_ESURF) | (1u << MS_S_VOL) | (1u << MS_S_EBEND) | (1u << MS_S_MINEDGE2) |
@@ -913,6 +925,12 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
       int rc = tilt_pass_f(c, f, 1, false, 0.0);
       if (rc) return rc;
       added_after = true;
+      // k_tilt<1> has written the slot's partials again (the energy fold of this evaluation may still be ahead:
+      // queue_energy_and_gradient): the rim source's sums go in once more, behind it
+      if (k > 0 && (modules & f.mod_rs)) {
+        rc = rim_pass(c, f, false, 0.0, f.tilts, false);
+        if (rc) return rc;
+      }
     }
     if (k > 0 && (modules & f.mod_dt)) {
       int rc = disk_target_pass(c, f, 1, false, 0.0, f.tilts, true, false);
@@ -1107,7 +1125,7 @@ void energies_from_mailbox(const ms_ctx* c, double e[4]) {
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e[3] += c->h_scal[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
-    if (c->params.modules & f.mod_tilt) e[3] += c->h_scal[f.s_etilt];
+    if (c->params.modules & (f.mod_tilt | f.mod_rs)) e[3] += c->h_scal[f.s_etilt];  // (the rim source rides in this slot)
     if (c->params.modules & f.mod_smooth) e[3] += c->h_scal[f.s_ets];
     if (c->params.modules & f.mod_bt) e[1] += c->h_scal[f.s_ebt];
     if (c->params.modules & f.mod_dt) e[3] += c->h_scal[f.s_edt];

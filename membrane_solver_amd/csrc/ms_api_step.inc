@@ -444,6 +444,13 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   const bool tilt = (c->params.modules & MS_ANY_TILT_MODS) != 0;
   TiltField* tfl[3];
   const int n_tf = active_fields(c, c->params.modules, tfl);
+  // A rim source in follow mode takes its center from x when this step's energy pass at x runs, and the trials reuse it
+  // (tilt_rim_source_in.py:318 reads the mesh, not the trial positions: without an enforcer the mesh stays at x through
+  // the search).  With an enforcer the reference moves the mesh to every trial: that lane is not built.
+  for (int k = 0; k < n_tf; ++k)
+    if ((c->params.modules & tfl[k]->mod_rs) && tfl[k]->rs_follow && (sp->enforce_volume || sp->enforce_pins))
+      return fail(c, MS_ERR_STATE, "tilt_rim_source in follow mode (pin_to_circle_mode: fit) with a constraint enforcer "
+                                   "on the line search is outside the device path");
   // reuse_energy0 == 2: an accepted trial doubles as the next step's energy/factor pass
   const bool carry_mode = sp->reuse_energy0 >= 2 && !tilt;
   if (c->ahead.valid && !c->ahead.go_known && !(c->carry.kc_pending && carry_mode && c->carry.carry_valid)) {

@@ -38,7 +38,7 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
   }
   for (int l = 1; l <= 2; ++l) {
     TiltField& f = c->tf[l];
-    if (!(mods & (f.mod_tilt | f.mod_smooth | f.mod_bt | f.mod_dt))) continue;
+    if (!(mods & f.mods())) continue;
     const double* tilts = trial ? f.trial : f.tilts;
     if ((mods & f.mod_tilt) && c->relax_va_valid && f.va) {
       // positions frozen, vertex areas at hand: the reference's own form of this evaluation, one streaming pass
@@ -71,6 +71,12 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
       if (rc) return rc;
       mask |= 1u << f.s_ets;
     }
+    if (mods & f.mod_rs) {
+      // behind the magnitude pass (its partials, its rows of f.grad) and every other pass that adds into f.grad
+      rc = rim_pass(c, f, false, 0.0, tilts, gradient);
+      if (rc) return rc;
+      mask |= 1u << f.s_etilt;
+    }
   }
   return mask ? reduce_slots(c, mask) : MS_OK;
 }
@@ -81,7 +87,7 @@ double tilt_energy_from(const ms_ctx* c, const double* hs) {
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e += hs[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
-    if (c->params.modules & f.mod_tilt) e += hs[f.s_etilt];
+    if (c->params.modules & (f.mod_tilt | f.mod_rs)) e += hs[f.s_etilt];  // (tilt magnitude + rim source)
     if (c->params.modules & f.mod_smooth) e += hs[f.s_ets];
     if (c->params.modules & f.mod_bt) e += hs[f.s_ebt];
     if (c->params.modules & f.mod_dt) e += hs[f.s_edt];
@@ -103,7 +109,7 @@ bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs
     const bool tilt_on = single ? (mods & MS_MOD_TILT) != 0 : (mods & f.mod_tilt) != 0;
     const bool bt_on = single ? (mods & MS_MOD_BENDING_TILT) != 0 : (mods & f.mod_bt) != 0;
     const bool ts_on = single ? (mods & MS_MOD_TILT_SMOOTH) != 0 : (mods & f.mod_smooth) != 0;
-    if (!single && (mods & f.mod_dt)) return false;  // (the disk target keeps its own passes)
+    if (!single && (mods & (f.mod_dt | f.mod_rs))) return false;  // (the disk target and the rim source keep their own passes)
     o.tilts = f.tilts;
     o.src = along_dir ? f.dir : f.grad;
     o.bt_vert = nullptr;
@@ -318,7 +324,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
       q.has_ts = (mods & f.mod_smooth) ? 1 : 0;
       q.has_dt = (mods & f.mod_dt) ? 1 : 0;
       q.fixed_bit = f.fixed_bit;
-      ok = ok && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
+      ok = ok && !(mods & f.mod_rs) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
            (!q.has_dt || (f.dt_target && f.disk && f.dt_target_valid));
     }
     const size_t need = relax_fused_lds_bytes(c->cap, t.max_ent, t.max_tile_facets);
@@ -437,7 +443,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
     if (mods & MS_MOD_TILT_SMOOTH) head.e_slot[n++] = MS_S_ETS;
     for (int l = 1; l <= 2; ++l) {
       const TiltField& f = c->tf[l];
-      if (mods & f.mod_tilt) head.e_slot[n++] = f.s_etilt;
+      if (mods & (f.mod_tilt | f.mod_rs)) head.e_slot[n++] = f.s_etilt;
       if (mods & f.mod_smooth) head.e_slot[n++] = f.s_ets;
       if (mods & f.mod_bt) head.e_slot[n++] = f.s_ebt;
       if (mods & f.mod_dt) head.e_slot[n++] = f.s_edt;
@@ -597,7 +603,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     ms_ctx* c;
     ~VaScope() {
       c->relax_va_valid = false;
-      for (int l = 0; l < 3; ++l) c->tf[l].dt_target_valid = false;
+      for (int l = 0; l < 3; ++l) c->tf[l].dt_target_valid = c->tf[l].rs_coef_valid = false;
     }
   } va_scope{c};
   c->relax_va_valid = jacobi_smooth_by_param;  // leaflet driver only (the single field has no such form)
@@ -606,6 +612,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     // the relaxation -- and the device program's captured lists -- then only take differences
     TiltField& f = *fl[k];
     f.dt_target_valid = false;
+    f.rs_coef_valid = false;  // (the first rim pass of this relaxation computes the coefficients, the others reuse them)
     if (!(mods & f.mod_dt)) continue;
     rc = disk_target_pass(c, f, 0, false, 0.0, f.tilts, false, false);
     if (rc) return rc;
@@ -739,7 +746,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     if (r || used) return r;
     return search(along_dir, sign, E0, E_acc, accepted);
   };
-  if (c->exec_on && c->exec_relax) {
+  if (c->exec_on && c->exec_relax && !(mods & MS_LEAFLET_RS)) {  // (the rim source's kernels are not recorded)
     // one-tile context: the whole solve below as ONE launch (ms_internal.h: ExecRelaxHead)
     bool used = false;
     rc = relax_program(c, rp, fl, nf, norm_mask, &iters, &evals, &used);
@@ -937,7 +944,7 @@ int leaflet_ready(ms_ctx* c, const char* who, TiltField** fl, int* nf) {
   *nf = 0;
   for (int l = 1; l <= 2; ++l) {
     TiltField& f = c->tf[l];
-    if (!(mods & (f.mod_tilt | f.mod_smooth | f.mod_bt | f.mod_dt))) continue;
+    if (!(mods & f.mods())) continue;
     if (!f.tilts) return fail(c, MS_ERR_STATE, std::string(who) + ": ms_set_leaflet_tilts was not called for an active leaflet");
     fl[(*nf)++] = &f;
   }
@@ -967,7 +974,7 @@ int ms_leaflet_tilt_energy_and_gradient_ex(ms_ctx* c, int module_form, double* e
   for (int l = 0; l < 2; ++l) {
     if (!outs[l]) continue;
     TiltField& f = c->tf[1 + l];
-    if (f.tilts && (c->params.modules & (f.mod_tilt | f.mod_smooth | f.mod_bt | f.mod_dt))) {
+    if (f.tilts && (c->params.modules & f.mods())) {
       rc = patch_to_ext(c, f.grad, outs[l], 3);
       if (rc) return rc;
     } else {

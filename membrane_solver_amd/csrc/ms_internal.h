@@ -424,6 +424,38 @@ struct EdgePenGradArgs {
 };
 hipError_t launch_edgepen_energy(const EdgePenEnergyArgs& a, hipStream_t s);
 hipError_t launch_edgepen_grad(const EdgePenGradArgs& a, hipStream_t s);
+// tilt_rim_source_in/out (ms_rim.hip): E = sum over the rim rows of c_row . t_row, c_row = sum over the row's rim edges
+// of -1/2 gamma L r_hat; the workgroup sums go into the field's tilt-magnitude partials (MS_S_ETILT_IN / _OUT) behind
+// the pass that writes them -- or define them when tilt_<leaflet> itself is off -- and c into the tilt gradient.  Rows
+// are the library's (til.iperm applied).
+struct RimArgs {
+  const double* x;
+  const double* d;        // trial direction or nullptr, alpha: exactly what EnergyArgs hands k_energy
+  double alpha;
+  const uint8_t* vflags;  // (a fixed row does not move in a trial)
+  int n_touch;
+  const int32_t* vrow;    // rim rows, ascending
+  const int32_t* off;     // n_touch + 1: CSR over the rows' rim edges, ascending edge order
+  const int32_t* other;   // the other end's row
+  const double* gamma;    // the edge's strength, per CSR entry
+  double center[3];       // fixed frame: tilt_rim_source_center
+  double normal[3];       // unit normal of the circle's plane
+  const double* center_dev;  // follow mode: the center k_rim_frame wrote (else nullptr)
+  double* coef;           // [3 n_touch] c_row: k_rim_coef writes it, k_rim_apply reads it when use_coef ...
+  int use_coef;           // ... and forms the rows itself when not
+  const double* tilts;
+  double* tilt_grad;      // c_row added into the row, or nullptr
+  double* partials;       // workgroup w -> [slot * n_tiles + tile0 + w]
+  int n_tiles, tile0, n_cells;  // n_cells: tiles of the context (define: the cells past `grid` are zeroed)
+  int slot, define;       // define: store (no pass before this one wrote the slot) instead of add
+  int grid;               // workgroups of the launch: min(tiles, ceil(n_touch / 256))
+  double* wg_sums;        // [grid] per-workgroup sums ...
+  uint32_t* done;         // ... counted here; the workgroup that arrives last adds them up in index order ...
+  double* energy;         // ... into the module's own energy (ms_get_leaflet_rim_source_energy)
+};
+hipError_t launch_rim_frame(const RimArgs& a, double* center_out, hipStream_t s);
+hipError_t launch_rim_coef(const RimArgs& a, hipStream_t s);
+hipError_t launch_rim_apply(const RimArgs& a, hipStream_t s);
 struct RowDotArgs {
   int tile0, nv, T;
   const double* g;

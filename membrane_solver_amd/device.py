@@ -315,6 +315,44 @@ class DeviceMesh:
         self._chk(L.lib().ms_set_leaflet_disk_target(self._h, lf, mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                                      ctypes.byref(p)), "ms_set_leaflet_disk_target")
 
+    def set_leaflet_rim_source(self, leaflet: str, tail=None, head=None, gamma=None, *, center=(0.0, 0.0, 0.0),
+                               normal=(0.0, 0.0, 1.0), follow: bool = False):
+        """tilt_rim_source_in/out: the rim edges as external rows with their strength gamma, and the circle's frame
+        (``follow``: the center is the mean of the rim rows of the evaluated positions); no edges clear the tables."""
+        lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]
+        if tail is None:
+            self._chk(L.lib().ms_set_leaflet_rim_source(self._h, lf, 0, None, None, None, None),
+                      "ms_set_leaflet_rim_source")
+            return
+        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
+        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
+        g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
+        if not (len(t) == len(h) == len(g)):
+            raise ValueError("set_leaflet_rim_source: tail, head and gamma must have the same length")
+        n = len(t)
+        if n == 0:  # (a non-NULL pointer: tables that hold no edge)
+            t = h = np.zeros(1, np.int32)
+            g = np.zeros(1)
+        p = L.ms_rim_source_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)),
+                                   1 if follow else 0)
+        self._chk(L.lib().ms_set_leaflet_rim_source(self._h, lf, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32),
+                                                    _pd(g), ctypes.byref(p)), "ms_set_leaflet_rim_source")
+
+    def leaflet_rim_source_energy(self, leaflet: str) -> float:
+        """The rim source's own energy as the last evaluation summed it (ms_get_leaflet_rim_source_energy)."""
+        lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]
+        e = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_get_leaflet_rim_source_energy(self._h, lf, ctypes.byref(e)),
+                  "ms_get_leaflet_rim_source_energy")
+        return float(e.value)
+
+    def leaflet_rim_source_stats(self, leaflet: str):
+        """Launch counts of the rim source's three kernels (ms_leaflet_rim_source_stats)."""
+        lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]
+        v = np.zeros(3)
+        self._chk(L.lib().ms_leaflet_rim_source_stats(self._h, lf, _pd(v)), "ms_leaflet_rim_source_stats")
+        return {"frame_launches": int(v[0]), "coef_launches": int(v[1]), "apply_launches": int(v[2])}
+
     def get_leaflet_tilts(self, leaflet: str) -> np.ndarray:
         out = np.empty((self.nv, 3), dtype=np.float64)
         lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]

@@ -15,7 +15,8 @@ from ...geometry.mesh import mirror_for
 LEAFLET_BITS = {("tilt", "in"): L.MS_MOD_TILT_IN, ("tilt", "out"): L.MS_MOD_TILT_OUT,
                 ("smooth", "in"): L.MS_MOD_TILT_SMOOTH_IN, ("smooth", "out"): L.MS_MOD_TILT_SMOOTH_OUT,
                 ("bt", "in"): L.MS_MOD_BENDING_TILT_IN, ("bt", "out"): L.MS_MOD_BENDING_TILT_OUT,
-                ("disk", "in"): L.MS_MOD_TILT_DISK_TARGET_IN, ("disk", "out"): L.MS_MOD_TILT_DISK_TARGET_OUT}
+                ("disk", "in"): L.MS_MOD_TILT_DISK_TARGET_IN, ("disk", "out"): L.MS_MOD_TILT_DISK_TARGET_OUT,
+                ("rim", "in"): L.MS_MOD_TILT_RIM_SOURCE_IN, ("rim", "out"): L.MS_MOD_TILT_RIM_SOURCE_OUT}
 
 # options of the reference's leaflet modules that change their result and are not on the device path
 _UNSUPPORTED_KEYS = (
@@ -223,6 +224,212 @@ def disk_target_params(mesh, param_resolver, global_params, leaflet: str):
             "normal": tuple(np.asarray(normal, dtype=float).reshape(3)), "radius": radius}
 
 
+class _Options:
+    """Stand-in for an entity of the reference (``.options``) when the options come from an ArrayMesh's tables."""
+
+    __slots__ = ("options",)
+
+    def __init__(self, options):
+        self.options = options or {}
+
+
+def pin_to_circle_group(options):
+    """tilt_rim_source_in.py:50-54, as the reference has it: a vertex without options (None or empty) has no group;
+    options whose ``pin_to_circle_group`` is None -- the key absent from non-empty options included, the reference
+    reads ``options.get`` -- mean "default"."""
+    if not options:
+        return None
+    group = options.get("pin_to_circle_group")
+    return "default" if group is None else str(group)
+
+
+def contact_line_strength(param_resolver, obj, leaflet: str) -> float:
+    """gamma of one rim edge (modules/energy/contact_mapping.py:36-131): the strength key from the edge's options and
+    then the global, else ``contact_gamma``, else ``h * delta_epsilon_over_a`` (or ``delta_epsilon / a``), each with
+    the leaflet's suffix first and then without, then the si / physical unit conversion."""
+    key = f"tilt_rim_source_strength_{leaflet}"
+    val = param_resolver.get(obj, key)
+    if val is None:
+        val = param_resolver.get(None, key)
+    if val is not None:
+        return float(val)
+    suffix = f"_{leaflet}"
+
+    def get_key(base):
+        got = param_resolver.get(obj, base + suffix)
+        if got is None:
+            got = param_resolver.get(None, base + suffix)
+        if got is not None:
+            return got
+        got = param_resolver.get(obj, base)
+        if got is None:
+            got = param_resolver.get(None, base)
+        return got
+
+    def convert(raw):
+        units = str(param_resolver.get(None, "tilt_rim_source_contact_units") or "solver").strip().lower()
+        if units not in {"si", "physical", "physical_si"}:
+            return float(raw)
+        length = param_resolver.get(None, "tilt_rim_source_contact_length_unit_m")
+        kappa = param_resolver.get(None, "tilt_rim_source_contact_kappa_ref_J")
+        if length is None or kappa is None or abs(float(length)) < 1e-30 or abs(float(kappa)) < 1e-30:
+            return float(raw)
+        return float(raw) * float(length) / float(kappa)
+
+    direct = get_key("tilt_rim_source_contact_gamma")
+    if direct is not None:
+        return convert(float(direct))
+    h = get_key("tilt_rim_source_contact_h")
+    if h is None:
+        return 0.0
+    ratio = get_key("tilt_rim_source_contact_delta_epsilon_over_a")
+    if ratio is None:
+        de, a = get_key("tilt_rim_source_contact_delta_epsilon"), get_key("tilt_rim_source_contact_a")
+        if de is None or a is None:
+            return 0.0
+        ratio = float(de) / float(a)
+    return convert(float(h) * float(ratio))
+
+
+def _rim_entities(mesh):
+    """-> (options per row {row: dict}, edges [(tail row, head row, options)]) of a reference Mesh or an ArrayMesh."""
+    row_of = mesh.vertex_index_to_row
+    if isinstance(getattr(mesh, "vertices", None), dict):
+        vopts = {}
+        for vid, v in mesh.vertices.items():
+            row = row_of.get(int(vid))
+            if row is not None:
+                vopts[int(row)] = getattr(v, "options", None) or {}
+        edges = []
+        for e in mesh.edges.values():
+            t, h = row_of.get(int(e.tail_index)), row_of.get(int(e.head_index))
+            if t is not None and h is not None:
+                edges.append((int(t), int(h), getattr(e, "options", None) or {}))
+        return vopts, edges
+    er = getattr(mesh, "edge_rows", None)
+    if er is None:
+        raise L.MembraneHipError("tilt_rim_source on a mesh without an edge table (ArrayMesh(edges=, edge_options=)) "
+                                 "is outside the HIP hot path")
+    vopts = {int(r): (o or {}) for r, o in (getattr(mesh, "vertex_options", None) or {}).items()}
+    eo = getattr(mesh, "edge_options", None) or {}
+    return vopts, [(int(er[k, 0]), int(er[k, 1]), eo.get(k) or {}) for k in range(len(er))]
+
+
+def _side_counts(mesh, tail, head):
+    """How many triangles each edge is a side of (the reference's len(edge_to_facets[edge]))."""
+    tri, _f = mesh.triangle_row_cache()
+    nv = len(mesh.vertex_ids)
+    if tri is None or len(tri) == 0 or len(tail) == 0:
+        return np.zeros(len(tail), dtype=np.int64)
+    tri = np.asarray(tri, dtype=np.int64).reshape(-1, 3)
+    a = np.concatenate([tri[:, 0], tri[:, 1], tri[:, 2]])
+    b = np.concatenate([tri[:, 1], tri[:, 2], tri[:, 0]])
+    keys, cnt = np.unique(np.minimum(a, b) * nv + np.maximum(a, b), return_counts=True)
+    t, h = np.asarray(tail, dtype=np.int64), np.asarray(head, dtype=np.int64)
+    want = np.minimum(t, h) * nv + np.maximum(t, h)
+    pos = np.searchsorted(keys, want)
+    pos[pos >= len(keys)] = 0
+    return np.where(keys[pos] == want, cnt[pos], 0)
+
+
+def rim_source_params(mesh, param_resolver, global_params, leaflet: str):
+    """Resolved tables of tilt_rim_source_<leaflet> (tilt_rim_source_in.py:57-336) as kwargs of
+    DeviceMesh.set_leaflet_rim_source, or None when the module contributes nothing (no group, no rim edge, every gamma
+    0: :386-404).  Rim edges: both ends carry ``pin_to_circle_group == tilt_rim_source_group_<leaflet>``; with
+    ``tilt_rim_source_edge_mode`` boundary (the default) only sides of exactly one triangle.  Frame: fixed center
+    ``tilt_rim_source_center`` and the ``pin_to_circle_normal`` of the first rim row (row order) that carries one, else
+    (0,0,1); follow (center = mean of the rim rows) when a rim row resolves ``pin_to_circle_mode`` to fit -- then a
+    ``pin_to_circle_normal`` is required (the reference's SVD plane fit is host work)."""
+    raw = _get(param_resolver, global_params, f"tilt_rim_source_group_{leaflet}")
+    group = None if raw is None else str(raw).strip()
+    if not group:
+        return None
+    mode = str(_get(param_resolver, global_params, "tilt_rim_source_edge_mode") or "boundary").strip().lower()
+    mode = "all" if mode == "all" else "boundary"
+    vopts, edges = _rim_entities(mesh)
+    member = {row for row, o in vopts.items() if pin_to_circle_group(o) == group}
+    sel = [(t, h, o) for (t, h, o) in edges if t in member and h in member]
+    if sel and mode == "boundary":
+        cnt = _side_counts(mesh, [s[0] for s in sel], [s[1] for s in sel])
+        sel = [s for s, n in zip(sel, cnt) if n == 1]
+    if not sel:
+        return None
+    resolver = param_resolver if param_resolver is not None else _GlobalOnly(global_params)
+    gamma = np.array([contact_line_strength(resolver, _Options(o), leaflet) for (_t, _h, o) in sel], dtype=np.float64)
+    if not np.any(gamma):
+        return None
+    tail = np.array([s[0] for s in sel], dtype=np.int32)
+    head = np.array([s[1] for s in sel], dtype=np.int32)
+    rim_rows = np.unique(np.concatenate([tail, head]))
+
+    def opt(row, key):
+        o = vopts.get(int(row)) or {}
+        val = o.get(key)
+        return global_params.get(key) if val is None and global_params is not None else val
+
+    follow = any(str(opt(r, "pin_to_circle_mode") or "fixed").strip().lower() == "fit" for r in rim_rows)
+    normal = None
+    for r in rim_rows:
+        rawn = opt(r, "pin_to_circle_normal")
+        if rawn is None:
+            continue
+        vec = np.asarray(rawn, dtype=float).reshape(3)
+        if float(np.linalg.norm(vec)) >= 1e-15:
+            normal = vec / float(np.linalg.norm(vec))
+            break
+    if normal is None:
+        if follow:
+            raise L.MembraneHipError(f"tilt_rim_source_{leaflet} in follow mode (pin_to_circle_mode: fit) without "
+                                     "pin_to_circle_normal on a rim vertex (SVD plane fit of the rim rows) is outside "
+                                     "the HIP hot path")
+        normal = np.array([0.0, 0.0, 1.0])
+    if leaflet == "out" and not follow:
+        normal = np.array([0.0, 0.0, 1.0])  # tilt_rim_source_out.py:311-312: its fixed frame never reads the rows' normal
+    center = _get(param_resolver, global_params, "tilt_rim_source_center")
+    center = np.asarray([0.0, 0.0, 0.0] if center is None else center, dtype=float).reshape(3)
+    return {"tail": tail, "head": head, "gamma": gamma, "center": tuple(float(v) for v in center),
+            "normal": tuple(float(v) for v in normal), "follow": bool(follow)}
+
+
+class _GlobalOnly:
+    def __init__(self, gp):
+        self.gp = gp
+
+    def get(self, obj, name):
+        opts = getattr(obj, "options", None) if obj is not None else None
+        if opts and name in opts:
+            return opts[name]
+        return self.gp.get(name) if self.gp is not None else None
+
+
+def rim_source_key(prm):
+    """Hashable identity of rim_source_params' result (the Minimizer re-uploads when it changes)."""
+    if prm is None:
+        return None
+    return (prm["tail"].tobytes(), prm["head"].tobytes(), prm["gamma"].tobytes(), prm["center"], prm["normal"],
+            prm["follow"])
+
+
+def rim_source_host_tables(nv: int, iperm, tail, head, gamma):
+    """The row -> rim edge CSR as the library builds it (ms_rim_source_tables_host: the code
+    ms_set_leaflet_rim_source runs), rows in the library's order (``iperm``: external row -> library row)."""
+    ip = np.ascontiguousarray(np.asarray(iperm, dtype=np.int32).reshape(-1))
+    t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
+    h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
+    g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
+    n = len(t)
+    cnt = np.zeros(2, dtype=np.int32)
+    vrow, off = np.zeros(2 * n + 1, np.int32), np.zeros(2 * n + 2, np.int32)
+    other, og = np.zeros(2 * n + 1, np.int32), np.zeros(2 * n + 1)
+    i32 = lambda a: a.ctypes.data_as(L._I32)  # noqa: E731
+    rc = L.lib().ms_rim_source_tables_host(int(nv), i32(ip), n, i32(t), i32(h), g.ctypes.data_as(L._D), i32(cnt),
+                                           i32(vrow), i32(off), i32(other), og.ctypes.data_as(L._D))
+    L.check(rc, None, "ms_rim_source_tables_host")
+    ne, nt = int(cnt[0]), int(cnt[1])
+    return {"n_edges": ne, "vrow": vrow[:nt].copy(), "off": off[:nt + 1].copy(), "other": other[:2 * ne].copy(),
+            "csr_gamma": og[:2 * ne].copy()}
+
+
 def check_bt_supported(global_params) -> None:
     mode = str(global_params.get("bending_gradient_mode", "analytic") or "analytic").strip().lower()
     if mode != "analytic":
@@ -266,6 +473,24 @@ def evaluate(mesh, global_params, param_resolver, *, kind: str, leaflet: str, po
         if prm is None:
             return 0.0
         dm.set_leaflet_disk_target(leaflet, **prm)
+    if kind == "rim":
+        prm = rim_source_params(mesh, param_resolver, global_params, leaflet)
+        if prm is None:
+            return 0.0
+        if prm["follow"]:
+            # tilt_rim_source_in.py:318: the followed center is read from the MESH, whatever `positions` the caller
+            # evaluates on -- a fixed frame for this one call
+            rows = np.unique(np.concatenate([prm["tail"], prm["head"]]))
+            center = np.mean(np.asarray(mesh.positions_view(), dtype=np.float64)[rows], axis=0)
+            prm = dict(prm, center=tuple(float(v) for v in center), follow=False)
+        dm.set_leaflet_rim_source(leaflet, **prm)
+        dm.set_params(modules=LEAFLET_BITS[(kind, leaflet)])
+        # no shape gradient (grad_arr stays as it is); the tilt gradient is the coefficient field itself
+        E = float(dm.energy()[3])
+        if tilt_grad_arr is not None:
+            _e, gi, go = dm.leaflet_tilt_energy_and_gradient(want_gradient=True)
+            tilt_grad_arr += gi if leaflet == "in" else go
+        return E
     dm.set_params(modules=LEAFLET_BITS[(kind, leaflet)])
     if kind == "disk":
         if grad_arr is not None:

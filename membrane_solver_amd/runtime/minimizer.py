@@ -68,18 +68,23 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "tilt_disk_target_out": L.MS_MOD_TILT_DISK_TARGET_OUT,
                 "body_area_penalty": L.MS_MOD_AREA_PENALTY, "line_tension": L.MS_MOD_LINE_TENSION,
                 "edge_length_penalty": L.MS_MOD_EDGE_LENGTH_PENALTY,
+                "tilt_rim_source_in": L.MS_MOD_TILT_RIM_SOURCE_IN, "tilt_rim_source_out": L.MS_MOD_TILT_RIM_SOURCE_OUT,
                 # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
                 # accepted in its switched-off state (strength 0, as in the caveolin decks)
                 "gaussian_curvature": 0, "rim_slope_match_out": 0}
 _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_tilt": 1, "tilt_smoothness": 3,
                 "tilt_in": 3, "tilt_out": 3, "tilt_smoothness_in": 3, "tilt_smoothness_out": 3,
                 "bending_tilt_in": 1, "bending_tilt_out": 1, "tilt_disk_target_in": 3, "tilt_disk_target_out": 3,
-                "body_area_penalty": 2, "line_tension": 0, "edge_length_penalty": 0, "gaussian_curvature": None, "rim_slope_match_out": None}
+                "body_area_penalty": 2, "line_tension": 0, "edge_length_penalty": 0, "gaussian_curvature": None, "rim_slope_match_out": None,
+                # (their sums ride in the leaflet's tilt-magnitude slot of energies[3]; each reports its own energy)
+                "tilt_rim_source_in": None, "tilt_rim_source_out": None}
+_RIM_MODULES = ("tilt_rim_source_in", "tilt_rim_source_out")
 _EDGE_MODULES = ("line_tension", "edge_length_penalty")  # they share the lane behind the energy and the gradient pass
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
 _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
-                 | _LEAFLET_BT_BITS | L.MS_MOD_TILT_DISK_TARGET_IN | L.MS_MOD_TILT_DISK_TARGET_OUT)
+                 | _LEAFLET_BT_BITS | L.MS_MOD_TILT_DISK_TARGET_IN | L.MS_MOD_TILT_DISK_TARGET_OUT
+                 | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT)
 _TILT_BITS = _SINGLE_TILT_BITS | _LEAFLET_BITS
 # scalar slot of every module that shares energies[3]
 _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": L.MS_S_ETILT_IN,
@@ -178,14 +183,15 @@ class Minimizer:
                 raise TypeError(f"energy module {name!r} lacks compute_energy_and_gradient_array")
             # an edge module on a mesh built without edges stays refused: nothing could be tagged or given a target,
             # and the deck would run with that module's energy at zero
-            no_edges = name in _EDGE_MODULES and not _line.has_edge_table(self.mesh)
+            # (the rim sources select edges as well: without an edge table nothing could be a rim edge)
+            no_edges = name in _EDGE_MODULES + _RIM_MODULES and not _line.has_edge_table(self.mesh)
             if name not in _ENERGY_BITS or no_edges:
                 where = " on a mesh without an edge table (ArrayMesh(edges=, edge_options=))" if no_edges else ""
                 raise L.MembraneHipError(
                     f"energy module {name!r}{where} is outside the HIP hot path (surface, bending, volume, tilt, "
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
                     "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
-                    "body_area_penalty, line_tension, edge_length_penalty)")
+                    "body_area_penalty, line_tension, edge_length_penalty, tilt_rim_source_in, tilt_rim_source_out)")
         if "body_area_penalty" in self.energy_module_names and any(
                 _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
             raise L.MembraneHipError("body_area_penalty together with tilt modules is outside the HIP hot path")
@@ -244,6 +250,7 @@ class Minimizer:
         mods = 0
         self._const_energy = {}
         disk_params = {}
+        rim_params = {}
         vol_mode = gp.get("volume_constraint_mode", "lagrange")
         area_params = None
         for name in self.energy_module_names:
@@ -285,6 +292,11 @@ class Minimizer:
                 if prm is not None:  # tilt_disk_target_in.py:175-191
                     mods |= _ENERGY_BITS[name]
                     disk_params[name[17:]] = prm
+            elif name in _RIM_MODULES:
+                prm = _lc.rim_source_params(self.mesh, self.param_resolver, gp, name[16:])
+                if prm is not None:  # tilt_rim_source_in.py:386-404: no group, no rim edge, every gamma 0
+                    mods |= _ENERGY_BITS[name]
+                    rim_params[name[16:]] = prm
             else:
                 mods |= _ENERGY_BITS[name]
         target = 0.0
@@ -345,6 +357,11 @@ class Minimizer:
                 if mir._leaflet_keys.get("bend_disk_" + lf) != key:
                     dm.set_leaflet_disk_target(lf, **prm)
                     mir._leaflet_keys["bend_disk_" + lf] = key
+            for lf, prm in rim_params.items():  # keyed on topology, rim edges, gamma and frame
+                key = (mir._topo_key, _lc.rim_source_key(prm))
+                if mir._leaflet_keys.get("bend_rim_" + lf) != key:
+                    dm.set_leaflet_rim_source(lf, **prm)
+                    mir._leaflet_keys["bend_rim_" + lf] = key
             if mods & _LEAFLET_BT_BITS:
                 _lc.check_bt_supported(gp)
                 if mods & (L.MS_MOD_BENDING | L.MS_MOD_BENDING_TILT):
@@ -468,12 +485,23 @@ class Minimizer:
                 out["edge_length_penalty"] = pen_e
             if "surface" in out:
                 out["surface"] = float(e[0]) - line_e - pen_e if dm.modules & L.MS_MOD_SURFACE else 0.0
+        # a rim source adds its sums into the leaflet's tilt-magnitude slot: it reports its own energy, and whoever reports
+        # energies[3] or that slot reports it without the rim source's part
+        rim_e = {lf: (dm.leaflet_rim_source_energy(lf) if dm.modules & _ENERGY_BITS["tilt_rim_source_" + lf] else 0.0)
+                 for lf in ("in", "out")}
+        for lf in ("in", "out"):
+            if "tilt_rim_source_" + lf in out:
+                out["tilt_rim_source_" + lf] = rim_e[lf]
         for table in (_TILT_SCALAR, _BEND_SCALAR):
             sharing = [n for n in out if n in table]
             if len(sharing) > 1:  # they share one entry of the energy vector: split via the scalars
                 sc = dm.fetch_scalars()
                 for n in sharing:
                     out[n] = float(sc[table[n]]) if dm.modules & _ENERGY_BITS[n] else 0.0
+                    if n in ("tilt_in", "tilt_out") and dm.modules & _ENERGY_BITS[n]:
+                        out[n] -= rim_e[n[5:]]
+            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"]):
+                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"]
         return out
 
     # -- constraint enforcement (minimizer.py:1103-1188) ---------------------------
