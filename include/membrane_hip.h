@@ -87,6 +87,13 @@ extern "C" {
  * slot (MS_S_ETILT_IN / MS_S_ETILT_OUT, energies[3]) behind the pass that writes it: no reduction slot of its own. */
 #define MS_MOD_TILT_RIM_SOURCE_IN 524288u
 #define MS_MOD_TILT_RIM_SOURCE_OUT 1048576u
+/* inter-leaflet coupling E = 1/2 k_c int |t_out + s t_in|^2 dA, s = -1 ("difference") or +1 ("sum")
+ * (modules/energy/tilt_coupling.py:114-262): per facet with |n| >= 1e-12, coeff = 0.5 k_c ((q0 + q1 + q2) / 3) with
+ * q_v = |t_out,v + s t_in,v|^2, E = sum coeff A_f; shape gradient coeff dA_f/dv_k; tilt gradients k_c d_v A_v (out) and
+ * k_c s d_v A_v (in).  Modulus and sign come from ms_set_tilt_coupling.  Its sums are added into the outer leaflet's
+ * tilt-magnitude slot (MS_S_ETILT_OUT, energies[3]) behind the passes that write it: no reduction slot of its own.
+ * Reads both leaflet fields; single context only; not together with a single-field tilt module. */
+#define MS_MOD_TILT_COUPLING 2097152u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -399,6 +406,16 @@ int ms_leaflet_rim_source_stats(ms_ctx *ctx, int leaflet, double stats[3]);
 int ms_rim_source_tables_host(int nv, const int32_t *iperm, int n_edges, const int32_t *tail, const int32_t *head,
                               const double *gamma, int32_t counts[2], int32_t *vrow, int32_t *off, int32_t *other,
                               double *csr_gamma);
+/* tilt_coupling: modulus k_c (tilt_coupling_modulus, finite) and sign -1 ("difference"), +1 ("sum") or 0 (off; the
+ * module bit is then refused by the passes).  Any other sign is refused.  Takes effect when MS_MOD_TILT_COUPLING is in
+ * ms_params.modules.  Single context only. */
+int ms_set_tilt_coupling(ms_ctx *ctx, double modulus, int sign);
+/* the module's own energy as its LAST LAUNCH summed it, whatever that launch evaluated: an evaluation at x, a line-search
+ * trial, or -- after ms_relax_leaflet_tilts -- possibly a rejected trial of the relaxation, not the stored fields.  Run
+ * ms_energy first to read it for the stored state (its sums are also part of energies[3]). */
+int ms_get_tilt_coupling_energy(ms_ctx *ctx, double *energy);
+/* launches so far: {k_couple<0>, k_couple<1>, k_couple_vec} */
+int ms_tilt_coupling_stats(ms_ctx *ctx, double stats[3]);
 /* per-vertex (kappa, c0) of bending_tilt_in / bending_tilt_out (modules/energy/bt_params.py:225-318:
  * bending_modulus_in|out else bending_modulus; spontaneous_curvature_in|out else the global one) */
 int ms_set_leaflet_bending(ms_ctx *ctx, int leaflet, const double *kappa /* nv */, const double *c0 /* nv */);

@@ -34,6 +34,7 @@ MS_MOD_AREA_PENALTY = 65536
 MS_MOD_LINE_TENSION = 131072
 MS_MOD_EDGE_LENGTH_PENALTY = 262144
 MS_MOD_TILT_RIM_SOURCE_IN, MS_MOD_TILT_RIM_SOURCE_OUT = 524288, 1048576
+MS_MOD_TILT_COUPLING = 2097152
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
@@ -173,6 +174,9 @@ SIGNATURES = {
     "ms_leaflet_rim_source_stats": (ctypes.c_int, [_P, ctypes.c_int, _D]),
     "ms_rim_source_tables_host": (ctypes.c_int, [ctypes.c_int, _I32, ctypes.c_int, _I32, _I32, _D, _I32, _I32, _I32,
                                                  _I32, _D]),
+    "ms_set_tilt_coupling": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int]),
+    "ms_get_tilt_coupling_energy": (ctypes.c_int, [_P, _D]),
+    "ms_tilt_coupling_stats": (ctypes.c_int, [_P, _D]),
     "ms_leaflet_tilt_energy_and_gradient": (ctypes.c_int, [_P, _D, _D, _D]),
     "ms_leaflet_tilt_energy_and_gradient_ex": (ctypes.c_int, [_P, ctypes.c_int, _D, _D, _D]),
     "ms_relax_leaflet_tilts": (ctypes.c_int, [_P, ctypes.POINTER(ms_tilt_relax_params),
@@ -261,6 +265,7 @@ _lib = None
 def build(force: bool = False, fp_contract: str | None = None) -> str:
     """Compile libmembrane_hip.so for gfx950 with hipcc (csrc/Makefile)."""
     srcs = [os.path.join(_CSRC, f) for f in ("ms_kernels.hip", "ms_pins.hip", "ms_line.hip", "ms_edgepen.hip",
+                                             "ms_rim.hip", "ms_couple.hip", "ms_api_couple.inc",
                                              "ms_api.cpp", "ms_tiles.cpp", "ms_internal.h", "Makefile")]
     srcs.append(os.path.join(_PKG, "..", "include", "membrane_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(

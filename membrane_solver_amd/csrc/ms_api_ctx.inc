@@ -125,11 +125,23 @@ struct ms_ctx {
     bool rs_coef_valid = false;    // rs.coef holds c of the frozen surface of a running relaxation
     double* rs_center = nullptr;   // (inside d_rim)
     long rs_launches[3] = {0, 0, 0};  // k_rim_frame, k_rim_coef, k_rim_apply
+    // tilt_coupling reads BOTH leaflet fields (mod_cpl on each); its energy rides in the outer leaflet's tilt-magnitude
+    // slot (mod_cpl_slot on that field only)
+    uint32_t mod_cpl = 0, mod_cpl_slot = 0;
     // every module bit that reads this leaflet field
-    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs; }
+    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl; }
+    // every module bit whose sums land in this field's tilt-magnitude slot (s_etilt)
+    uint32_t etilt_mods() const { return mod_tilt | mod_rs | mod_cpl_slot; }
     bool any_free = true;     // some row of this field is not clamped (kept current by the flag setters)
     double* va = nullptr;      // relaxation: barycentric vertex areas of the frozen positions
   } tf[3];
+  // tilt_coupling (ms_set_tilt_coupling): modulus, sign (-1 difference / +1 sum / 0 off); d_cpl holds the
+  // per-workgroup sums of the last launch (the module's own energy is their sum)
+  double cpl_k = 0.0;
+  int cpl_sign = 0;
+  void* d_cpl = nullptr;
+  long cpl_launches[3] = {0, 0, 0};  // k_couple<0>, k_couple<1>, k_couple_vec
+  bool cpl_force_tile = false;       // MS_COUPLE_VEC=0: the frozen form through the tile kernel as well (A/B)
   CarryState carry;
   bool precond = false;      // ms_stepper_params.precondition of the step in progress (CG only)
   // speculative line-search ladder (ms_step): when the last accepted step needed n > 1 Armijo trials, the next

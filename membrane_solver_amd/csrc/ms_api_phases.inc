@@ -15,6 +15,11 @@ int edgepen_energy_run(ms_ctx* c, bool use_dir, double alpha);  // (ms_api_edgep
 int edgepen_grad_run(ms_ctx* c, double* g, bool volrow);
 // tilt_rim_source_in/out: c . t of the rim rows at x (+ alpha d) into the field's tilt-magnitude partials (ms_api_rim.inc)
 int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const double* tilts, bool gradient);
+// tilt_coupling: 1/2 k_c |t_out + s t_in|^2 of x (+ alpha d) into the outer leaflet's tilt-magnitude partials, behind the
+// rim source's pass where both run (ms_api_couple.inc).  trial_tilts: the fields' `trial` rows; cell: CPL_CELL_*
+enum { CPL_CELL_AUTO = -1, CPL_CELL_LEAVE = 0, CPL_CELL_ADD = 1 };
+int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gradient_into_g, bool tilt_gradients,
+                bool trial_tilts, int cell = CPL_CELL_AUTO, double* g_out = nullptr);
 inline int exec_flush(ms_ctx* c) {
   if (!c->exec_on) return MS_OK;
   const hipError_t e = c->exec.flush();
@@ -155,13 +160,13 @@ constexpr uint32_t MS_LEAFLET_DT = MS_MOD_TILT_DISK_TARGET_IN | MS_MOD_TILT_DISK
 // the rim sources: no slot of their own (MS_NSCAL is full) -- their sums ride in the leaflet's tilt-magnitude slot -- and no
 // shape gradient, so they are not in MS_TILT_SHAPE_MODS
 constexpr uint32_t MS_LEAFLET_RS = MS_MOD_TILT_RIM_SOURCE_IN | MS_MOD_TILT_RIM_SOURCE_OUT;
-constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS;
+constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING;
 constexpr uint32_t MS_ANY_TILT_MODS = MS_TILT_MODS | MS_LEAFLET_MODS;
 // the edge modules: energy added into the MS_S_ESURF partials behind the energy pass, gradient into G behind K_C; they
 // share one lane of the step (one trial per launch, every Armijo decision the host's, the separate direction pass)
 constexpr uint32_t MS_EDGE_MODS = MS_MOD_LINE_TENSION | MS_MOD_EDGE_LENGTH_PENALTY;
 // modules whose shape gradient is added into g by a pass after K_C (so the direction cannot be fused)
-constexpr uint32_t MS_TILT_SHAPE_MODS = MS_MOD_TILT | MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT;
+constexpr uint32_t MS_TILT_SHAPE_MODS = MS_MOD_TILT | MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_MOD_TILT_COUPLING;
 using TiltField = ms_ctx::TiltField;
 using RoundPlan = ms_ctx::RoundPlanT;
 
@@ -767,7 +772,8 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   }
   for (int l = 1; l <= 2 && (modules & MS_LEAFLET_MODS); ++l) {  // leaflet fields, same protocol
     TiltField& f = c->tf[l];
-    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs))) continue;
+    // (the coupling alone is reason enough: its trial energy is taken with BOTH leaflets projected onto the trial surface)
+    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl))) continue;
     int rc = MS_OK;
     const double* tilts = f.tilts;
     if (use_dir) {
@@ -796,6 +802,9 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     if (!(modules & f.mod_rs)) continue;
     if (int rc_r = rim_pass(c, f, use_dir, alpha, use_dir ? f.trial : f.tilts, false)) return rc_r;
   }
+  // tilt_coupling: behind the rim source of the outer leaflet (the order of the adds into a cell is fixed)
+  if (modules & MS_MOD_TILT_COUPLING)
+    if (int rc_c = couple_pass(c, modules, use_dir, alpha, false, false, /*trial_tilts=*/use_dir)) return rc_c;
   if (reduce_now) {
     constexpr uint32_t core = (1u << MS_S_ESURF) | (1u << MS_S_VOL) | (1u << MS_S_EBEND) | (1u << MS_S_MINEDGE2) |
                               (1u << MS_S_GUARD);
@@ -937,6 +946,14 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
       if (rc) return rc;
       added_after = true;
     }
+  }
+  // tilt_coupling: its shape gradient behind the loop's; its energy goes into the outer leaflet's cells once more when
+  // k_tilt<1> above has rewritten them (behind the rim source's re-add), and nowhere when nobody has
+  if ((modules & MS_MOD_TILT_COUPLING) && g_out) {
+    int rc = couple_pass(c, modules, false, 0.0, true, false, false,
+                         (modules & c->tf[2].mod_tilt) ? CPL_CELL_ADD : CPL_CELL_LEAVE, g_out);
+    if (rc) return rc;
+    added_after = true;
   }
   // the gradient kernel's <g, gC> partials predate those additions: take them again of the complete gradient
   if (added_after && g_out && (modules & MS_CON_VOLUME))
@@ -1125,7 +1142,7 @@ void energies_from_mailbox(const ms_ctx* c, double e[4]) {
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e[3] += c->h_scal[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
-    if (c->params.modules & (f.mod_tilt | f.mod_rs)) e[3] += c->h_scal[f.s_etilt];  // (the rim source rides in this slot)
+    if (c->params.modules & f.etilt_mods()) e[3] += c->h_scal[f.s_etilt];  // (the rim source and the coupling ride in this slot)
     if (c->params.modules & f.mod_smooth) e[3] += c->h_scal[f.s_ets];
     if (c->params.modules & f.mod_bt) e[1] += c->h_scal[f.s_ebt];
     if (c->params.modules & f.mod_dt) e[3] += c->h_scal[f.s_edt];

@@ -78,6 +78,12 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
       mask |= 1u << f.s_etilt;
     }
   }
+  if (mods & MS_MOD_TILT_COUPLING) {
+    // behind both leaflets' passes: it adds into both tilt gradients and into the outer leaflet's magnitude partials
+    rc = couple_pass(c, mods, false, 0.0, false, gradient, trial);
+    if (rc) return rc;
+    mask |= 1u << c->tf[2].s_etilt;
+  }
   return mask ? reduce_slots(c, mask) : MS_OK;
 }
 double tilt_energy_from(const ms_ctx* c, const double* hs) {
@@ -87,7 +93,7 @@ double tilt_energy_from(const ms_ctx* c, const double* hs) {
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e += hs[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
-    if (c->params.modules & (f.mod_tilt | f.mod_rs)) e += hs[f.s_etilt];  // (tilt magnitude + rim source)
+    if (c->params.modules & f.etilt_mods()) e += hs[f.s_etilt];  // (tilt magnitude + rim source + coupling)
     if (c->params.modules & f.mod_smooth) e += hs[f.s_ets];
     if (c->params.modules & f.mod_bt) e += hs[f.s_ebt];
     if (c->params.modules & f.mod_dt) e += hs[f.s_edt];
@@ -109,7 +115,8 @@ bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs
     const bool tilt_on = single ? (mods & MS_MOD_TILT) != 0 : (mods & f.mod_tilt) != 0;
     const bool bt_on = single ? (mods & MS_MOD_BENDING_TILT) != 0 : (mods & f.mod_bt) != 0;
     const bool ts_on = single ? (mods & MS_MOD_TILT_SMOOTH) != 0 : (mods & f.mod_smooth) != 0;
-    if (!single && (mods & (f.mod_dt | f.mod_rs))) return false;  // (the disk target and the rim source keep their own passes)
+    // (the disk target, the rim source and the coupling keep their own passes)
+    if (!single && (mods & (f.mod_dt | f.mod_rs | f.mod_cpl))) return false;
     o.tilts = f.tilts;
     o.src = along_dir ? f.dir : f.grad;
     o.bt_vert = nullptr;
@@ -324,7 +331,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
       q.has_ts = (mods & f.mod_smooth) ? 1 : 0;
       q.has_dt = (mods & f.mod_dt) ? 1 : 0;
       q.fixed_bit = f.fixed_bit;
-      ok = ok && !(mods & f.mod_rs) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
+      ok = ok && !(mods & (f.mod_rs | f.mod_cpl)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
            (!q.has_dt || (f.dt_target && f.disk && f.dt_target_valid));
     }
     const size_t need = relax_fused_lds_bytes(c->cap, t.max_ent, t.max_tile_facets);
@@ -443,7 +450,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
     if (mods & MS_MOD_TILT_SMOOTH) head.e_slot[n++] = MS_S_ETS;
     for (int l = 1; l <= 2; ++l) {
       const TiltField& f = c->tf[l];
-      if (mods & (f.mod_tilt | f.mod_rs)) head.e_slot[n++] = f.s_etilt;
+      if (mods & f.etilt_mods()) head.e_slot[n++] = f.s_etilt;
       if (mods & f.mod_smooth) head.e_slot[n++] = f.s_ets;
       if (mods & f.mod_bt) head.e_slot[n++] = f.s_ebt;
       if (mods & f.mod_dt) head.e_slot[n++] = f.s_edt;
@@ -746,7 +753,8 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     if (r || used) return r;
     return search(along_dir, sign, E0, E_acc, accepted);
   };
-  if (c->exec_on && c->exec_relax && !(mods & MS_LEAFLET_RS)) {  // (the rim source's kernels are not recorded)
+  // (the rim source's and the coupling's kernels are not recorded)
+  if (c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_COUPLING))) {
     // one-tile context: the whole solve below as ONE launch (ms_internal.h: ExecRelaxHead)
     bool used = false;
     rc = relax_program(c, rp, fl, nf, norm_mask, &iters, &evals, &used);

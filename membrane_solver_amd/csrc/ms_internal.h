@@ -456,6 +456,29 @@ struct RimArgs {
 hipError_t launch_rim_frame(const RimArgs& a, double* center_out, hipStream_t s);
 hipError_t launch_rim_coef(const RimArgs& a, hipStream_t s);
 hipError_t launch_rim_apply(const RimArgs& a, hipStream_t s);
+// tilt_coupling (ms_couple.hip): E = 1/2 k_c int |t_out + s t_in|^2 dA, k_tilt's lumped arithmetic on the field
+// d = t_out + s t_in.  k_couple<0/1> per tile on x (+ alpha d); k_couple_vec per vertex on the frozen surface's areas.
+struct CoupleArgs {
+  DeviceMesh m;
+  int tile0, tile1;
+  const double* x;
+  const double* d;        // trial direction or nullptr, alpha: exactly what TiltArgs hands k_tilt
+  double alpha;
+  const double* t_in;     // (nvp,3) both leaflets' tilts
+  const double* t_out;
+  double k_c, sign;       // tilt_coupling_modulus; -1.0 "difference" / +1.0 "sum"
+  double* g;              // k_couple<1>: shape gradient ADDED, or nullptr
+  double* tg_in;          // k_c s d_v A_v ADDED, or nullptr
+  double* tg_out;         // k_c d_v A_v ADDED, or nullptr
+  const double* va;       // k_couple_vec: barycentric vertex areas of the frozen positions (nvp)
+  double* partials;       // the tile's cell [slot * n_tiles + tile] ...
+  int slot, cell_mode;    // ... 0 left alone, 1 added to (a pass before this one defined it), 2 defined
+  double* wg_sums;        // [tile1 - tile0] per-workgroup sums: the module's own energy is their sum in index order,
+                          // taken on the host when asked for (ms_get_tilt_coupling_energy)
+};
+size_t couple_lds_bytes(int T, int cap, int max_ent, int mode);
+hipError_t launch_couple(const CoupleArgs& a, int mode, int cap, int max_ent, hipStream_t s);
+hipError_t launch_couple_vec(const CoupleArgs& a, int with_grad, hipStream_t s);
 struct RowDotArgs {
   int tile0, nv, T;
   const double* g;

@@ -353,6 +353,23 @@ class DeviceMesh:
         self._chk(L.lib().ms_leaflet_rim_source_stats(self._h, lf, _pd(v)), "ms_leaflet_rim_source_stats")
         return {"frame_launches": int(v[0]), "coef_launches": int(v[1]), "apply_launches": int(v[2])}
 
+    def set_tilt_coupling(self, modulus: float, sign: int):
+        """tilt_coupling: modulus k_c and sign -1 ("difference"), +1 ("sum") or 0 (off) (ms_set_tilt_coupling)."""
+        self._chk(L.lib().ms_set_tilt_coupling(self._h, float(modulus), int(sign)), "ms_set_tilt_coupling")
+
+    def tilt_coupling_energy(self) -> float:
+        """The coupling's own energy as its last launch summed it, whatever that launch evaluated
+        (ms_get_tilt_coupling_energy); call energy() first to read it for the stored state."""
+        e = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_get_tilt_coupling_energy(self._h, ctypes.byref(e)), "ms_get_tilt_coupling_energy")
+        return float(e.value)
+
+    def tilt_coupling_stats(self):
+        """Launch counts of the coupling's kernels (ms_tilt_coupling_stats)."""
+        v = np.zeros(3)
+        self._chk(L.lib().ms_tilt_coupling_stats(self._h, _pd(v)), "ms_tilt_coupling_stats")
+        return {"energy_launches": int(v[0]), "gradient_launches": int(v[1]), "vec_launches": int(v[2])}
+
     def get_leaflet_tilts(self, leaflet: str) -> np.ndarray:
         out = np.empty((self.nv, 3), dtype=np.float64)
         lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]

@@ -430,6 +430,69 @@ def rim_source_host_tables(nv: int, iperm, tail, head, gamma):
             "csr_gamma": og[:2 * ne].copy()}
 
 
+_COUPLING_MODES = {"difference": -1, "diff": -1, "minus": -1, "sub": -1, "sum": 1, "add": 1, "plus": 1}
+
+
+def coupling_params(param_resolver, global_params):
+    """(k_c, sign) of tilt_coupling (modules/energy/tilt_coupling.py:24-40): ``tilt_coupling_modulus`` and
+    ``tilt_coupling_mode`` with the misspelt ``tilt_couping_mode`` as fallback; sign -1 for difference / diff / minus /
+    sub, +1 for sum / add / plus.  None when the module contributes nothing: unknown or absent mode, or k_c == 0."""
+    mode = _get(param_resolver, global_params, "tilt_coupling_mode")
+    if mode is None:
+        mode = _get(param_resolver, global_params, "tilt_couping_mode")
+    if mode is None:
+        return None
+    sign = _COUPLING_MODES.get(str(mode).strip().lower())
+    k_c = float(_get(param_resolver, global_params, "tilt_coupling_modulus") or 0.0)
+    if sign is None or k_c == 0.0:
+        return None
+    return k_c, sign
+
+
+def evaluate_coupling(mesh, global_params, param_resolver, *, positions, tilts_in, tilts_out, grad_arr,
+                      tilt_in_grad_arr, tilt_out_grad_arr) -> float:
+    """tilt_coupling on caller arrays (H2D/D2H per call: the parity seam, not the hot loop): energy; shape gradient
+    ADDED into ``grad_arr``, tilt gradients ADDED into ``tilt_in_grad_arr`` / ``tilt_out_grad_arr`` (each optional)."""
+    prm = coupling_params(param_resolver, global_params)
+    if prm is None:
+        return 0.0
+    tri, _f = mesh.triangle_row_cache()
+    if tri is None or len(tri) == 0:
+        return 0.0
+    nv = len(mesh.vertex_ids)
+    fields = {}
+    for lf, t in (("in", tilts_in), ("out", tilts_out)):
+        if t is None:
+            t = mesh.tilts_in_view() if lf == "in" else mesh.tilts_out_view()
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        if t.shape != (nv, 3):
+            raise ValueError(f"tilts_{lf} must have shape (N_vertices, 3)")
+        fields[lf] = t
+    for name, arr in (("tilt_in_grad_arr", tilt_in_grad_arr), ("tilt_out_grad_arr", tilt_out_grad_arr)):
+        if arr is not None and np.shape(arr) != (nv, 3):
+            raise ValueError(f"{name} must have shape (N_vertices, 3)")
+    mir = mirror_for(mesh)
+    dm = mir.sync(positions=None if positions is mesh.positions_view() else positions)
+    for lf in ("in", "out"):
+        dm.set_leaflet_tilts(lf, fields[lf], tilt_modulus=0.0, smoothness=0.0)
+    mir._leaflet_keys = {}  # foreign arrays were uploaded
+    dm.set_tilt_coupling(*prm)
+    dm.set_params(modules=L.MS_MOD_TILT_COUPLING)
+    if grad_arr is not None:
+        e, g = dm.energy_and_gradient(want_grad=True, raw=True)
+        grad_arr += g
+        E = float(e[3])
+    else:
+        E = float(dm.energy()[3])
+    if tilt_in_grad_arr is not None or tilt_out_grad_arr is not None:
+        _e, gi, go = dm.leaflet_tilt_energy_and_gradient(want_gradient=True)
+        if tilt_in_grad_arr is not None:
+            tilt_in_grad_arr += gi
+        if tilt_out_grad_arr is not None:
+            tilt_out_grad_arr += go
+    return E
+
+
 def check_bt_supported(global_params) -> None:
     mode = str(global_params.get("bending_gradient_mode", "analytic") or "analytic").strip().lower()
     if mode != "analytic":

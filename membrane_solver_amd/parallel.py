@@ -340,6 +340,9 @@ class HipShardBackend:
         if modules & (L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT):
             raise L.MembraneHipError("the tilt_rim_source_in/out modules are not sharded (single GPU only; "
                                      "ms_set_params refuses them on a sharded context as well)")
+        if modules & L.MS_MOD_TILT_COUPLING:
+            raise L.MembraneHipError("the tilt_coupling module is not sharded (single GPU only; ms_set_params refuses "
+                                     "it on a sharded context as well)")
         tilt_bits = modules & ~(L.MS_MOD_SURFACE | L.MS_MOD_BENDING | L.MS_MOD_VOLUME_PENALTY | L.MS_CON_VOLUME
                                 | getattr(L, "MS_TRACK_VOLUME", 0))
         if tilt_bits:

@@ -69,6 +69,7 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "body_area_penalty": L.MS_MOD_AREA_PENALTY, "line_tension": L.MS_MOD_LINE_TENSION,
                 "edge_length_penalty": L.MS_MOD_EDGE_LENGTH_PENALTY,
                 "tilt_rim_source_in": L.MS_MOD_TILT_RIM_SOURCE_IN, "tilt_rim_source_out": L.MS_MOD_TILT_RIM_SOURCE_OUT,
+                "tilt_coupling": L.MS_MOD_TILT_COUPLING,
                 # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
                 # accepted in its switched-off state (strength 0, as in the caveolin decks)
                 "gaussian_curvature": 0, "rim_slope_match_out": 0}
@@ -77,14 +78,16 @@ _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_til
                 "bending_tilt_in": 1, "bending_tilt_out": 1, "tilt_disk_target_in": 3, "tilt_disk_target_out": 3,
                 "body_area_penalty": 2, "line_tension": 0, "edge_length_penalty": 0, "gaussian_curvature": None, "rim_slope_match_out": None,
                 # (their sums ride in the leaflet's tilt-magnitude slot of energies[3]; each reports its own energy)
-                "tilt_rim_source_in": None, "tilt_rim_source_out": None}
+                "tilt_rim_source_in": None, "tilt_rim_source_out": None,
+                # (its sums ride in the outer leaflet's tilt-magnitude slot; it reports its own energy)
+                "tilt_coupling": None}
 _RIM_MODULES = ("tilt_rim_source_in", "tilt_rim_source_out")
 _EDGE_MODULES = ("line_tension", "edge_length_penalty")  # they share the lane behind the energy and the gradient pass
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
 _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
                  | _LEAFLET_BT_BITS | L.MS_MOD_TILT_DISK_TARGET_IN | L.MS_MOD_TILT_DISK_TARGET_OUT
-                 | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT)
+                 | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING)
 _TILT_BITS = _SINGLE_TILT_BITS | _LEAFLET_BITS
 # scalar slot of every module that shares energies[3]
 _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": L.MS_S_ETILT_IN,
@@ -191,7 +194,8 @@ class Minimizer:
                     f"energy module {name!r}{where} is outside the HIP hot path (surface, bending, volume, tilt, "
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
                     "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
-                    "body_area_penalty, line_tension, edge_length_penalty, tilt_rim_source_in, tilt_rim_source_out)")
+                    "body_area_penalty, line_tension, edge_length_penalty, tilt_rim_source_in, tilt_rim_source_out, "
+                    "tilt_coupling)")
         if "body_area_penalty" in self.energy_module_names and any(
                 _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
             raise L.MembraneHipError("body_area_penalty together with tilt modules is outside the HIP hot path")
@@ -251,6 +255,7 @@ class Minimizer:
         self._const_energy = {}
         disk_params = {}
         rim_params = {}
+        coupling = None
         vol_mode = gp.get("volume_constraint_mode", "lagrange")
         area_params = None
         for name in self.energy_module_names:
@@ -297,6 +302,10 @@ class Minimizer:
                 if prm is not None:  # tilt_rim_source_in.py:386-404: no group, no rim edge, every gamma 0
                     mods |= _ENERGY_BITS[name]
                     rim_params[name[16:]] = prm
+            elif name == "tilt_coupling":
+                coupling = _lc.coupling_params(self.param_resolver, gp)
+                if coupling is not None:  # tilt_coupling.py:129-132: unknown or absent mode, or k_c == 0
+                    mods |= _ENERGY_BITS[name]
             else:
                 mods |= _ENERGY_BITS[name]
         target = 0.0
@@ -362,6 +371,11 @@ class Minimizer:
                 if mir._leaflet_keys.get("bend_rim_" + lf) != key:
                     dm.set_leaflet_rim_source(lf, **prm)
                     mir._leaflet_keys["bend_rim_" + lf] = key
+            if coupling is not None:  # keyed on modulus and sign ("bend_": not a tilt upload, mark_device_leaflets_current)
+                key = (id(dm), coupling)
+                if mir._leaflet_keys.get("bend_coupling") != key:
+                    dm.set_tilt_coupling(*coupling)
+                    mir._leaflet_keys["bend_coupling"] = key
             if mods & _LEAFLET_BT_BITS:
                 _lc.check_bt_supported(gp)
                 if mods & (L.MS_MOD_BENDING | L.MS_MOD_BENDING_TILT):
@@ -492,6 +506,10 @@ class Minimizer:
         for lf in ("in", "out"):
             if "tilt_rim_source_" + lf in out:
                 out["tilt_rim_source_" + lf] = rim_e[lf]
+        # the coupling rides in the outer leaflet's slot in the same way
+        cpl_e = dm.tilt_coupling_energy() if dm.modules & L.MS_MOD_TILT_COUPLING else 0.0
+        if "tilt_coupling" in out:
+            out["tilt_coupling"] = cpl_e
         for table in (_TILT_SCALAR, _BEND_SCALAR):
             sharing = [n for n in out if n in table]
             if len(sharing) > 1:  # they share one entry of the energy vector: split via the scalars
@@ -499,9 +517,9 @@ class Minimizer:
                 for n in sharing:
                     out[n] = float(sc[table[n]]) if dm.modules & _ENERGY_BITS[n] else 0.0
                     if n in ("tilt_in", "tilt_out") and dm.modules & _ENERGY_BITS[n]:
-                        out[n] -= rim_e[n[5:]]
-            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"]):
-                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"]
+                        out[n] -= rim_e[n[5:]] + (cpl_e if n == "tilt_out" else 0.0)
+            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e):
+                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e
         return out
 
     # -- constraint enforcement (minimizer.py:1103-1188) ---------------------------
