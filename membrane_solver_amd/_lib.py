@@ -264,9 +264,8 @@ _lib = None
 
 def build(force: bool = False, fp_contract: str | None = None) -> str:
     """Compile libmembrane_hip.so for gfx950 with hipcc (csrc/Makefile)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("ms_kernels.hip", "ms_pins.hip", "ms_line.hip", "ms_edgepen.hip",
-                                             "ms_rim.hip", "ms_couple.hip", "ms_api_couple.inc",
-                                             "ms_api.cpp", "ms_tiles.cpp", "ms_internal.h", "Makefile")]
+    # every source of the library: what csrc/ holds outside its build directory, and the public header
+    srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f != "build"]
     srcs.append(os.path.join(_PKG, "..", "include", "membrane_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

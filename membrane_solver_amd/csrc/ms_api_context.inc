@@ -257,13 +257,13 @@ void ms_destroy(ms_ctx* c) {
                   c->tf[1].kappa, c->tf[1].c0, c->tf[1].bt_vert, c->tf[2].kappa, c->tf[2].c0, c->tf[2].bt_vert,
                   c->tf[1].disk, c->tf[1].diff, c->tf[2].disk, c->tf[2].diff, c->tf[0].va, c->tf[1].va, c->tf[2].va,
                   c->state, c->d_partials, c->d_scal, c->d_stage, c->d_bnd_rows, c->d_bnd_off,
-                  c->d_halo_rows, c->d_scal_all, c->d_pins, c->d_line, c->d_edgepen, c->tf[1].d_rim, c->tf[2].d_rim,
+                  c->d_halo_rows, c->d_scal_all, c->d_pins, c->edge[0].d_blob, c->edge[1].d_blob, c->tf[1].d_rim, c->tf[2].d_rim,
                   c->d_cpl};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
-  for (auto* prof : {c->line_prof, c->edgepen_prof})
+  for (auto& lane : c->edge)
     for (int w = 0; w < 2; ++w)
-      for (auto& ev : prof[w]) {
+      for (auto& ev : lane.prof[w]) {
         (void)hipEventDestroy(ev.first);
         (void)hipEventDestroy(ev.second);
       }
@@ -407,14 +407,11 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
     return fail(c, MS_ERR_STATE, "the body_area_penalty module is not sharded (single GPU only)");
   if ((p->modules & MS_MOD_AREA_PENALTY) && (p->modules & MS_ANY_TILT_MODS))
     return fail(c, MS_ERR_STATE, "body_area_penalty together with a tilt-family module is outside the device path");
-  if ((p->modules & MS_MOD_LINE_TENSION) && c->shard_count != 1)
-    return fail(c, MS_ERR_STATE, "the line_tension module is not sharded (single GPU only)");
-  if ((p->modules & MS_MOD_LINE_TENSION) && (p->modules & MS_ANY_TILT_MODS))
-    return fail(c, MS_ERR_STATE, "line_tension together with a tilt-family module is outside the device path");
-  if ((p->modules & MS_MOD_EDGE_LENGTH_PENALTY) && c->shard_count != 1)
-    return fail(c, MS_ERR_STATE, "the edge_length_penalty module is not sharded (single GPU only)");
-  if ((p->modules & MS_MOD_EDGE_LENGTH_PENALTY) && (p->modules & MS_ANY_TILT_MODS))
-    return fail(c, MS_ERR_STATE, "edge_length_penalty together with a tilt-family module is outside the device path");
+  for (const EdgeTerm& t : kEdgeTerms) {
+    if ((p->modules & t.bit) && c->shard_count != 1) return fail(c, MS_ERR_STATE, edge_not_sharded(t));
+    if ((p->modules & t.bit) && (p->modules & MS_ANY_TILT_MODS))
+      return fail(c, MS_ERR_STATE, std::string(t.name) + " together with a tilt-family module is outside the device path");
+  }
   if ((p->modules & MS_LEAFLET_RS) && c->shard_count != 1)
     return fail(c, MS_ERR_STATE, "the tilt_rim_source_in/out modules are not sharded (single GPU only)");
   if ((p->modules & MS_MOD_TILT_COUPLING) && c->shard_count != 1)

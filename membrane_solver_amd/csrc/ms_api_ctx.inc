@@ -372,20 +372,17 @@ struct ms_ctx {
   PinGradArgs pin_grad{};
   int pin_lane = -1;
   long pin_enforce_launches = 0, pin_grad_launches = 0, pin_trials = 0;
-  // line_tension (ms_set_line_tension): one allocation holds every table, the per-workgroup sums and the module's energy
-  void* d_line = nullptr;
-  LineEnergyArgs line_en{};
-  LineGradArgs line_gr{};
-  bool line_set = false;
-  long line_launches[2] = {0, 0};  // k_line_energy, k_line_grad
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> line_prof[2];  // event brackets while profiling (ms_line_stats)
-  // edge_length_penalty (ms_set_edge_length_penalty): the same, for its two kernels
-  void* d_edgepen = nullptr;
-  EdgePenEnergyArgs edgepen_en{};
-  EdgePenGradArgs edgepen_gr{};
-  bool edgepen_set = false;
-  long edgepen_launches[2] = {0, 0};  // k_edgepen_energy, k_edgepen_grad
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> edgepen_prof[2];  // (ms_edge_penalty_stats)
+  // the edge lane (ms_api_edge.inc): edge[t] is the state of kEdgeTerms[t] -- line_tension, then edge_length_penalty.
+  // One allocation holds every table of a term, the per-workgroup sums and the module's energy
+  struct EdgeLane {
+    void* d_blob = nullptr;
+    EdgeEnergyArgs en{};
+    EdgeGradArgs gr{};
+    bool set = false;
+    long launches[2] = {0, 0};  // energy kernel, gradient kernel
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof[2];  // event brackets while profiling (ms_line_stats, ...)
+  };
+  EdgeLane edge[2];
   const StageCtl& stage() const { return stage_; }
  private:
   friend struct StageScope;

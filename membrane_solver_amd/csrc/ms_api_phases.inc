@@ -9,10 +9,20 @@ inline hipStream_t S(ms_ctx* c) {
   return c->stream;
 }
 int pin_grad_run(ms_ctx* c, bool volrow);  // (ms_api_pins.inc)
-int line_energy_run(ms_ctx* c, bool use_dir, double alpha);  // (ms_api_line.inc)
-int line_grad_run(ms_ctx* c, double* g, bool volrow);
-int edgepen_energy_run(ms_ctx* c, bool use_dir, double alpha);  // (ms_api_edgepen.inc)
-int edgepen_grad_run(ms_ctx* c, double* g, bool volrow);
+// the edge lane (ms_api_edge.inc): its terms in launch order, kEdgeTerms[t] going with c->edge[t]
+struct EdgeTableMsgs {
+  const char *row, *first, *second, *perm;
+};
+struct EdgeTerm {
+  uint32_t bit;        // MS_MOD_*
+  const char* name;    // the module's
+  const char* setter;  // as messages name it
+  bool second;         // the term's column is the tables' second one (el0 / ol0), not the first (eg / og)
+  EdgeTableMsgs msgs;
+};
+extern const EdgeTerm kEdgeTerms[2];
+int edge_energy_run(ms_ctx* c, int term, bool use_dir, double alpha);
+int edge_grad_run(ms_ctx* c, int term, double* g, bool volrow);
 // tilt_rim_source_in/out: c . t of the rim rows at x (+ alpha d) into the field's tilt-magnitude partials (ms_api_rim.inc)
 int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const double* tilts, bool gradient);
 // tilt_coupling: 1/2 k_c |t_out + s t_in|^2 of x (+ alpha d) into the outer leaflet's tilt-magnitude partials, behind the
@@ -640,10 +650,10 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   }
   if (bt && !c->d_bt_vert) return fail(c, MS_ERR_STATE, "bending_tilt: ms_set_params did not allocate its buffers");
   // the edge modules take the penalties' lane: one trial per launch, every Armijo decision the host's
-  if ((modules & MS_EDGE_MODS) && (st.pair_on > 1 || st.cur_gate != nullptr || lbt))
-    return fail(c, MS_ERR_STATE, (modules & MS_MOD_LINE_TENSION)
-                                     ? "line_tension: the energy pass was queued on the device-decided lane"
-                                     : "edge_length_penalty: the energy pass was queued on the device-decided lane");
+  if (st.pair_on > 1 || st.cur_gate != nullptr || lbt)
+    for (const EdgeTerm& t : kEdgeTerms)
+      if (modules & t.bit)
+        return fail(c, MS_ERR_STATE, std::string(t.name) + ": the energy pass was queued on the device-decided lane");
   a.partials = c->d_partials;
   a.bending_model = c->params.bending_model;
   a.modules = modules;
@@ -740,14 +750,13 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
       if (write_factors) c->factors_leaflet = l;
     }
   }
-  // line_tension: gamma |e| of the tagged edges added into the MS_S_ESURF partials the launch above has just written
-  // (k_energy stores that slot's partial for every tile of the range whatever the module mask -- 0.0 without
-  // MS_MOD_SURFACE -- so the cell is defined before the add); the fold below then carries surface + line energy
-  if (modules & MS_MOD_LINE_TENSION)
-    if (int rc_l = line_energy_run(c, use_dir, alpha)) return rc_l;
-  // edge_length_penalty: 0.5 k (|e| - L0)^2 into the same cells, behind k_line_energy: the order of the two adds is fixed
-  if (modules & MS_MOD_EDGE_LENGTH_PENALTY)
-    if (int rc_p = edgepen_energy_run(c, use_dir, alpha)) return rc_p;
+  // the edge terms: gamma |e| of the tagged edges, then 0.5 k (|e| - L0)^2 of the charged ones, added into the
+  // MS_S_ESURF partials the launch above has just written (k_energy stores that slot's partial for every tile of the
+  // range whatever the module mask -- 0.0 without MS_MOD_SURFACE -- so the cell is defined before the add); the fold
+  // below then carries surface + edge energy.  The order of the two adds into a cell is the table's
+  for (int t = 0; t < 2; ++t)
+    if (modules & kEdgeTerms[t].bit)
+      if (int rc_e = edge_energy_run(c, t, use_dir, alpha)) return rc_e;
   if (modules & MS_TILT_MODS) {
     int rc = MS_OK;
     const double* tilts = c->tf[0].tilts;
@@ -879,19 +888,17 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
     ProfScope ps(c, gradient_lean_instance(a) ? 9 : 1, a.gate, a.gate_want);
     HIPCHK(c, launch_gradient(a, c->cap, c->til.max_ent, c->stream));
   }
-  // line_tension: its rows added into the G that K_C has just written (before pin_grad_run projects the full gradient),
+  // the edge terms: their rows added into the G that K_C has just written (before pin_grad_run projects the full gradient),
   // and the <g,gC> partials corrected by the change.  The direction scalars of K_C's fused epilogue would predate the
   // addition: the callers take the separate direction pass (queue_energy_and_gradient)
   if ((modules_in & MS_EDGE_MODS) && g_out) {
-    if (dir_mode || a.gate != nullptr)
-      return fail(c, MS_ERR_STATE, (modules_in & MS_MOD_LINE_TENSION)
-                                       ? "line_tension cannot use the fused direction pass or a gated gradient pass"
-                                       : "edge_length_penalty cannot use the fused direction pass or a gated gradient pass");
-    if (modules_in & MS_MOD_LINE_TENSION)
-      if (int rc_l = line_grad_run(c, g_out, a.gC != nullptr)) return rc_l;
-    // (behind k_line_grad: both add into the same rows of G and the same <g,gC> cells, in this order)
-    if (modules_in & MS_MOD_EDGE_LENGTH_PENALTY)
-      if (int rc_p = edgepen_grad_run(c, g_out, a.gC != nullptr)) return rc_p;
+    // (both terms add into the same rows of G and the same <g,gC> cells, in the table's order)
+    for (int t = 0; t < 2; ++t) {
+      if (!(modules_in & kEdgeTerms[t].bit)) continue;
+      if (dir_mode || a.gate != nullptr)
+        return fail(c, MS_ERR_STATE, std::string(kEdgeTerms[t].name) + " cannot use the fused direction pass or a gated gradient pass");
+      if (int rc_e = edge_grad_run(c, t, g_out, a.gC != nullptr)) return rc_e;
+    }
   }
   for (int k = 0; k < n_lbt; ++k) {
     TiltField& f = c->tf[lbt_order[k]];

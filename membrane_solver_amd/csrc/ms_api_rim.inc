@@ -4,17 +4,17 @@
 // one-tile interpreter: the pass flushes it first.
 namespace {
 
-constexpr LineTableMsgs kRimMsgs = {"ms_set_leaflet_rim_source: edge row out of range", "",
+constexpr EdgeTableMsgs kRimMsgs = {"ms_set_leaflet_rim_source: edge row out of range", "",
                                     "ms_set_leaflet_rim_source: gamma must be finite",
                                     "ms_set_leaflet_rim_source: row permutation out of range"};
 
-// The row -> rim edge CSR from external rows: the builder of the edge modules (ms_api_line.inc) with a first column of
+// The row -> rim edge CSR from external rows: the builder of the edge lane (ms_api_edge.inc) with a first column of
 // ones -- it drops an edge whose first column is 0, and a rim edge with gamma == 0 still makes its ends rim rows (they
 // count in the follow mode's mean) -- and gamma as the second column, carried to the CSR.
 const char* build_rim_tables(int nv, const int32_t* iperm, int n_edges, const int32_t* tail, const int32_t* head,
-                             const double* gamma, LineTables& t) {
+                             const double* gamma, EdgeTables& t) {
   const std::vector<double> ones((size_t)std::max(n_edges, 0), 1.0);
-  return build_line_tables(nv, iperm, n_edges, tail, head, ones.data(), gamma, kRimMsgs, t);
+  return build_edge_tables(nv, iperm, n_edges, tail, head, ones.data(), gamma, kRimMsgs, t);
 }
 
 // c . t of the rim rows at x (+ alpha d) into the field's tilt-magnitude partials; gradient: c added into f.grad
@@ -95,7 +95,7 @@ int ms_set_leaflet_rim_source(ms_ctx* c, int leaflet, int n_edges, const int32_t
   }
   nn = std::sqrt(nn);
   if (!(nn >= 1e-15)) return fail(c, MS_ERR_INVALID, "ms_set_leaflet_rim_source: a non-zero plane normal is required");
-  LineTables tb;
+  EdgeTables tb;
   if (const char* why = build_rim_tables(c->til.nv, c->til.iperm.data(), n_edges, tail, head, gamma, tb))
     return fail(c, MS_ERR_INVALID, why);
   const int tiles = c->tile1 - c->tile0;
@@ -151,7 +151,7 @@ int ms_rim_source_tables_host(int nv, const int32_t* iperm, int n_edges, const i
                               double* csr_gamma) {
   if (nv < 0 || n_edges < 0 || !iperm || !tail || !head || !gamma || !counts || !vrow || !off || !other || !csr_gamma)
     return fail(nullptr, MS_ERR_INVALID, "ms_rim_source_tables_host: bad argument");
-  LineTables t;
+  EdgeTables t;
   if (const char* why = build_rim_tables(nv, iperm, n_edges, tail, head, gamma, t)) return fail(nullptr, MS_ERR_INVALID, why);
   counts[0] = (int32_t)t.et.size();
   counts[1] = (int32_t)t.vrow.size();

@@ -582,8 +582,8 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
   const uint32_t mods = c->params.modules;
   if (mods & MS_ANY_TILT_MODS) return fail(c, MS_ERR_STATE, "the tilt modules are not sharded yet (single GPU only)");
   if (mods & MS_MOD_AREA_PENALTY) return fail(c, MS_ERR_STATE, "the body_area_penalty module is not sharded (single GPU only)");
-  if (mods & MS_MOD_LINE_TENSION) return fail(c, MS_ERR_STATE, "the line_tension module is not sharded (single GPU only)");
-  if (mods & MS_MOD_EDGE_LENGTH_PENALTY) return fail(c, MS_ERR_STATE, "the edge_length_penalty module is not sharded (single GPU only)");
+  for (const EdgeTerm& t : kEdgeTerms)  // (MS_MOD_LINE_TENSION, MS_MOD_EDGE_LENGTH_PENALTY)
+    if (mods & t.bit) return fail(c, MS_ERR_STATE, edge_not_sharded(t));
   if (sp->precondition) return fail(c, MS_ERR_STATE, "ConjugateGradient(precondition=True) is not sharded (single GPU only)");
   // (line_search.py:428-487: every trial projected onto the target volume -- the projection is not sharded; running the
   // plain lane instead would be a different trajectory, silently)

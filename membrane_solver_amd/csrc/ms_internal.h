@@ -355,75 +355,45 @@ struct PinGradArgs {
 };
 hipError_t launch_pin_enforce(const PinEnforceArgs& a, hipStream_t s);
 hipError_t launch_pin_grad(const PinGradArgs& a, hipStream_t s);
-// line_tension (ms_line.hip): E = sum gamma |x_h - x_t| over the tagged edges, added into the MS_S_ESURF partials behind
-// the energy pass, and its gradient added into G behind the gradient pass.  Rows are the library's (til.iperm applied).
-struct LineEnergyArgs {
+// The edge lane (ms_edge.hip): line_tension, E = sum gamma |x_h - x_t| over the tagged edges, and edge_length_penalty,
+// E = sum (0.5 k) (|x_h - x_t| - L0)^2 over the edges that carry a target length.  A term's energy is added into the
+// MS_S_ESURF partials behind the energy pass and its gradient into G behind the gradient pass, line_tension's launch
+// before edge_length_penalty's.  Both terms use one table layout: `col` is gamma or L0.  Rows are the library's
+// (til.iperm applied).
+enum : int { EDGE_LINE = 0, EDGE_PEN = 1 };
+struct EdgeEnergyArgs {
   const double* x;
   const double* d;        // trial direction or nullptr, alpha: exactly what EnergyArgs hands k_energy
   double alpha;
   const uint8_t* vflags;  // (a fixed row does not move in a trial)
+  double k;               // EDGE_PEN: edge_stiffness (global only)
   int n_edges;
-  const int32_t* tail;    // edge table, ascending edge order, gamma != 0 only
+  const int32_t* tail;    // edge table, ascending edge order (EDGE_LINE: gamma != 0 only)
   const int32_t* head;
-  const double* gamma;
+  const double* col;      // gamma / target length per edge
   double* partials;       // the energy pass's: workgroup w adds into [MS_S_ESURF * n_tiles + tile0 + w]
   int n_tiles, tile0;
   int grid;               // workgroups of the launch: min(tiles, ceil(n_edges / 256))
   double* wg_sums;        // [grid] per-workgroup sums ...
   uint32_t* done;         // ... counted here; the workgroup that arrives last adds them up in index order ...
-  double* energy;         // ... into the module's own energy (ms_get_line_energy)
+  double* energy;         // ... into the module's own energy (ms_get_line_energy, ms_get_edge_penalty_energy)
 };
-struct LineGradArgs {
+struct EdgeGradArgs {
   const double* x;
   double* g;
   const double* gc;       // the volume row K_C wrote, or nullptr
+  double k;               // EDGE_PEN: edge_stiffness
   int n_touch;
   const int32_t* vrow;    // touched rows, ascending
-  const int32_t* off;     // n_touch + 1: CSR over the rows' tagged edges, ascending edge order
+  const int32_t* off;     // n_touch + 1: CSR over the rows' edges of the term, ascending edge order
   const int32_t* other;   // the other end's row
-  const double* gamma;
+  const double* col;      // gamma / target length of the edge, per CSR entry
   double* partials;       // the gradient pass's: workgroup w adds sum dg_v . gC_v into [MS_S_GGC * n_tiles + tile0 + w]
   int n_tiles, tile0;
   int grid;
 };
-hipError_t launch_line_energy(const LineEnergyArgs& a, hipStream_t s);
-hipError_t launch_line_grad(const LineGradArgs& a, hipStream_t s);
-// edge_length_penalty (ms_edgepen.hip): E = sum (0.5 k) (|x_h - x_t| - L0)^2 over the edges that carry a target length,
-// added into the MS_S_ESURF partials behind the energy pass (and behind k_line_energy), its gradient into G behind the
-// gradient pass (and behind k_line_grad).  The tables have the layout of line_tension's, L0 in the place of gamma.
-struct EdgePenEnergyArgs {
-  const double* x;
-  const double* d;        // trial direction or nullptr, alpha: exactly what EnergyArgs hands k_energy
-  double alpha;
-  const uint8_t* vflags;  // (a fixed row does not move in a trial)
-  double k;               // edge_stiffness (global only)
-  int n_edges;
-  const int32_t* tail;    // edge table, ascending edge order
-  const int32_t* head;
-  const double* l0;       // target length per edge
-  double* partials;       // the energy pass's: workgroup w adds into [MS_S_ESURF * n_tiles + tile0 + w]
-  int n_tiles, tile0;
-  int grid;               // workgroups of the launch: min(tiles, ceil(n_edges / 256))
-  double* wg_sums;        // [grid] per-workgroup sums ...
-  uint32_t* done;         // ... counted here; the workgroup that arrives last adds them up in index order ...
-  double* energy;         // ... into the module's own energy (ms_get_edge_penalty_energy)
-};
-struct EdgePenGradArgs {
-  const double* x;
-  double* g;
-  const double* gc;       // the volume row K_C wrote, or nullptr
-  double k;
-  int n_touch;
-  const int32_t* vrow;    // touched rows, ascending
-  const int32_t* off;     // n_touch + 1: CSR over the rows' charged edges, ascending edge order
-  const int32_t* other;   // the other end's row
-  const double* l0;       // the edge's target length, per CSR entry
-  double* partials;       // the gradient pass's: workgroup w adds sum dg_v . gC_v into [MS_S_GGC * n_tiles + tile0 + w]
-  int n_tiles, tile0;
-  int grid;
-};
-hipError_t launch_edgepen_energy(const EdgePenEnergyArgs& a, hipStream_t s);
-hipError_t launch_edgepen_grad(const EdgePenGradArgs& a, hipStream_t s);
+hipError_t launch_edge_energy(int term, const EdgeEnergyArgs& a, hipStream_t s);
+hipError_t launch_edge_grad(int term, const EdgeGradArgs& a, hipStream_t s);
 // tilt_rim_source_in/out (ms_rim.hip): E = sum over the rim rows of c_row . t_row, c_row = sum over the row's rim edges
 // of -1/2 gamma L r_hat; the workgroup sums go into the field's tilt-magnitude partials (MS_S_ETILT_IN / _OUT) behind
 // the pass that writes them -- or define them when tilt_<leaflet> itself is off -- and c into the tilt gradient.  Rows

@@ -8,47 +8,12 @@
 // per rim row and no atomics; k_rim_apply sums c . t and, on request, adds c into the field's tilt gradient.  While a
 // relaxation runs the positions are frozen: c is computed once and every evaluation only applies it.  k_rim_frame is
 // the follow mode's center: the mean of the rim rows of x.  Every sum is fixed-order (thread t takes items t,
-// t + stride, ... in order, then a halving tree in LDS): a run is bitwise reproducible in both modes of
-// ms_set_deterministic.
-#include "ms_internal.h"
+// t + stride, ... in order, then a halving tree in LDS; ms_stream_dev.h): a run is bitwise reproducible in both modes
+// of ms_set_deterministic.
+#include "ms_stream_dev.h"
 
 namespace ms {
 namespace {
-
-constexpr int LB = 256;
-
-struct P3 {
-  double x, y, z;
-};
-// x + alpha d as the tile kernels form it (ms_kernels.hip, axpy1): the trial position of a row is the same double here
-__device__ __forceinline__ double axpy1(double x, double alpha, double d) {
-#ifdef MS_FP_CONTRACT_OFF
-  return x + alpha * d;
-#else
-  return fma(alpha, d, x);
-#endif
-}
-__device__ __forceinline__ P3 row_at(const RimArgs& a, int r) {
-  const size_t o = 3 * (size_t)r;
-  P3 p{a.x[o], a.x[o + 1], a.x[o + 2]};
-  if (a.d != nullptr && !(a.vflags[r] & VF_FIXED))
-    p = P3{axpy1(p.x, a.alpha, a.d[o]), axpy1(p.y, a.alpha, a.d[o + 1]), axpy1(p.z, a.alpha, a.d[o + 2])};
-  return p;
-}
-
-// fixed-order sum over the workgroup; every thread gets the total
-__device__ double tree_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = LB / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  v = red[0];
-  __syncthreads();
-  return v;
-}
 
 // c_row of rim row i: its rim edges in CSR order (tilt_rim_source_in.py:409-449 per edge)
 __device__ P3 rim_coef_of(const RimArgs& a, long long i) {
@@ -106,7 +71,6 @@ __global__ __launch_bounds__(LB) void k_rim_coef(RimArgs a) {
 
 __global__ __launch_bounds__(LB) void k_rim_apply(RimArgs a) {
   __shared__ double red[LB];
-  __shared__ int is_last;
   const int w = blockIdx.x;
   const long long stride = (long long)a.grid * LB;
   double s = 0.0;
@@ -128,22 +92,9 @@ __global__ __launch_bounds__(LB) void k_rim_apply(RimArgs a) {
   double* cells = a.partials + (size_t)a.slot * a.n_tiles + a.tile0;
   if (a.define && w == 0)  // no pass before this one wrote the slot: the tiles without a workgroup of this launch hold 0
     for (int k = a.grid + threadIdx.x; k < a.n_cells; k += LB) cells[k] = 0.0;
-  if (threadIdx.x == 0) {
-    // (no other workgroup of this launch touches the cell)
-    cells[w] = a.define ? s : cells[w] + s;
-    a.wg_sums[w] = s;
-    __threadfence();
-    is_last = atomicAdd(a.done, 1u) == (unsigned)a.grid - 1u;
-  }
-  __syncthreads();
-  if (is_last && threadIdx.x == 0) {
-    // the module's own energy: the workgroups' sums in index order, whichever workgroup arrived last
-    __threadfence();
-    double tot = 0.0;
-    for (int k = 0; k < a.grid; ++k) tot += __hip_atomic_load(a.wg_sums + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *a.energy = tot;
-    *a.done = 0u;  // (for the next launch)
-  }
+  // (no other workgroup of this launch touches the cell)
+  if (threadIdx.x == 0) cells[w] = a.define ? s : cells[w] + s;
+  publish_wg_sum(s, w, a.grid, a.wg_sums, a.done, a.energy);
 }
 
 }  // namespace

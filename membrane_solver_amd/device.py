@@ -129,70 +129,62 @@ class DeviceMesh:
         delta = self.body_area() - a0
         return 0.5 * k * delta * delta
 
-    def set_line_tension(self, tail=None, head=None, gamma=None):
-        """Tagged edges of the line_tension module as external rows with their gamma, in ascending edge order (used
-        while MS_MOD_LINE_TENSION is in the module mask); no arguments clear the tables."""
+    def _set_edge_term(self, entry, what, tail, head, col, *extra):
+        """One setter of the edge lane: external rows with their column, or no arguments to clear the tables."""
+        fn = getattr(L.lib(), entry)
         if tail is None:
-            self._chk(L.lib().ms_set_line_tension(self._h, 0, None, None, None), "ms_set_line_tension")
+            self._chk(fn(self._h, 0, None, None, None, *[0.0 for _ in extra]), entry)
             return
         t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
         h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
-        g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
-        if not (len(t) == len(h) == len(g)):
-            raise ValueError("set_line_tension: tail, head and gamma must have the same length")
+        c = np.ascontiguousarray(np.asarray(col, dtype=np.float64).reshape(-1))
+        if not (len(t) == len(h) == len(c)):
+            raise ValueError(f"{entry[3:]}: tail, head and {what} must have the same length")
         n = len(t)
         if n == 0:  # (a non-NULL pointer: tables that hold no edge)
             t = h = np.zeros(1, np.int32)
-            g = np.zeros(1)
-        self._chk(L.lib().ms_set_line_tension(self._h, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32), _pd(g)),
-                  "ms_set_line_tension")
+            c = np.zeros(1)
+        self._chk(fn(self._h, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32), _pd(c), *extra), entry)
+
+    def _edge_term_energy(self, entry) -> float:
+        e = ctypes.c_double(0.0)
+        self._chk(getattr(L.lib(), entry)(self._h, ctypes.byref(e)), entry)
+        return float(e.value)
+
+    def _edge_term_stats(self, entry):
+        v = np.zeros(4)
+        self._chk(getattr(L.lib(), entry)(self._h, _pd(v)), entry)
+        return {"energy_launches": int(v[0]), "grad_launches": int(v[1]), "energy_us": float(v[2]),
+                "grad_us": float(v[3])}
+
+    def set_line_tension(self, tail=None, head=None, gamma=None):
+        """Tagged edges of the line_tension module as external rows with their gamma, in ascending edge order (used
+        while MS_MOD_LINE_TENSION is in the module mask); no arguments clear the tables."""
+        self._set_edge_term("ms_set_line_tension", "gamma", tail, head, gamma)
 
     def line_energy(self) -> float:
         """The line_tension module's own energy as the last energy pass summed it (ms_get_line_energy)."""
-        e = ctypes.c_double(0.0)
-        self._chk(L.lib().ms_get_line_energy(self._h, ctypes.byref(e)), "ms_get_line_energy")
-        return float(e.value)
+        return self._edge_term_energy("ms_get_line_energy")
 
     def line_stats(self):
         """Launch counts of the two line_tension kernels and their event-timed microseconds (ms_line_stats)."""
-        v = np.zeros(4)
-        self._chk(L.lib().ms_line_stats(self._h, _pd(v)), "ms_line_stats")
-        return {"energy_launches": int(v[0]), "grad_launches": int(v[1]), "energy_us": float(v[2]),
-                "grad_us": float(v[3])}
+        return self._edge_term_stats("ms_line_stats")
 
     def set_edge_length_penalty(self, tail=None, head=None, target_length=None, k=100.0):
         """Charged edges of the edge_length_penalty module as external rows with their target lengths, in ascending
         edge order, and the one stiffness k (used while MS_MOD_EDGE_LENGTH_PENALTY is in the module mask); no
         arguments clear the tables."""
-        if tail is None:
-            self._chk(L.lib().ms_set_edge_length_penalty(self._h, 0, None, None, None, 0.0), "ms_set_edge_length_penalty")
-            return
-        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
-        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
-        l0 = np.ascontiguousarray(np.asarray(target_length, dtype=np.float64).reshape(-1))
-        if not (len(t) == len(h) == len(l0)):
-            raise ValueError("set_edge_length_penalty: tail, head and target_length must have the same length")
-        n = len(t)
-        if n == 0:  # (a non-NULL pointer: tables that hold no edge)
-            t = h = np.zeros(1, np.int32)
-            l0 = np.zeros(1)
-        self._chk(L.lib().ms_set_edge_length_penalty(self._h, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32),
-                                                     _pd(l0), float(k)), "ms_set_edge_length_penalty")
+        self._set_edge_term("ms_set_edge_length_penalty", "target_length", tail, head, target_length, float(k))
 
     def edge_penalty_energy(self) -> float:
         """The edge_length_penalty module's own energy as the last energy pass summed it
         (ms_get_edge_penalty_energy)."""
-        e = ctypes.c_double(0.0)
-        self._chk(L.lib().ms_get_edge_penalty_energy(self._h, ctypes.byref(e)), "ms_get_edge_penalty_energy")
-        return float(e.value)
+        return self._edge_term_energy("ms_get_edge_penalty_energy")
 
     def edge_penalty_stats(self):
         """Launch counts of the two edge_length_penalty kernels and their event-timed microseconds
         (ms_edge_penalty_stats)."""
-        v = np.zeros(4)
-        self._chk(L.lib().ms_edge_penalty_stats(self._h, _pd(v)), "ms_edge_penalty_stats")
-        return {"energy_launches": int(v[0]), "grad_launches": int(v[1]), "energy_us": float(v[2]),
-                "grad_us": float(v[3])}
+        return self._edge_term_stats("ms_edge_penalty_stats")
 
     @property
     def modules(self) -> int:

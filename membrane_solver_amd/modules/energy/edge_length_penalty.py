@@ -14,9 +14,8 @@ from typing import Dict
 import numpy as np
 
 from ... import _lib as L
-from ...geometry.mesh import mirror_for
 from ..constraints.pins import _entities
-from .line_tension import check_triangle_sides as _check_triangle_sides
+from . import edge_common as _edge
 
 NAME = "edge_length_penalty"
 
@@ -66,35 +65,15 @@ def charged_edges(mesh, global_params):
 
 
 def check_triangle_sides(tri_rows, nv: int, tail, head, numbers=None) -> None:
-    """line_tension.check_triangle_sides with this module's name in the message: a charged edge must be a side of
-    some triangle (the device's minimum edge length, the line search's safe step, runs over triangle sides)."""
-    try:
-        _check_triangle_sides(tri_rows, nv, tail, head, numbers)
-    except L.MembraneHipError as exc:
-        raise L.MembraneHipError(str(exc).replace("line_tension: tagged edge", NAME + ": charged edge", 1)) from None
+    """A charged edge must be a side of some triangle (edge_common.check_triangle_sides)."""
+    _edge.check_triangle_sides(NAME, "charged", tri_rows, nv, tail, head, numbers)
 
 
 def host_tables(nv: int, iperm, tail, head, target_length, k: float):
     """The device tables as the library builds them (ms_edge_penalty_tables_host: the code ms_set_edge_length_penalty
     runs), for inspection: the edge table {tail, head, l0} and the vertex -> edge CSR {vrow, off, other, csr_l0}, rows
     in the library's order (``iperm``: external row -> library row).  k == 0 keeps no edge."""
-    ip = np.ascontiguousarray(np.asarray(iperm, dtype=np.int32).reshape(-1))
-    t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
-    h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
-    l0 = np.ascontiguousarray(np.asarray(target_length, dtype=np.float64).reshape(-1))
-    n = len(t)
-    cnt = np.zeros(2, dtype=np.int32)
-    et, eh, el = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32), np.zeros(n + 1)
-    vrow, off = np.zeros(2 * n + 1, np.int32), np.zeros(2 * n + 2, np.int32)
-    other, ol = np.zeros(2 * n + 1, np.int32), np.zeros(2 * n + 1)
-    i32 = lambda a: a.ctypes.data_as(L._I32)  # noqa: E731
-    d = lambda a: a.ctypes.data_as(L._D)  # noqa: E731
-    rc = L.lib().ms_edge_penalty_tables_host(int(nv), i32(ip), n, i32(t), i32(h), d(l0), float(k), i32(cnt), i32(et),
-                                             i32(eh), d(el), i32(vrow), i32(off), i32(other), d(ol))
-    L.check(rc, None, "ms_edge_penalty_tables_host")
-    ne, nt = int(cnt[0]), int(cnt[1])
-    return {"tail": et[:ne].copy(), "head": eh[:ne].copy(), "l0": el[:ne].copy(), "vrow": vrow[:nt].copy(),
-            "off": off[:nt + 1].copy(), "other": other[:2 * ne].copy(), "csr_l0": ol[:2 * ne].copy()}
+    return _edge.host_tables("ms_edge_penalty_tables_host", "l0", nv, iperm, tail, head, target_length, float(k))
 
 
 def upload(mesh, global_params, dm, charged=None) -> bool:
@@ -116,28 +95,13 @@ def upload(mesh, global_params, dm, charged=None) -> bool:
 def compute_energy_and_gradient_array(mesh, global_params, param_resolver, *, positions: np.ndarray,
                                       index_map: Dict[int, int], grad_arr: np.ndarray) -> float:
     _ = index_map, param_resolver
-    mir = mirror_for(mesh)
-    dm = mir.sync(positions=None if positions is mesh.positions_view() else positions)
-    if not upload(mesh, global_params, dm):
-        return 0.0
-    dm.set_params(modules=L.MS_MOD_EDGE_LENGTH_PENALTY)
-    if grad_arr is not None:
-        e, g = dm.energy_and_gradient(want_grad=True, raw=True)
-        np.add(grad_arr, g, out=grad_arr)
-    else:
-        e = dm.energy()
-    return float(e[0])
+    return _edge.compute_energy_and_gradient_array(upload, L.MS_MOD_EDGE_LENGTH_PENALTY, mesh, global_params,
+                                                   positions, grad_arr)
 
 
 def compute_energy_and_gradient(mesh, global_params, param_resolver, *, compute_gradient: bool = True):
-    positions = mesh.positions_view()
-    grad_arr = np.zeros_like(positions) if compute_gradient else None
-    E = compute_energy_and_gradient_array(mesh, global_params, param_resolver, positions=positions,
-                                          index_map=mesh.vertex_index_to_row, grad_arr=grad_arr)
-    if not compute_gradient:
-        return float(E), {}
-    return float(E), {int(vid): grad_arr[row].copy() for row, vid in enumerate(mesh.vertex_ids)
-                      if np.any(grad_arr[row])}
+    return _edge.compute_energy_and_gradient(compute_energy_and_gradient_array, mesh, global_params, param_resolver,
+                                             compute_gradient)
 
 
 __all__ = ["compute_energy_and_gradient", "compute_energy_and_gradient_array", "charged_edges", "edge_is_selected",

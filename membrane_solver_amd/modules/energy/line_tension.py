@@ -13,8 +13,8 @@ from typing import Dict
 import numpy as np
 
 from ... import _lib as L
-from ...geometry.mesh import mirror_for
 from ..constraints.pins import _entities
+from . import edge_common as _edge
 
 
 def edge_is_tagged(opts) -> bool:
@@ -64,45 +64,15 @@ def tagged_edges(mesh, global_params):
 
 
 def check_triangle_sides(tri_rows, nv: int, tail, head, numbers=None) -> None:
-    """A tagged edge must be a side of some triangle: the reference's minimum edge length (the line search's safe
-    step) runs over all edges, the device's over triangle sides, so an edge outside the triangulation would change
-    the search silently."""
-    if len(tail) == 0:
-        return
-    tri = np.asarray(tri_rows, dtype=np.int64).reshape(-1, 3)
-    a = np.concatenate([tri[:, 0], tri[:, 1], tri[:, 2]])
-    b = np.concatenate([tri[:, 1], tri[:, 2], tri[:, 0]])
-    sides = np.unique(np.minimum(a, b) * int(nv) + np.maximum(a, b))
-    t, h = np.asarray(tail, dtype=np.int64), np.asarray(head, dtype=np.int64)
-    bad = np.flatnonzero(~np.isin(np.minimum(t, h) * int(nv) + np.maximum(t, h), sides))
-    if len(bad):
-        k = int(bad[0])
-        which = k if numbers is None else int(numbers[k])
-        raise L.MembraneHipError(f"line_tension: tagged edge {which} (rows {int(t[k])}, {int(h[k])}) is not a side of "
-                                 "any triangle; edges outside the triangulation are outside the HIP hot path")
+    """A tagged edge must be a side of some triangle (edge_common.check_triangle_sides)."""
+    _edge.check_triangle_sides("line_tension", "tagged", tri_rows, nv, tail, head, numbers)
 
 
 def host_tables(nv: int, iperm, tail, head, gamma):
     """The device tables as the library builds them (ms_line_tables_host: the code ms_set_line_tension runs), for
-    inspection: the edge table {tail, head, gamma} and the vertex -> edge CSR {vrow, off, other, gamma}, rows in the
-    library's order (``iperm``: external row -> library row)."""
-    ip = np.ascontiguousarray(np.asarray(iperm, dtype=np.int32).reshape(-1))
-    t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
-    h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
-    g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
-    n = len(t)
-    cnt = np.zeros(2, dtype=np.int32)
-    et, eh, eg = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32), np.zeros(n + 1)
-    vrow, off = np.zeros(2 * n + 1, np.int32), np.zeros(2 * n + 2, np.int32)
-    other, og = np.zeros(2 * n + 1, np.int32), np.zeros(2 * n + 1)
-    i32 = lambda a: a.ctypes.data_as(L._I32)  # noqa: E731
-    d = lambda a: a.ctypes.data_as(L._D)  # noqa: E731
-    rc = L.lib().ms_line_tables_host(int(nv), i32(ip), n, i32(t), i32(h), d(g), i32(cnt), i32(et), i32(eh), d(eg),
-                                     i32(vrow), i32(off), i32(other), d(og))
-    L.check(rc, None, "ms_line_tables_host")
-    ne, nt = int(cnt[0]), int(cnt[1])
-    return {"tail": et[:ne].copy(), "head": eh[:ne].copy(), "gamma": eg[:ne].copy(), "vrow": vrow[:nt].copy(),
-            "off": off[:nt + 1].copy(), "other": other[:2 * ne].copy(), "csr_gamma": og[:2 * ne].copy()}
+    inspection: the edge table {tail, head, gamma} and the vertex -> edge CSR {vrow, off, other, csr_gamma}, rows in
+    the library's order (``iperm``: external row -> library row)."""
+    return _edge.host_tables("ms_line_tables_host", "gamma", nv, iperm, tail, head, gamma)
 
 
 def upload(mesh, global_params, dm) -> bool:
@@ -120,28 +90,13 @@ def upload(mesh, global_params, dm) -> bool:
 def compute_energy_and_gradient_array(mesh, global_params, param_resolver, *, positions: np.ndarray,
                                       index_map: Dict[int, int], grad_arr: np.ndarray) -> float:
     _ = index_map, param_resolver
-    mir = mirror_for(mesh)
-    dm = mir.sync(positions=None if positions is mesh.positions_view() else positions)
-    if not upload(mesh, global_params, dm):
-        return 0.0  # line_tension.py:113-115
-    dm.set_params(modules=L.MS_MOD_LINE_TENSION)
-    if grad_arr is not None:
-        e, g = dm.energy_and_gradient(want_grad=True, raw=True)
-        np.add(grad_arr, g, out=grad_arr)
-    else:
-        e = dm.energy()
-    return float(e[0])
+    return _edge.compute_energy_and_gradient_array(upload, L.MS_MOD_LINE_TENSION, mesh, global_params, positions,
+                                                   grad_arr)  # (0.0 without a charged edge: line_tension.py:113-115)
 
 
 def compute_energy_and_gradient(mesh, global_params, param_resolver, *, compute_gradient: bool = True):
-    positions = mesh.positions_view()
-    grad_arr = np.zeros_like(positions) if compute_gradient else None
-    E = compute_energy_and_gradient_array(mesh, global_params, param_resolver, positions=positions,
-                                          index_map=mesh.vertex_index_to_row, grad_arr=grad_arr)
-    if not compute_gradient:
-        return float(E), {}
-    return float(E), {int(vid): grad_arr[row].copy() for row, vid in enumerate(mesh.vertex_ids)
-                      if np.any(grad_arr[row])}
+    return _edge.compute_energy_and_gradient(compute_energy_and_gradient_array, mesh, global_params, param_resolver,
+                                             compute_gradient)
 
 
 __all__ = ["compute_energy_and_gradient", "compute_energy_and_gradient_array", "tagged_edges", "edge_is_tagged",

@@ -401,3 +401,98 @@ def test_changed_targets_are_uploaded_again():
     mz.global_params.set("edge_stiffness", 0.0)
     mz.compute_energy()
     assert not mz._device()[1].modules & L.MS_MOD_EDGE_LENGTH_PENALTY
+
+
+def _np_edge_terms(P, t, h, coef_of_len):
+    """-> (lengths, gradient (nv,3)) of sum f(|e|) over the edges, coef_of_len(len) = f'(len)."""
+    vec = P[h] - P[t]
+    ln = np.linalg.norm(vec, axis=1)
+    g = np.zeros_like(P)
+    np.add.at(g, t, -(coef_of_len(ln) / ln)[:, None] * vec)
+    np.add.at(g, h, (coef_of_len(ln) / ln)[:, None] * vec)
+    return ln, g
+
+
+@pytest.mark.parametrize("fixed_order", [False, True])
+def test_the_two_edge_terms_keep_their_own_tables(fixed_order):
+    """line_tension on edges 0..299 and edge_length_penalty on edges 250..479 of a several-tile icosphere (two
+    workgroups of k_line_energy, one of k_edgepen_energy): each term's own energy to 1e-12 relative and the two terms'
+    gradient to 1e-10 of max|g| against NumPy (the bars of test_module_energy_and_gradient_match_reference); clearing one
+    term leaves the other's energy and gradient bit for bit; each term's statistics count its own launches."""
+    from membrane_solver_amd import meshgen
+
+    P0, T = meshgen.icosphere(4)
+    P = meshgen.smooth_displace(P0)
+    tri = np.asarray(T, dtype=np.int64)
+    a = np.concatenate([tri[:, 0], tri[:, 1], tri[:, 2]])
+    b = np.concatenate([tri[:, 1], tri[:, 2], tri[:, 0]])
+    key = np.unique(np.minimum(a, b) * len(P) + np.maximum(a, b))
+    et, eh = (key // len(P)).astype(np.int32), (key % len(P)).astype(np.int32)
+    assert len(P) == 162 and len(et) == 480
+    lt, lh, gam = et[:300], eh[:300], 0.5 + 0.01 * np.arange(300)
+    pt, ph, l0, k = et[250:], eh[250:], 0.2 + 0.001 * np.arange(230), 3.0
+    ln_l, g_line = _np_edge_terms(P, lt, lh, lambda ln: gam)
+    ln_p, g_pen = _np_edge_terms(P, pt, ph, lambda ln: k * (ln - l0))
+    e_line, e_pen = float((gam * ln_l).sum()), float((0.5 * k * (ln_p - l0) ** 2).sum())
+    both = L.MS_MOD_LINE_TENSION | L.MS_MOD_EDGE_LENGTH_PENALTY
+
+    def fresh():
+        dm = DeviceMesh(P, T, tile_vertices=64)
+        dm.set_deterministic(fixed_order)
+        dm.set_surface_tension(np.ones(len(T)))
+        return dm
+
+    def alone(dm, bit):
+        dm.set_params(modules=bit)
+        e, g = dm.energy_and_gradient(raw=True)
+        return e.copy(), g.copy()
+
+    # a run where the other term was never set
+    dm = fresh()
+    dm.set_edge_length_penalty(pt, ph, l0, k)
+    pen_only = alone(dm, L.MS_MOD_EDGE_LENGTH_PENALTY) + (dm.edge_penalty_energy(),)
+    dm.close()
+    dm = fresh()
+    dm.set_line_tension(lt, lh, gam)
+    line_only = alone(dm, L.MS_MOD_LINE_TENSION) + (dm.line_energy(),)
+    dm.close()
+
+    dm = fresh()
+    assert dm.tile_stats()["n_tiles"] > 1
+    dm.set_params(modules=L.MS_MOD_SURFACE)
+    e0, g0 = dm.energy_and_gradient(raw=True)
+    dm.set_line_tension(lt, lh, gam)
+    dm.set_edge_length_penalty(pt, ph, l0, k)
+    assert dm.line_stats()["energy_launches"] == 0 and dm.edge_penalty_stats()["energy_launches"] == 0
+    dm.set_params(modules=L.MS_MOD_SURFACE | both)
+    e1, g1 = dm.energy_and_gradient(raw=True)
+    E_line, E_pen = dm.line_energy(), dm.edge_penalty_energy()
+    scale = np.abs(g_line + g_pen).max()
+    print(f"fixed_order={fixed_order}: dE_line/E={abs(E_line - e_line) / e_line:.3e} dE_pen/E={abs(E_pen - e_pen) / e_pen:.3e} "
+          f"dg/max|g|={np.abs(g1 - g0 - g_line - g_pen).max() / scale:.3e}")
+    assert abs(E_line - e_line) <= 1e-12 * e_line
+    assert abs(E_pen - e_pen) <= 1e-12 * e_pen
+    assert abs(e1[0] - (e0[0] + e_line + e_pen)) <= 1e-12 * abs(e1[0])
+    assert np.abs((g1 - g0) - (g_line + g_pen)).max() <= 1e-10 * scale
+    # each term counts the launches of its own lane
+    count = lambda st: (st["energy_launches"], st["grad_launches"])  # noqa: E731
+    n_line, n_pen = count(dm.line_stats()), count(dm.edge_penalty_stats())
+    assert n_line == n_pen and min(n_line) >= 1
+    alone(dm, L.MS_MOD_LINE_TENSION)
+    assert count(dm.line_stats()) == (2 * n_line[0], 2 * n_line[1]) and count(dm.edge_penalty_stats()) == n_pen
+    # line_tension cleared: the penalty's tables are untouched
+    dm.set_line_tension()
+    e, g = alone(dm, L.MS_MOD_EDGE_LENGTH_PENALTY)
+    assert np.array_equal(e, pen_only[0]) and np.array_equal(g, pen_only[1])
+    assert dm.edge_penalty_energy() == pen_only[2] and dm.line_energy() == 0.0
+    e, g = alone(dm, both)  # (the cleared term's bit contributes nothing)
+    assert np.array_equal(e, pen_only[0]) and np.array_equal(g, pen_only[1])
+    # and the other way round
+    dm.set_line_tension(lt, lh, gam)
+    dm.set_edge_length_penalty()
+    e, g = alone(dm, L.MS_MOD_LINE_TENSION)
+    assert np.array_equal(e, line_only[0]) and np.array_equal(g, line_only[1])
+    assert dm.line_energy() == line_only[2] and dm.edge_penalty_energy() == 0.0
+    e, g = alone(dm, both)
+    assert np.array_equal(e, line_only[0]) and np.array_equal(g, line_only[1])
+    dm.close()

@@ -364,3 +364,60 @@ def test_cut_icosphere_sizes_at_the_resident_tile_edges(freq, k):
     assert st[0] == tiles_want
     assert st[4] == 0 and st[5] == nf and st[6] == 3 * nf
     assert np.array_equal(np.sort(perm), np.arange(nv))
+
+
+def _csrc_copy(tmp_path, monkeypatch):
+    """A copy of csrc/ with a library newer than nothing in it: every source an hour old, the library a minute old."""
+    import shutil
+    import time
+
+    from membrane_solver_amd import _lib
+
+    csrc = tmp_path / "csrc"
+    shutil.copytree(_lib._CSRC, csrc, ignore=shutil.ignore_patterns("build"))
+    lib = tmp_path / "libmembrane_hip.so"
+    lib.write_bytes(b"")
+    now = time.time()
+    for f in csrc.iterdir():
+        os.utime(f, (now - 3600, now - 3600))
+    os.utime(lib, (now - 60, now - 60))
+    calls = []
+    monkeypatch.setattr(_lib, "_CSRC", str(csrc))
+    monkeypatch.setattr(_lib, "LIB_PATH", str(lib))
+    monkeypatch.setattr(_lib.subprocess, "check_call", lambda cmd, *a, **k: calls.append(list(cmd)))
+    return _lib, csrc, calls
+
+
+@pytest.mark.parametrize("edited", ["ms_edge.hip", "ms_stream_dev.h", "ms_api_edge.inc", "ms_api_step.inc"])
+def test_build_runs_make_after_an_edit(tmp_path, monkeypatch, edited):
+    """_lib.build() takes its staleness list from the directory: an edit to any source, a header or an included part
+    as much as a translation unit, rebuilds the library."""
+    _lib, csrc, calls = _csrc_copy(tmp_path, monkeypatch)
+    os.utime(csrc / edited)
+    assert _lib.build() == _lib.LIB_PATH
+    assert len(calls) == 1 and calls[0][0] == "make" and str(csrc) in calls[0] and "-B" not in calls[0]
+
+
+def test_build_leaves_an_up_to_date_library_alone(tmp_path, monkeypatch):
+    _lib, _csrc, calls = _csrc_copy(tmp_path, monkeypatch)
+    assert _lib.build() == _lib.LIB_PATH and calls == []
+    assert _lib.build(force=True) == _lib.LIB_PATH and len(calls) == 1 and "-B" in calls[0]
+
+
+def test_makefile_lists_every_translation_unit():
+    """Every *.hip in csrc/ that no other source #includes is in the Makefile's SRCS, with its object in OBJS."""
+    csrc = os.path.join(ROOT, "membrane_solver_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    included = set()
+    for f in files:
+        if os.path.isfile(os.path.join(csrc, f)) and f != "Makefile":
+            included |= set(re.findall(r'#include\s+"([^"]+)"', open(os.path.join(csrc, f)).read()))
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    srcs = re.search(r"^SRCS := (.*)$", mk, flags=re.M).group(1).split()
+    objs = re.search(r"^OBJS := (.*)$", mk, flags=re.M).group(1).split()
+    units = [f for f in files if f.endswith(".hip") and f not in included]
+    assert "ms_edge.hip" in units and "ms_couple.hip" not in units
+    for f in units:
+        assert f in srcs, f
+        assert "$(BUILD)/" + f[:-4] + ".o" in objs, f
+    assert len(srcs) == len(objs)

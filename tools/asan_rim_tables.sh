@@ -9,7 +9,7 @@ O=$(mktemp -d)
 make -s -C $C -j16 || exit 1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
   -std=c++17 -Wno-unused-result -I$C -I$R/include -x hip $R/tools/micro/asan_rim_tables.cpp $C/ms_api.cpp $C/ms_tiles.cpp -x none \
-  $C/build/ms_kernels.o $C/build/ms_pins.o $C/build/ms_line.o $C/build/ms_edgepen.o $C/build/ms_rim.o \
+  $C/build/ms_kernels.o $C/build/ms_pins.o $C/build/ms_edge.o $C/build/ms_rim.o \
   -fsanitize=address,undefined -ldl -o $O/asan_rim_tables || exit 1
 $O/asan_rim_tables
 rc=$?
