@@ -198,7 +198,19 @@ typedef struct ms_stepper_params {
                               (minimizer.py:1379): every trial that passed the guard runs
                               the pin program (ms_enforce_pins) before the volume projection
                               (if enforce_volume) and its energy.  Needs ms_set_pins;
-                              unqueued trials.                                       */
+                              unqueued trials.
+                              Next to a tilt family (single field or leaflets, rim sources
+                              in the fixed frame and tilt_coupling included) a trial is:
+                              x + alpha d and the guard alone (the un-enforced trial is
+                              never evaluated), the pin program, the stored tilts projected
+                              onto the pinned surface into the field's trial buffer, the
+                              energy passes there.  An accepted trial keeps that projection;
+                              a rejected trial and an exhausted search leave the tilts bit
+                              for bit as they were after the projection at x
+                              (line_search.py:475-481, :493-498).
+                              Refused: pins next to tilt modules together with the volume
+                              constraint (row or enforcer); a rim source in follow mode
+                              with any enforcer; sharded contexts.                  */
 } ms_stepper_params;
 
 typedef struct ms_step_result {
@@ -727,7 +739,9 @@ int ms_set_pins(ms_ctx *ctx, int n_params, const double *params, int n_stages, c
 /* pin_to_plane.enforce_constraint then pin_to_circle.enforce_constraint (in the order the tables hold them) on
  * buffer X, in place: one k_pin_enforce launch. */
 int ms_enforce_pins(ms_ctx *ctx);
-/* stats: {lane (-1 no tables, 0 skip, 1 project), k_pin_enforce launches, k_pin_grad launches, trials projected} */
+/* stats: {lane (-1 no tables, 0 skip, 1 project), runs of the enforcement program, runs of the gradient pass, trials
+ * projected}.  A run is a k_pin_enforce / k_pin_grad launch or, on a one-tile context, a record of the one-workgroup
+ * interpreter's pack (MS_EXEC_PINS=0: always a launch). */
 int ms_pin_stats(ms_ctx *ctx, int64_t stats[4]);
 /* Tilt relaxations of multi-tile meshes: the backtracking search (runtime/steppers/tilt_relaxation.py:326-347,
  * 380-398, 918-973, 1150-1230: up to twelve halvings of the step on E(P(t + step*src)), positions frozen) runs as

@@ -218,6 +218,7 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
     c->pair_enable = false;  // (several trials per launch buy nothing inside one workgroup)
     c->exec_relax = !(getenv("MS_EXEC_RELAX") != nullptr && atoi(getenv("MS_EXEC_RELAX")) == 0);
     c->exec_fused = !(getenv("MS_EXEC_FUSED") != nullptr && atoi(getenv("MS_EXEC_FUSED")) == 0);
+    c->exec_pins = !(getenv("MS_EXEC_PINS") != nullptr && atoi(getenv("MS_EXEC_PINS")) == 0);
   }
   c->shard_chain_enable = !(getenv("MS_SHARD_CHAIN") != nullptr && atoi(getenv("MS_SHARD_CHAIN")) == 0);
   // tilt relaxations of multi-tile meshes: the backtracking search as multi-trial passes (MS_TSEARCH=0: one launch per

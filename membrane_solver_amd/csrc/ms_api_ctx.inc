@@ -27,6 +27,7 @@ struct StageCtl {
   // re-projected in between): the shape kernels are not launched again -- their energies are in the mailbox, the
   // bending_tilt records in place -- only the tilt modules' passes run and only their slots are folded
   bool energy_tilt_only = false;
+  bool positions_only = false;  // phase_energy: the launch is wanted for x + alpha d and the guard alone (ms_step, pins next to tilt modules): no module is evaluated, and what the context remembers of its factor buffers stays
   bool proj_at_x_in_normals = false;  // phase_energy: the normals launch also projects the leaflets' stored tilts onto x in place (ms_step)
 };
 // What the step logic carries from one evaluation to the next.  "Queue something in the state a later step will be in"
@@ -358,6 +359,7 @@ struct ms_ctx {
   bool exec_relax = true;    // tilt relaxations run as a device program (CK_RELAX); MS_EXEC_RELAX=0: host-driven
   bool exec_fused = true;    // leaflet relaxations with the frozen geometry on the CU (CK_RELAX_FUSED); MS_EXEC_FUSED=0:
                              // the generic program (always, with fixed-order sums: it is bit for bit the kernels)
+  bool exec_pins = true;     // k_pin_enforce / k_pin_grad as records of the pack (CK_PIN_*); MS_EXEC_PINS=0: launches behind a flush
   long relax_fused_runs = 0;
   double* d_relax_cells = nullptr;           // [0] trial coefficient, [1] Fletcher-Reeves beta (written by the program)
   unsigned long long* h_relax_box = nullptr; // pinned result mailbox of the program: {iterations, evaluations, parity, done}

@@ -821,6 +821,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     if (rc) return rc;
   }
   if (bend && write_factors) c->carry.factors_valid = !use_dir;
+  if (st.positions_only) return MS_OK;  // (no factor was written and no record: fK / fA and their owner are as they were)
   if (!lbt) c->factors_leaflet = 0;
   c->carry.bt_valid = (bt || lbt) && !use_dir;
   return MS_OK;

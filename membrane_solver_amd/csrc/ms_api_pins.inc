@@ -1,6 +1,7 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit): pin_to_plane /
 // pin_to_circle -- the tables (ms_set_pins), the enforcement program on X (k_pin_enforce) and the project lane's
-// gradient pass (k_pin_grad).  Neither kernel is recorded by the one-tile interpreter: both flush it first.
+// gradient pass (k_pin_grad).  The one-tile interpreter records both (CK_PIN_ENFORCE, CK_PIN_GRAD); MS_EXEC_PINS=0: both flush it
+// first and run as launches of their own.  The launch counters count program runs either way.
 namespace {
 
 inline bool pins_set(const ms_ctx* c) { return c->pin_lane >= 0; }
@@ -9,10 +10,9 @@ inline bool pins_project(const ms_ctx* c) { return c->pin_lane == MS_PIN_LANE_PR
 // run the enforcement program on X (what every caller then sees moved: the state of x is stale)
 int pin_enforce_run(ms_ctx* c) {
   if (!pins_set(c) || c->pin_enf.n_stages == 0) return MS_OK;
-  if (int rc = exec_flush(c)) return rc;
   PinEnforceArgs a = c->pin_enf;
   a.x = c->buf[MS_BUF_X];
-  HIPCHK(c, launch_pin_enforce(a, c->stream));
+  HIPCHK(c, launch_pin_enforce(a, c->stream, c->exec_pins));  // (a record of the pack, or a launch behind a flush)
   ++c->pin_enforce_launches;
   c->carry.factors_valid = false;
   c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
@@ -23,7 +23,6 @@ int pin_enforce_run(ms_ctx* c) {
 // tile0's <g,gC> / <gC,gC> partials by the change at the touched rows (before the fold takes them)
 int pin_grad_run(ms_ctx* c, bool volrow) {
   if (!pins_project(c)) return MS_OK;
-  if (int rc = exec_flush(c)) return rc;
   PinGradArgs a = c->pin_grad;
   a.x = c->buf[MS_BUF_X];
   a.g = c->buf[MS_BUF_G];
@@ -31,7 +30,7 @@ int pin_grad_run(ms_ctx* c, bool volrow) {
   a.partials = c->d_partials;
   a.n_tiles = c->til.n_tiles;
   a.tile = c->tile0;
-  HIPCHK(c, launch_pin_grad(a, c->stream));
+  HIPCHK(c, launch_pin_grad(a, c->stream, c->exec_pins));
   ++c->pin_grad_launches;
   return MS_OK;
 }

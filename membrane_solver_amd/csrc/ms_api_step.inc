@@ -285,7 +285,8 @@ int queue_round(ms_ctx* c, const ms_stepper_params* sp, const RoundPlan& plan, i
     // the accepted trial), gated on "the accepted trial is the one in the ordinary buffers"; every change of the
     // context is undone afterwards.  Its direction fold can open the round after this one (queue_ahead).
     // (of the carried state the pass writes factors_valid, dir_implicit, pd_neg_pg, last_g and the three flags the
-    // pin project lane clears; it never runs with a tilt module, so nothing of it touches the rest)
+    // pin project lane clears; it never runs with a tilt module -- rounds are queued only without one and without an
+    // enforcer, pins next to tilt modules included -- so nothing of it touches the rest)
     const bool next_hist = next_use_history(c, cg, restart);
     const CarryState s_carry = c->carry;
     std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
@@ -451,6 +452,10 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     if ((c->params.modules & tfl[k]->mod_rs) && tfl[k]->rs_follow && (sp->enforce_volume || sp->enforce_pins))
       return fail(c, MS_ERR_STATE, "tilt_rim_source in follow mode (pin_to_circle_mode: fit) with a constraint enforcer "
                                    "on the line search is outside the device path");
+  const bool pin_tilt = sp->enforce_pins != 0 && pins_set(c) && tilt;  // (the lane of pins next to a tilt family)
+  if (pin_tilt && ((c->params.modules & MS_CON_VOLUME) || sp->enforce_volume))
+    return fail(c, MS_ERR_STATE, "pin_to_plane / pin_to_circle next to tilt modules together with the volume constraint "
+                                 "are outside the device path");
   // reuse_energy0 == 2: an accepted trial doubles as the next step's energy/factor pass
   const bool carry_mode = sp->reuse_energy0 >= 2 && !tilt;
   if (c->ahead.valid && !c->ahead.go_known && !(c->carry.kc_pending && carry_mode && c->carry.carry_valid)) {
@@ -574,7 +579,9 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   double min_edge = std::sqrt(c->h_scal[MS_S_MINEDGE2]);
   // energy_fn projects the stored tilts first (minimizer.py:581-588).  With leaflet bending_tilt the energy pass below
   // launches the normals of x anyway: the projections ride in that launch (same normals, same arithmetic)
-  const bool proj_in_normals = tilt && (c->params.modules & MS_LEAFLET_BT) != 0 && !(c->params.modules & MS_TILT_MODS);
+  // (not next to pins: there the projection at x is what a rejected search must leave behind bit for bit, and it is
+  // taken by the kernel that projects every trial and that ms_project_tilts_to_tangent launches)
+  const bool proj_in_normals = tilt && (c->params.modules & MS_LEAFLET_BT) != 0 && !(c->params.modules & MS_TILT_MODS) && !pin_tilt;
   for (int k = 0; k < n_tf && !proj_in_normals; ++k) {
     rc = tilt_pass_f(c, *tfl[k], 2, false, 0.0);
     if (rc) return rc;
@@ -657,8 +664,12 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   // energy is taken -- three more passes per trial, one trial at a time
   // pins (ms_stepper_params.enforce_pins): the pin program on every trial first, then the volume projection if that
   // is on as well (constraint_manager.enforce_all runs the modules in their order; the pins are listed first)
+  // pins next to a tilt family (single field or leaflets): per trial the positions (and the guard) alone, the pin
+  // program on them, the stored tilts projected onto the ENFORCED surface, the energy passes there; a rejected trial
+  // puts the tilts back as well (line_search.py:475-481: needs_tilt_restore is on whenever there is an enforcer)
   const bool enforce_vol = sp->enforce_volume != 0 && volrow && !tilt;
-  const bool enforce_pin = sp->enforce_pins != 0 && pins_set(c) && !tilt;
+  const bool enforce_pin = sp->enforce_pins != 0 && pins_set(c);
+  const bool enforce_tilt = pin_tilt;
   const bool enforce = enforce_vol || enforce_pin;
   const bool can_chain = c->speculate && carry_mode && !tilt &&
                          !(c->params.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY | MS_EDGE_MODS)) && !enforce && !precond;
@@ -687,9 +698,20 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     kc_queued = false;  // (a gradient pass queued behind an earlier, fully rejected round found its gate closed)
     if (!(can_chain && safe_small)) {
       unchained_ran = true;
-      rc = phase_energy(c, c->params.modules, true, alpha, true, !safe_small, carry_mode && !enforce);
-      if (rc) return rc;
-      rc = fetch(c);
+      if (enforce_tilt) {
+        // the un-enforced trial is never evaluated: the shape kernel with an empty module word leaves x + alpha d in
+        // the trial buffer and the guard's partials (StageCtl::positions_only: no energy term, no projection, no tilt
+        // pass, nothing the context carries changes); the host waits for the fold only when it has to see the guard
+        StageCtl st;
+        st.positions_only = true;
+        StageScope scope(c, st);
+        rc = phase_energy(c, 0u, true, alpha, true, !safe_small, false, /*reduce_now=*/!safe_small);
+        if (rc == MS_OK && !safe_small) rc = fetch(c);
+      } else {
+        rc = phase_energy(c, c->params.modules, true, alpha, true, !safe_small, carry_mode && !enforce);
+        if (rc) return rc;
+        rc = fetch(c);
+      }
       if (rc) return rc;
       if (!safe_small && c->h_scal[MS_S_GUARD] > 0.0) {
         ++out->guard_rejects;
@@ -709,10 +731,17 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
           ++c->pin_trials;
         }
         if (rc == MS_OK && enforce_vol) rc = ms_project_volume_cached(c, c->params.target_volume, 1e-12, 3, 0, nullptr, nullptr);
+        // energy_fn on the enforced trial projects the stored tilts onto it first (minimizer.py:581-588): into `trial`,
+        // which takes the field's place for the evaluation -- the tilts of x stay where they are, bit for bit
+        for (int k = 0; k < n_tf && rc == MS_OK && enforce_tilt; ++k)
+          rc = tilt_pass_f(c, *tfl[k], 2, false, 0.0, tfl[k]->tilts, tfl[k]->trial);
+        for (int k = 0; k < n_tf && enforce_tilt; ++k) std::swap(tfl[k]->tilts, tfl[k]->trial);
         if (rc == MS_OK) rc = phase_energy(c, c->params.modules, false, 0.0, false, false, carry_mode);
         if (rc == MS_OK) rc = fetch(c);
+        for (int k = 0; k < n_tf && enforce_tilt; ++k) std::swap(tfl[k]->tilts, tfl[k]->trial);  // (accept() swaps them in)
         std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);  // (the projected trial is the trial buffer again)
         if (rc) return rc;
+        if (enforce_tilt) c->carry.bt_valid = false;  // (the bending_tilt records describe the trial until it is accepted)
         if (carry_mode) c->carry.factors_valid = false;  // (they belong to the trial point until it is accepted)
       }
       ++out->trials;
@@ -724,7 +753,8 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       }
       // a rejected trial restores the positions, not the tilts: energy_fn stored their projection
       // onto the trial surface (line_search.py:456-487 without an enforcer; DESIGN.md section 4)
-      for (int k = 0; k < n_tf; ++k) std::swap(tfl[k]->tilts, tfl[k]->trial);
+      // (with an enforcer the tilts go back with the positions, line_search.py:475-481: they were never moved)
+      for (int k = 0; k < n_tf && !enforce_tilt; ++k) std::swap(tfl[k]->tilts, tfl[k]->trial);
       min_rejected = alpha;
       alpha *= sp->beta;
       ++it;

@@ -166,6 +166,17 @@ __device__ __forceinline__ void exec_dispatch(exec_kptr base, int off, double* l
         for (int64_t i = threadIdx.x; i < a.n; i += blockDim.x) a.p[i] = 0.0;
       });
       break;
+    case CK_PIN_ENFORCE:
+      // (both pin bodies are one workgroup of 256 threads with fixed-order trees in 3 * 256 doubles of the block's LDS)
+      exec_plain<PinEnforceArgs, EXEC_ONCE>(base, off, [lds](const PinEnforceArgs& a, const ExecCmdHead&, int) {
+        pin_dev::pin_enforce_body(a, reinterpret_cast<double(*)[pin_dev::PB]>(lds));
+      });
+      break;
+    case CK_PIN_GRAD:
+      exec_plain<PinGradArgs, EXEC_ONCE>(base, off, [lds](const PinGradArgs& a, const ExecCmdHead&, int) {
+        pin_dev::pin_grad_body(a, reinterpret_cast<double(*)[pin_dev::PB]>(lds));
+      });
+      break;
     default: break;  // (CK_RELAX / CK_RELAX_FUSED: k_exec runs them itself)
   }
 }

@@ -353,8 +353,10 @@ struct PinGradArgs {
   double* partials;
   int n_tiles, tile;
 };
-hipError_t launch_pin_enforce(const PinEnforceArgs& a, hipStream_t s);
-hipError_t launch_pin_grad(const PinGradArgs& a, hipStream_t s);
+// record: on a stream with a recorder the program becomes a record of the pack (CK_PIN_ENFORCE / CK_PIN_GRAD) instead of
+// a launch behind a flush
+hipError_t launch_pin_enforce(const PinEnforceArgs& a, hipStream_t s, bool record);
+hipError_t launch_pin_grad(const PinGradArgs& a, hipStream_t s, bool record);
 // The edge lane (ms_edge.hip): line_tension, E = sum gamma |x_h - x_t| over the tagged edges, and edge_length_penalty,
 // E = sum (0.5 k) (|x_h - x_t| - L0)^2 over the edges that carry a target length.  A term's energy is added into the
 // MS_S_ESURF partials behind the energy pass and its gradient into G behind the gradient pass, line_tension's launch
@@ -474,7 +476,8 @@ struct AxpyMaskedArgs {
 // travels as the kernel's argument block.  Results are bit for bit those of the launch-per-kernel path.
 enum : uint16_t {
   CK_ENERGY = 1, CK_GRADIENT, CK_TILT, CK_BT, CK_TS, CK_TVEC, CK_DISK, CK_REDUCE, CK_DIRECTION, CK_ROWDOT,
-  CK_AXPY_MASKED, CK_MEMSET, CK_RELAX, CK_RELAX_FUSED, CK_TSEARCH  // (CK_TSEARCH: the single-step-size form of k_tsearch, mode = fields)
+  CK_AXPY_MASKED, CK_MEMSET, CK_RELAX, CK_RELAX_FUSED, CK_TSEARCH,  // (CK_TSEARCH: the single-step-size form of k_tsearch, mode = fields)
+  CK_PIN_ENFORCE, CK_PIN_GRAD  // the pin program and the project lane's pass (ms_pins_dev.h), one workgroup each
 };
 struct ExecCmdHead {
   uint16_t kind;

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "ms_internal.h"
+#include "ms_pins_dev.h"  // the pin bodies the interpreter records (CK_PIN_ENFORCE, CK_PIN_GRAD)
 
 #ifndef MS_RSQRT_NORM
 #define MS_RSQRT_NORM 1  // facet normal length and its reciprocal from one refined rsqrt (norm_and_inverse)

@@ -28,10 +28,13 @@ modules (``tilt``, ``bending_tilt``, ``tilt_smoothness`` and their ``_in`` /
 and the switched-off ``rim_slope_match_out`` as host-side constants.
 
 Constraints: ``volume`` and the pins (``pin_to_plane`` / ``pin_to_circle``: the pin program on every
-line-search trial and in every enforce context, their rows removed from the gradient in the project lane).
+line-search trial and in every enforce context, their rows removed from the gradient in the project lane).  Next to
+the tilt modules, single field or leaflets, a trial is: positions, pin program, the stored tilts projected onto the
+pinned surface, energy there; a rejected trial puts the tilts back with the positions.
 
 Out of scope here (raises MembraneHipError): every other energy module,
-constraints other than ``volume``, ``pin_to_plane`` and ``pin_to_circle``, pins with tilt modules, the benchmark toggles of the leaflet modules
+constraints other than ``volume``, ``pin_to_plane`` and ``pin_to_circle``, pins next to tilt modules together with the
+``volume`` constraint, the benchmark toggles of the leaflet modules
 (modules/energy/leaflet_common._UNSUPPORTED_KEYS), the reference's auto
 mesh-quality repair hook.
 """
@@ -434,10 +437,10 @@ class Minimizer:
         changing the tags or the pin parameters) and upload the device tables; an empty program (nothing tagged, or
         only slide circles of fewer than three members, which the reference skips) clears them; the project-or-skip decision is the reference's KKT solve on C = [volume row;
         pin rows] at the current positions (runtime/constraint_projection.py:101-129)."""
-        if mods & _TILT_BITS:
-            raise L.MembraneHipError("pin_to_plane / pin_to_circle together with tilt modules are outside the HIP "
-                                     "hot path")
         volrow = bool(mods & L.MS_CON_VOLUME)
+        if mods & _TILT_BITS and (volrow or "volume" in self.constraint_module_names):
+            raise L.MembraneHipError("pin_to_plane / pin_to_circle next to tilt modules together with the volume "
+                                     "constraint are outside the HIP hot path")
         key = (mir._topo_key, id(dm), volrow, np.asarray(self.mesh.fixed_mask, dtype=bool).tobytes())
         if key == self._pin_key:
             return
@@ -538,6 +541,13 @@ class Minimizer:
             return moved
         target = self._target_volume()
         if target is None or "volume" not in self.constraint_module_names:
+            if self._pin_names and context in ("finalize", "mesh_operation") and dm.modules & _TILT_BITS:
+                # minimizer.py:1186, :1224: the pins alone are an enforcer as well -- the tilts go onto the tangent
+                # planes of the pinned surface before the next evaluation reads them.  Keyed on the LISTED pin modules,
+                # not on _pins_active: the reference projects whenever a constraint module with enforce_constraint is
+                # loaded (_has_enforceable_constraints), an empty pin program included
+                dm.project_tilts_to_tangent()
+                moved = True
             return moved
         max_iter = 12 if context in ("finalize", "mesh_operation") else 3
         iters, _v = dm.project_volume(target, tol=1e-12, max_iter=max_iter, first_step_cached=first_step_cached)
