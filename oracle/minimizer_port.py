@@ -405,7 +405,9 @@ def leaflet_tilt_cg_preconditioner(p: Problem, pos, fixed_in, fixed_out, vertex_
 
 # runtime/steppers/tilt_relaxation.py:426-1478 relax_leaflet_tilts, default options (per-step projection
 # refresh without tilt constraints = projecting already projected fields; no update modes, no fallback)
-def relax_leaflet_tilts(p: Problem, pos: np.ndarray) -> dict:
+def relax_leaflet_tilts(p: Problem, pos: np.ndarray, trace: list | None = None) -> dict:
+    """``trace``: a list that receives ("gnorm", |g|) per gradient evaluation and ("trial", E0, E1) per line-search
+    trial, in order -- the decisions the loop branches on (tests/relax_cases.py); it changes no arithmetic."""
     stats = {"iters": 0, "evals": 0}
     mode = str(p.gp.get("tilt_solve_mode", "fixed") or "").strip().lower()
     if mode in ("", "none", "off", "false", "fixed") or mode not in ("nested", "coupled"):
@@ -460,6 +462,8 @@ def relax_leaflet_tilts(p: Problem, pos: np.ndarray) -> dict:
         gi[fx_in] = 0.0
         go[fx_out] = 0.0
         gnorm = float(np.sqrt(np.sum(gi[~fx_in] ** 2) + np.sum(go[~fx_out] ** 2)))
+        if trace is not None:
+            trace.append(("gnorm", gnorm))
         return E, gi, go, gnorm
 
     def search(E0, sign, d_in, d_out):
@@ -468,6 +472,8 @@ def relax_leaflet_tilts(p: Problem, pos: np.ndarray) -> dict:
             a, b = trial_of(sign * step, d_in, d_out)
             E1 = tilt_dependent_energy_leaflets(p, pos, a, b, va)
             stats["evals"] += 1
+            if trace is not None:
+                trace.append(("trial", float(E0), float(E1)))
             if E1 <= E0:
                 return True, a, b, E1
             step *= 0.5
@@ -595,7 +601,8 @@ def tilt_cg_preconditioner(p: Problem, pos: np.ndarray, fixed_mask: np.ndarray) 
 
 
 # runtime/steppers/tilt_relaxation.py:237-424 relax_tilts (positions frozen)
-def relax_tilts(p: Problem, pos: np.ndarray) -> dict:
+def relax_tilts(p: Problem, pos: np.ndarray, trace: list | None = None) -> dict:
+    """``trace``: as in relax_leaflet_tilts."""
     stats = {"iters": 0, "evals": 0}
     mode = str(p.gp.get("tilt_solve_mode", "fixed") or "").strip().lower()
     if mode in ("", "none", "off", "false", "fixed") or mode not in ("nested", "coupled"):
@@ -642,7 +649,10 @@ def relax_tilts(p: Problem, pos: np.ndarray) -> dict:
         E, tg = energy_and_tilt_gradient(p, pos, t)
         stats["evals"] += 1
         tg[fixed] = 0.0
-        return E, tg, float(np.linalg.norm(tg[~fixed]))
+        gnorm = float(np.linalg.norm(tg[~fixed]))
+        if trace is not None:
+            trace.append(("gnorm", gnorm))
+        return E, tg, gnorm
 
     if solver == "gd":
         for _ in range(max_iters):
@@ -654,6 +664,8 @@ def relax_tilts(p: Problem, pos: np.ndarray) -> dict:
                 trial = trial_of(tilts, -step, tg)
                 E1 = tilt_dependent_energy(p, pos, trial)
                 stats["evals"] += 1
+                if trace is not None:
+                    trace.append(("trial", float(E0), float(E1)))
                 if E1 <= E0:
                     tilts, accepted = trial, True
                     break
@@ -682,6 +694,8 @@ def relax_tilts(p: Problem, pos: np.ndarray) -> dict:
                 trial = trial_of(tilts, step, direction)
                 E1 = tilt_dependent_energy(p, pos, trial)
                 stats["evals"] += 1
+                if trace is not None:
+                    trace.append(("trial", float(E0), float(E1)))
                 if E1 <= E0:
                     tilts, E0, accepted = trial, E1, True
                     break
