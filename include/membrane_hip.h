@@ -683,6 +683,21 @@ int ms_profile_read(ms_ctx *ctx, double total_ms[MS_PROF_KINDS],
  * host replays it from the same doubles), [5] rounds queued for a step that had not started yet (behind the running
  * gradient pass; ms_minimize only), [6] those the step adopted, [7] those dropped. */
 int ms_queue_stats(ms_ctx *ctx, int64_t stats[8]);
+/* Read-only trial log of the most recent ms_step call (a step of ms_minimize's kernel-per-phase path included): one
+ * row per alpha of the backtracking ladder, in the order the loop of runtime/steppers/line_search.py:357-421 sees
+ * them.  Row (MS_TRIAL_COLS doubles): {alpha, trial energy as the host replayed the decision from it, Armijo
+ * right-hand side energy0 + c * alpha * <g,d>, trials of the energy launch that evaluated it (1: a gated stage or a
+ * trial the host decided alone), slot of the trial inside that launch, flags}.  MS_TRIAL_BEHIND: the trial lay behind
+ * the accepted slot of its launch -- evaluated, not part of the search (ms_queue_stats counts these as wasted);
+ * MS_TRIAL_GUARD: the normal-rotation guard rejected the alpha and no energy was taken (the energy column is 0).
+ * The log holds at most that call's max_iter rows; *n_rows is the number logged, of which min(*n_rows, max_rows) are
+ * copied (rows may be NULL when max_rows is 0).  first_launch_hist (may be NULL): since ms_create, the number of
+ * queued rounds whose first launch evaluated 1, 2, ... 8 trials.  Keeping the log changes no launch and no result.
+ * No reference counterpart. */
+#define MS_TRIAL_COLS 6
+#define MS_TRIAL_BEHIND 1
+#define MS_TRIAL_GUARD 2
+int ms_search_trials(ms_ctx *ctx, double *rows, int max_rows, int *n_rows, int64_t first_launch_hist[8]);
 /* The fused gradient + direction pass of ms_step (CG history, no constraint row, single context) does not store the
  * direction when the last direction with history was no descent direction: the step is expected to fail without a
  * trial (conjugate_gradient.py:78-96 then line_search.py:325-328) and the stepper to restart along -g, so nobody

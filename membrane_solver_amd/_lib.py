@@ -40,6 +40,7 @@ MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
 MS_STEPPER_GD, MS_STEPPER_CG = 0, 1
 MS_PIN_LANE_SKIP, MS_PIN_LANE_PROJECT = 0, 1
+MS_TRIAL_COLS, MS_TRIAL_BEHIND, MS_TRIAL_GUARD = 6, 1, 2
 
 (MS_BUF_X, MS_BUF_XT, MS_BUF_G, MS_BUF_GC, MS_BUF_D, MS_BUF_PG, MS_BUF_PD, MS_BUF_FK,
  MS_BUF_FA, MS_BUF_SCAL) = range(10)
@@ -231,6 +232,7 @@ SIGNATURES = {
     "ms_profile_enable": (ctypes.c_int, [_P, ctypes.c_int]),
     "ms_profile_read": (ctypes.c_int, [_P, _D, _I64]),
     "ms_queue_stats": (ctypes.c_int, [_P, _I64]),
+    "ms_search_trials": (ctypes.c_int, [_P, _D, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _I64]),
     "ms_direction_stats": (ctypes.c_int, [_P, _I64, _I64]),
     "ms_exec_stats": (ctypes.c_int, [_P, _I64]),
     "ms_resident_stats": (ctypes.c_int, [_P, _I64]),

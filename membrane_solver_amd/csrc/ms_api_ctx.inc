@@ -201,6 +201,15 @@ struct ms_ctx {
   long queue_mismatches = 0;           // host and device decisions that differed (every one is also a hard error)
   long q_rounds = 0, q_multi = 0, q_wasted = 0, q_side_accepts = 0;  // queue statistics (ms_queue_stats)
   int escalate_after = 3;              // rejections after which a search goes to multi-trial launches (MS_ESCALATE=n)
+  // ms_search_trials: the trials of the most recent ms_step call in the order line_search.py's loop sees them (read
+  // only: what the step had waited for anyway), and how many trials the first launch of every round evaluated
+  struct TrialRow {
+    double alpha, energy, rhs;
+    int launch, slot, flags;
+  };
+  std::vector<TrialRow> trial_log;
+  size_t trial_log_cap = 0;            // that call's max_iter
+  long first_launch_hist[MS_MAX_TRIALS] = {0};
   // multi-trial launch: trials 0 .. n-2 of a ladder are evaluated in the same energy launch as trial n-1
   // (k_energy<MULTI>); the last trial uses the ordinary outputs, early trial j the side set j
   bool pair_enable = true;       // MS_PAIR=0 switches it off

@@ -90,6 +90,26 @@ int ms_queue_stats(ms_ctx* c, int64_t stats[8]) {
   return MS_OK;
 }
 
+int ms_search_trials(ms_ctx* c, double* rows, int max_rows, int* n_rows, int64_t first_launch_hist[8]) {
+  static_assert(MS_MAX_TRIALS == 8, "ms_search_trials: the histogram has one bin per launch size");
+  if (!c || !n_rows || max_rows < 0 || (max_rows > 0 && !rows)) return MS_ERR_INVALID;
+  const int n = (int)c->trial_log.size();
+  *n_rows = n;
+  for (int k = 0; k < std::min(n, max_rows); ++k) {
+    const ms_ctx::TrialRow& t = c->trial_log[(size_t)k];
+    double* r = rows + (size_t)MS_TRIAL_COLS * k;
+    r[0] = t.alpha;
+    r[1] = t.energy;
+    r[2] = t.rhs;
+    r[3] = (double)t.launch;
+    r[4] = (double)t.slot;
+    r[5] = (double)t.flags;
+  }
+  if (first_launch_hist)
+    for (int k = 0; k < MS_MAX_TRIALS; ++k) first_launch_hist[k] = c->first_launch_hist[k];
+  return MS_OK;
+}
+
 int ms_direction_stats(ms_ctx* c, int64_t* skipped, int64_t* materialized) {
   if (!c || !skipped || !materialized) return MS_ERR_INVALID;
   *skipped = c->dir_skipped;

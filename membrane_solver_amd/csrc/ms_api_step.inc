@@ -438,6 +438,8 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   if (!c || !sp || !out) return fail(c, MS_ERR_INVALID, "ms_step: NULL argument");
   if (c->shard_count != 1) return fail(c, MS_ERR_STATE, "ms_step: sharded contexts use the phase API");
   memset(out, 0, sizeof(*out));
+  c->trial_log.clear();  // (ms_search_trials: this call's trials)
+  c->trial_log_cap = (size_t)(sp->max_iter > 0 ? sp->max_iter : 10);
   const bool cg = sp->stepper == MS_STEPPER_CG;
   const int restart = sp->restart_interval > 0 ? sp->restart_interval : 10;
   // conjugate_gradient.py:78-82: steepest descent on first call and every restart
@@ -690,6 +692,10 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       return ms_step(c, sp, step_size, tol, out);
     }
   }
+  // ms_search_trials: one row per alpha of the ladder (launch: trials of the energy launch that evaluated it)
+  auto log_trial = [&](double a, double E_t, double rhs_t, int launch, int slot, int flags) {
+    if (c->trial_log.size() < c->trial_log_cap) c->trial_log.push_back({a, E_t, rhs_t, launch, slot, flags});
+  };
   int it = 0;
   bool unchained_ran = false;  // a trial went through the context's own mailbox (its scalars replaced x's there)
   const bool s_maxg2_x = c->carry.maxg2_valid;
@@ -715,6 +721,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       if (rc) return rc;
       if (!safe_small && c->h_scal[MS_S_GUARD] > 0.0) {
         ++out->guard_rejects;
+        log_trial(alpha, 0.0, energy0 + sp->c * alpha * g_dot_d, 1, 0, MS_TRIAL_GUARD);
         min_rejected = alpha;
         alpha *= sp->beta;
         ++it;
@@ -747,6 +754,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       ++out->trials;
       energies_from_mailbox(c, e);
       const double E_t = e[0] + e[1] + e[2] + e[3];
+      log_trial(alpha, E_t, energy0 + sp->c * alpha * g_dot_d, 1, 0, 0);
       if (E_t <= energy0 + sp->c * alpha * g_dot_d) {
         accept(alpha, E_t);
         return MS_OK;
@@ -791,6 +799,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     double rhs[MS_MAX_TRIALS + ms_ctx::SPEC_STAGES];
     for (int j = 0; j < n_round; ++j) rhs[j] = energy0 + sp->c * alphas[j] * g_dot_d;
     ++c->q_rounds;
+    ++c->first_launch_hist[n0 - 1];
     // ---- take the results in order, replaying the device's decisions from the same doubles --------------------
     // first launch: every set was folded by ONE k_reduce launch, so they land together
     double v[MS_MAX_TRIALS][MS_NSCAL];
@@ -806,6 +815,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     for (int j = 0; j < n0 && acc < 0; ++j) {
       ++out->trials;
       const double E_t = stage_energy(c, v[j]);
+      log_trial(alphas[j], E_t, rhs[j], n0, j, 0);
       if (E_t <= rhs[j]) {
         acc = j;
         E_acc = E_t;
@@ -813,6 +823,8 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
         min_rejected = alphas[j];
       }
     }
+    // (the trials of the launch behind its accepted one are not part of the search: evaluated, never looked at)
+    for (int j = acc + 1; acc >= 0 && j < n0; ++j) log_trial(alphas[j], stage_energy(c, v[j]), rhs[j], n0, j, MS_TRIAL_BEHIND);
     rc = verify_decision(c, acc < 0 ? DEC_CONTINUE : (acc == n0 - 1 ? DEC_ACCEPT_MAIN : DEC_ACCEPT_SIDE), dev_code,
                          "the first launch of a round");
     if (rc) return rc;
@@ -868,6 +880,7 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
       if (rc) return rc;
       ++out->trials;
       const double E_t = stage_energy(c, vals);
+      log_trial(alphas[n0 + s2 - 1], E_t, rhs[n0 + s2 - 1], 1, 0, 0);
       const bool ok = E_t <= rhs[n0 + s2 - 1];
       rc = verify_decision(c, ok ? DEC_ACCEPT_MAIN : DEC_CONTINUE, code, "a gated stage");
       if (rc) return rc;

@@ -663,6 +663,24 @@ class DeviceMesh:
                 "side_accepts": int(v[3]), "mismatches": int(v[4]), "ahead": int(v[5]), "adopted": int(v[6]),
                 "dropped": int(v[7])}
 
+    def search_trials(self):
+        """Trial log of the most recent step (include/membrane_hip.h, ms_search_trials):
+        -> {alpha, energy, rhs (float arrays), launch, slot (int arrays), behind, guard (bool arrays), one entry per
+        logged trial in ladder order; first_launch_hist: {trials of a round's first launch: rounds since creation}}."""
+        lib = L.lib()
+        n = ctypes.c_int(0)
+        hist = np.zeros(8, dtype=np.int64)
+        self._chk(lib.ms_search_trials(self._h, None, 0, ctypes.byref(n), hist.ctypes.data_as(L._I64)),
+                  "ms_search_trials")
+        rows = np.zeros((max(n.value, 1), L.MS_TRIAL_COLS))
+        self._chk(lib.ms_search_trials(self._h, _pd(rows), rows.shape[0], ctypes.byref(n), None), "ms_search_trials")
+        rows = rows[: n.value]
+        flags = rows[:, 5].astype(np.int64)
+        return {"alpha": rows[:, 0].copy(), "energy": rows[:, 1].copy(), "rhs": rows[:, 2].copy(),
+                "launch": rows[:, 3].astype(np.int64), "slot": rows[:, 4].astype(np.int64),
+                "behind": (flags & L.MS_TRIAL_BEHIND) != 0, "guard": (flags & L.MS_TRIAL_GUARD) != 0,
+                "first_launch_hist": {k + 1: int(hist[k]) for k in range(8)}}
+
     def direction_stats(self):
         """Fused direction passes that left D unstored, and directions written out afterwards (ms_direction_stats)."""
         v = np.zeros(2, dtype=np.int64)
