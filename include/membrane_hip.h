@@ -94,6 +94,14 @@ extern "C" {
  * tilt-magnitude slot (MS_S_ETILT_OUT, energies[3]) behind the passes that write it: no reduction slot of its own.
  * Reads both leaflet fields; single context only; not together with a single-field tilt module. */
 #define MS_MOD_TILT_COUPLING 2097152u
+/* split splay / twist tilt-gradient energy of the inner leaflet (modules/energy/tilt_splay_twist_in.py:113-252,
+ * ambient_v1 transport, native divergence): per facet n = (v1 - v0) x (v2 - v0), g_k = (n x e_k) / max(n.n, 1e-20),
+ * div = sum t_k . g_k, curl_n = (sum g_k x t_k) . n_hat, E = 1/2 sum A_f (k_splay div^2 + k_twist curl_n^2); tilt
+ * gradient A_f k_splay div g_k + A_f k_twist curl_n (n_hat x g_k); no shape gradient.  The moduli come from
+ * ms_set_tilt_splay_twist.  Its sums are added into the inner leaflet's smoothness slot (MS_S_ETS_IN, energies[3])
+ * behind the pass that writes it: no reduction slot of its own.  Single context only; not together with a single-field
+ * tilt module, nor with pins or the volume enforcer on the line search. */
+#define MS_MOD_TILT_SPLAY_TWIST_IN 4194304u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -428,6 +436,16 @@ int ms_set_tilt_coupling(ms_ctx *ctx, double modulus, int sign);
 int ms_get_tilt_coupling_energy(ms_ctx *ctx, double *energy);
 /* launches so far: {k_couple<0>, k_couple<1>, k_couple_vec} */
 int ms_tilt_coupling_stats(ms_ctx *ctx, double stats[3]);
+/* tilt_splay_twist_in: the moduli k_splay (tilt_splay_modulus_in, else bending_modulus_in, else bending_modulus) and
+ * k_twist (tilt_twist_modulus_in, else tilt_twist_modulus, else 0), finite and non-negative.  Both 0: the bit
+ * contributes exactly nothing.  Takes effect when MS_MOD_TILT_SPLAY_TWIST_IN is in ms_params.modules.  Single context
+ * only. */
+int ms_set_tilt_splay_twist(ms_ctx *ctx, double k_splay, double k_twist);
+/* the module's own energy as its LAST LAUNCH summed it, whatever that launch evaluated (ms_get_tilt_coupling_energy's
+ * caveat holds): run ms_energy first to read it for the stored state (its sums are also part of energies[3]). */
+int ms_get_tilt_splay_twist_energy(ms_ctx *ctx, double *energy);
+/* launches so far: {k_splay<0>, k_splay<1>} */
+int ms_tilt_splay_twist_stats(ms_ctx *ctx, double stats[2]);
 /* per-vertex (kappa, c0) of bending_tilt_in / bending_tilt_out (modules/energy/bt_params.py:225-318:
  * bending_modulus_in|out else bending_modulus; spontaneous_curvature_in|out else the global one) */
 int ms_set_leaflet_bending(ms_ctx *ctx, int leaflet, const double *kappa /* nv */, const double *c0 /* nv */);

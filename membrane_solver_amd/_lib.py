@@ -35,6 +35,7 @@ MS_MOD_LINE_TENSION = 131072
 MS_MOD_EDGE_LENGTH_PENALTY = 262144
 MS_MOD_TILT_RIM_SOURCE_IN, MS_MOD_TILT_RIM_SOURCE_OUT = 524288, 1048576
 MS_MOD_TILT_COUPLING = 2097152
+MS_MOD_TILT_SPLAY_TWIST_IN = 4194304
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
@@ -178,6 +179,9 @@ SIGNATURES = {
     "ms_set_tilt_coupling": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int]),
     "ms_get_tilt_coupling_energy": (ctypes.c_int, [_P, _D]),
     "ms_tilt_coupling_stats": (ctypes.c_int, [_P, _D]),
+    "ms_set_tilt_splay_twist": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_double]),
+    "ms_get_tilt_splay_twist_energy": (ctypes.c_int, [_P, _D]),
+    "ms_tilt_splay_twist_stats": (ctypes.c_int, [_P, _D]),
     "ms_leaflet_tilt_energy_and_gradient": (ctypes.c_int, [_P, _D, _D, _D]),
     "ms_leaflet_tilt_energy_and_gradient_ex": (ctypes.c_int, [_P, ctypes.c_int, _D, _D, _D]),
     "ms_relax_leaflet_tilts": (ctypes.c_int, [_P, ctypes.POINTER(ms_tilt_relax_params),

@@ -130,9 +130,13 @@ struct ms_ctx {
     // slot (mod_cpl_slot on that field only)
     uint32_t mod_cpl = 0, mod_cpl_slot = 0;
     // every module bit that reads this leaflet field
-    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl; }
+    // tilt_splay_twist_in reads the inner leaflet's field; its energy rides in that field's smoothness slot
+    uint32_t mod_st = 0;
+    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl | mod_st; }
     // every module bit whose sums land in this field's tilt-magnitude slot (s_etilt)
     uint32_t etilt_mods() const { return mod_tilt | mod_rs | mod_cpl_slot; }
+    // every module bit whose sums land in this field's smoothness slot (s_ets)
+    uint32_t ets_mods() const { return mod_smooth | mod_st; }
     bool any_free = true;     // some row of this field is not clamped (kept current by the flag setters)
     double* va = nullptr;      // relaxation: barycentric vertex areas of the frozen positions
   } tf[3];
@@ -143,6 +147,11 @@ struct ms_ctx {
   void* d_cpl = nullptr;
   long cpl_launches[3] = {0, 0, 0};  // k_couple<0>, k_couple<1>, k_couple_vec
   bool cpl_force_tile = false;       // MS_COUPLE_VEC=0: the frozen form through the tile kernel as well (A/B)
+  // tilt_splay_twist_in (ms_set_tilt_splay_twist): the two moduli; d_st holds the per-workgroup sums of the last launch
+  double st_k_splay = 0.0, st_k_twist = 0.0;
+  bool st_set = false;
+  void* d_st = nullptr;
+  long st_launches[2] = {0, 0};  // k_splay<0>, k_splay<1>
   CarryState carry;
   bool precond = false;      // ms_stepper_params.precondition of the step in progress (CG only)
   // speculative line-search ladder (ms_step): when the last accepted step needed n > 1 Armijo trials, the next

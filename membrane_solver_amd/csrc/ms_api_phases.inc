@@ -30,6 +30,10 @@ int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const 
 enum { CPL_CELL_AUTO = -1, CPL_CELL_LEAVE = 0, CPL_CELL_ADD = 1 };
 int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gradient_into_g, bool tilt_gradients,
                 bool trial_tilts, int cell = CPL_CELL_AUTO, double* g_out = nullptr);
+// tilt_splay_twist_in: 1/2 A_f (k_splay div^2 + k_twist curl_n^2) of x (+ alpha d) and `tilts` into the inner leaflet's
+// smoothness partials, behind the smoothness pass where both run (ms_api_splay.inc).  tilt_grad: dE/dt ADDED there, or
+// nullptr (energy only).  The cells are ADDED to when tilt_smoothness_in's pass defined them, DEFINED otherwise
+int splay_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const double* tilts, double* tilt_grad);
 inline int exec_flush(ms_ctx* c) {
   if (!c->exec_on) return MS_OK;
   const hipError_t e = c->exec.flush();
@@ -170,7 +174,7 @@ constexpr uint32_t MS_LEAFLET_DT = MS_MOD_TILT_DISK_TARGET_IN | MS_MOD_TILT_DISK
 // the rim sources: no slot of their own (MS_NSCAL is full) -- their sums ride in the leaflet's tilt-magnitude slot -- and no
 // shape gradient, so they are not in MS_TILT_SHAPE_MODS
 constexpr uint32_t MS_LEAFLET_RS = MS_MOD_TILT_RIM_SOURCE_IN | MS_MOD_TILT_RIM_SOURCE_OUT;
-constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING;
+constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN;
 constexpr uint32_t MS_ANY_TILT_MODS = MS_TILT_MODS | MS_LEAFLET_MODS;
 // the edge modules: energy added into the MS_S_ESURF partials behind the energy pass, gradient into G behind K_C; they
 // share one lane of the step (one trial per launch, every Armijo decision the host's, the separate direction pass)
@@ -782,7 +786,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   for (int l = 1; l <= 2 && (modules & MS_LEAFLET_MODS); ++l) {  // leaflet fields, same protocol
     TiltField& f = c->tf[l];
     // (the coupling alone is reason enough: its trial energy is taken with BOTH leaflets projected onto the trial surface)
-    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl))) continue;
+    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st))) continue;
     int rc = MS_OK;
     const double* tilts = f.tilts;
     if (use_dir) {
@@ -814,6 +818,10 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   // tilt_coupling: behind the rim source of the outer leaflet (the order of the adds into a cell is fixed)
   if (modules & MS_MOD_TILT_COUPLING)
     if (int rc_c = couple_pass(c, modules, use_dir, alpha, false, false, /*trial_tilts=*/use_dir)) return rc_c;
+  // tilt_splay_twist_in: behind the inner leaflet's smoothness pass (k_tsmooth<0> above, or the one launch of
+  // tilt_energy_pass), at x and at every trial with the tilts projected onto it
+  if (modules & c->tf[1].mod_st)
+    if (int rc_s = splay_pass(c, modules, use_dir, alpha, use_dir ? c->tf[1].trial : c->tf[1].tilts, nullptr)) return rc_s;
   if (reduce_now) {
     constexpr uint32_t core = (1u << MS_S_ESURF) | (1u << MS_S_VOL) | (1u << MS_S_EBEND) | (1u << MS_S_MINEDGE2) |
                               (1u << MS_S_GUARD);
@@ -963,6 +971,8 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
     if (rc) return rc;
     added_after = true;
   }
+  // tilt_splay_twist_in: no shape gradient to add, and no pass above rewrites the inner leaflet's smoothness cells
+  // (k_tsmooth has no shape gradient either): they still hold this evaluation's sums and are LEFT as they are
   // the gradient kernel's <g, gC> partials predate those additions: take them again of the complete gradient
   if (added_after && g_out && (modules & MS_CON_VOLUME))
     HIPCHK(c, launch_row_dot(c->tile0, c->tile1, c->til.nv, c->til.own, g_out, c->buf[MS_BUF_GC], c->d_partials,
@@ -1151,7 +1161,7 @@ void energies_from_mailbox(const ms_ctx* c, double e[4]) {
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
     if (c->params.modules & f.etilt_mods()) e[3] += c->h_scal[f.s_etilt];  // (the rim source and the coupling ride in this slot)
-    if (c->params.modules & f.mod_smooth) e[3] += c->h_scal[f.s_ets];
+    if (c->params.modules & f.ets_mods()) e[3] += c->h_scal[f.s_ets];  // (the splay / twist term rides in this slot)
     if (c->params.modules & f.mod_bt) e[1] += c->h_scal[f.s_ebt];
     if (c->params.modules & f.mod_dt) e[3] += c->h_scal[f.s_edt];
   }

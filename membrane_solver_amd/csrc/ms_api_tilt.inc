@@ -71,6 +71,12 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
       if (rc) return rc;
       mask |= 1u << f.s_ets;
     }
+    if (mods & f.mod_st) {
+      // behind the smoothness pass (its partials) and every pass above that adds into f.grad
+      rc = splay_pass(c, mods, false, 0.0, tilts, gradient ? f.grad : nullptr);
+      if (rc) return rc;
+      mask |= 1u << f.s_ets;
+    }
     if (mods & f.mod_rs) {
       // behind the magnitude pass (its partials, its rows of f.grad) and every other pass that adds into f.grad
       rc = rim_pass(c, f, false, 0.0, tilts, gradient);
@@ -94,7 +100,7 @@ double tilt_energy_from(const ms_ctx* c, const double* hs) {
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
     if (c->params.modules & f.etilt_mods()) e += hs[f.s_etilt];  // (tilt magnitude + rim source + coupling)
-    if (c->params.modules & f.mod_smooth) e += hs[f.s_ets];
+    if (c->params.modules & f.ets_mods()) e += hs[f.s_ets];  // (smoothness + splay / twist)
     if (c->params.modules & f.mod_bt) e += hs[f.s_ebt];
     if (c->params.modules & f.mod_dt) e += hs[f.s_edt];
   }
@@ -115,8 +121,8 @@ bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs
     const bool tilt_on = single ? (mods & MS_MOD_TILT) != 0 : (mods & f.mod_tilt) != 0;
     const bool bt_on = single ? (mods & MS_MOD_BENDING_TILT) != 0 : (mods & f.mod_bt) != 0;
     const bool ts_on = single ? (mods & MS_MOD_TILT_SMOOTH) != 0 : (mods & f.mod_smooth) != 0;
-    // (the disk target, the rim source and the coupling keep their own passes)
-    if (!single && (mods & (f.mod_dt | f.mod_rs | f.mod_cpl))) return false;
+    // (the disk target, the rim source, the coupling and the splay / twist term keep their own passes)
+    if (!single && (mods & (f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st))) return false;
     o.tilts = f.tilts;
     o.src = along_dir ? f.dir : f.grad;
     o.bt_vert = nullptr;
@@ -331,7 +337,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
       q.has_ts = (mods & f.mod_smooth) ? 1 : 0;
       q.has_dt = (mods & f.mod_dt) ? 1 : 0;
       q.fixed_bit = f.fixed_bit;
-      ok = ok && !(mods & (f.mod_rs | f.mod_cpl)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
+      ok = ok && !(mods & (f.mod_rs | f.mod_cpl | f.mod_st)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
            (!q.has_dt || (f.dt_target && f.disk && f.dt_target_valid));
     }
     const size_t need = relax_fused_lds_bytes(c->cap, t.max_ent, t.max_tile_facets);
@@ -451,7 +457,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
     for (int l = 1; l <= 2; ++l) {
       const TiltField& f = c->tf[l];
       if (mods & f.etilt_mods()) head.e_slot[n++] = f.s_etilt;
-      if (mods & f.mod_smooth) head.e_slot[n++] = f.s_ets;
+      if (mods & f.ets_mods()) head.e_slot[n++] = f.s_ets;
       if (mods & f.mod_bt) head.e_slot[n++] = f.s_ebt;
       if (mods & f.mod_dt) head.e_slot[n++] = f.s_edt;
     }
@@ -753,8 +759,8 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     if (r || used) return r;
     return search(along_dir, sign, E0, E_acc, accepted);
   };
-  // (the rim source's and the coupling's kernels are not recorded)
-  if (c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_COUPLING))) {
+  // (the rim source's, the coupling's and the splay / twist term's kernels are not recorded)
+  if (c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN))) {
     // one-tile context: the whole solve below as ONE launch (ms_internal.h: ExecRelaxHead)
     bool used = false;
     rc = relax_program(c, rp, fl, nf, norm_mask, &iters, &evals, &used);

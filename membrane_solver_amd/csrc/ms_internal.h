@@ -451,6 +451,24 @@ struct CoupleArgs {
 size_t couple_lds_bytes(int T, int cap, int max_ent, int mode);
 hipError_t launch_couple(const CoupleArgs& a, int mode, int cap, int max_ent, hipStream_t s);
 hipError_t launch_couple_vec(const CoupleArgs& a, int with_grad, hipStream_t s);
+// tilt_splay_twist_in (ms_splay.hip): E = 1/2 sum_f A_f (k_splay div^2 + k_twist curl_n^2) of the inner leaflet's tilts,
+// k_tsmooth's data flow.  k_splay<0/1> per tile on x (+ alpha d).
+struct SplayArgs {
+  DeviceMesh m;
+  int tile0, tile1;
+  const double* x;
+  const double* d;        // trial direction or nullptr, alpha: exactly what TsArgs hands k_tsmooth
+  double alpha;
+  const double* tilts;    // (nvp,3) the inner leaflet's tilts
+  double k_splay, k_twist;
+  double* tilt_grad;      // k_splay<1>: dE/dt ADDED here
+  double* partials;       // the tile's cell [slot * n_tiles + tile] ...
+  int slot, cell_mode;    // ... 0 left alone, 1 added to (a pass before this one defined it), 2 defined
+  double* wg_sums;        // [tile1 - tile0] per-workgroup sums: the module's own energy is their sum in index order,
+                          // taken on the host when asked for (ms_get_tilt_splay_twist_energy)
+};
+size_t splay_lds_bytes(int T, int cap, int max_ent, int mode);
+hipError_t launch_splay(const SplayArgs& a, int mode, int cap, int max_ent, hipStream_t s);
 struct RowDotArgs {
   int tile0, nv, T;
   const double* g;

@@ -3807,6 +3807,7 @@ hipError_t launch_curvature_raw(int nv, int nf, const double* pos, const int32_t
 #include "ms_exec.inc"
 #include "ms_resident.inc"
 #include "ms_couple.hip"  // tilt_coupling: k_couple<0/1>, k_couple_vec (they use the tile helpers above)
+#include "ms_splay.hip"  // tilt_splay_twist_in: k_splay<0/1> (likewise)
 
 }  // namespace ms
 #if MS_GATE_PROBE

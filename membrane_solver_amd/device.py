@@ -362,6 +362,23 @@ class DeviceMesh:
         self._chk(L.lib().ms_tilt_coupling_stats(self._h, _pd(v)), "ms_tilt_coupling_stats")
         return {"energy_launches": int(v[0]), "gradient_launches": int(v[1]), "vec_launches": int(v[2])}
 
+    def set_tilt_splay_twist(self, k_splay: float, k_twist: float):
+        """tilt_splay_twist_in: the splay and twist moduli, finite and non-negative (ms_set_tilt_splay_twist)."""
+        self._chk(L.lib().ms_set_tilt_splay_twist(self._h, float(k_splay), float(k_twist)), "ms_set_tilt_splay_twist")
+
+    def tilt_splay_twist_energy(self) -> float:
+        """The splay / twist term's own energy as its last launch summed it, whatever that launch evaluated
+        (ms_get_tilt_splay_twist_energy); call energy() first to read it for the stored state."""
+        e = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_get_tilt_splay_twist_energy(self._h, ctypes.byref(e)), "ms_get_tilt_splay_twist_energy")
+        return float(e.value)
+
+    def tilt_splay_twist_stats(self):
+        """Launch counts of the splay / twist kernels (ms_tilt_splay_twist_stats)."""
+        v = np.zeros(2)
+        self._chk(L.lib().ms_tilt_splay_twist_stats(self._h, _pd(v)), "ms_tilt_splay_twist_stats")
+        return {"energy_launches": int(v[0]), "gradient_launches": int(v[1])}
+
     def get_leaflet_tilts(self, leaflet: str) -> np.ndarray:
         out = np.empty((self.nv, 3), dtype=np.float64)
         lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]

@@ -493,6 +493,81 @@ def evaluate_coupling(mesh, global_params, param_resolver, *, positions, tilts_i
     return E
 
 
+def splay_twist_params(param_resolver, global_params):
+    """(k_splay, k_twist, divergence mode) of tilt_splay_twist_in (modules/energy/tilt_splay_twist_in.py:16-50), in the
+    reference's order: ``tilt_splay_modulus_in`` else ``bending_modulus_in`` else ``bending_modulus`` (the fallback is
+    taken on None only: an explicit 0.0 stays 0); ``tilt_twist_modulus_in`` else ``tilt_twist_modulus`` else 0; a
+    negative modulus raises ValueError; ``tilt_divergence_mode_in`` else ``tilt_divergence_mode``, default native,
+    anything but native / vertex_recovered raises ValueError."""
+    val = _get(param_resolver, global_params, "tilt_splay_modulus_in")
+    if val is None:
+        val = _get(param_resolver, global_params, "bending_modulus_in")
+    if val is None:
+        val = _get(param_resolver, global_params, "bending_modulus")
+    k_splay = float(val or 0.0)
+    if k_splay < 0.0:
+        raise ValueError("tilt_splay_modulus_in must be non-negative.")
+    val = _get(param_resolver, global_params, "tilt_twist_modulus_in")
+    if val is None:
+        val = _get(param_resolver, global_params, "tilt_twist_modulus")
+    k_twist = float(val or 0.0)
+    if k_twist < 0.0:
+        raise ValueError("tilt_twist_modulus_in must be non-negative.")
+    val = _get(param_resolver, global_params, "tilt_divergence_mode_in")
+    if val is None:
+        val = _get(param_resolver, global_params, "tilt_divergence_mode")
+    mode = str(val or "native").strip().lower()
+    if mode not in {"native", "vertex_recovered"}:
+        raise ValueError("tilt_divergence_mode_in must be 'native' or 'vertex_recovered'.")
+    return k_splay, k_twist, mode
+
+
+def splay_twist_device_params(param_resolver, global_params):
+    """(k_splay, k_twist) for DeviceMesh.set_tilt_splay_twist, or None when the module contributes nothing (both moduli
+    0: tilt_splay_twist_in.py:134-135).  Everything is resolved before that early return, as in the reference (:128-133):
+    a bad mode or transport model raises with both moduli 0 as well.  The vertex_recovered divergence is not on the
+    device path."""
+    k_splay, k_twist, mode = splay_twist_params(param_resolver, global_params)
+    check_supported(global_params if global_params is not None else {})
+    if k_splay == 0.0 and k_twist == 0.0:
+        return None
+    if mode != "native":
+        raise L.MembraneHipError(f"tilt_splay_twist_in with tilt_divergence_mode {mode!r} is outside the HIP hot path "
+                                 "(only the native divergence is on the device)")
+    return k_splay, k_twist
+
+
+def evaluate_splay_twist(mesh, global_params, param_resolver, *, positions, tilts_in, tilt_in_grad_arr) -> float:
+    """tilt_splay_twist_in on caller arrays (H2D/D2H per call: the parity seam, not the hot loop): energy; tilt gradient
+    ADDED into ``tilt_in_grad_arr`` (optional).  No shape gradient: the caller's ``grad_arr`` is never touched."""
+    prm = splay_twist_device_params(param_resolver, global_params)
+    if prm is None:
+        return 0.0
+    tri, _f = mesh.triangle_row_cache()
+    if tri is None or len(tri) == 0:
+        return 0.0
+    nv = len(mesh.vertex_ids)
+    if tilts_in is None:
+        tilts_in = mesh.tilts_in_view()
+    tilts_in = np.ascontiguousarray(tilts_in, dtype=np.float64)
+    if tilts_in.shape != (nv, 3):
+        raise ValueError("tilts_in must have shape (N_vertices, 3)")
+    if tilt_in_grad_arr is not None and np.shape(tilt_in_grad_arr) != (nv, 3):
+        raise ValueError("tilt_in_grad_arr must have shape (N_vertices, 3)")
+    mir = mirror_for(mesh)
+    dm = mir.sync(positions=None if positions is mesh.positions_view() else positions)
+    dm.set_leaflet_tilts("in", tilts_in, tilt_modulus=0.0, smoothness=0.0)
+    dm.set_leaflet_tilts("out", np.zeros((nv, 3)), tilt_modulus=0.0, smoothness=0.0)
+    mir._leaflet_keys = {}  # foreign arrays were uploaded
+    dm.set_tilt_splay_twist(*prm)
+    dm.set_params(modules=L.MS_MOD_TILT_SPLAY_TWIST_IN)
+    if tilt_in_grad_arr is None:
+        return float(dm.energy()[3])
+    E, gi, _go = dm.leaflet_tilt_energy_and_gradient(want_gradient=True)
+    tilt_in_grad_arr += gi
+    return float(E)
+
+
 def check_bt_supported(global_params) -> None:
     mode = str(global_params.get("bending_gradient_mode", "analytic") or "analytic").strip().lower()
     if mode != "analytic":

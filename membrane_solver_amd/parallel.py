@@ -343,6 +343,9 @@ class HipShardBackend:
         if modules & L.MS_MOD_TILT_COUPLING:
             raise L.MembraneHipError("the tilt_coupling module is not sharded (single GPU only; ms_set_params refuses "
                                      "it on a sharded context as well)")
+        if modules & L.MS_MOD_TILT_SPLAY_TWIST_IN:
+            raise L.MembraneHipError("the tilt_splay_twist_in module is not sharded (single GPU only; ms_set_params "
+                                     "refuses it on a sharded context as well)")
         tilt_bits = modules & ~(L.MS_MOD_SURFACE | L.MS_MOD_BENDING | L.MS_MOD_VOLUME_PENALTY | L.MS_CON_VOLUME
                                 | getattr(L, "MS_TRACK_VOLUME", 0))
         if tilt_bits:

@@ -72,7 +72,7 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "body_area_penalty": L.MS_MOD_AREA_PENALTY, "line_tension": L.MS_MOD_LINE_TENSION,
                 "edge_length_penalty": L.MS_MOD_EDGE_LENGTH_PENALTY,
                 "tilt_rim_source_in": L.MS_MOD_TILT_RIM_SOURCE_IN, "tilt_rim_source_out": L.MS_MOD_TILT_RIM_SOURCE_OUT,
-                "tilt_coupling": L.MS_MOD_TILT_COUPLING,
+                "tilt_coupling": L.MS_MOD_TILT_COUPLING, "tilt_splay_twist_in": L.MS_MOD_TILT_SPLAY_TWIST_IN,
                 # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
                 # accepted in its switched-off state (strength 0, as in the caveolin decks)
                 "gaussian_curvature": 0, "rim_slope_match_out": 0}
@@ -83,14 +83,17 @@ _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_til
                 # (their sums ride in the leaflet's tilt-magnitude slot of energies[3]; each reports its own energy)
                 "tilt_rim_source_in": None, "tilt_rim_source_out": None,
                 # (its sums ride in the outer leaflet's tilt-magnitude slot; it reports its own energy)
-                "tilt_coupling": None}
+                "tilt_coupling": None,
+                # (its sums ride in the inner leaflet's smoothness slot; it reports its own energy)
+                "tilt_splay_twist_in": None}
 _RIM_MODULES = ("tilt_rim_source_in", "tilt_rim_source_out")
 _EDGE_MODULES = ("line_tension", "edge_length_penalty")  # they share the lane behind the energy and the gradient pass
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
 _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
                  | _LEAFLET_BT_BITS | L.MS_MOD_TILT_DISK_TARGET_IN | L.MS_MOD_TILT_DISK_TARGET_OUT
-                 | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING)
+                 | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING
+                 | L.MS_MOD_TILT_SPLAY_TWIST_IN)
 _TILT_BITS = _SINGLE_TILT_BITS | _LEAFLET_BITS
 # scalar slot of every module that shares energies[3]
 _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": L.MS_S_ETILT_IN,
@@ -198,7 +201,7 @@ class Minimizer:
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
                     "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
                     "body_area_penalty, line_tension, edge_length_penalty, tilt_rim_source_in, tilt_rim_source_out, "
-                    "tilt_coupling)")
+                    "tilt_coupling, tilt_splay_twist_in)")
         if "body_area_penalty" in self.energy_module_names and any(
                 _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
             raise L.MembraneHipError("body_area_penalty together with tilt modules is outside the HIP hot path")
@@ -259,6 +262,7 @@ class Minimizer:
         disk_params = {}
         rim_params = {}
         coupling = None
+        splay_twist = None
         vol_mode = gp.get("volume_constraint_mode", "lagrange")
         area_params = None
         for name in self.energy_module_names:
@@ -309,6 +313,10 @@ class Minimizer:
                 coupling = _lc.coupling_params(self.param_resolver, gp)
                 if coupling is not None:  # tilt_coupling.py:129-132: unknown or absent mode, or k_c == 0
                     mods |= _ENERGY_BITS[name]
+            elif name == "tilt_splay_twist_in":
+                splay_twist = _lc.splay_twist_device_params(self.param_resolver, gp)
+                if splay_twist is not None:  # tilt_splay_twist_in.py:134-135: both moduli 0
+                    mods |= _ENERGY_BITS[name]
             else:
                 mods |= _ENERGY_BITS[name]
         target = 0.0
@@ -357,6 +365,16 @@ class Minimizer:
             mir.upload_surface_tension()
         if any_bend:
             mir.upload_bending_params(gp, model)
+        if mods & L.MS_MOD_TILT_SPLAY_TWIST_IN:
+            if mods & _SINGLE_TILT_BITS:
+                raise L.MembraneHipError("tilt_splay_twist_in together with a single-field tilt module is outside the "
+                                         "HIP hot path")
+            if self._pin_names:
+                raise L.MembraneHipError("tilt_splay_twist_in next to pin_to_plane / pin_to_circle is outside the HIP "
+                                         "hot path")
+            if "volume" in self.constraint_module_names:
+                raise L.MembraneHipError("tilt_splay_twist_in next to the volume constraint's enforcer is outside the "
+                                         "HIP hot path")
         if (mods & _SINGLE_TILT_BITS) and (mods & _LEAFLET_BITS):
             raise L.MembraneHipError("single-field and leaflet tilt modules together are outside the HIP hot path")
         if mods & _LEAFLET_BITS:
@@ -379,6 +397,11 @@ class Minimizer:
                 if mir._leaflet_keys.get("bend_coupling") != key:
                     dm.set_tilt_coupling(*coupling)
                     mir._leaflet_keys["bend_coupling"] = key
+            if splay_twist is not None:  # keyed on the two moduli ("bend_": not a tilt upload)
+                key = (id(dm), splay_twist)
+                if mir._leaflet_keys.get("bend_splay_twist") != key:
+                    dm.set_tilt_splay_twist(*splay_twist)
+                    mir._leaflet_keys["bend_splay_twist"] = key
             if mods & _LEAFLET_BT_BITS:
                 _lc.check_bt_supported(gp)
                 if mods & (L.MS_MOD_BENDING | L.MS_MOD_BENDING_TILT):
@@ -513,6 +536,10 @@ class Minimizer:
         cpl_e = dm.tilt_coupling_energy() if dm.modules & L.MS_MOD_TILT_COUPLING else 0.0
         if "tilt_coupling" in out:
             out["tilt_coupling"] = cpl_e
+        # the splay / twist term rides in the inner leaflet's smoothness slot in the same way
+        st_e = dm.tilt_splay_twist_energy() if dm.modules & L.MS_MOD_TILT_SPLAY_TWIST_IN else 0.0
+        if "tilt_splay_twist_in" in out:
+            out["tilt_splay_twist_in"] = st_e
         for table in (_TILT_SCALAR, _BEND_SCALAR):
             sharing = [n for n in out if n in table]
             if len(sharing) > 1:  # they share one entry of the energy vector: split via the scalars
@@ -521,8 +548,10 @@ class Minimizer:
                     out[n] = float(sc[table[n]]) if dm.modules & _ENERGY_BITS[n] else 0.0
                     if n in ("tilt_in", "tilt_out") and dm.modules & _ENERGY_BITS[n]:
                         out[n] -= rim_e[n[5:]] + (cpl_e if n == "tilt_out" else 0.0)
-            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e):
-                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e
+                    if n == "tilt_smoothness_in" and dm.modules & _ENERGY_BITS[n]:
+                        out[n] -= st_e
+            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e or st_e):
+                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e - st_e
         return out
 
     # -- constraint enforcement (minimizer.py:1103-1188) ---------------------------
