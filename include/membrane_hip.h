@@ -102,6 +102,15 @@ extern "C" {
  * behind the pass that writes it: no reduction slot of its own.  Single context only; not together with a single-field
  * tilt module, nor with pins or the volume enforcer on the line search. */
 #define MS_MOD_TILT_SPLAY_TWIST_IN 4194304u
+/* soft contact term on an inclusion rim that drives the bilayer boundary mode theta_B = theta_in + theta_out
+ * (modules/energy/tilt_rim_source_bilayer.py:416-515): E = -sum gamma L (1/2 (t_in,tail + t_in,head) +
+ * 1/2 (t_out,tail + t_out,head)) . r_hat over the rim edges; the same vector -1/2 gamma L r_hat goes into BOTH tilt
+ * gradients at both ends; no shape gradient.  The edges, their gamma and the circle's frame come from
+ * ms_set_rim_source_bilayer: one table and one apply pass serve both fields.  Its sums are added into the outer leaflet's
+ * tilt-magnitude slot (MS_S_ETILT_OUT, energies[3]) behind the passes that write it (tilt_out, tilt_rim_source_out) and
+ * ahead of tilt_coupling: no reduction slot of its own.  Reads both leaflet fields; single context only; not together
+ * with a single-field tilt module. */
+#define MS_MOD_TILT_RIM_SOURCE_BILAYER 8388608u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -426,6 +435,16 @@ int ms_leaflet_rim_source_stats(ms_ctx *ctx, int leaflet, double stats[3]);
 int ms_rim_source_tables_host(int nv, const int32_t *iperm, int n_edges, const int32_t *tail, const int32_t *head,
                               const double *gamma, int32_t counts[2], int32_t *vrow, int32_t *off, int32_t *other,
                               double *csr_gamma);
+/* tilt_rim_source_bilayer: ms_set_leaflet_rim_source's tables, checks and frame rules (ms_rim_source_params), kept once per
+ * context and applied to both leaflet fields in one pass.  tail == NULL clears the tables.  Takes effect when
+ * MS_MOD_TILT_RIM_SOURCE_BILAYER is in ms_params.modules; tilt_rim_source_in / _out next to it keep tables of their own.
+ * Single context only. */
+int ms_set_rim_source_bilayer(ms_ctx *ctx, int n_edges, const int32_t *tail, const int32_t *head, const double *gamma,
+                              const ms_rim_source_params *params);
+/* the module's own energy at the last evaluation (its sums are also part of energies[3]) */
+int ms_get_rim_source_bilayer_energy(ms_ctx *ctx, double *energy);
+/* launches so far: {k_rim_frame, k_rim_coef, k_rim_apply2} */
+int ms_rim_source_bilayer_stats(ms_ctx *ctx, double stats[3]);
 /* tilt_coupling: modulus k_c (tilt_coupling_modulus, finite) and sign -1 ("difference"), +1 ("sum") or 0 (off; the
  * module bit is then refused by the passes).  Any other sign is refused.  Takes effect when MS_MOD_TILT_COUPLING is in
  * ms_params.modules.  Single context only. */

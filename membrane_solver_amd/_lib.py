@@ -35,6 +35,7 @@ MS_MOD_LINE_TENSION = 131072
 MS_MOD_EDGE_LENGTH_PENALTY = 262144
 MS_MOD_TILT_RIM_SOURCE_IN, MS_MOD_TILT_RIM_SOURCE_OUT = 524288, 1048576
 MS_MOD_TILT_COUPLING = 2097152
+MS_MOD_TILT_RIM_SOURCE_BILAYER = 8388608
 MS_MOD_TILT_SPLAY_TWIST_IN = 4194304
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
@@ -176,6 +177,9 @@ SIGNATURES = {
     "ms_leaflet_rim_source_stats": (ctypes.c_int, [_P, ctypes.c_int, _D]),
     "ms_rim_source_tables_host": (ctypes.c_int, [ctypes.c_int, _I32, ctypes.c_int, _I32, _I32, _D, _I32, _I32, _I32,
                                                  _I32, _D]),
+    "ms_set_rim_source_bilayer": (ctypes.c_int, [_P, ctypes.c_int, _I32, _I32, _D, ctypes.POINTER(ms_rim_source_params)]),
+    "ms_get_rim_source_bilayer_energy": (ctypes.c_int, [_P, _D]),
+    "ms_rim_source_bilayer_stats": (ctypes.c_int, [_P, _D]),
     "ms_set_tilt_coupling": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int]),
     "ms_get_tilt_coupling_energy": (ctypes.c_int, [_P, _D]),
     "ms_tilt_coupling_stats": (ctypes.c_int, [_P, _D]),

@@ -33,8 +33,8 @@ int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gr
   a.va = nullptr;
   a.partials = c->d_partials;
   a.slot = fo.s_etilt;
-  // tilt_out and tilt_rim_source_out off: no pass before this one left anything in the slot's cells
-  a.cell_mode = cell != CPL_CELL_AUTO ? cell : ((modules & (fo.mod_tilt | fo.mod_rs)) ? 1 : 2);
+  // tilt_out, tilt_rim_source_out and tilt_rim_source_bilayer off: no pass before this one left anything in the slot's cells
+  a.cell_mode = cell != CPL_CELL_AUTO ? cell : ((modules & (fo.mod_tilt | fo.mod_rs | fo.mod_rb_slot)) ? 1 : 2);
   a.wg_sums = dp;
   // a relaxation in progress: x is frozen and the mode-3 set-up launch left the barycentric vertex areas (the same
   // doubles in either leaflet's array)

@@ -129,12 +129,15 @@ struct ms_ctx {
     // tilt_coupling reads BOTH leaflet fields (mod_cpl on each); its energy rides in the outer leaflet's tilt-magnitude
     // slot (mod_cpl_slot on that field only)
     uint32_t mod_cpl = 0, mod_cpl_slot = 0;
+    // tilt_rim_source_bilayer reads BOTH leaflet fields as well (mod_rb on each) and rides in the same slot (mod_rb_slot
+    // on the outer field only); its tables are the context's (ms_ctx::rb), not a field's
+    uint32_t mod_rb = 0, mod_rb_slot = 0;
     // every module bit that reads this leaflet field
     // tilt_splay_twist_in reads the inner leaflet's field; its energy rides in that field's smoothness slot
     uint32_t mod_st = 0;
-    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl | mod_st; }
+    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl | mod_st | mod_rb; }
     // every module bit whose sums land in this field's tilt-magnitude slot (s_etilt)
-    uint32_t etilt_mods() const { return mod_tilt | mod_rs | mod_cpl_slot; }
+    uint32_t etilt_mods() const { return mod_tilt | mod_rs | mod_cpl_slot | mod_rb_slot; }
     // every module bit whose sums land in this field's smoothness slot (s_ets)
     uint32_t ets_mods() const { return mod_smooth | mod_st; }
     bool any_free = true;     // some row of this field is not clamped (kept current by the flag setters)
@@ -147,6 +150,15 @@ struct ms_ctx {
   void* d_cpl = nullptr;
   long cpl_launches[3] = {0, 0, 0};  // k_couple<0>, k_couple<1>, k_couple_vec
   bool cpl_force_tile = false;       // MS_COUPLE_VEC=0: the frozen form through the tile kernel as well (A/B)
+  // tilt_rim_source_bilayer (ms_set_rim_source_bilayer): ONE table for both leaflet fields -- the allocation, arguments,
+  // followed center and cached coefficients of TiltField::rs, kept per context
+  void* d_rimb = nullptr;
+  RimArgs rb{};
+  bool rb_set = false;
+  bool rb_follow = false;
+  bool rb_coef_valid = false;    // rb.coef holds c of the frozen surface of a running relaxation
+  double* rb_center = nullptr;   // (inside d_rimb)
+  long rb_launches[3] = {0, 0, 0};  // k_rim_frame, k_rim_coef, k_rim_apply2
   // tilt_splay_twist_in (ms_set_tilt_splay_twist): the two moduli; d_st holds the per-workgroup sums of the last launch
   double st_k_splay = 0.0, st_k_twist = 0.0;
   bool st_set = false;

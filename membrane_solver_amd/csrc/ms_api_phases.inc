@@ -28,6 +28,12 @@ int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const 
 // tilt_coupling: 1/2 k_c |t_out + s t_in|^2 of x (+ alpha d) into the outer leaflet's tilt-magnitude partials, behind the
 // rim source's pass where both run (ms_api_couple.inc).  trial_tilts: the fields' `trial` rows; cell: CPL_CELL_*
 enum { CPL_CELL_AUTO = -1, CPL_CELL_LEAVE = 0, CPL_CELL_ADD = 1 };
+// tilt_rim_source_bilayer: c . (t_in + t_out) of the rim rows at x (+ alpha d) into the outer leaflet's tilt-magnitude
+// partials, behind tilt_rim_source_out's pass and ahead of the coupling's (ms_api_rim.inc).  trial_tilts: the fields'
+// `trial` rows; gradient: c added into both fields' grad; cell: RB_CELL_*
+enum { RB_CELL_AUTO = -1, RB_CELL_ADD = 0, RB_CELL_DEFINE = 1 };
+int rim_bilayer_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool trial_tilts, bool gradient,
+                     int cell = RB_CELL_AUTO);
 int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gradient_into_g, bool tilt_gradients,
                 bool trial_tilts, int cell = CPL_CELL_AUTO, double* g_out = nullptr);
 // tilt_splay_twist_in: 1/2 A_f (k_splay div^2 + k_twist curl_n^2) of x (+ alpha d) and `tilts` into the inner leaflet's
@@ -174,7 +180,9 @@ constexpr uint32_t MS_LEAFLET_DT = MS_MOD_TILT_DISK_TARGET_IN | MS_MOD_TILT_DISK
 // the rim sources: no slot of their own (MS_NSCAL is full) -- their sums ride in the leaflet's tilt-magnitude slot -- and no
 // shape gradient, so they are not in MS_TILT_SHAPE_MODS
 constexpr uint32_t MS_LEAFLET_RS = MS_MOD_TILT_RIM_SOURCE_IN | MS_MOD_TILT_RIM_SOURCE_OUT;
-constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN;
+// (tilt_rim_source_bilayer is NOT part of MS_LEAFLET_RS: that mask selects the per-field tables and passes; the lanes
+// that decline a rim source name both)
+constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_RIM_SOURCE_BILAYER;
 constexpr uint32_t MS_ANY_TILT_MODS = MS_TILT_MODS | MS_LEAFLET_MODS;
 // the edge modules: energy added into the MS_S_ESURF partials behind the energy pass, gradient into G behind K_C; they
 // share one lane of the step (one trial per launch, every Armijo decision the host's, the separate direction pass)
@@ -786,7 +794,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   for (int l = 1; l <= 2 && (modules & MS_LEAFLET_MODS); ++l) {  // leaflet fields, same protocol
     TiltField& f = c->tf[l];
     // (the coupling alone is reason enough: its trial energy is taken with BOTH leaflets projected onto the trial surface)
-    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st))) continue;
+    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb))) continue;
     int rc = MS_OK;
     const double* tilts = f.tilts;
     if (use_dir) {
@@ -815,7 +823,10 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     if (!(modules & f.mod_rs)) continue;
     if (int rc_r = rim_pass(c, f, use_dir, alpha, use_dir ? f.trial : f.tilts, false)) return rc_r;
   }
-  // tilt_coupling: behind the rim source of the outer leaflet (the order of the adds into a cell is fixed)
+  // tilt_rim_source_bilayer: behind the outer leaflet's own rim source, with both fields' trial tilts on a trial
+  if (modules & MS_MOD_TILT_RIM_SOURCE_BILAYER)
+    if (int rc_b = rim_bilayer_pass(c, modules, use_dir, alpha, /*trial_tilts=*/use_dir, false)) return rc_b;
+  // tilt_coupling: behind the rim sources of the outer leaflet (the order of the adds into a cell is fixed)
   if (modules & MS_MOD_TILT_COUPLING)
     if (int rc_c = couple_pass(c, modules, use_dir, alpha, false, false, /*trial_tilts=*/use_dir)) return rc_c;
   // tilt_splay_twist_in: behind the inner leaflet's smoothness pass (k_tsmooth<0> above, or the one launch of
@@ -954,6 +965,11 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
       // queue_energy_and_gradient): the rim source's sums go in once more, behind it
       if (k > 0 && (modules & f.mod_rs)) {
         rc = rim_pass(c, f, false, 0.0, f.tilts, false);
+        if (rc) return rc;
+      }
+      // ... and the bilayer rim source's, behind the outer leaflet's (k == 2): the order of an energy pass's adds
+      if (k == 2 && (modules & f.mod_rb_slot)) {
+        rc = rim_bilayer_pass(c, modules, false, 0.0, false, false, RB_CELL_ADD);
         if (rc) return rc;
       }
     }

@@ -1,7 +1,8 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit):
 // tilt_rim_source_in/out -- the rim tables (ms_set_leaflet_rim_source) and the pass next to the disk-target pass:
-// k_rim_frame (follow mode), k_rim_coef (once per relaxation) and k_rim_apply.  None of the three is recorded by the
-// one-tile interpreter: the pass flushes it first.
+// k_rim_frame (follow mode), k_rim_coef (once per relaxation) and k_rim_apply -- and tilt_rim_source_bilayer
+// (ms_set_rim_source_bilayer): the same tables kept once per context, k_rim_frame / k_rim_coef as they are and
+// k_rim_apply2 on both leaflet fields.  None of the four is recorded by the one-tile interpreter: the passes flush it first.
 namespace {
 
 constexpr EdgeTableMsgs kRimMsgs = {"ms_set_leaflet_rim_source: edge row out of range", "",
@@ -17,6 +18,56 @@ const char* build_rim_tables(int nv, const int32_t* iperm, int n_edges, const in
   return build_edge_tables(nv, iperm, n_edges, tail, head, ones.data(), gamma, kRimMsgs, t);
 }
 
+// one rim table's state: TiltField's rs_* members (tilt_rim_source_in / _out) or the context's rb_* (the bilayer module)
+struct RimState {
+  void*& d_rim;
+  RimArgs& rs;
+  bool& set;
+  bool& follow;
+  bool& coef_valid;
+  double*& center;
+  long* launches;
+};
+RimState rim_state(ms_ctx::TiltField& f) {
+  return {f.d_rim, f.rs, f.rs_set, f.rs_follow, f.rs_coef_valid, f.rs_center, f.rs_launches};
+}
+RimState rim_state(ms_ctx* c) {
+  return {c->d_rimb, c->rb, c->rb_set, c->rb_follow, c->rb_coef_valid, c->rb_center, c->rb_launches};
+}
+
+// what every rim pass hands its kernels besides the tilts: the positions, the partials' geometry and the frame
+void rim_fill(ms_ctx* c, const RimState& st, RimArgs& a, bool use_dir, double alpha, int slot, bool define) {
+  a.x = c->buf[MS_BUF_X];
+  a.d = use_dir ? trial_dir(c) : nullptr;
+  a.alpha = trial_alpha(c, alpha);
+  a.vflags = c->d_vflags;
+  a.partials = c->d_partials;
+  a.n_tiles = c->til.n_tiles;
+  a.tile0 = c->tile0;
+  a.n_cells = c->tile1 - c->tile0;
+  a.slot = slot;
+  a.define = define ? 1 : 0;
+  a.center_dev = st.follow ? st.center : nullptr;
+}
+
+// the followed center and, while a relaxation holds x frozen, the coefficients: computed by the relaxation's first
+// evaluation and reused by the others (the protocol of the disk target's profile, disk_target_pass)
+int rim_coefficients(ms_ctx* c, const RimState& st, RimArgs& a, bool use_dir) {
+  const bool frozen = c->relax_va_valid && !use_dir;
+  if (st.follow && !use_dir && !(frozen && st.coef_valid)) {
+    // the center of x; a trial (use_dir) keeps the one of the evaluation at x before it
+    HIPCHK(c, launch_rim_frame(a, st.center, c->stream));
+    ++st.launches[0];
+  }
+  a.use_coef = frozen ? 1 : 0;
+  if (frozen && !st.coef_valid) {
+    HIPCHK(c, launch_rim_coef(a, c->stream));
+    ++st.launches[1];
+    st.coef_valid = true;
+  }
+  return MS_OK;
+}
+
 // c . t of the rim rows at x (+ alpha d) into the field's tilt-magnitude partials; gradient: c added into f.grad
 int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const double* tilts, bool gradient) {
   if (!f.rs_set)
@@ -29,78 +80,87 @@ int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const 
                         sizeof(double) * (size_t)(c->tile1 - c->tile0));
   }
   if (int rc = exec_flush(c)) return rc;
+  const RimState st = rim_state(f);
   RimArgs a = f.rs;
-  a.x = c->buf[MS_BUF_X];
-  a.d = use_dir ? trial_dir(c) : nullptr;
-  a.alpha = trial_alpha(c, alpha);
-  a.vflags = c->d_vflags;
+  // tilt_<leaflet> off: no pass before this one left anything in the slot's cells
+  rim_fill(c, st, a, use_dir, alpha, f.s_etilt, !(c->params.modules & f.mod_tilt));
   a.tilts = tilts;
   a.tilt_grad = gradient ? f.grad : nullptr;
-  a.partials = c->d_partials;
-  a.n_tiles = c->til.n_tiles;
-  a.tile0 = c->tile0;
-  a.n_cells = c->tile1 - c->tile0;
-  a.slot = f.s_etilt;
-  // tilt_<leaflet> off: no pass before this one left anything in the slot's cells
-  a.define = (c->params.modules & f.mod_tilt) ? 0 : 1;
-  a.center_dev = f.rs_follow ? f.rs_center : nullptr;
-  // a relaxation in progress: x is frozen, the coefficients are computed by its first evaluation and reused by the others
-  // (the protocol of the disk target's profile, disk_target_pass)
-  const bool frozen = c->relax_va_valid && !use_dir;
   ProfScope ps(c, 6);
-  if (f.rs_follow && !use_dir && !(frozen && f.rs_coef_valid)) {
-    // the center of x; a trial (use_dir) keeps the one of the evaluation at x before it
-    HIPCHK(c, launch_rim_frame(a, f.rs_center, c->stream));
-    ++f.rs_launches[0];
-  }
-  a.use_coef = frozen ? 1 : 0;
-  if (frozen && !f.rs_coef_valid) {
-    HIPCHK(c, launch_rim_coef(a, c->stream));
-    ++f.rs_launches[1];
-    f.rs_coef_valid = true;
-  }
+  if (int rc = rim_coefficients(c, st, a, use_dir)) return rc;
   HIPCHK(c, launch_rim_apply(a, c->stream));
   ++f.rs_launches[2];
   return MS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ms_set_leaflet_rim_source(ms_ctx* c, int leaflet, int n_edges, const int32_t* tail, const int32_t* head,
-                              const double* gamma, const ms_rim_source_params* p) {
-  if (!c) return MS_ERR_INVALID;
-  if (leaflet != MS_LEAFLET_IN && leaflet != MS_LEAFLET_OUT)
-    return fail(c, MS_ERR_INVALID, "ms_set_leaflet_rim_source: leaflet must be MS_LEAFLET_IN or MS_LEAFLET_OUT");
-  if (c->shard_count != 1)
-    return fail(c, MS_ERR_STATE, "ms_set_leaflet_rim_source: the tilt_rim_source modules are not sharded (single GPU only)");
-  ms_ctx::TiltField& f = c->tf[1 + leaflet];
-  if (f.d_rim) {
-    HIPCHK(c, hipStreamSynchronize(S(c)));
-    HIPCHK(c, hipFree(f.d_rim));
-    f.d_rim = nullptr;
+// tilt_rim_source_bilayer: c . (t_in + t_out) of the rim rows at x (+ alpha d) into the OUTER leaflet's tilt-magnitude
+// partials, behind tilt_out's and tilt_rim_source_out's passes and ahead of the coupling's; gradient: c added into both
+// fields' grad.  cell: RB_CELL_AUTO adds when a pass before this one wrote the cells and defines them when none did.
+int rim_bilayer_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool trial_tilts, bool gradient, int cell) {
+  if (!c->rb_set)
+    return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer active but ms_set_rim_source_bilayer was never called");
+  ms_ctx::TiltField &fi = c->tf[1], &fo = c->tf[2];
+  const double* t_in = trial_tilts ? fi.trial : fi.tilts;
+  const double* t_out = trial_tilts ? fo.trial : fo.tilts;
+  if (!t_in || !t_out)
+    return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer active but a leaflet's tilt field was never set (ms_set_leaflet_tilts)");
+  if (gradient && (!fi.grad || !fo.grad))
+    return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer: a leaflet has no tilt gradient buffer");
+  const bool written = (modules & (fo.mod_tilt | fo.mod_rs)) != 0;
+  const bool define = cell == RB_CELL_AUTO ? !written : cell == RB_CELL_DEFINE;
+  if (c->rb.n_touch == 0) {  // tables without an edge: nothing to add; the cells nobody else defines hold 0
+    if (!define) return MS_OK;
+    return zero_doubles(c, c->d_partials + (size_t)fo.s_etilt * c->til.n_tiles + c->tile0,
+                        sizeof(double) * (size_t)(c->tile1 - c->tile0));
   }
-  f.rs = RimArgs{};
-  f.rs_set = f.rs_follow = f.rs_coef_valid = false;
-  f.rs_center = nullptr;
+  if (int rc = exec_flush(c)) return rc;
+  const RimState st = rim_state(c);
+  RimArgs a = c->rb;
+  rim_fill(c, st, a, use_dir, alpha, fo.s_etilt, define);
+  a.tilts = t_in;
+  a.tilt_grad = gradient ? fi.grad : nullptr;
+  ProfScope ps(c, 6);
+  if (int rc = rim_coefficients(c, st, a, use_dir)) return rc;
+  HIPCHK(c, launch_rim_apply2(a, t_out, gradient ? fo.grad : nullptr, c->stream));
+  ++c->rb_launches[2];
+  return MS_OK;
+}
+
+// the setters' common part: the old tables freed, the arguments checked, the CSR built and uploaded as ONE blob
+int rim_upload(ms_ctx* c, const char* who, const RimState& st, int n_edges, const int32_t* tail, const int32_t* head,
+               const double* gamma, const ms_rim_source_params* p) {
+  const std::string w(who);
+  if (c->shard_count != 1)
+    return fail(c, MS_ERR_STATE, w + ": the tilt_rim_source modules are not sharded (single GPU only)");
+  if (st.d_rim) {
+    HIPCHK(c, hipStreamSynchronize(S(c)));
+    HIPCHK(c, hipFree(st.d_rim));
+    st.d_rim = nullptr;
+  }
+  st.rs = RimArgs{};
+  st.set = st.follow = st.coef_valid = false;
+  st.center = nullptr;
   c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies held are the old term's)
   if (!tail) return MS_OK;
-  if (n_edges < 0 || !head || !gamma || !p) return fail(c, MS_ERR_INVALID, "ms_set_leaflet_rim_source: bad argument");
+  if (n_edges < 0 || !head || !gamma || !p) return fail(c, MS_ERR_INVALID, w + ": bad argument");
   double nn = 0.0;
   for (int k = 0; k < 3; ++k) {
     if (!std::isfinite(p->center[k]) || !std::isfinite(p->normal[k]))
-      return fail(c, MS_ERR_INVALID, "ms_set_leaflet_rim_source: center and normal must be finite");
+      return fail(c, MS_ERR_INVALID, w + ": center and normal must be finite");
     nn += p->normal[k] * p->normal[k];
   }
   nn = std::sqrt(nn);
-  if (!(nn >= 1e-15)) return fail(c, MS_ERR_INVALID, "ms_set_leaflet_rim_source: a non-zero plane normal is required");
+  if (!(nn >= 1e-15)) return fail(c, MS_ERR_INVALID, w + ": a non-zero plane normal is required");
   EdgeTables tb;
-  if (const char* why = build_rim_tables(c->til.nv, c->til.iperm.data(), n_edges, tail, head, gamma, tb))
-    return fail(c, MS_ERR_INVALID, why);
+  if (const char* why = build_rim_tables(c->til.nv, c->til.iperm.data(), n_edges, tail, head, gamma, tb)) {
+    // (the builder's texts name the leaflet setter)
+    const std::string msg(why);
+    const size_t colon = msg.find(':');
+    return fail(c, MS_ERR_INVALID, colon == std::string::npos ? w + ": " + msg : w + msg.substr(colon));
+  }
   const int tiles = c->tile1 - c->tile0;
   const int ne = (int)tb.et.size(), nt = (int)tb.vrow.size();
-  if (nt > 0 && tiles <= 0) return fail(c, MS_ERR_STATE, "ms_set_leaflet_rim_source: the context has no tiles");
+  if (nt > 0 && tiles <= 0) return fail(c, MS_ERR_STATE, w + ": the context has no tiles");
   const int grid = nt > 0 ? std::min(tiles, (nt + 255) / 256) : 0;
   // one allocation: doubles first (gamma per CSR entry, the coefficients, the workgroup sums, the module's energy, the
   // follow mode's center, the arrival counter's cell), then the int tables
@@ -121,11 +181,11 @@ int ms_set_leaflet_rim_source(ms_ctx* c, int leaflet, int n_edges, const int32_t
     return o;
   };
   const size_t o_v = put(tb.vrow), o_o = put(tb.off), o_x = put(tb.other);
-  HIPCHK(c, hipMalloc(&f.d_rim, blob.size() * sizeof(double)));
-  HIPCHK(c, hipMemcpy(f.d_rim, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-  double* dp = static_cast<double*>(f.d_rim);
+  HIPCHK(c, hipMalloc(&st.d_rim, blob.size() * sizeof(double)));
+  HIPCHK(c, hipMemcpy(st.d_rim, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
+  double* dp = static_cast<double*>(st.d_rim);
   const int32_t* di = reinterpret_cast<const int32_t*>(dp + n_dbl);
-  RimArgs& a = f.rs;
+  RimArgs& a = st.rs;
   a.n_touch = nt;
   a.vrow = di + o_v;
   a.off = di + o_o;
@@ -140,9 +200,48 @@ int ms_set_leaflet_rim_source(ms_ctx* c, int leaflet, int n_edges, const int32_t
     a.center[k] = p->center[k];
     a.normal[k] = p->normal[k] / nn;  // tilt_rim_source_in.py:150-159
   }
-  f.rs_center = dp + o_cen;
-  f.rs_follow = p->follow != 0;
-  f.rs_set = true;
+  st.center = dp + o_cen;
+  st.follow = p->follow != 0;
+  st.set = true;
+  return MS_OK;
+}
+
+int rim_energy(ms_ctx* c, const RimState& st, double* energy) {
+  *energy = 0.0;
+  if (!st.set || st.rs.n_touch == 0) return MS_OK;  // (0.0 as uploaded until the first evaluation)
+  HIPCHK(c, hipStreamSynchronize(S(c)));
+  HIPCHK(c, hipMemcpy(energy, st.rs.energy, sizeof(double), hipMemcpyDeviceToHost));
+  return MS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ms_set_leaflet_rim_source(ms_ctx* c, int leaflet, int n_edges, const int32_t* tail, const int32_t* head,
+                              const double* gamma, const ms_rim_source_params* p) {
+  if (!c) return MS_ERR_INVALID;
+  if (leaflet != MS_LEAFLET_IN && leaflet != MS_LEAFLET_OUT)
+    return fail(c, MS_ERR_INVALID, "ms_set_leaflet_rim_source: leaflet must be MS_LEAFLET_IN or MS_LEAFLET_OUT");
+  return rim_upload(c, "ms_set_leaflet_rim_source", rim_state(c->tf[1 + leaflet]), n_edges, tail, head, gamma, p);
+}
+
+int ms_set_rim_source_bilayer(ms_ctx* c, int n_edges, const int32_t* tail, const int32_t* head, const double* gamma,
+                              const ms_rim_source_params* p) {
+  if (!c) return MS_ERR_INVALID;
+  if (c->shard_count != 1)
+    return fail(c, MS_ERR_STATE, "ms_set_rim_source_bilayer: the tilt_rim_source_bilayer module is not sharded (single GPU only)");
+  return rim_upload(c, "ms_set_rim_source_bilayer", rim_state(c), n_edges, tail, head, gamma, p);
+}
+
+int ms_get_rim_source_bilayer_energy(ms_ctx* c, double* energy) {
+  if (!c || !energy) return fail(c, MS_ERR_INVALID, "ms_get_rim_source_bilayer_energy: bad argument");
+  return rim_energy(c, rim_state(c), energy);
+}
+
+int ms_rim_source_bilayer_stats(ms_ctx* c, double stats[3]) {
+  if (!c || !stats) return MS_ERR_INVALID;
+  for (int k = 0; k < 3; ++k) stats[k] = (double)c->rb_launches[k];
   return MS_OK;
 }
 
@@ -165,12 +264,7 @@ int ms_rim_source_tables_host(int nv, const int32_t* iperm, int n_edges, const i
 int ms_get_leaflet_rim_source_energy(ms_ctx* c, int leaflet, double* energy) {
   if (!c || !energy || (leaflet != MS_LEAFLET_IN && leaflet != MS_LEAFLET_OUT))
     return fail(c, MS_ERR_INVALID, "ms_get_leaflet_rim_source_energy: bad argument");
-  *energy = 0.0;
-  const ms_ctx::TiltField& f = c->tf[1 + leaflet];
-  if (!f.rs_set || f.rs.n_touch == 0) return MS_OK;  // (0.0 as uploaded until the first evaluation)
-  HIPCHK(c, hipStreamSynchronize(S(c)));
-  HIPCHK(c, hipMemcpy(energy, f.rs.energy, sizeof(double), hipMemcpyDeviceToHost));
-  return MS_OK;
+  return rim_energy(c, rim_state(c->tf[1 + leaflet]), energy);
 }
 
 int ms_leaflet_rim_source_stats(ms_ctx* c, int leaflet, double stats[3]) {

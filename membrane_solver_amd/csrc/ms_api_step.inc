@@ -454,6 +454,9 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
     if ((c->params.modules & tfl[k]->mod_rs) && tfl[k]->rs_follow && (sp->enforce_volume || sp->enforce_pins))
       return fail(c, MS_ERR_STATE, "tilt_rim_source in follow mode (pin_to_circle_mode: fit) with a constraint enforcer "
                                    "on the line search is outside the device path");
+  if ((c->params.modules & MS_MOD_TILT_RIM_SOURCE_BILAYER) && c->rb_follow && (sp->enforce_volume || sp->enforce_pins))
+    return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer in follow mode (pin_to_circle_mode: fit) with a constraint "
+                                 "enforcer on the line search is outside the device path");
   // (no reference fixture for the enforcers next to the splay / twist term yet)
   if ((c->params.modules & MS_MOD_TILT_SPLAY_TWIST_IN) && (sp->enforce_volume || (sp->enforce_pins != 0 && pins_set(c))))
     return fail(c, MS_ERR_STATE, "tilt_splay_twist_in together with pin_to_plane / pin_to_circle or the volume enforcer on "

@@ -84,6 +84,13 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
       mask |= 1u << f.s_etilt;
     }
   }
+  if (mods & MS_MOD_TILT_RIM_SOURCE_BILAYER) {
+    // behind both leaflets' blocks (their magnitude passes have written both grads, the outer one's its cells): c into
+    // both tilt gradients, c . (t_in + t_out) into the outer leaflet's magnitude partials
+    rc = rim_bilayer_pass(c, mods, false, 0.0, trial, gradient);
+    if (rc) return rc;
+    mask |= 1u << c->tf[2].s_etilt;
+  }
   if (mods & MS_MOD_TILT_COUPLING) {
     // behind both leaflets' passes: it adds into both tilt gradients and into the outer leaflet's magnitude partials
     rc = couple_pass(c, mods, false, 0.0, false, gradient, trial);
@@ -121,8 +128,8 @@ bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs
     const bool tilt_on = single ? (mods & MS_MOD_TILT) != 0 : (mods & f.mod_tilt) != 0;
     const bool bt_on = single ? (mods & MS_MOD_BENDING_TILT) != 0 : (mods & f.mod_bt) != 0;
     const bool ts_on = single ? (mods & MS_MOD_TILT_SMOOTH) != 0 : (mods & f.mod_smooth) != 0;
-    // (the disk target, the rim source, the coupling and the splay / twist term keep their own passes)
-    if (!single && (mods & (f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st))) return false;
+    // (the disk target, the rim sources, the coupling and the splay / twist term keep their own passes)
+    if (!single && (mods & (f.mod_rb | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st))) return false;
     o.tilts = f.tilts;
     o.src = along_dir ? f.dir : f.grad;
     o.bt_vert = nullptr;
@@ -337,7 +344,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
       q.has_ts = (mods & f.mod_smooth) ? 1 : 0;
       q.has_dt = (mods & f.mod_dt) ? 1 : 0;
       q.fixed_bit = f.fixed_bit;
-      ok = ok && !(mods & (f.mod_rs | f.mod_cpl | f.mod_st)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
+      ok = ok && !(mods & (f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
            (!q.has_dt || (f.dt_target && f.disk && f.dt_target_valid));
     }
     const size_t need = relax_fused_lds_bytes(c->cap, t.max_ent, t.max_tile_facets);
@@ -617,6 +624,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     ~VaScope() {
       c->relax_va_valid = false;
       for (int l = 0; l < 3; ++l) c->tf[l].dt_target_valid = c->tf[l].rs_coef_valid = false;
+      c->rb_coef_valid = false;
     }
   } va_scope{c};
   c->relax_va_valid = jacobi_smooth_by_param;  // leaflet driver only (the single field has no such form)
@@ -626,6 +634,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     TiltField& f = *fl[k];
     f.dt_target_valid = false;
     f.rs_coef_valid = false;  // (the first rim pass of this relaxation computes the coefficients, the others reuse them)
+    c->rb_coef_valid = false;
     if (!(mods & f.mod_dt)) continue;
     rc = disk_target_pass(c, f, 0, false, 0.0, f.tilts, false, false);
     if (rc) return rc;
@@ -760,7 +769,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     return search(along_dir, sign, E0, E_acc, accepted);
   };
   // (the rim source's, the coupling's and the splay / twist term's kernels are not recorded)
-  if (c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN))) {
+  if (c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN))) {
     // one-tile context: the whole solve below as ONE launch (ms_internal.h: ExecRelaxHead)
     bool used = false;
     rc = relax_program(c, rp, fl, nf, norm_mask, &iters, &evals, &used);

@@ -428,6 +428,9 @@ struct RimArgs {
 hipError_t launch_rim_frame(const RimArgs& a, double* center_out, hipStream_t s);
 hipError_t launch_rim_coef(const RimArgs& a, hipStream_t s);
 hipError_t launch_rim_apply(const RimArgs& a, hipStream_t s);
+// tilt_rim_source_bilayer: k_rim_apply on both leaflet fields at once (a.tilts / a.tilt_grad the inner leaflet's, t_out /
+// tg_out the outer one's; tg_out is read only where a.tilt_grad is set); the sums go into a.slot = MS_S_ETILT_OUT
+hipError_t launch_rim_apply2(const RimArgs& a, const double* t_out, double* tg_out, hipStream_t s);
 // tilt_coupling (ms_couple.hip): E = 1/2 k_c int |t_out + s t_in|^2 dA, k_tilt's lumped arithmetic on the field
 // d = t_out + s t_in.  k_couple<0/1> per tile on x (+ alpha d); k_couple_vec per vertex on the frozen surface's areas.
 struct CoupleArgs {

@@ -97,6 +97,41 @@ __global__ __launch_bounds__(LB) void k_rim_apply(RimArgs a) {
   publish_wg_sum(s, w, a.grid, a.wg_sums, a.done, a.energy);
 }
 
+// tilt_rim_source_bilayer (modules/energy/tilt_rim_source_bilayer.py:416-515): the same coefficients applied to both
+// leaflet fields in one pass -- E = sum over the rim rows of c_row . (t_in,row + t_out,row), and c_row added into both
+// tilt gradients.  k_rim_apply's shape: a.tilts / a.tilt_grad are the inner leaflet's, t_out / tg_out the outer one's;
+// c_row comes from the cache or from rim_coef_of, so its doubles are the ones tilt_rim_source_in / _out get.
+__global__ __launch_bounds__(LB) void k_rim_apply2(RimArgs a, const double* __restrict__ t_out, double* __restrict__ tg_out) {
+  __shared__ double red[LB];
+  const int w = blockIdx.x;
+  const long long stride = (long long)a.grid * LB;
+  double s = 0.0;
+  for (long long i = (long long)w * LB + threadIdx.x; i < a.n_touch; i += stride) {
+    P3 c;
+    if (a.use_coef)
+      c = P3{a.coef[3 * i], a.coef[3 * i + 1], a.coef[3 * i + 2]};
+    else
+      c = rim_coef_of(a, i);
+    const size_t o = 3 * (size_t)a.vrow[i];
+    s += c.x * (a.tilts[o] + t_out[o]) + c.y * (a.tilts[o + 1] + t_out[o + 1]) + c.z * (a.tilts[o + 2] + t_out[o + 2]);
+    if (a.tilt_grad != nullptr) {  // (one thread owns the row, in both fields)
+      a.tilt_grad[o] += c.x;
+      a.tilt_grad[o + 1] += c.y;
+      a.tilt_grad[o + 2] += c.z;
+      tg_out[o] += c.x;
+      tg_out[o + 1] += c.y;
+      tg_out[o + 2] += c.z;
+    }
+  }
+  s = tree_sum(s, red);
+  double* cells = a.partials + (size_t)a.slot * a.n_tiles + a.tile0;
+  if (a.define && w == 0)  // no pass before this one wrote the slot: the tiles without a workgroup of this launch hold 0
+    for (int k = a.grid + threadIdx.x; k < a.n_cells; k += LB) cells[k] = 0.0;
+  // (no other workgroup of this launch touches the cell)
+  if (threadIdx.x == 0) cells[w] = a.define ? s : cells[w] + s;
+  publish_wg_sum(s, w, a.grid, a.wg_sums, a.done, a.energy);
+}
+
 }  // namespace
 
 hipError_t launch_rim_frame(const RimArgs& a, double* center_out, hipStream_t s) {
@@ -114,6 +149,12 @@ hipError_t launch_rim_coef(const RimArgs& a, hipStream_t s) {
 hipError_t launch_rim_apply(const RimArgs& a, hipStream_t s) {
   if (a.n_touch <= 0 || a.grid <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_rim_apply, dim3(a.grid), dim3(LB), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rim_apply2(const RimArgs& a, const double* t_out, double* tg_out, hipStream_t s) {
+  if (a.n_touch <= 0 || a.grid <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rim_apply2, dim3(a.grid), dim3(LB), 0, s, a, t_out, tg_out);
   return hipGetLastError();
 }
 

@@ -345,6 +345,39 @@ class DeviceMesh:
         self._chk(L.lib().ms_leaflet_rim_source_stats(self._h, lf, _pd(v)), "ms_leaflet_rim_source_stats")
         return {"frame_launches": int(v[0]), "coef_launches": int(v[1]), "apply_launches": int(v[2])}
 
+    def set_rim_source_bilayer(self, tail=None, head=None, gamma=None, *, center=(0.0, 0.0, 0.0),
+                               normal=(0.0, 0.0, 1.0), follow: bool = False):
+        """tilt_rim_source_bilayer: set_leaflet_rim_source's tables, kept once for both leaflet fields
+        (ms_set_rim_source_bilayer); no edges clear them."""
+        if tail is None:
+            self._chk(L.lib().ms_set_rim_source_bilayer(self._h, 0, None, None, None, None), "ms_set_rim_source_bilayer")
+            return
+        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
+        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
+        g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
+        if not (len(t) == len(h) == len(g)):
+            raise ValueError("set_rim_source_bilayer: tail, head and gamma must have the same length")
+        n = len(t)
+        if n == 0:  # (a non-NULL pointer: tables that hold no edge)
+            t = h = np.zeros(1, np.int32)
+            g = np.zeros(1)
+        p = L.ms_rim_source_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)),
+                                   1 if follow else 0)
+        self._chk(L.lib().ms_set_rim_source_bilayer(self._h, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32),
+                                                    _pd(g), ctypes.byref(p)), "ms_set_rim_source_bilayer")
+
+    def rim_source_bilayer_energy(self) -> float:
+        """The bilayer rim source's own energy as the last evaluation summed it (ms_get_rim_source_bilayer_energy)."""
+        e = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_get_rim_source_bilayer_energy(self._h, ctypes.byref(e)), "ms_get_rim_source_bilayer_energy")
+        return float(e.value)
+
+    def rim_source_bilayer_stats(self):
+        """Launch counts of the bilayer rim source's three kernels (ms_rim_source_bilayer_stats)."""
+        v = np.zeros(3)
+        self._chk(L.lib().ms_rim_source_bilayer_stats(self._h, _pd(v)), "ms_rim_source_bilayer_stats")
+        return {"frame_launches": int(v[0]), "coef_launches": int(v[1]), "apply_launches": int(v[2])}
+
     def set_tilt_coupling(self, modulus: float, sign: int):
         """tilt_coupling: modulus k_c and sign -1 ("difference"), +1 ("sum") or 0 (off) (ms_set_tilt_coupling)."""
         self._chk(L.lib().ms_set_tilt_coupling(self._h, float(modulus), int(sign)), "ms_set_tilt_coupling")

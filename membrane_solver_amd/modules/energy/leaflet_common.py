@@ -246,14 +246,15 @@ def pin_to_circle_group(options):
 def contact_line_strength(param_resolver, obj, leaflet: str) -> float:
     """gamma of one rim edge (modules/energy/contact_mapping.py:36-131): the strength key from the edge's options and
     then the global, else ``contact_gamma``, else ``h * delta_epsilon_over_a`` (or ``delta_epsilon / a``), each with
-    the leaflet's suffix first and then without, then the si / physical unit conversion."""
-    key = f"tilt_rim_source_strength_{leaflet}"
+    the leaflet's suffix first and then without, then the si / physical unit conversion.  ``leaflet`` None: the bilayer
+    module's suffix-free keys (tilt_rim_source_bilayer.py:129-136, contact_suffix "")."""
+    key = f"tilt_rim_source_strength_{leaflet}" if leaflet else "tilt_rim_source_strength"
     val = param_resolver.get(obj, key)
     if val is None:
         val = param_resolver.get(None, key)
     if val is not None:
         return float(val)
-    suffix = f"_{leaflet}"
+    suffix = f"_{leaflet}" if leaflet else ""
 
     def get_key(base):
         got = param_resolver.get(obj, base + suffix)
@@ -332,18 +333,13 @@ def _side_counts(mesh, tail, head):
     return np.where(keys[pos] == want, cnt[pos], 0)
 
 
-def rim_source_params(mesh, param_resolver, global_params, leaflet: str):
-    """Resolved tables of tilt_rim_source_<leaflet> (tilt_rim_source_in.py:57-336) as kwargs of
-    DeviceMesh.set_leaflet_rim_source, or None when the module contributes nothing (no group, no rim edge, every gamma
-    0: :386-404).  Rim edges: both ends carry ``pin_to_circle_group == tilt_rim_source_group_<leaflet>``; with
-    ``tilt_rim_source_edge_mode`` boundary (the default) only sides of exactly one triangle.  Frame: fixed center
-    ``tilt_rim_source_center`` and the ``pin_to_circle_normal`` of the first rim row (row order) that carries one, else
-    (0,0,1); follow (center = mean of the rim rows) when a rim row resolves ``pin_to_circle_mode`` to fit -- then a
-    ``pin_to_circle_normal`` is required (the reference's SVD plane fit is host work)."""
-    raw = _get(param_resolver, global_params, f"tilt_rim_source_group_{leaflet}")
+def rim_source_selection(mesh, param_resolver, global_params, leaflet: str | None = None):
+    """-> (options per row, the selected rim edges [(tail row, head row, options)]) of a rim source; no group, or no
+    edge with both ends in it (boundary mode: and on the boundary), selects nothing."""
+    raw = _get(param_resolver, global_params, f"tilt_rim_source_group_{leaflet}" if leaflet else "tilt_rim_source_group")
     group = None if raw is None else str(raw).strip()
     if not group:
-        return None
+        return {}, []
     mode = str(_get(param_resolver, global_params, "tilt_rim_source_edge_mode") or "boundary").strip().lower()
     mode = "all" if mode == "all" else "boundary"
     vopts, edges = _rim_entities(mesh)
@@ -351,7 +347,27 @@ def rim_source_params(mesh, param_resolver, global_params, leaflet: str):
     sel = [(t, h, o) for (t, h, o) in edges if t in member and h in member]
     if sel and mode == "boundary":
         cnt = _side_counts(mesh, [s[0] for s in sel], [s[1] for s in sel])
-        sel = [s for s, n in zip(sel, cnt) if n == 1]
+        # (tilt_rim_source_bilayer.py:67 keeps the edges with fewer than two triangles)
+        sel = [s for s, n in zip(sel, cnt) if (n == 1 if leaflet else n < 2)]
+    return vopts, sel
+
+
+def rim_source_params(mesh, param_resolver, global_params, leaflet: str | None = None):
+    """Resolved tables of tilt_rim_source_<leaflet> (tilt_rim_source_in.py:57-336) as kwargs of
+    DeviceMesh.set_leaflet_rim_source, or None when the module contributes nothing (no group, no rim edge, every gamma
+    0: :386-404).  Rim edges: both ends carry ``pin_to_circle_group == tilt_rim_source_group_<leaflet>``; with
+    ``tilt_rim_source_edge_mode`` boundary (the default) only sides of exactly one triangle.  Frame: fixed center
+    ``tilt_rim_source_center`` and the ``pin_to_circle_normal`` of the first rim row (row order) that carries one, else
+    (0,0,1); follow (center = mean of the rim rows) when a rim row resolves ``pin_to_circle_mode`` to fit -- then a
+    ``pin_to_circle_normal`` is required (the reference's SVD plane fit is host work).
+
+    ``leaflet`` None resolves tilt_rim_source_bilayer (tilt_rim_source_bilayer.py:58-255, :431-479), as kwargs of
+    DeviceMesh.set_rim_source_bilayer: the group is ``tilt_rim_source_group`` and the strength chain is read without a
+    leaflet suffix; boundary mode keeps the edges with FEWER THAN TWO triangles (:67); the fixed frame's normal is
+    always (0,0,1), whatever the rows carry (:478-479).  The stage-A restriction to the outermost midpoint chain needs
+    ``theory_parity_lane: stage_a_emergent``, which check_supported refuses: it is not built."""
+    name = f"tilt_rim_source_{leaflet}" if leaflet else "tilt_rim_source_bilayer"
+    vopts, sel = rim_source_selection(mesh, param_resolver, global_params, leaflet)
     if not sel:
         return None
     resolver = param_resolver if param_resolver is not None else _GlobalOnly(global_params)
@@ -379,12 +395,13 @@ def rim_source_params(mesh, param_resolver, global_params, leaflet: str):
             break
     if normal is None:
         if follow:
-            raise L.MembraneHipError(f"tilt_rim_source_{leaflet} in follow mode (pin_to_circle_mode: fit) without "
+            raise L.MembraneHipError(f"{name} in follow mode (pin_to_circle_mode: fit) without "
                                      "pin_to_circle_normal on a rim vertex (SVD plane fit of the rim rows) is outside "
                                      "the HIP hot path")
         normal = np.array([0.0, 0.0, 1.0])
-    if leaflet == "out" and not follow:
-        normal = np.array([0.0, 0.0, 1.0])  # tilt_rim_source_out.py:311-312: its fixed frame never reads the rows' normal
+    if leaflet != "in" and not follow:
+        # tilt_rim_source_out.py:311-312, tilt_rim_source_bilayer.py:478-479: their fixed frame never reads the rows' normal
+        normal = np.array([0.0, 0.0, 1.0])
     center = _get(param_resolver, global_params, "tilt_rim_source_center")
     center = np.asarray([0.0, 0.0, 0.0] if center is None else center, dtype=float).reshape(3)
     return {"tail": tail, "head": head, "gamma": gamma, "center": tuple(float(v) for v in center),
@@ -491,6 +508,56 @@ def evaluate_coupling(mesh, global_params, param_resolver, *, positions, tilts_i
         if tilt_out_grad_arr is not None:
             tilt_out_grad_arr += go
     return E
+
+
+def evaluate_rim_bilayer(mesh, global_params, param_resolver, *, positions, tilts_in, tilts_out, tilt_in_grad_arr,
+                         tilt_out_grad_arr) -> float:
+    """tilt_rim_source_bilayer on caller arrays (H2D/D2H per call: the parity seam, not the hot loop): energy; the SAME
+    coefficient rows ADDED into ``tilt_in_grad_arr`` and ``tilt_out_grad_arr`` (each optional).  No shape gradient: the
+    caller's ``grad_arr`` is never touched.  The early returns keep the reference's order (:431-462): no group and no
+    selected edge return 0.0 before the tilt shapes are looked at, a bad shape raises before gamma is."""
+    check_supported(global_params if global_params is not None else {})
+    tri, _f = mesh.triangle_row_cache()
+    if tri is None or len(tri) == 0:
+        return 0.0
+    nv = len(mesh.vertex_ids)
+    if not rim_source_selection(mesh, param_resolver, global_params, None)[1]:
+        return 0.0
+    fields = {}
+    for lf, t in (("in", tilts_in), ("out", tilts_out)):
+        if t is None:
+            t = mesh.tilts_in_view() if lf == "in" else mesh.tilts_out_view()
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        if t.shape != (nv, 3):
+            raise ValueError(f"tilts_{lf} must have shape (N_vertices, 3)")
+        fields[lf] = t
+    prm = rim_source_params(mesh, param_resolver, global_params, None)
+    if prm is None:
+        return 0.0
+    for name, arr in (("tilt_in_grad_arr", tilt_in_grad_arr), ("tilt_out_grad_arr", tilt_out_grad_arr)):
+        if arr is not None and np.shape(arr) != (nv, 3):
+            raise ValueError(f"{name} must have shape (N_vertices, 3)")
+    if prm["follow"]:
+        # tilt_rim_source_bilayer.py:355: the followed center is read from the MESH, whatever `positions` the caller
+        # evaluates on -- a fixed frame for this one call
+        rows = np.unique(np.concatenate([prm["tail"], prm["head"]]))
+        center = np.mean(np.asarray(mesh.positions_view(), dtype=np.float64)[rows], axis=0)
+        prm = dict(prm, center=tuple(float(v) for v in center), follow=False)
+    mir = mirror_for(mesh)
+    dm = mir.sync(positions=None if positions is mesh.positions_view() else positions)
+    for lf in ("in", "out"):
+        dm.set_leaflet_tilts(lf, fields[lf], tilt_modulus=0.0, smoothness=0.0)
+    mir._leaflet_keys = {}  # foreign arrays were uploaded
+    dm.set_rim_source_bilayer(**prm)
+    dm.set_params(modules=L.MS_MOD_TILT_RIM_SOURCE_BILAYER)
+    if tilt_in_grad_arr is None and tilt_out_grad_arr is None:
+        return float(dm.energy()[3])
+    E, gi, go = dm.leaflet_tilt_energy_and_gradient(want_gradient=True)
+    if tilt_in_grad_arr is not None:
+        tilt_in_grad_arr += gi
+    if tilt_out_grad_arr is not None:
+        tilt_out_grad_arr += go
+    return float(E)
 
 
 def splay_twist_params(param_resolver, global_params):

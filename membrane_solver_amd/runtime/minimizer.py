@@ -73,6 +73,7 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "edge_length_penalty": L.MS_MOD_EDGE_LENGTH_PENALTY,
                 "tilt_rim_source_in": L.MS_MOD_TILT_RIM_SOURCE_IN, "tilt_rim_source_out": L.MS_MOD_TILT_RIM_SOURCE_OUT,
                 "tilt_coupling": L.MS_MOD_TILT_COUPLING, "tilt_splay_twist_in": L.MS_MOD_TILT_SPLAY_TWIST_IN,
+                "tilt_rim_source_bilayer": L.MS_MOD_TILT_RIM_SOURCE_BILAYER,
                 # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
                 # accepted in its switched-off state (strength 0, as in the caveolin decks)
                 "gaussian_curvature": 0, "rim_slope_match_out": 0}
@@ -85,15 +86,18 @@ _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_til
                 # (its sums ride in the outer leaflet's tilt-magnitude slot; it reports its own energy)
                 "tilt_coupling": None,
                 # (its sums ride in the inner leaflet's smoothness slot; it reports its own energy)
-                "tilt_splay_twist_in": None}
+                "tilt_splay_twist_in": None,
+                # (its sums ride in the outer leaflet's tilt-magnitude slot as well; it reports its own energy)
+                "tilt_rim_source_bilayer": None}
 _RIM_MODULES = ("tilt_rim_source_in", "tilt_rim_source_out")
+_RIM_BILAYER = "tilt_rim_source_bilayer"  # one table for both leaflet fields (DeviceMesh.set_rim_source_bilayer)
 _EDGE_MODULES = ("line_tension", "edge_length_penalty")  # they share the lane behind the energy and the gradient pass
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
 _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
                  | _LEAFLET_BT_BITS | L.MS_MOD_TILT_DISK_TARGET_IN | L.MS_MOD_TILT_DISK_TARGET_OUT
                  | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING
-                 | L.MS_MOD_TILT_SPLAY_TWIST_IN)
+                 | L.MS_MOD_TILT_SPLAY_TWIST_IN | L.MS_MOD_TILT_RIM_SOURCE_BILAYER)
 _TILT_BITS = _SINGLE_TILT_BITS | _LEAFLET_BITS
 # scalar slot of every module that shares energies[3]
 _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": L.MS_S_ETILT_IN,
@@ -193,7 +197,7 @@ class Minimizer:
             # an edge module on a mesh built without edges stays refused: nothing could be tagged or given a target,
             # and the deck would run with that module's energy at zero
             # (the rim sources select edges as well: without an edge table nothing could be a rim edge)
-            no_edges = name in _EDGE_MODULES + _RIM_MODULES and not _line.has_edge_table(self.mesh)
+            no_edges = name in _EDGE_MODULES + _RIM_MODULES + (_RIM_BILAYER,) and not _line.has_edge_table(self.mesh)
             if name not in _ENERGY_BITS or no_edges:
                 where = " on a mesh without an edge table (ArrayMesh(edges=, edge_options=))" if no_edges else ""
                 raise L.MembraneHipError(
@@ -201,6 +205,7 @@ class Minimizer:
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
                     "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
                     "body_area_penalty, line_tension, edge_length_penalty, tilt_rim_source_in, tilt_rim_source_out, "
+                    "tilt_rim_source_bilayer, "
                     "tilt_coupling, tilt_splay_twist_in)")
         if "body_area_penalty" in self.energy_module_names and any(
                 _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
@@ -261,6 +266,7 @@ class Minimizer:
         self._const_energy = {}
         disk_params = {}
         rim_params = {}
+        rim_bilayer = None
         coupling = None
         splay_twist = None
         vol_mode = gp.get("volume_constraint_mode", "lagrange")
@@ -309,6 +315,10 @@ class Minimizer:
                 if prm is not None:  # tilt_rim_source_in.py:386-404: no group, no rim edge, every gamma 0
                     mods |= _ENERGY_BITS[name]
                     rim_params[name[16:]] = prm
+            elif name == _RIM_BILAYER:
+                rim_bilayer = _lc.rim_source_params(self.mesh, self.param_resolver, gp, None)
+                if rim_bilayer is not None:  # tilt_rim_source_bilayer.py:431-462: no group, no rim edge, every gamma 0
+                    mods |= _ENERGY_BITS[name]
             elif name == "tilt_coupling":
                 coupling = _lc.coupling_params(self.param_resolver, gp)
                 if coupling is not None:  # tilt_coupling.py:129-132: unknown or absent mode, or k_c == 0
@@ -319,6 +329,18 @@ class Minimizer:
                     mods |= _ENERGY_BITS[name]
             else:
                 mods |= _ENERGY_BITS[name]
+        if rim_bilayer is not None:  # (refused before anything is uploaded)
+            if mods & _SINGLE_TILT_BITS:
+                raise L.MembraneHipError("tilt_rim_source_bilayer together with a single-field tilt module is outside "
+                                         "the HIP hot path")
+            if rim_bilayer["follow"] and (self._pin_names or "volume" in self.constraint_module_names):
+                raise L.MembraneHipError("tilt_rim_source_bilayer in follow mode (pin_to_circle_mode: fit) next to "
+                                         "pin_to_plane / pin_to_circle or the volume constraint's enforcer on the line "
+                                         "search is outside the HIP hot path")
+            if not (np.all(np.isfinite(rim_bilayer["gamma"])) and np.all(np.isfinite(rim_bilayer["center"]))
+                    and np.all(np.isfinite(rim_bilayer["normal"]))):
+                raise L.MembraneHipError("tilt_rim_source_bilayer: gamma, tilt_rim_source_center and the frame's normal "
+                                         "must be finite")
         target = 0.0
         stiffness = float(gp.get("volume_stiffness") or 0.0)
         body = mir.body
@@ -392,6 +414,11 @@ class Minimizer:
                 if mir._leaflet_keys.get("bend_rim_" + lf) != key:
                     dm.set_leaflet_rim_source(lf, **prm)
                     mir._leaflet_keys["bend_rim_" + lf] = key
+            if rim_bilayer is not None:  # keyed like the leaflets' tables
+                key = (mir._topo_key, _lc.rim_source_key(rim_bilayer))
+                if mir._leaflet_keys.get("bend_rim_bilayer") != key:
+                    dm.set_rim_source_bilayer(**rim_bilayer)
+                    mir._leaflet_keys["bend_rim_bilayer"] = key
             if coupling is not None:  # keyed on modulus and sign ("bend_": not a tilt upload, mark_device_leaflets_current)
                 key = (id(dm), coupling)
                 if mir._leaflet_keys.get("bend_coupling") != key:
@@ -536,6 +563,10 @@ class Minimizer:
         cpl_e = dm.tilt_coupling_energy() if dm.modules & L.MS_MOD_TILT_COUPLING else 0.0
         if "tilt_coupling" in out:
             out["tilt_coupling"] = cpl_e
+        # ... and so does the bilayer rim source
+        rb_e = dm.rim_source_bilayer_energy() if dm.modules & L.MS_MOD_TILT_RIM_SOURCE_BILAYER else 0.0
+        if _RIM_BILAYER in out:
+            out[_RIM_BILAYER] = rb_e
         # the splay / twist term rides in the inner leaflet's smoothness slot in the same way
         st_e = dm.tilt_splay_twist_energy() if dm.modules & L.MS_MOD_TILT_SPLAY_TWIST_IN else 0.0
         if "tilt_splay_twist_in" in out:
@@ -547,11 +578,11 @@ class Minimizer:
                 for n in sharing:
                     out[n] = float(sc[table[n]]) if dm.modules & _ENERGY_BITS[n] else 0.0
                     if n in ("tilt_in", "tilt_out") and dm.modules & _ENERGY_BITS[n]:
-                        out[n] -= rim_e[n[5:]] + (cpl_e if n == "tilt_out" else 0.0)
+                        out[n] -= rim_e[n[5:]] + ((cpl_e + rb_e) if n == "tilt_out" else 0.0)
                     if n == "tilt_smoothness_in" and dm.modules & _ENERGY_BITS[n]:
                         out[n] -= st_e
-            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e or st_e):
-                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e - st_e
+            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e or st_e or rb_e):
+                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e - st_e - rb_e
         return out
 
     # -- constraint enforcement (minimizer.py:1103-1188) ---------------------------
