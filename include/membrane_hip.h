@@ -111,6 +111,18 @@ extern "C" {
  * ahead of tilt_coupling: no reduction slot of its own.  Reads both leaflet fields; single context only; not together
  * with a single-field tilt module. */
 #define MS_MOD_TILT_RIM_SOURCE_BILAYER 8388608u
+/* contact work of the inner leaflet's boundary mode theta_B on an inclusion's ring of vertices
+ * (modules/energy/tilt_thetaB_contact_in.py:200-268 geometry, :336-405 energy): the ring rows are ordered by angle in
+ * the frame of the current positions AT EVERY EVALUATION, w_i = 1/2 (|p_next - p_i| + |p_i - p_prev|) around the closed
+ * ring, r_hat_i the in-plane unit vector from the center, theta_i = t_in,i . r_hat_i, R_eff = sum w |r| / wsum.
+ * E = -2 pi R_eff gamma theta_B ("scalar" work mode, no gradient) or -2 pi R_eff gamma (sum w theta / wsum)
+ * ("field_linear", tilt gradient -(2 pi R_eff gamma / wsum) w_i r_hat_i), plus 1/2 k sum w (theta - theta_B)^2 with tilt
+ * gradient k w_i (theta_i - theta_B) r_hat_i in the legacy penalty mode.  No shape gradient; the outer leaflet is not
+ * touched.  Rows, frame and strengths come from ms_set_thetab_contact, theta_B from ms_set_thetab_value.  Its sums are
+ * added into the inner leaflet's tilt-magnitude slot (MS_S_ETILT_IN, energies[3]) behind the passes that write it
+ * (tilt_in, tilt_rim_source_in): no reduction slot of its own.  Single context only; not together with a single-field
+ * tilt module. */
+#define MS_MOD_TILT_THETAB_CONTACT_IN 16777216u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -445,6 +457,37 @@ int ms_set_rim_source_bilayer(ms_ctx *ctx, int n_edges, const int32_t *tail, con
 int ms_get_rim_source_bilayer_energy(ms_ctx *ctx, double *energy);
 /* launches so far: {k_rim_frame, k_rim_coef, k_rim_apply2} */
 int ms_rim_source_bilayer_stats(ms_ctx *ctx, double stats[3]);
+/* tilt_thetaB_contact_in: the ring rows (tilt_thetaB_contact_in.py:178-197, in vertex_ids order), the frame (:56-67 center,
+ * :82-91 normal -- the fitted-plane branch stays host work: a normal is required) and the strengths (:133-142, :150-175).
+ * rows are external rows, validated: in range and unique; at most MS_THETAB_MAX_ROWS of them (one workgroup orders the
+ * ring in LDS), more is refused.  Every parameter must be finite and the normal non-zero (it is normalised here).
+ * rows == NULL clears the tables; a refused call leaves the table in use as it was.  Takes effect when
+ * MS_MOD_TILT_THETAB_CONTACT_IN is in ms_params.modules.  Single context only. */
+#define MS_THETAB_MAX_ROWS 4096
+#define MS_THETAB_WORK_SCALAR 0
+#define MS_THETAB_WORK_FIELD_LINEAR 1
+typedef struct ms_thetab_contact_params {
+  double center[3];  /* tilt_thetaB_center */
+  double normal[3];  /* tilt_thetaB_normal */
+  double k;          /* tilt_thetaB_strength_in */
+  double gamma;      /* tilt_thetaB_contact_strength_in */
+  int work_mode;     /* tilt_thetaB_contact_work_mode: MS_THETAB_WORK_* */
+  int penalty_mode;  /* tilt_thetaB_contact_penalty_mode: 1 = legacy */
+} ms_thetab_contact_params;
+int ms_set_thetab_contact(ms_ctx *ctx, int n_rows, const int32_t *rows, const ms_thetab_contact_params *params);
+/* theta_B (tilt_thetaB_value, tilt_thetaB_contact_in.py:145-147): it changes between steps, so it is no part of the tables */
+int ms_set_thetab_value(ms_ctx *ctx, double theta_b);
+/* the module's own energy at the last evaluation (its sums are also part of energies[3]) */
+int ms_get_thetab_contact_energy(ms_ctx *ctx, double *energy);
+/* {sum w theta / wsum, R_eff, wsum} of the last evaluation (all 0 where the ring contributes nothing) */
+int ms_get_thetab_contact_scalars(ms_ctx *ctx, double out[3]);
+/* update_scalar_params (tilt_thetaB_contact_in.py:271-302) on the device's state: the ring of the current positions and
+ * the stored inner tilts are evaluated (no energy cell is written), and in the legacy penalty mode with k > 0 and a ring
+ * that contributes theta_B = sum w theta / wsum + 2 pi R_eff gamma / (k wsum) replaces the stored value.  theta_b gets
+ * the value now stored, changed whether it was replaced.  ms_get_thetab_contact_scalars then returns this ring's. */
+int ms_update_thetab_value(ms_ctx *ctx, double *theta_b, int *changed);
+/* launches so far: {k_thetab_geom, k_thetab_apply} */
+int ms_thetab_contact_stats(ms_ctx *ctx, double stats[2]);
 /* tilt_coupling: modulus k_c (tilt_coupling_modulus, finite) and sign -1 ("difference"), +1 ("sum") or 0 (off; the
  * module bit is then refused by the passes).  Any other sign is refused.  Takes effect when MS_MOD_TILT_COUPLING is in
  * ms_params.modules.  Single context only. */

@@ -37,6 +37,9 @@ MS_MOD_TILT_RIM_SOURCE_IN, MS_MOD_TILT_RIM_SOURCE_OUT = 524288, 1048576
 MS_MOD_TILT_COUPLING = 2097152
 MS_MOD_TILT_RIM_SOURCE_BILAYER = 8388608
 MS_MOD_TILT_SPLAY_TWIST_IN = 4194304
+MS_MOD_TILT_THETAB_CONTACT_IN = 16777216
+MS_THETAB_MAX_ROWS = 4096
+MS_THETAB_WORK_SCALAR, MS_THETAB_WORK_FIELD_LINEAR = 0, 1
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
@@ -87,6 +90,11 @@ class ms_leaflet_params(ctypes.Structure):
 
 class ms_rim_source_params(ctypes.Structure):
     _fields_ = [("center", ctypes.c_double * 3), ("normal", ctypes.c_double * 3), ("follow", ctypes.c_int)]
+
+
+class ms_thetab_contact_params(ctypes.Structure):
+    _fields_ = [("center", ctypes.c_double * 3), ("normal", ctypes.c_double * 3), ("k", ctypes.c_double),
+                ("gamma", ctypes.c_double), ("work_mode", ctypes.c_int), ("penalty_mode", ctypes.c_int)]
 
 
 class ms_disk_target_params(ctypes.Structure):
@@ -180,6 +188,12 @@ SIGNATURES = {
     "ms_set_rim_source_bilayer": (ctypes.c_int, [_P, ctypes.c_int, _I32, _I32, _D, ctypes.POINTER(ms_rim_source_params)]),
     "ms_get_rim_source_bilayer_energy": (ctypes.c_int, [_P, _D]),
     "ms_rim_source_bilayer_stats": (ctypes.c_int, [_P, _D]),
+    "ms_set_thetab_contact": (ctypes.c_int, [_P, ctypes.c_int, _I32, ctypes.POINTER(ms_thetab_contact_params)]),
+    "ms_set_thetab_value": (ctypes.c_int, [_P, ctypes.c_double]),
+    "ms_get_thetab_contact_energy": (ctypes.c_int, [_P, _D]),
+    "ms_get_thetab_contact_scalars": (ctypes.c_int, [_P, _D]),
+    "ms_update_thetab_value": (ctypes.c_int, [_P, _D, ctypes.POINTER(ctypes.c_int)]),
+    "ms_thetab_contact_stats": (ctypes.c_int, [_P, _D]),
     "ms_set_tilt_coupling": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int]),
     "ms_get_tilt_coupling_energy": (ctypes.c_int, [_P, _D]),
     "ms_tilt_coupling_stats": (ctypes.c_int, [_P, _D]),

@@ -181,6 +181,7 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
     f1.mod_cpl = MS_MOD_TILT_COUPLING;
     f1.mod_rb = MS_MOD_TILT_RIM_SOURCE_BILAYER;
     f1.mod_st = MS_MOD_TILT_SPLAY_TWIST_IN;
+    f1.mod_tb = MS_MOD_TILT_THETAB_CONTACT_IN;
     TiltField& f2 = c->tf[2];
     f2.fixed_bit = VF_TILT_FIXED_OUT; f2.mod_tilt = MS_MOD_TILT_OUT; f2.mod_smooth = MS_MOD_TILT_SMOOTH_OUT;
     f2.s_etilt = MS_S_ETILT_OUT; f2.s_ets = MS_S_ETS_OUT; f2.s_gn2 = MS_S_TGNORM2_OUT; f2.s_rz = MS_S_TRZ_OUT;
@@ -262,7 +263,7 @@ void ms_destroy(ms_ctx* c) {
                   c->tf[1].disk, c->tf[1].diff, c->tf[2].disk, c->tf[2].diff, c->tf[0].va, c->tf[1].va, c->tf[2].va,
                   c->state, c->d_partials, c->d_scal, c->d_stage, c->d_bnd_rows, c->d_bnd_off,
                   c->d_halo_rows, c->d_scal_all, c->d_pins, c->edge[0].d_blob, c->edge[1].d_blob, c->tf[1].d_rim, c->tf[2].d_rim,
-                  c->d_cpl, c->d_st, c->d_rimb};
+                  c->d_cpl, c->d_st, c->d_rimb, c->d_tb};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& lane : c->edge)
@@ -422,6 +423,10 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
     return fail(c, MS_ERR_STATE, "the tilt_rim_source_bilayer module is not sharded (single GPU only)");
   if ((p->modules & MS_MOD_TILT_RIM_SOURCE_BILAYER) && (p->modules & MS_TILT_MODS))
     return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer together with a single-field tilt module is outside the device path");
+  if ((p->modules & MS_MOD_TILT_THETAB_CONTACT_IN) && c->shard_count != 1)
+    return fail(c, MS_ERR_STATE, "the tilt_thetaB_contact_in module is not sharded (single GPU only)");
+  if ((p->modules & MS_MOD_TILT_THETAB_CONTACT_IN) && (p->modules & MS_TILT_MODS))
+    return fail(c, MS_ERR_STATE, "tilt_thetaB_contact_in together with a single-field tilt module is outside the device path");
   if ((p->modules & MS_MOD_TILT_COUPLING) && c->shard_count != 1)
     return fail(c, MS_ERR_STATE, "the tilt_coupling module is not sharded (single GPU only)");
   if ((p->modules & MS_MOD_TILT_COUPLING) && (p->modules & MS_TILT_MODS))

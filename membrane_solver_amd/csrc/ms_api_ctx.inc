@@ -135,9 +135,14 @@ struct ms_ctx {
     // every module bit that reads this leaflet field
     // tilt_splay_twist_in reads the inner leaflet's field; its energy rides in that field's smoothness slot
     uint32_t mod_st = 0;
-    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl | mod_st | mod_rb; }
+    // tilt_thetaB_contact_in reads the inner leaflet's field and rides in its tilt-magnitude slot behind the rim source;
+    // its tables are the context's (ms_ctx::tb)
+    uint32_t mod_tb = 0;
+    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl | mod_st | mod_rb | mod_tb; }
     // every module bit whose sums land in this field's tilt-magnitude slot (s_etilt)
     uint32_t etilt_mods() const { return mod_tilt | mod_rs | mod_cpl_slot | mod_rb_slot; }
+    // ... and the theta_B contact term on top of them: what the readers of the slot ask
+    uint32_t etilt_all() const { return etilt_mods() | mod_tb; }
     // every module bit whose sums land in this field's smoothness slot (s_ets)
     uint32_t ets_mods() const { return mod_smooth | mod_st; }
     bool any_free = true;     // some row of this field is not clamped (kept current by the flag setters)
@@ -159,6 +164,15 @@ struct ms_ctx {
   bool rb_coef_valid = false;    // rb.coef holds c of the frozen surface of a running relaxation
   double* rb_center = nullptr;   // (inside d_rimb)
   long rb_launches[3] = {0, 0, 0};  // k_rim_frame, k_rim_coef, k_rim_apply2
+  // tilt_thetaB_contact_in (ms_set_thetab_contact): one allocation holds the per-row table, the record, the scalars, the
+  // module's energy and the rows; theta_B is the host's (ms_set_thetab_value) and goes to every apply launch by value
+  void* d_tb = nullptr;
+  ThetabArgs tb{};
+  bool tb_set = false;
+  double tb_theta = 0.0;
+  bool tb_relax = false;        // a relaxation is running: x is frozen ...
+  bool tb_geom_valid = false;   // ... and the table holds its ring (the first evaluation's geometry pass)
+  long tb_launches[2] = {0, 0};  // k_thetab_geom, k_thetab_apply
   // tilt_splay_twist_in (ms_set_tilt_splay_twist): the two moduli; d_st holds the per-workgroup sums of the last launch
   double st_k_splay = 0.0, st_k_twist = 0.0;
   bool st_set = false;

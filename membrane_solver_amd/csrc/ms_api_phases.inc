@@ -36,6 +36,12 @@ int rim_bilayer_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bo
                      int cell = RB_CELL_AUTO);
 int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gradient_into_g, bool tilt_gradients,
                 bool trial_tilts, int cell = CPL_CELL_AUTO, double* g_out = nullptr);
+// tilt_thetaB_contact_in: the ring ordered on x (+ alpha d) and the contact energy of `tilts` (the inner leaflet's rows
+// belonging to those positions) into the inner leaflet's tilt-magnitude partials, behind tilt_rim_source_in's pass
+// (ms_api_thetab.inc).  tilt_grad: the rows' gradient added there, or nullptr; cell: TB_CELL_*
+enum { TB_CELL_AUTO = -1, TB_CELL_ADD = 0, TB_CELL_DEFINE = 1 };
+int thetab_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const double* tilts, double* tilt_grad,
+                int cell = TB_CELL_AUTO);
 // tilt_splay_twist_in: 1/2 A_f (k_splay div^2 + k_twist curl_n^2) of x (+ alpha d) and `tilts` into the inner leaflet's
 // smoothness partials, behind the smoothness pass where both run (ms_api_splay.inc).  tilt_grad: dE/dt ADDED there, or
 // nullptr (energy only).  The cells are ADDED to when tilt_smoothness_in's pass defined them, DEFINED otherwise
@@ -182,7 +188,7 @@ constexpr uint32_t MS_LEAFLET_DT = MS_MOD_TILT_DISK_TARGET_IN | MS_MOD_TILT_DISK
 constexpr uint32_t MS_LEAFLET_RS = MS_MOD_TILT_RIM_SOURCE_IN | MS_MOD_TILT_RIM_SOURCE_OUT;
 // (tilt_rim_source_bilayer is NOT part of MS_LEAFLET_RS: that mask selects the per-field tables and passes; the lanes
 // that decline a rim source name both)
-constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_RIM_SOURCE_BILAYER;
+constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_THETAB_CONTACT_IN;
 constexpr uint32_t MS_ANY_TILT_MODS = MS_TILT_MODS | MS_LEAFLET_MODS;
 // the edge modules: energy added into the MS_S_ESURF partials behind the energy pass, gradient into G behind K_C; they
 // share one lane of the step (one trial per launch, every Armijo decision the host's, the separate direction pass)
@@ -794,7 +800,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   for (int l = 1; l <= 2 && (modules & MS_LEAFLET_MODS); ++l) {  // leaflet fields, same protocol
     TiltField& f = c->tf[l];
     // (the coupling alone is reason enough: its trial energy is taken with BOTH leaflets projected onto the trial surface)
-    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb))) continue;
+    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb | f.mod_tb))) continue;
     int rc = MS_OK;
     const double* tilts = f.tilts;
     if (use_dir) {
@@ -823,6 +829,10 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     if (!(modules & f.mod_rs)) continue;
     if (int rc_r = rim_pass(c, f, use_dir, alpha, use_dir ? f.trial : f.tilts, false)) return rc_r;
   }
+  // tilt_thetaB_contact_in: behind the inner leaflet's rim source; the ring is ordered on THIS evaluation's positions (its
+  // scalar work mode has no gradient, yet its energy moves with x through R_eff: every Armijo trial takes it again)
+  if (modules & c->tf[1].mod_tb)
+    if (int rc_t = thetab_pass(c, modules, use_dir, alpha, use_dir ? c->tf[1].trial : c->tf[1].tilts, nullptr)) return rc_t;
   // tilt_rim_source_bilayer: behind the outer leaflet's own rim source, with both fields' trial tilts on a trial
   if (modules & MS_MOD_TILT_RIM_SOURCE_BILAYER)
     if (int rc_b = rim_bilayer_pass(c, modules, use_dir, alpha, /*trial_tilts=*/use_dir, false)) return rc_b;
@@ -965,6 +975,11 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
       // queue_energy_and_gradient): the rim source's sums go in once more, behind it
       if (k > 0 && (modules & f.mod_rs)) {
         rc = rim_pass(c, f, false, 0.0, f.tilts, false);
+        if (rc) return rc;
+      }
+      // ... and the theta_B contact term's, behind the inner leaflet's (k == 1)
+      if (k == 1 && (modules & f.mod_tb)) {
+        rc = thetab_pass(c, modules, false, 0.0, f.tilts, nullptr, TB_CELL_ADD);
         if (rc) return rc;
       }
       // ... and the bilayer rim source's, behind the outer leaflet's (k == 2): the order of an energy pass's adds
@@ -1176,7 +1191,7 @@ void energies_from_mailbox(const ms_ctx* c, double e[4]) {
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e[3] += c->h_scal[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
-    if (c->params.modules & f.etilt_mods()) e[3] += c->h_scal[f.s_etilt];  // (the rim source and the coupling ride in this slot)
+    if (c->params.modules & f.etilt_all()) e[3] += c->h_scal[f.s_etilt];  // (the rim source, the coupling and the theta_B contact term ride in this slot)
     if (c->params.modules & f.ets_mods()) e[3] += c->h_scal[f.s_ets];  // (the splay / twist term rides in this slot)
     if (c->params.modules & f.mod_bt) e[1] += c->h_scal[f.s_ebt];
     if (c->params.modules & f.mod_dt) e[3] += c->h_scal[f.s_edt];

@@ -83,6 +83,12 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
       if (rc) return rc;
       mask |= 1u << f.s_etilt;
     }
+    if (mods & f.mod_tb) {
+      // behind the rim source's pass: the same cells, the same rows of f.grad
+      rc = thetab_pass(c, mods, false, 0.0, tilts, gradient ? f.grad : nullptr);
+      if (rc) return rc;
+      mask |= 1u << f.s_etilt;
+    }
   }
   if (mods & MS_MOD_TILT_RIM_SOURCE_BILAYER) {
     // behind both leaflets' blocks (their magnitude passes have written both grads, the outer one's its cells): c into
@@ -106,7 +112,7 @@ double tilt_energy_from(const ms_ctx* c, const double* hs) {
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e += hs[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
-    if (c->params.modules & f.etilt_mods()) e += hs[f.s_etilt];  // (tilt magnitude + rim source + coupling)
+    if (c->params.modules & f.etilt_all()) e += hs[f.s_etilt];  // (tilt magnitude + rim source + coupling + theta_B contact)
     if (c->params.modules & f.ets_mods()) e += hs[f.s_ets];  // (smoothness + splay / twist)
     if (c->params.modules & f.mod_bt) e += hs[f.s_ebt];
     if (c->params.modules & f.mod_dt) e += hs[f.s_edt];
@@ -130,6 +136,7 @@ bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs
     const bool ts_on = single ? (mods & MS_MOD_TILT_SMOOTH) != 0 : (mods & f.mod_smooth) != 0;
     // (the disk target, the rim sources, the coupling and the splay / twist term keep their own passes)
     if (!single && (mods & (f.mod_rb | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st))) return false;
+    if (!single && (mods & f.mod_tb)) return false;  // (and so does the theta_B contact term)
     o.tilts = f.tilts;
     o.src = along_dir ? f.dir : f.grad;
     o.bt_vert = nullptr;
@@ -344,7 +351,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
       q.has_ts = (mods & f.mod_smooth) ? 1 : 0;
       q.has_dt = (mods & f.mod_dt) ? 1 : 0;
       q.fixed_bit = f.fixed_bit;
-      ok = ok && !(mods & (f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
+      ok = ok && !(mods & (f.mod_tb | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
            (!q.has_dt || (f.dt_target && f.disk && f.dt_target_valid));
     }
     const size_t need = relax_fused_lds_bytes(c->cap, t.max_ent, t.max_tile_facets);
@@ -463,7 +470,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
     if (mods & MS_MOD_TILT_SMOOTH) head.e_slot[n++] = MS_S_ETS;
     for (int l = 1; l <= 2; ++l) {
       const TiltField& f = c->tf[l];
-      if (mods & f.etilt_mods()) head.e_slot[n++] = f.s_etilt;
+      if (mods & f.etilt_all()) head.e_slot[n++] = f.s_etilt;
       if (mods & f.ets_mods()) head.e_slot[n++] = f.s_ets;
       if (mods & f.mod_bt) head.e_slot[n++] = f.s_ebt;
       if (mods & f.mod_dt) head.e_slot[n++] = f.s_edt;
@@ -625,9 +632,14 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
       c->relax_va_valid = false;
       for (int l = 0; l < 3; ++l) c->tf[l].dt_target_valid = c->tf[l].rs_coef_valid = false;
       c->rb_coef_valid = false;
+      c->tb_relax = c->tb_geom_valid = false;
     }
   } va_scope{c};
   c->relax_va_valid = jacobi_smooth_by_param;  // leaflet driver only (the single field has no such form)
+  // tilt_thetaB_contact_in: x is frozen from here on whatever the preconditioner -- the ring is ordered by the first
+  // evaluation of this relaxation and the others only apply its table
+  c->tb_relax = true;
+  c->tb_geom_valid = false;
   for (int k = 0; k < nf && c->relax_va_valid; ++k) {
     // prime the frozen-surface caches of the disk target (radius, theta(r) r_hat) before the loop: every evaluation of
     // the relaxation -- and the device program's captured lists -- then only take differences
@@ -768,8 +780,8 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     if (r || used) return r;
     return search(along_dir, sign, E0, E_acc, accepted);
   };
-  // (the rim source's, the coupling's and the splay / twist term's kernels are not recorded)
-  if (c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN))) {
+  // (the rim source's, the coupling's, the splay / twist term's and the theta_B contact term's kernels are not recorded)
+  if (c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_THETAB_CONTACT_IN))) {
     // one-tile context: the whole solve below as ONE launch (ms_internal.h: ExecRelaxHead)
     bool used = false;
     rc = relax_program(c, rp, fl, nf, norm_mask, &iters, &evals, &used);

@@ -431,6 +431,40 @@ hipError_t launch_rim_apply(const RimArgs& a, hipStream_t s);
 // tilt_rim_source_bilayer: k_rim_apply on both leaflet fields at once (a.tilts / a.tilt_grad the inner leaflet's, t_out /
 // tg_out the outer one's; tg_out is read only where a.tilt_grad is set); the sums go into a.slot = MS_S_ETILT_OUT
 hipError_t launch_rim_apply2(const RimArgs& a, const double* t_out, double* tg_out, hipStream_t s);
+// tilt_thetaB_contact_in (ms_thetab.hip): the ring rows ordered by angle on x (+ alpha d) by ONE workgroup
+// (k_thetab_geom: the per-row table w / r_hat / keep and the record {wsum, R_eff, n_kept, contributes}), then
+// k_thetab_apply on that table: theta_i = t_in,i . r_hat_i, the energy of the active modes into the inner leaflet's
+// tilt-magnitude partials (cell 0 of MS_S_ETILT_IN, added or defined), the rows of the tilt gradient on request and
+// {sum w theta / wsum, R_eff, wsum} for the scalar update.  Rows are the library's (til.iperm applied), in the
+// setter's order (ties of the angular order are broken by that order).
+struct ThetabArgs {
+  const double* x;
+  const double* d;        // trial direction or nullptr, alpha: exactly what EnergyArgs hands k_energy
+  double alpha;
+  const uint8_t* vflags;  // (a fixed row does not move in a trial)
+  int n;                  // ring rows, 1 .. MS_THETAB_MAX_ROWS
+  const int32_t* rows;
+  double center[3];       // tilt_thetaB_center
+  double normal[3];       // unit normal of the ring's plane
+  double u[3], v[3];      // in-plane axes (tilt_thetaB_contact_in.py:97-111)
+  double* w;              // [n] arc-length weight of the row, formed on the full ring
+  double* rhat;           // [3 n] in-plane unit vector from the center
+  int32_t* keep;          // [n] |r| > 1e-12
+  double* rec;            // {wsum over the kept rows, R_eff, n_kept, 1 when the ring contributes / 0 for the 1e-12 returns}
+  const double* tilts;    // inner leaflet
+  double* tilt_grad;      // the rows' gradient added here, or nullptr
+  double k, gamma, theta_b;
+  int field_linear, penalty;
+  double* partials;       // the energy -> [slot * n_tiles + tile0]; nullptr: scalars only (no cell, no energy written)
+  int n_tiles, tile0, n_cells;  // n_cells: tiles of the context (define: the cells past the first are zeroed)
+  int slot, define;       // define: store (no pass before this one wrote the slot) instead of add
+  double* wg_sums;        // [1] the workgroup's sum ...
+  uint32_t* done;         // ... counted here (publish_wg_sum, one workgroup) ...
+  double* energy;         // ... into the module's own energy (ms_get_thetab_contact_energy)
+  double* scalars;        // {sum w theta / wsum, R_eff, wsum}; all 0 when the ring contributes nothing
+};
+hipError_t launch_thetab_geom(const ThetabArgs& a, hipStream_t s);
+hipError_t launch_thetab_apply(const ThetabArgs& a, hipStream_t s);
 // tilt_coupling (ms_couple.hip): E = 1/2 k_c int |t_out + s t_in|^2 dA, k_tilt's lumped arithmetic on the field
 // d = t_out + s t_in.  k_couple<0/1> per tile on x (+ alpha d); k_couple_vec per vertex on the frozen surface's areas.
 struct CoupleArgs {

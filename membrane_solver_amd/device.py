@@ -412,6 +412,56 @@ class DeviceMesh:
         self._chk(L.lib().ms_tilt_splay_twist_stats(self._h, _pd(v)), "ms_tilt_splay_twist_stats")
         return {"energy_launches": int(v[0]), "gradient_launches": int(v[1])}
 
+    def set_thetab_contact(self, rows=None, *, center=(0.0, 0.0, 0.0), normal=(0.0, 0.0, 1.0), k: float = 0.0,
+                           gamma: float = 0.0, work_mode: str = "scalar", penalty_mode: str = "off"):
+        """tilt_thetaB_contact_in: the ring's rows (external, in vertex_ids order), frame and strengths
+        (ms_set_thetab_contact); no rows clear the tables."""
+        if rows is None:
+            self._chk(L.lib().ms_set_thetab_contact(self._h, 0, None, None), "ms_set_thetab_contact")
+            return
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        n = len(r)
+        if n == 0:  # (a non-NULL pointer: a table that holds no row)
+            r = np.zeros(1, np.int32)
+        work = {"scalar": L.MS_THETAB_WORK_SCALAR, "field_linear": L.MS_THETAB_WORK_FIELD_LINEAR}
+        penalty = {"off": 0, "legacy": 1}
+        if work_mode not in work or penalty_mode not in penalty:  # (leaflet_common.thetab_contact_modes resolves the aliases)
+            raise ValueError("set_thetab_contact: work_mode must be 'scalar' or 'field_linear' and penalty_mode 'off' or "
+                             f"'legacy', not {work_mode!r} / {penalty_mode!r}")
+        p = L.ms_thetab_contact_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)),
+                                       float(k), float(gamma), work[work_mode], penalty[penalty_mode])
+        self._chk(L.lib().ms_set_thetab_contact(self._h, n, r.ctypes.data_as(L._I32), ctypes.byref(p)),
+                  "ms_set_thetab_contact")
+
+    def set_thetab_value(self, theta_b: float):
+        """theta_B of the contact term (tilt_thetaB_value, ms_set_thetab_value)."""
+        self._chk(L.lib().ms_set_thetab_value(self._h, float(theta_b)), "ms_set_thetab_value")
+
+    def thetab_contact_energy(self) -> float:
+        """The contact term's own energy as the last evaluation summed it (ms_get_thetab_contact_energy)."""
+        e = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_get_thetab_contact_energy(self._h, ctypes.byref(e)), "ms_get_thetab_contact_energy")
+        return float(e.value)
+
+    def thetab_contact_scalars(self):
+        """{sum w theta / wsum, R_eff, wsum} of the last evaluation (ms_get_thetab_contact_scalars)."""
+        v = np.zeros(3)
+        self._chk(L.lib().ms_get_thetab_contact_scalars(self._h, _pd(v)), "ms_get_thetab_contact_scalars")
+        return {"theta_mean": float(v[0]), "r_eff": float(v[1]), "wsum": float(v[2])}
+
+    def update_thetab_value(self):
+        """update_scalar_params on the device's positions and stored inner tilts (ms_update_thetab_value): the stored
+        theta_B and whether the call replaced it."""
+        tb, ch = ctypes.c_double(0.0), ctypes.c_int(0)
+        self._chk(L.lib().ms_update_thetab_value(self._h, ctypes.byref(tb), ctypes.byref(ch)), "ms_update_thetab_value")
+        return float(tb.value), bool(ch.value)
+
+    def thetab_contact_stats(self):
+        """Launch counts of the contact term's two kernels (ms_thetab_contact_stats)."""
+        v = np.zeros(2)
+        self._chk(L.lib().ms_thetab_contact_stats(self._h, _pd(v)), "ms_thetab_contact_stats")
+        return {"geom_launches": int(v[0]), "apply_launches": int(v[1])}
+
     def get_leaflet_tilts(self, leaflet: str) -> np.ndarray:
         out = np.empty((self.nv, 3), dtype=np.float64)
         lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]

@@ -560,6 +560,165 @@ def evaluate_rim_bilayer(mesh, global_params, param_resolver, *, positions, tilt
     return float(E)
 
 
+def thetab_contact_group(param_resolver, global_params):
+    """The ring's group (tilt_thetaB_contact_in.py:46-53): ``tilt_thetaB_group_in``, else
+    ``rim_slope_match_disk_group``; None when neither names one."""
+    raw = _get(param_resolver, global_params, "tilt_thetaB_group_in")
+    if raw is None:
+        raw = _get(param_resolver, global_params, "rim_slope_match_disk_group")
+    if raw is None:
+        return None
+    group = str(raw).strip()
+    return group if group else None
+
+
+def thetab_contact_rows(mesh, group: str) -> np.ndarray:
+    """Rows whose options carry ``rim_slope_match_group == group`` or ``tilt_thetaB_group == group``, in vertex_ids order
+    (tilt_thetaB_contact_in.py:178-197): vertex options of a reference Mesh, or ``vertex_options`` of an array mesh."""
+    tagged = lambda o: o.get("rim_slope_match_group") == group or o.get("tilt_thetaB_group") == group  # noqa: E731
+    verts = getattr(mesh, "vertices", None)
+    rows = []
+    if isinstance(verts, dict):
+        for vid in mesh.vertex_ids:
+            if tagged(getattr(verts[int(vid)], "options", None) or {}):
+                row = mesh.vertex_index_to_row.get(int(vid))
+                if row is not None:
+                    rows.append(int(row))
+    else:
+        vopts = getattr(mesh, "vertex_options", None) or {}
+        row_of = mesh.vertex_index_to_row
+        for vid in mesh.vertex_ids:
+            row = row_of.get(int(vid))
+            if row is not None and tagged(vopts.get(int(row)) or {}):
+                rows.append(int(row))
+    return np.asarray(rows, dtype=np.int64)
+
+
+def thetab_contact_modes(global_params):
+    """(work mode, penalty mode) of tilt_thetaB_contact_in (:150-175): ``field_linear`` or the default ``scalar``;
+    ``legacy`` for legacy / on / true / 1, else ``off``."""
+    raw = None if global_params is None else global_params.get("tilt_thetaB_contact_work_mode")
+    work = "field_linear" if raw is not None and str(raw).strip().lower() == "field_linear" else "scalar"
+    raw = None if global_params is None else global_params.get("tilt_thetaB_contact_penalty_mode")
+    pen = "legacy" if raw is not None and str(raw).strip().lower() in {"legacy", "on", "true", "1"} else "off"
+    return work, pen
+
+
+def thetab_value(global_params) -> float:
+    """theta_B (tilt_thetaB_contact_in.py:145-147)."""
+    return float((global_params.get("tilt_thetaB_value") if global_params is not None else None) or 0.0)
+
+
+def thetab_contact_params(mesh, param_resolver, global_params):
+    """Resolved parameters of tilt_thetaB_contact_in as kwargs of DeviceMesh.set_thetab_contact, or None where the
+    reference returns 0.0 before it looks at a position: no group (:351-353), no tagged row (:208-210), k == gamma == 0
+    (:373-374).  The two 1e-12 returns depend on the positions: the device takes them.  Refused: a missing or zero
+    ``tilt_thetaB_normal`` (the SVD plane fit of the ring, :70-91, stays host work), a ring above the device's size and
+    non-finite parameters."""
+    group = thetab_contact_group(param_resolver, global_params)
+    if group is None:
+        return None
+    rows = thetab_contact_rows(mesh, group)
+    if rows.size == 0:
+        return None
+    k = float(_get(param_resolver, global_params, "tilt_thetaB_strength_in") or 0.0)
+    gamma = float(_get(param_resolver, global_params, "tilt_thetaB_contact_strength_in") or 0.0)
+    if k == 0.0 and gamma == 0.0:  # (whatever the frame: the reference's result is 0.0 with a fitted normal as well)
+        return None
+    center = _get(param_resolver, global_params, "tilt_thetaB_center")
+    center = np.asarray([0.0, 0.0, 0.0] if center is None else center, dtype=float).reshape(3)
+    raw = _get(param_resolver, global_params, "tilt_thetaB_normal")
+    normal = None if raw is None else np.asarray(raw, dtype=float).reshape(3)
+    if normal is not None and not np.all(np.isfinite(normal)):
+        raise L.MembraneHipError("tilt_thetaB_contact_in: tilt_thetaB_normal must be finite")
+    if normal is None or float(np.linalg.norm(normal)) < 1e-15:
+        raise L.MembraneHipError("tilt_thetaB_contact_in without a non-zero tilt_thetaB_normal (SVD plane fit of the "
+                                 "ring rows) is outside the HIP hot path")
+    if rows.size > L.MS_THETAB_MAX_ROWS:
+        raise L.MembraneHipError(f"tilt_thetaB_contact_in: a ring of {rows.size} rows is above the "
+                                 f"{L.MS_THETAB_MAX_ROWS} the device orders")
+    if not (np.isfinite(k) and np.isfinite(gamma) and np.all(np.isfinite(center))
+            and np.isfinite(thetab_value(global_params))):
+        raise L.MembraneHipError("tilt_thetaB_contact_in: tilt_thetaB_strength_in, tilt_thetaB_contact_strength_in, "
+                                 "tilt_thetaB_center and tilt_thetaB_value must be finite")
+    work, pen = thetab_contact_modes(global_params)
+    return {"rows": rows.astype(np.int32), "center": tuple(float(v) for v in center),
+            "normal": tuple(float(v) for v in normal), "k": k, "gamma": gamma, "work_mode": work, "penalty_mode": pen}
+
+
+def thetab_contact_key(prm):
+    """Hashable identity of thetab_contact_params' result (the Minimizer re-uploads when it changes; theta_B is no part
+    of it: it changes between steps and goes to the device by ms_set_thetab_value)."""
+    if prm is None:
+        return None
+    return (prm["rows"].tobytes(), prm["center"], prm["normal"], prm["k"], prm["gamma"], prm["work_mode"],
+            prm["penalty_mode"])
+
+
+def _thetab_upload(mesh, global_params, param_resolver, positions, tilts_in):
+    """The contact term alone on caller arrays -> (DeviceMesh, mirror), or None where the term contributes nothing."""
+    check_supported(global_params if global_params is not None else {})
+    if thetab_contact_group(param_resolver, global_params) is None:
+        return None
+    nv = len(mesh.vertex_ids)
+    if tilts_in is None:
+        tilts_in = mesh.tilts_in_view()
+    tilts_in = np.ascontiguousarray(tilts_in, dtype=np.float64)
+    if tilts_in.shape != (nv, 3):
+        raise ValueError("tilts_in must have shape (N_vertices, 3)")
+    prm = thetab_contact_params(mesh, param_resolver, global_params)
+    if prm is None:
+        return None
+    mir = mirror_for(mesh)
+    dm = mir.sync(positions=None if positions is mesh.positions_view() else positions)
+    dm.set_leaflet_tilts("in", tilts_in, tilt_modulus=0.0, smoothness=0.0)
+    dm.set_leaflet_tilts("out", np.zeros((nv, 3)), tilt_modulus=0.0, smoothness=0.0)
+    mir._leaflet_keys = {}  # foreign arrays were uploaded
+    dm.set_thetab_contact(**prm)
+    dm.set_thetab_value(thetab_value(global_params))
+    dm.set_params(modules=L.MS_MOD_TILT_THETAB_CONTACT_IN)
+    return dm, mir
+
+
+def evaluate_thetab_contact(mesh, global_params, param_resolver, *, positions, tilts_in, tilt_in_grad_arr) -> float:
+    """tilt_thetaB_contact_in on caller arrays (H2D/D2H per call: the parity seam, not the hot loop): energy; tilt
+    gradient ADDED into ``tilt_in_grad_arr`` (optional).  No shape gradient and nothing for the outer leaflet.  0.0
+    exactly where the reference returns early: no group, no rows, k == gamma == 0 and the two 1e-12 returns (the
+    device's "contributes nothing" state: every sum is skipped)."""
+    up = _thetab_upload(mesh, global_params, param_resolver, positions, tilts_in)
+    if up is None:
+        return 0.0
+    dm, _mir = up
+    if tilt_in_grad_arr is not None and np.shape(tilt_in_grad_arr) != (len(mesh.vertex_ids), 3):
+        raise ValueError("tilt_in_grad_arr must have shape (N_vertices, 3)")
+    if tilt_in_grad_arr is None:
+        return float(dm.energy()[3])
+    E, gi, _go = dm.leaflet_tilt_energy_and_gradient(want_gradient=True)
+    tilt_in_grad_arr += gi
+    return float(E)
+
+
+def thetab_update_scalar(mesh, global_params, param_resolver) -> None:
+    """update_scalar_params of tilt_thetaB_contact_in (:271-302) on the mesh's positions and inner tilts: legacy penalty
+    mode with k > 0 only; theta_B = sum w theta / wsum + 2 pi R_eff gamma / (k wsum) written into
+    ``tilt_thetaB_value``."""
+    if thetab_contact_modes(global_params)[1] != "legacy":
+        return
+    up = _thetab_upload(mesh, global_params, param_resolver, mesh.positions_view(), None)
+    if up is None:
+        return
+    tb, changed = up[0].update_thetab_value()
+    if changed:
+        _set_param(global_params, "tilt_thetaB_value", float(tb))
+
+
+def _set_param(global_params, key, value) -> None:
+    if hasattr(global_params, "set"):
+        global_params.set(key, value)
+    else:
+        global_params[key] = value
+
+
 def splay_twist_params(param_resolver, global_params):
     """(k_splay, k_twist, divergence mode) of tilt_splay_twist_in (modules/energy/tilt_splay_twist_in.py:16-50), in the
     reference's order: ``tilt_splay_modulus_in`` else ``bending_modulus_in`` else ``bending_modulus`` (the fallback is

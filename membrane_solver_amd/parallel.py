@@ -343,6 +343,9 @@ class HipShardBackend:
         if modules & L.MS_MOD_TILT_RIM_SOURCE_BILAYER:
             raise L.MembraneHipError("the tilt_rim_source_bilayer module is not sharded (single GPU only; ms_set_params "
                                      "refuses it on a sharded context as well)")
+        if modules & L.MS_MOD_TILT_THETAB_CONTACT_IN:
+            raise L.MembraneHipError("the tilt_thetaB_contact_in module is not sharded (single GPU only; ms_set_params "
+                                     "refuses it on a sharded context as well)")
         if modules & L.MS_MOD_TILT_COUPLING:
             raise L.MembraneHipError("the tilt_coupling module is not sharded (single GPU only; ms_set_params refuses "
                                      "it on a sharded context as well)")

@@ -74,6 +74,7 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "tilt_rim_source_in": L.MS_MOD_TILT_RIM_SOURCE_IN, "tilt_rim_source_out": L.MS_MOD_TILT_RIM_SOURCE_OUT,
                 "tilt_coupling": L.MS_MOD_TILT_COUPLING, "tilt_splay_twist_in": L.MS_MOD_TILT_SPLAY_TWIST_IN,
                 "tilt_rim_source_bilayer": L.MS_MOD_TILT_RIM_SOURCE_BILAYER,
+                "tilt_thetaB_contact_in": L.MS_MOD_TILT_THETAB_CONTACT_IN,
                 # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
                 # accepted in its switched-off state (strength 0, as in the caveolin decks)
                 "gaussian_curvature": 0, "rim_slope_match_out": 0}
@@ -88,16 +89,19 @@ _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_til
                 # (its sums ride in the inner leaflet's smoothness slot; it reports its own energy)
                 "tilt_splay_twist_in": None,
                 # (its sums ride in the outer leaflet's tilt-magnitude slot as well; it reports its own energy)
-                "tilt_rim_source_bilayer": None}
+                "tilt_rim_source_bilayer": None,
+                # (its sums ride in the inner leaflet's tilt-magnitude slot; it reports its own energy)
+                "tilt_thetaB_contact_in": None}
 _RIM_MODULES = ("tilt_rim_source_in", "tilt_rim_source_out")
 _RIM_BILAYER = "tilt_rim_source_bilayer"  # one table for both leaflet fields (DeviceMesh.set_rim_source_bilayer)
+_THETAB = "tilt_thetaB_contact_in"  # the ring's table of the context (DeviceMesh.set_thetab_contact)
 _EDGE_MODULES = ("line_tension", "edge_length_penalty")  # they share the lane behind the energy and the gradient pass
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
 _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
                  | _LEAFLET_BT_BITS | L.MS_MOD_TILT_DISK_TARGET_IN | L.MS_MOD_TILT_DISK_TARGET_OUT
                  | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING
-                 | L.MS_MOD_TILT_SPLAY_TWIST_IN | L.MS_MOD_TILT_RIM_SOURCE_BILAYER)
+                 | L.MS_MOD_TILT_SPLAY_TWIST_IN | L.MS_MOD_TILT_RIM_SOURCE_BILAYER | L.MS_MOD_TILT_THETAB_CONTACT_IN)
 _TILT_BITS = _SINGLE_TILT_BITS | _LEAFLET_BITS
 # scalar slot of every module that shares energies[3]
 _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": L.MS_S_ETILT_IN,
@@ -205,7 +209,7 @@ class Minimizer:
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
                     "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
                     "body_area_penalty, line_tension, edge_length_penalty, tilt_rim_source_in, tilt_rim_source_out, "
-                    "tilt_rim_source_bilayer, "
+                    "tilt_rim_source_bilayer, tilt_thetaB_contact_in, "
                     "tilt_coupling, tilt_splay_twist_in)")
         if "body_area_penalty" in self.energy_module_names and any(
                 _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
@@ -267,6 +271,7 @@ class Minimizer:
         disk_params = {}
         rim_params = {}
         rim_bilayer = None
+        thetab = None
         coupling = None
         splay_twist = None
         vol_mode = gp.get("volume_constraint_mode", "lagrange")
@@ -319,6 +324,12 @@ class Minimizer:
                 rim_bilayer = _lc.rim_source_params(self.mesh, self.param_resolver, gp, None)
                 if rim_bilayer is not None:  # tilt_rim_source_bilayer.py:431-462: no group, no rim edge, every gamma 0
                     mods |= _ENERGY_BITS[name]
+            elif name == _THETAB:
+                # tilt_thetaB_contact_in.py:351-374: no group, no tagged row, k == gamma == 0 (refusals: a missing normal,
+                # a ring above the device's size, non-finite parameters)
+                thetab = _lc.thetab_contact_params(self.mesh, self.param_resolver, gp)
+                if thetab is not None:
+                    mods |= _ENERGY_BITS[name]
             elif name == "tilt_coupling":
                 coupling = _lc.coupling_params(self.param_resolver, gp)
                 if coupling is not None:  # tilt_coupling.py:129-132: unknown or absent mode, or k_c == 0
@@ -341,6 +352,10 @@ class Minimizer:
                     and np.all(np.isfinite(rim_bilayer["normal"]))):
                 raise L.MembraneHipError("tilt_rim_source_bilayer: gamma, tilt_rim_source_center and the frame's normal "
                                          "must be finite")
+        if thetab is not None and mods & _SINGLE_TILT_BITS:  # (refused before anything is uploaded)
+            raise L.MembraneHipError("tilt_thetaB_contact_in together with a single-field tilt module is outside the "
+                                     "HIP hot path")
+        self._thetab_update = thetab is not None and thetab["penalty_mode"] == "legacy" and thetab["k"] > 0.0
         target = 0.0
         stiffness = float(gp.get("volume_stiffness") or 0.0)
         body = mir.body
@@ -419,6 +434,12 @@ class Minimizer:
                 if mir._leaflet_keys.get("bend_rim_bilayer") != key:
                     dm.set_rim_source_bilayer(**rim_bilayer)
                     mir._leaflet_keys["bend_rim_bilayer"] = key
+            if thetab is not None:  # keyed like the rim tables; theta_B goes with every configuration
+                key = (mir._topo_key, id(dm), _lc.thetab_contact_key(thetab))
+                if mir._leaflet_keys.get("bend_thetab") != key:
+                    dm.set_thetab_contact(**thetab)
+                    mir._leaflet_keys["bend_thetab"] = key
+                dm.set_thetab_value(_lc.thetab_value(gp))
             if coupling is not None:  # keyed on modulus and sign ("bend_": not a tilt upload, mark_device_leaflets_current)
                 key = (id(dm), coupling)
                 if mir._leaflet_keys.get("bend_coupling") != key:
@@ -567,6 +588,10 @@ class Minimizer:
         rb_e = dm.rim_source_bilayer_energy() if dm.modules & L.MS_MOD_TILT_RIM_SOURCE_BILAYER else 0.0
         if _RIM_BILAYER in out:
             out[_RIM_BILAYER] = rb_e
+        # ... and the theta_B contact term in the inner leaflet's slot
+        tb_e = dm.thetab_contact_energy() if dm.modules & L.MS_MOD_TILT_THETAB_CONTACT_IN else 0.0
+        if _THETAB in out:
+            out[_THETAB] = tb_e
         # the splay / twist term rides in the inner leaflet's smoothness slot in the same way
         st_e = dm.tilt_splay_twist_energy() if dm.modules & L.MS_MOD_TILT_SPLAY_TWIST_IN else 0.0
         if "tilt_splay_twist_in" in out:
@@ -578,11 +603,12 @@ class Minimizer:
                 for n in sharing:
                     out[n] = float(sc[table[n]]) if dm.modules & _ENERGY_BITS[n] else 0.0
                     if n in ("tilt_in", "tilt_out") and dm.modules & _ENERGY_BITS[n]:
-                        out[n] -= rim_e[n[5:]] + ((cpl_e + rb_e) if n == "tilt_out" else 0.0)
+                        out[n] -= rim_e[n[5:]] + ((cpl_e + rb_e) if n == "tilt_out" else tb_e)
                     if n == "tilt_smoothness_in" and dm.modules & _ENERGY_BITS[n]:
                         out[n] -= st_e
-            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e or st_e or rb_e):
-                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e - st_e - rb_e
+            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e or st_e or rb_e
+                                                                     or tb_e):
+                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e - st_e - rb_e - tb_e
         return out
 
     # -- constraint enforcement (minimizer.py:1103-1188) ---------------------------
@@ -661,6 +687,16 @@ class Minimizer:
             dm.relax_tilts(**rp)
         return True
 
+    def _update_scalar_params(self, dm) -> None:
+        """minimizer.py:1234, :1309 -> tilt_thetaB_contact_in.update_scalar_params (:271-302): theta_B of the legacy
+        penalty mode from the ring's three scalars on the device's positions and stored inner tilts
+        (ms_update_thetab_value), written back into ``tilt_thetaB_value``.  Skipped when the penalty mode is off."""
+        if not getattr(self, "_thetab_update", False) or not dm.modules & L.MS_MOD_TILT_THETAB_CONTACT_IN:
+            return
+        tb, changed = dm.update_thetab_value()
+        if changed:
+            _lc._set_param(self.global_params, "tilt_thetaB_value", float(tb))
+
     @property
     def _energy_offset(self) -> float:
         """Sum of the host-side constant modules (set by _device())."""
@@ -681,6 +717,9 @@ class Minimizer:
         wants to see individual steps: no callback, quiet, and the stepper's device_step is the
         stock one (tests and tools wrap it to log steps)."""
         st = self.stepper
+        if getattr(self, "_thetab_update", False):
+            # theta_B is updated twice per step from the device's scalars (_update_scalar_params): the Python loop's work
+            return False
         return (callback is None and self.quiet and isinstance(st, BaseStepper)
                 and "device_step" not in vars(st) and type(st).device_step is BaseStepper.device_step)
 
@@ -813,9 +852,11 @@ class Minimizer:
                     dirty_box[0] = False
                 callback(self.mesh, i)
                 mir, dm = self._device()
+            self._update_scalar_params(dm)  # minimizer.py:1234
             if dm.modules & (_TILT_BITS):
                 if self._relax_tilts(dm):  # minimizer.py:1237-1307, before the convergence check
                     dirty_box[0] = True
+            self._update_scalar_params(dm)  # minimizer.py:1309
             step_mode = str(gp.get("step_size_mode", "adaptive") or "adaptive").lower()
             fixed_step = float(gp.get("step_size", self.step_size) or self.step_size)
             step_size_in = fixed_step if step_mode == "fixed" else self.step_size

@@ -1,0 +1,496 @@
+"""Host side of tilt_thetaB_contact_in (no GPU): a NumPy restatement of the term against every case of
+thetab_contact_cases.npz (energies to 1e-12 relative, gradients to 1e-11, the same cyclic order), parameter and mode
+resolution, row collection, the early returns, every refusal, the plugin's names and flags, the scalar-update formula
+against the fixtures' theta_B, the Minimizer's wiring and breakdown arithmetic, and the C ABI."""
+
+import ctypes
+import inspect
+import json
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+from conftest import load_golden
+from membrane_solver_amd import _lib as L
+from membrane_solver_amd import meshgen
+from membrane_solver_amd.core.parameters import GlobalParameters, ParameterResolver
+from membrane_solver_amd.geometry.mesh import ArrayMesh
+from membrane_solver_amd.modules.energy import leaflet_common as lc
+from membrane_solver_amd.modules.energy import tilt_thetaB_contact_in as plugin
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAME = "tilt_thetaB_contact_in"
+BIT = L.MS_MOD_TILT_THETAB_CONTACT_IN
+CASES = load_golden("thetab_contact_cases.npz")
+NAMES = [str(n) for n in CASES["names"]]
+TRAJ = ("traj_disk6_gd_thetab_legacy_nested_cg.npz", "traj_disk6_cg_thetab_linear_coupled_pins.npz",
+        "traj_disk6_gd_thetab_scalar_surface.npz")
+G, K, GA, TB = "tilt_thetaB_group_in", "tilt_thetaB_strength_in", "tilt_thetaB_contact_strength_in", "tilt_thetaB_value"
+MS_ERR_INVALID = -1  # (include/membrane_hip.h)
+
+
+def case_mesh(name):
+    """The case's mesh as the generator built it: meshgen.disk_patch renumbered by a seeded permutation, the ring's rows
+    moved to the recorded positions -> (positions, triangles, tilts_in, gp, vertex options)"""
+    g = CASES
+    spec = json.loads(str(g[name + "__mesh"]))
+    P, T, _B = meshgen.disk_patch(spec["n_rings"], bulge=spec["bulge"])
+    perm = np.random.default_rng(spec["perm_seed"]).permutation(len(P))
+    P2 = np.empty_like(P)
+    P2[perm] = P
+    T2 = perm[np.asarray(T)].astype(np.int32)
+    rows = g[name + "__rows"].astype(np.int64)
+    P2[rows] = g[name + "__ring_positions"]
+    tin = np.zeros_like(P2)
+    tin[rows] = g[name + "__ring_tilts"]
+    vo = {int(k): v for k, v in json.loads(str(g[name + "__vopts"])).items()}
+    return P2, T2, tin, json.loads(str(g[name + "__gp"])), vo
+
+
+def restate(pos, tin, rows, gp):
+    """tilt_thetaB_contact_in.py:200-268, :336-405 in NumPy, the ring ordered by a rank count with ties broken by the
+    row's place in the table (what the device does) -> (E, gradient rows, scalars, kept rows in angular order, theta_B
+    after update_scalar_params)"""
+    n = len(rows)
+    tb = float(gp.get(TB) or 0.0)
+    k, gamma = float(gp.get(K) or 0.0), float(gp.get(GA) or 0.0)
+    work, pen = lc.thetab_contact_modes(gp)
+    zero = (0.0, np.zeros((n, 3)), np.zeros(3), np.zeros(0, np.int64), tb)
+    c = np.asarray(gp.get("tilt_thetaB_center", [0.0, 0.0, 0.0]), dtype=float)
+    nrm = np.asarray(gp["tilt_thetaB_normal"], dtype=float)
+    nrm = nrm / np.linalg.norm(nrm)
+    trial = np.array([0.0, 1.0, 0.0]) if abs(nrm[0]) > 0.9 else np.array([1.0, 0.0, 0.0])
+    u = trial - (trial @ nrm) * nrm
+    u /= np.linalg.norm(u)
+    v = np.cross(nrm, u)
+    v /= np.linalg.norm(v)
+    p = pos[rows]
+    r = (p - c) - ((p - c) @ nrm)[:, None] * nrm
+    ang = np.arctan2(r @ v, r @ u)
+    rank = np.array([sum((ang[j] < ang[i]) or (ang[j] == ang[i] and j < i) for j in range(n)) for i in range(n)])
+    order = np.empty(n, dtype=np.int64)
+    order[rank] = np.arange(n)
+    q = p[order]
+    w_o = 0.5 * (np.linalg.norm(np.roll(q, -1, axis=0) - q, axis=1) + np.linalg.norm(q - np.roll(q, 1, axis=0), axis=1))
+    w = np.empty(n)
+    w[order] = w_o
+    if w.sum() <= 1e-12:
+        return zero
+    rl = np.linalg.norm(r, axis=1)
+    keep = rl > 1e-12
+    if not keep.any() or w[keep].sum() <= 1e-12:
+        return zero
+    wsum = w[keep].sum()
+    rhat = np.zeros_like(r)
+    rhat[keep] = r[keep] / rl[keep][:, None]
+    theta = np.einsum("ij,ij->i", tin[rows], rhat)
+    mean, reff = float((w * theta)[keep].sum() / wsum), float((w * rl)[keep].sum() / wsum)
+    kept_order = rows[order][keep[order]]
+    tb_new = mean + 2.0 * np.pi * reff * gamma / (k * wsum) if (pen == "legacy" and k > 0.0) else tb
+    scal = np.array([mean, reff, wsum])
+    if k == 0.0 and gamma == 0.0:
+        return 0.0, np.zeros((n, 3)), scal, kept_order, tb_new
+    E, grad = 0.0, np.zeros((n, 3))
+    if gamma != 0.0:
+        E += -2.0 * np.pi * reff * gamma * (mean if work == "field_linear" else tb)
+        if work == "field_linear":
+            grad += (-(2.0 * np.pi * reff * gamma / wsum) * w * keep)[:, None] * rhat
+    if pen == "legacy" and k != 0.0:
+        E += 0.5 * k * float((w * (theta - tb) ** 2)[keep].sum())
+        grad += (k * w * (theta - tb) * keep)[:, None] * rhat
+    return E, grad, scal, kept_order, tb_new
+
+
+def same_cycle(a, b):
+    a, b = [int(x) for x in a], [int(x) for x in b]
+    if len(a) != len(b):
+        return False
+    if not a:
+        return True
+    if b[0] not in a:
+        return False
+    s = a.index(b[0])
+    return a[s:] + a[:s] == b
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_numpy_restatement_reproduces_the_reference(name):
+    g = CASES
+    P, _T, tin, gp, vo = case_mesh(name)
+    rows = g[name + "__rows"].astype(np.int64)
+    group = lc.thetab_contact_group(None, gp)
+    tagged = [r for r in sorted(vo) if group is not None and group in (vo[r].get("rim_slope_match_group"), vo[r].get("tilt_thetaB_group"))]
+    E_ref, grad_ref, scal_ref = float(g[name + "__E"]), g[name + "__ring_grad"], g[name + "__scalars"]
+    if not tagged:  # no group, or nobody carries it
+        assert E_ref == 0.0 and not grad_ref.any() and float(g[name + "__thetaB_updated"]) == gp[TB]
+        return
+    assert tagged == [int(r) for r in rows]
+    E, grad, scal, order, tb_new = restate(P, tin, rows, gp)
+    print(name, "E", E, "ref", E_ref, "scalars", scal, scal_ref, "theta_B", tb_new, float(g[name + "__thetaB_updated"]))
+    assert abs(E - E_ref) <= 1e-12 * abs(E_ref)
+    assert np.max(np.abs(grad - grad_ref)) <= 1e-11 * max(np.max(np.abs(grad_ref)), 1e-300)
+    assert same_cycle(order, g[name + "__order"]), "the cyclic order differs from the reference's argsort"
+    if len(g[name + "__order"]):
+        assert np.max(np.abs(scal - scal_ref) / np.abs(scal_ref)) <= 1e-12
+    assert abs(tb_new - float(g[name + "__thetaB_updated"])) <= 1e-12 * max(abs(tb_new), 1e-300)
+
+
+def test_the_sort_decides_the_answer():
+    """The rows of every ring of twelve or more are NOT in angular order: the table's order gives other weights.  (A
+    permutation of four rows may happen to be a rotation or a reflection of the ring.)"""
+    checked = 0
+    for name in NAMES:
+        g = CASES
+        if len(g[name + "__order"]) < 12:
+            continue
+        checked += 1
+        assert not same_cycle(g[name + "__rows"], g[name + "__order"]) and \
+            not same_cycle(g[name + "__rows"][::-1], g[name + "__order"]), name
+    assert checked >= 20
+
+
+@pytest.mark.parametrize("fname", TRAJ)
+def test_scalar_update_formula_against_the_trajectories(fname):
+    """theta_B moves only in the legacy penalty mode; there every step's two updates give new values."""
+    g = load_golden(fname)
+    gp = json.loads(str(g["gp_json"]))
+    tb = g["thetaB_log"]
+    assert len(tb) == 2 * int(g["n_steps"])
+    # the module's evaluations per line search (once at x, once per Armijo trial) and over the run
+    assert g["line_search_evals"].shape == (int(g["n_steps"]),) and g["line_search_evals"].min() >= 2
+    assert g["eval_counts"][1] >= g["line_search_evals"].sum()
+    if lc.thetab_contact_modes(gp)[1] == "legacy":
+        assert len(np.unique(tb)) >= int(g["n_steps"]) and float(g["thetaB_final"]) == tb[-1]
+    else:
+        assert np.all(tb == gp[TB]) and float(g["thetaB_final"]) == gp[TB]
+
+
+# -- parameters, modes, rows -------------------------------------------------------------------------------------------
+def test_group_resolution():
+    assert lc.thetab_contact_group(None, {}) is None
+    assert lc.thetab_contact_group(None, {G: "  "}) is None
+    assert lc.thetab_contact_group(None, {G: " disk "}) == "disk"
+    assert lc.thetab_contact_group(None, {"rim_slope_match_disk_group": "d"}) == "d"
+    assert lc.thetab_contact_group(None, {G: "a", "rim_slope_match_disk_group": "d"}) == "a"
+    gp = GlobalParameters({G: 7})
+    assert lc.thetab_contact_group(ParameterResolver(gp), gp) == "7"
+
+
+@pytest.mark.parametrize("raw,want", [(None, "scalar"), ("scalar", "scalar"), (" Field_Linear ", "field_linear"),
+                                      ("linear", "scalar"), (1, "scalar")])
+def test_work_mode(raw, want):
+    assert lc.thetab_contact_modes({} if raw is None else {"tilt_thetaB_contact_work_mode": raw})[0] == want
+
+
+@pytest.mark.parametrize("raw,want", [(None, "off"), ("legacy", "legacy"), (" ON", "legacy"), (True, "legacy"), (1, "legacy"),
+                                      ("off", "off"), ("yes", "off"), (0, "off")])
+def test_penalty_mode(raw, want):
+    assert lc.thetab_contact_modes({} if raw is None else {"tilt_thetaB_contact_penalty_mode": raw})[1] == want
+
+
+def _mesh(gp, vopts, n=4):
+    P, T, _B = meshgen.disk_patch(n)
+    return ArrayMesh(P, T, global_parameters=dict(gp), vertex_options=vopts)
+
+
+def _ring(r):
+    start = 1 + 3 * r * (r - 1)
+    return list(range(start, start + 6 * r))
+
+
+BASE = {G: "ring", K: 3.0, GA: 0.7, TB: 0.11, "tilt_thetaB_normal": [0.0, 0.0, 2.0]}
+
+
+def test_row_collection_and_parameters():
+    ring = _ring(2)
+    vo = {r: ({"rim_slope_match_group": "ring"} if j % 2 else {"tilt_thetaB_group": "ring"}) for j, r in enumerate(ring)}
+    vo[0] = {"tilt_thetaB_group": "other"}
+    vo[40] = {"rim_slope_match_group": "ring", "tilt_thetaB_group": "other"}
+    mesh = _mesh(BASE, vo)
+    assert lc.thetab_contact_rows(mesh, "ring").tolist() == ring + [40]  # vertex_ids order
+    assert lc.thetab_contact_rows(mesh, "other").tolist() == [0, 40]
+    assert lc.thetab_contact_rows(mesh, "nobody").tolist() == []
+    gp = mesh.global_parameters
+    prm = lc.thetab_contact_params(mesh, ParameterResolver(gp), gp)
+    assert prm["rows"].tolist() == ring + [40] and prm["rows"].dtype == np.int32
+    assert prm["center"] == (0.0, 0.0, 0.0) and prm["normal"] == (0.0, 0.0, 2.0)  # (the library normalises)
+    assert (prm["k"], prm["gamma"], prm["work_mode"], prm["penalty_mode"]) == (3.0, 0.7, "scalar", "off")
+    assert TB not in prm and lc.thetab_value(gp) == 0.11
+    key = lc.thetab_contact_key(prm)
+    gp2 = dict(BASE, **{TB: 0.5})
+    mesh2 = _mesh(gp2, vo)
+    assert lc.thetab_contact_key(lc.thetab_contact_params(mesh2, None, mesh2.global_parameters)) == key  # theta_B is no part
+    gp3 = dict(BASE, tilt_thetaB_contact_work_mode="field_linear")
+    mesh3 = _mesh(gp3, vo)
+    assert lc.thetab_contact_key(lc.thetab_contact_params(mesh3, None, mesh3.global_parameters)) != key
+
+
+@pytest.mark.parametrize("gp,tagged", [({k: v for k, v in BASE.items() if k != G}, True), (dict(BASE, **{G: " "}), True),
+                                       (BASE, False), (dict(BASE, **{K: 0.0, GA: 0.0}), True),
+                                       (dict(BASE, **{K: None, GA: None}), True)])
+def test_early_returns_write_nothing_and_need_no_device(gp, tagged, monkeypatch):
+    """no group, no tagged row, k == gamma == 0: exactly 0.0, nothing added, and no device is touched"""
+    monkeypatch.setattr(lc, "mirror_for", lambda *a, **k: (_ for _ in ()).throw(AssertionError("device touched")))
+    vo = {r: {"tilt_thetaB_group": "ring"} for r in _ring(2)} if tagged else {3: {"tilt_thetaB_group": "elsewhere"}}
+    mesh = _mesh(gp, vo)
+    g = mesh.global_parameters
+    res = ParameterResolver(g)
+    pos = mesh.positions_view()
+    gi = np.full_like(pos, 7.0)
+    kw = dict(positions=pos, index_map=mesh.vertex_index_to_row)
+    E = plugin.compute_energy_and_gradient_array(mesh, g, res, grad_arr=None, tilts_in=np.zeros_like(pos),
+                                                 tilt_in_grad_arr=gi, **kw)
+    assert E == 0.0 and isinstance(E, float) and np.all(gi == 7.0)
+    assert plugin.compute_energy_array(mesh, g, res, tilts_in=np.zeros_like(pos), **kw) == 0.0
+    assert plugin.compute_energy_and_gradient(mesh, g, res) == (0.0, {}, {})
+    assert plugin.compute_energy_and_gradient(mesh, g, res, compute_gradient=False) == (0.0, {})
+    plugin.update_scalar_params(mesh, g, res)
+    assert lc.thetab_contact_params(mesh, res, g) is None
+
+
+def test_update_scalar_params_acts_in_legacy_mode_only(monkeypatch):
+    monkeypatch.setattr(lc, "mirror_for", lambda *a, **k: (_ for _ in ()).throw(AssertionError("device touched")))
+    vo = {r: {"tilt_thetaB_group": "ring"} for r in _ring(2)}
+    for extra in ({}, {"tilt_thetaB_contact_penalty_mode": "off"}, {"tilt_thetaB_contact_work_mode": "field_linear"}):
+        mesh = _mesh(dict(BASE, **extra), vo)
+        plugin.update_scalar_params(mesh, mesh.global_parameters, ParameterResolver(mesh.global_parameters))
+        assert mesh.global_parameters.get(TB) == 0.11
+
+
+def test_refusals_of_the_parameters():
+    vo = {r: {"tilt_thetaB_group": "ring"} for r in _ring(2)}
+
+    def params(gp, v=vo, n=4):
+        mesh = _mesh(gp, v, n)
+        return lc.thetab_contact_params(mesh, ParameterResolver(mesh.global_parameters), mesh.global_parameters)
+
+    with pytest.raises(L.MembraneHipError, match="without a non-zero tilt_thetaB_normal"):
+        params({k: v for k, v in BASE.items() if k != "tilt_thetaB_normal"})
+    with pytest.raises(L.MembraneHipError, match="without a non-zero tilt_thetaB_normal"):
+        params(dict(BASE, tilt_thetaB_normal=[0.0, 0.0, 0.0]))
+    with pytest.raises(L.MembraneHipError, match="tilt_thetaB_normal must be finite"):
+        params(dict(BASE, tilt_thetaB_normal=[0.0, float("nan"), 1.0]))
+    for bad in ({K: float("inf")}, {GA: float("nan")}, {"tilt_thetaB_center": [0.0, float("inf"), 0.0]}, {TB: float("nan")}):
+        with pytest.raises(L.MembraneHipError, match="must be finite"):
+            params(dict(BASE, **bad))
+    n_big = 1 + 3 * 38 * 39  # disk_patch(38): 4447 vertices
+    assert n_big > L.MS_THETAB_MAX_ROWS == 4096
+    with pytest.raises(L.MembraneHipError, match=r"a ring of 4447 rows is above the 4096"):
+        params(BASE, {r: {"tilt_thetaB_group": "ring"} for r in range(n_big)}, 38)
+    with pytest.raises(L.MembraneHipError, match="tilt_thetaB_optimize"):
+        mesh = _mesh(dict(BASE, tilt_thetaB_optimize=True), vo)
+        plugin.compute_energy_array(mesh, mesh.global_parameters, None, positions=mesh.positions_view(), index_map={})
+
+
+def test_plugin_interface_matches_the_reference_names():
+    sig = json.loads(str(CASES["reference_signatures"]))
+    for fn, params in sig.items():
+        assert [p for p in inspect.signature(getattr(plugin, fn)).parameters] == params, fn
+    flags = json.loads(str(CASES["reference_flags"]))
+    assert plugin.USES_TILT_LEAFLETS is flags["USES_TILT_LEAFLETS"] is True
+    assert plugin.IS_EXTERNAL_WORK is flags["IS_EXTERNAL_WORK"] is True
+    assert set(plugin.__all__) == set(sig)
+
+
+# -- the Minimizer -----------------------------------------------------------------------------------------------------
+def _minimizer(gp, vopts, mods, cons=()):
+    from membrane_solver_amd.runtime.constraint_manager import ConstraintModuleManager
+    from membrane_solver_amd.runtime.energy_manager import EnergyModuleManager
+    from membrane_solver_amd.runtime.minimizer import Minimizer
+    from membrane_solver_amd.runtime.steppers import GradientDescent
+
+    P, T, _B = meshgen.disk_patch(4)
+    mesh = ArrayMesh(P, T, global_parameters=dict(gp), vertex_options=vopts, energy_modules=list(mods),
+                     constraint_modules=list(cons))
+    return Minimizer(mesh, mesh.global_parameters, GradientDescent(), EnergyModuleManager(list(mods)),
+                     ConstraintModuleManager(list(cons)), quiet=True)
+
+
+class _Refused(Exception):
+    pass
+
+
+def _no_device(monkeypatch):
+    """The refusals come before anything is uploaded: any upload or set_params in these tests is an error."""
+    from membrane_solver_amd.runtime import minimizer as mzr
+
+    class FakeDM:
+        modules = 0
+
+        def set_deterministic(self, on):
+            pass
+
+        def __getattr__(self, name):
+            raise _Refused("device call " + name)
+
+    class FakeMirror:
+        body = None
+        _topo_key = 0
+        _leaflet_keys = {}
+        dm = FakeDM()
+
+        def sync(self, **kw):
+            return self.dm
+
+        def __getattr__(self, name):
+            raise _Refused("mirror call " + name)
+
+    monkeypatch.setattr(mzr, "mirror_for", lambda *a, **k: FakeMirror())
+
+
+def test_minimizer_knows_the_module_and_refuses_before_any_upload(monkeypatch):
+    from membrane_solver_amd.runtime import minimizer as mzr
+
+    assert mzr._ENERGY_BITS[NAME] == BIT and mzr._ENERGY_SLOT[NAME] is None and mzr._LEAFLET_BITS & BIT
+    _no_device(monkeypatch)
+    vo = {r: {"tilt_thetaB_group": "ring"} for r in _ring(2)}
+    mz = _minimizer(dict(BASE, tilt_rigidity=1.0), vo, ["tilt", NAME])
+    with pytest.raises(L.MembraneHipError, match="tilt_thetaB_contact_in together with a single-field tilt module"):
+        mz._device()
+    mz = _minimizer({k: v for k, v in BASE.items() if k != "tilt_thetaB_normal"}, vo, ["tilt_in", NAME])
+    with pytest.raises(L.MembraneHipError, match="without a non-zero tilt_thetaB_normal"):
+        mz._device()
+    mz = _minimizer(dict(BASE, **{K: float("nan")}), vo, ["tilt_in", NAME])
+    with pytest.raises(L.MembraneHipError, match="must be finite"):
+        mz._device()
+    mz = _minimizer(dict(BASE, tilt_thetaB_optimize=True), vo, ["tilt_in", NAME])
+    with pytest.raises(L.MembraneHipError, match="tilt_thetaB_optimize"):
+        mz._device()
+    # accepted next to the pins and the volume constraint: the next thing IS an upload
+    for cons in ((), ("pin_to_circle",), ("volume",)):
+        mz = _minimizer(BASE, vo, ["tilt_in", NAME], cons)
+        with pytest.raises(_Refused):
+            mz._device()
+
+
+def test_runs_with_the_scalar_update_leave_the_library_loop():
+    """ms_minimize has no scalar update: a run whose theta_B moves is the Python loop's."""
+    vo = {r: {"tilt_thetaB_group": "ring"} for r in _ring(2)}
+    mz = _minimizer(BASE, vo, ["tilt_in", NAME])
+    mz._thetab_update = False
+    assert mz._fast_path_ok(None)
+    mz._thetab_update = True
+    assert not mz._fast_path_ok(None)
+
+    class Dev:
+        modules = BIT
+        calls = 0
+
+        def update_thetab_value(self):
+            self.calls += 1
+            return 0.25, True
+
+    dev = Dev()
+    mz._update_scalar_params(dev)
+    assert dev.calls == 1 and mz.global_params.get(TB) == 0.25
+    mz._thetab_update = False  # (penalty mode off: skipped)
+    mz._update_scalar_params(dev)
+    assert dev.calls == 1
+
+
+def test_breakdown_reports_the_module_and_takes_it_out_of_tilt_in(monkeypatch):
+    vo = {r: {"tilt_thetaB_group": "ring"} for r in _ring(2)}
+    mz = _minimizer(BASE, vo, ["surface", "tilt_in", "tilt_out", NAME])
+
+    class Dev:
+        modules = L.MS_MOD_SURFACE | L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | BIT
+
+        def energy(self):
+            return np.array([1.0, 0.0, 0.0, (0.25 - 3.0) + 0.5])
+
+        def fetch_scalars(self):
+            sc = np.zeros(L.MS_NSCAL)
+            sc[L.MS_S_ETILT_IN], sc[L.MS_S_ETILT_OUT] = 0.25 - 3.0, 0.5
+            return sc
+
+        def thetab_contact_energy(self):
+            return -3.0
+
+    monkeypatch.setattr(mz, "_device", lambda: (None, Dev()))
+    mz._const_energy = {}
+    assert mz.compute_energy_breakdown() == {"surface": 1.0, "tilt_in": 0.25, "tilt_out": 0.5, NAME: -3.0}
+    mz2 = _minimizer(BASE, vo, ["surface", "tilt_in", NAME])
+
+    class Dev2(Dev):
+        modules = L.MS_MOD_SURFACE | L.MS_MOD_TILT_IN | BIT
+
+        def energy(self):
+            return np.array([1.0, 0.0, 0.0, 0.25 - 3.0])
+
+    monkeypatch.setattr(mz2, "_device", lambda: (None, Dev2()))
+    mz2._const_energy = {}
+    assert mz2.compute_energy_breakdown() == {"surface": 1.0, "tilt_in": 0.25, NAME: -3.0}
+
+    class Dev3(Dev2):  # the module switched off: its entry is 0.0 and nobody is asked for its energy
+        modules = L.MS_MOD_SURFACE | L.MS_MOD_TILT_IN
+
+        def energy(self):
+            return np.array([1.0, 0.0, 0.0, 0.25])
+
+        def thetab_contact_energy(self):
+            raise AssertionError("not asked when the bit is off")
+
+    monkeypatch.setattr(mz2, "_device", lambda: (None, Dev3()))
+    assert mz2.compute_energy_breakdown() == {"surface": 1.0, "tilt_in": 0.25, NAME: 0.0}
+
+
+def test_sharded_driver_refuses_the_module():
+    from membrane_solver_amd.parallel import HipShardBackend
+
+    with pytest.raises(L.MembraneHipError, match="tilt_thetaB_contact_in module is not sharded"):
+        HipShardBackend.configure(types.SimpleNamespace(), modules=L.MS_MOD_SURFACE | BIT)
+    src = open(os.path.join(ROOT, "membrane_solver_amd", "csrc", "ms_api_context.inc")).read()
+    sp = src[src.index("int ms_set_params("):]
+    assert re.search(r"MS_MOD_TILT_THETAB_CONTACT_IN\) && c->shard_count != 1", sp)
+    assert re.search(r"MS_MOD_TILT_THETAB_CONTACT_IN\) && \(p->modules & MS_TILT_MODS\)", sp)
+
+
+# -- C ABI ---------------------------------------------------------------------------------------------------------------
+ABI = ("ms_set_thetab_contact", "ms_set_thetab_value", "ms_get_thetab_contact_energy", "ms_get_thetab_contact_scalars",
+       "ms_update_thetab_value", "ms_thetab_contact_stats")
+
+
+def test_c_abi_declares_the_module():
+    hdr = open(os.path.join(ROOT, "include", "membrane_hip.h")).read()
+    m = re.search(r"#define MS_MOD_TILT_THETAB_CONTACT_IN (\d+)u", hdr)
+    assert m and int(m.group(1)) == BIT == 16777216 == 2 * L.MS_MOD_TILT_RIM_SOURCE_BILAYER  # the next free bit
+    assert re.search(r"MS_NSCAL = 31\b", hdr)  # (no new reduction slot)
+    assert re.search(r"#define MS_THETAB_MAX_ROWS 4096\b", hdr)
+    for n in ABI:
+        assert re.search(r"\bint %s\(" % n, hdr) and hasattr(L.lib(), n)
+    assert set(ABI) <= set(L.SIGNATURES)
+    p = L.ms_thetab_contact_params()
+    assert [f[0] for f in p._fields_] == ["center", "normal", "k", "gamma", "work_mode", "penalty_mode"]
+    assert ctypes.sizeof(p) == 8 * 8 + 2 * 4
+
+
+def test_c_abi_argument_checks_without_a_device():
+    lib = L.lib()
+    e = ctypes.c_double(1.0)
+    v = (ctypes.c_double * 3)()
+    ch = ctypes.c_int(0)
+    assert lib.ms_set_thetab_contact(None, 0, None, None) == MS_ERR_INVALID
+    assert lib.ms_set_thetab_value(None, 0.1) == MS_ERR_INVALID
+    assert lib.ms_get_thetab_contact_energy(None, ctypes.byref(e)) == MS_ERR_INVALID
+    assert b"ms_get_thetab_contact_energy: bad argument" in lib.ms_last_error(None)
+    assert lib.ms_get_thetab_contact_scalars(None, v) == MS_ERR_INVALID
+    assert lib.ms_update_thetab_value(None, ctypes.byref(e), ctypes.byref(ch)) == MS_ERR_INVALID
+    assert lib.ms_thetab_contact_stats(None, v) == MS_ERR_INVALID
+
+
+def test_the_passes_that_cannot_carry_the_term_decline():
+    csrc = os.path.join(ROOT, "membrane_solver_amd", "csrc")
+    tilt = open(os.path.join(csrc, "ms_api_tilt.inc")).read()
+    phases = open(os.path.join(csrc, "ms_api_phases.inc")).read()
+    assert re.search(r"if \(!single && \(mods & f\.mod_tb\)\) return false;", tilt)  # tsearch_plan (and tgrad_plan through it)
+    assert re.search(r"ok = ok && !\(mods & \(f\.mod_tb \|", tilt)  # the relaxation program
+    assert re.search(r"exec_relax && !\(mods & \([^)]*MS_MOD_TILT_THETAB_CONTACT_IN", tilt)  # the one-tile recorder
+    m = re.search(r"constexpr uint32_t MS_LEAFLET_MODS = ([^;]*);", phases)
+    assert m and "MS_MOD_TILT_THETAB_CONTACT_IN" in m.group(1)  # (the resident step declines every tilt module)
+    m = re.search(r"constexpr uint32_t MS_TILT_SHAPE_MODS = ([^;]*);", phases)
+    assert m and "MS_MOD_TILT_THETAB_CONTACT_IN" not in m.group(1)  # no shape gradient
+    kern = open(os.path.join(csrc, "ms_thetab.hip")).read()
+    assert "asm" not in kern  # (no inline assembly)
