@@ -175,6 +175,11 @@ __device__ __forceinline__ void block_reduce_store(const double (&v)[NV], const 
 #ifndef MS_REDUCE_STAGED
 #define MS_REDUCE_STAGED 1
 #endif
+// -DMS_DECIDE_BATCH=0: fold_decide loads the direction scalars, then one trial set's energies per round trip, as it
+// did before the loads were batched (A/B).
+#ifndef MS_DECIDE_BATCH
+#define MS_DECIDE_BATCH 1
+#endif
 template <int NV>
 __device__ __forceinline__ void block_reduce_store_staged(const double (&v)[NV], const int (&ops)[NV],
                                                           const int (&slots)[NV], double* col,
@@ -3006,13 +3011,46 @@ __device__ __forceinline__ void fold_decide(const FoldArgs& a, uint32_t e_mask, 
   uint32_t code = DEC_CONTINUE;
   bool decide = true;
   double m_e0 = 0.0, m_c = 0.0, m_al = 0.0, m_beta = 0.0, m_slope = 0.0;
+#if MS_DECIDE_BATCH
+  // Every load the decision can need leaves before the first comparison: the direction scalars of a merged fold and,
+  // per trial set, its (at most two) energy slots in slot order.  All addresses are known on entry and the values are
+  // only consumed in order, so the decision costs ONE agent-scope round trip instead of one for the scalars plus one
+  // per trial set.  The loads stand where the serial ones stood -- behind the caller's arrival atomic and signal fence,
+  // control-dependent on its result.  (Registers picked with constant indices: a dynamically indexed array would go
+  // to scratch.)
+  double s_gn2 = 0.0, s_gdd = 0.0, s_md2 = 0.0, s_mg2 = 0.0;
+  if (merged) {
+    const double* const sc = a.set[a.n_sets - 1].scal;
+    s_gn2 = ld_agent(sc + MS_S_GNORM2);
+    s_gdd = ld_agent(sc + MS_S_GDOTD);
+    s_md2 = ld_agent(sc + MS_S_MAXD2);
+    s_mg2 = ld_agent(sc + MS_S_MAXG2);
+  }
+  const int n_e = __popc(e_mask);
+  const int es0 = n_e > 0 ? __ffs(e_mask) - 1 : 0;                            // first energy slot
+  const int es1 = n_e > 1 ? __ffs(e_mask & ~(1u << es0)) - 1 : es0;           // second one
+  double ev0[MS_MAX_TRIALS], ev1[MS_MAX_TRIALS];
+#pragma unroll
+  for (int j = 0; j < MS_MAX_TRIALS; ++j) {
+    ev0[j] = ev1[j] = 0.0;
+    if (j < a.n_sets && n_e > 0) {
+      ev0[j] = ld_agent(a.set[j].scal + es0);
+      if (n_e > 1) ev1[j] = ld_agent(a.set[j].scal + es1);
+    }
+  }
+#endif
   if (merged) {
     // first: does the search the host queued this launch for happen at all?  (FoldArgs::go_kind: 1 -- the direction
     // with history is no descent direction, the stepper restarts along -g; kind 2 -- the direction just written is one;
     // not converged; unguarded range)
     double* const sc = a.set[a.n_sets - 1].scal;
+#if MS_DECIDE_BATCH
+    (void)sc;
+    const double gn2 = s_gn2, gdd = s_gdd, md2 = s_md2, mg2 = s_mg2;
+#else
     const double gn2 = ld_agent(sc + MS_S_GNORM2), gdd = ld_agent(sc + MS_S_GDOTD);
     const double md2 = ld_agent(sc + MS_S_MAXD2), mg2 = ld_agent(sc + MS_S_MAXG2);
+#endif
     const bool restart = a.go_kind == 1;
     m_slope = restart ? -gn2 : gdd;  // <g,d> of the search
     const bool kind_ok = restart ? gdd >= 0.0 : gdd < 0.0;
@@ -3027,6 +3065,17 @@ __device__ __forceinline__ void fold_decide(const FoldArgs& a, uint32_t e_mask, 
   }
   for (int j = 0; j < a.n_sets && decide; ++j) {
     double E = 0.0;
+#if MS_DECIDE_BATCH
+    double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+    for (int k = 0; k < MS_MAX_TRIALS; ++k)
+      if (k == j) {
+        v0 = ev0[k];
+        v1 = ev1[k];
+      }
+    if (n_e > 0) E = v0;  // (slot order: the host adds surface + bending in this order)
+    if (n_e > 1) E = E + v1;
+#else
     bool first = true;
     for (int s = 0; s < MS_NSCAL; ++s)
       if (e_mask & (1u << s)) {  // (slot order: the host adds surface + bending in this order)
@@ -3034,6 +3083,7 @@ __device__ __forceinline__ void fold_decide(const FoldArgs& a, uint32_t e_mask, 
         E = first ? v : E + v;
         first = false;
       }
+#endif
     double rhs = a.rhs[j];
     if (merged) {
       // energy0 + (c alpha_j) <g,d> with alpha_j = alpha_{j-1} beta: the host's expressions, rounding for rounding
@@ -3183,6 +3233,7 @@ hipError_t launch_reduce(const FoldArgs& a, hipStream_t s) {
                  (a.side_full ? a.n_sets : 1) * __builtin_popcount(a.slot_mask & ~em);
   if (nb == 0) return hipSuccess;
   if (a.dec_out != nullptr && (a.counter == nullptr || em == 0)) return hipErrorInvalidValue;
+  if (a.dec_out != nullptr && __builtin_popcount(em) > 2) return hipErrorInvalidValue;  // (fold_decide: two energy slots per set)
   if (a.go_kind != 0 && (a.dec_out == nullptr || a.go_out == nullptr)) return hipErrorInvalidValue;
   // (one workgroup: the fold's tasks run one after the other; with one tile a fold is a copy of that tile's partials)
   if (ExecRecorder* r = exec_find(s)) return r->push(CK_REDUCE, 0, 0, 0, nb, 0, 0, &a, sizeof(a));

@@ -19,8 +19,9 @@ import shutil
 import subprocess
 import sys
 
-_NAME = re.compile(r"remark: Function Name: (\S+)")
-_FIELD = re.compile(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|"
+# (the compiler puts "file:line:col: " between "remark:" and the text when the build carries line information)
+_NAME = re.compile(r"remark: (?:\S+:\d+:\d+: +)?Function Name: (\S+)")
+_FIELD = re.compile(r"remark:\s+(?:\S+:\d+:\d+:\s+)?(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|"
                     r"LDS Size \[bytes/block\]|TotalSGPRs|VGPRs Spill|SGPRs Spill): (\d+)")
 _KEYS = {"VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "waves",
          "LDS Size [bytes/block]": "lds", "TotalSGPRs": "sgpr", "VGPRs Spill": "vspill", "SGPRs Spill": "sspill"}
