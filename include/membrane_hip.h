@@ -488,6 +488,46 @@ int ms_get_thetab_contact_scalars(ms_ctx *ctx, double out[3]);
 int ms_update_thetab_value(ms_ctx *ctx, double *theta_b, int *changed);
 /* launches so far: {k_thetab_geom, k_thetab_apply} */
 int ms_thetab_contact_stats(ms_ctx *ctx, double stats[2]);
+/* tilt_thetaB_boundary_in, the constraint t_in . d = theta_B on a ring of vertices
+ * (modules/constraints/tilt_thetaB_boundary_in.py:162-236): the ring rows (:89-109, in vertex_ids order) and the frame
+ * (:70-74 center, :77-86 normal -- the fitted-plane branch stays host work: a normal is required).  Per row
+ * r = (p - c) - ((p - c) . n) n, d = r_hat - (r_hat . N_v) N_v normalised, N_v the unit vertex normal; a row with
+ * |r| <= 1e-12 or |d| <= 1e-12 is dropped.  rows are external rows, validated: in range and unique, any number of them.
+ * Center and normal must be finite and the normal non-zero (it is normalised here).  rows == NULL clears the table; a
+ * refused call leaves the table in use as it was.  theta_B is the value of ms_set_thetab_value.  With a table set,
+ * ms_relax_leaflet_tilts enforces the constraint at its start and end and after accepted steps (ms_set_tilt_projection)
+ * and projects the inner tilt gradient of every evaluation (runtime/steppers/tilt_relaxation.py:612-616, :803-853,
+ * :1048-1052, :1372-1378, :1416-1417, :1474-1478).  Single context only. */
+typedef struct ms_thetab_boundary_params {
+  double center[3];  /* tilt_thetaB_center */
+  double normal[3];  /* tilt_thetaB_normal */
+} ms_thetab_boundary_params;
+int ms_set_thetab_boundary(ms_ctx *ctx, int n_rows, const int32_t *rows, const ms_thetab_boundary_params *params);
+/* tilt_projection_cadence / tilt_projection_interval (tilt_relaxation.py:494-510): a relaxation re-enforces the tilt
+ * constraint after every interval-th accepted step (per_step, the default with interval 1) or once behind its loop
+ * (per_pass).  Any other cadence and an interval < 1 are refused. */
+#define MS_TILT_PROJECTION_PER_STEP 0
+#define MS_TILT_PROJECTION_PER_PASS 1
+int ms_set_tilt_projection(ms_ctx *ctx, int cadence, int interval);
+/* enforce_tilt_constraint (tilt_thetaB_boundary_in.py:339-378) on the context's positions and the stored inner tilts:
+ * t <- t + (theta_B - t . d) d on the kept rows that are not tilt_fixed_in; nothing else is touched. */
+int ms_thetab_boundary_enforce(ms_ctx *ctx);
+/* _boundary_directions (:162-236) on the context's positions, per table row: d[3 n_rows] (0 where the row is dropped)
+ * and keep[n_rows] */
+int ms_thetab_boundary_directions(ms_ctx *ctx, double *d, uint8_t *keep);
+/* what _leaflet_tilt_gradients of the relaxation sees (tilt_relaxation.py:818-853): the evaluation of
+ * ms_leaflet_tilt_energy_and_gradient, then the inner gradient's rows g <- g - ((g . d) / (d . d)) d
+ * (constraint_manager.py:651-841 with runtime/constraint_projection.py:157-345: the rows are disjoint, so the KKT matrix
+ * is diagonal), then the fixed rows zeroed. */
+int ms_thetab_boundary_projected_gradient(ms_ctx *ctx, double *energy, double *grad_in, double *grad_out);
+/* launches so far: {k_tbb_geom, k_tbb_apply enforcing, k_tbb_apply projecting a gradient} */
+int ms_thetab_boundary_stats(ms_ctx *ctx, double stats[3]);
+/* Host only, no context: the ring row -> incident facet CSR ms_set_thetab_boundary uploads, built by the same code from
+ * external rows, external facets (tri: 3 n_facets rows) and a row permutation (iperm: external -> library row).
+ * off gets n_rows + 1 offsets; fv, where given, 3 * off[n_rows] library rows (the facets of a row in ascending facet
+ * order, every facet's corners in its own order).  fv == NULL: the offsets only, to size fv. */
+int ms_thetab_boundary_tables_host(int nv, const int32_t *iperm, int n_facets, const int32_t *tri, int n_rows,
+                                   const int32_t *rows, int32_t *off, int32_t *fv);
 /* tilt_coupling: modulus k_c (tilt_coupling_modulus, finite) and sign -1 ("difference"), +1 ("sum") or 0 (off; the
  * module bit is then refused by the passes).  Any other sign is refused.  Takes effect when MS_MOD_TILT_COUPLING is in
  * ms_params.modules.  Single context only. */

@@ -40,6 +40,7 @@ MS_MOD_TILT_SPLAY_TWIST_IN = 4194304
 MS_MOD_TILT_THETAB_CONTACT_IN = 16777216
 MS_THETAB_MAX_ROWS = 4096
 MS_THETAB_WORK_SCALAR, MS_THETAB_WORK_FIELD_LINEAR = 0, 1
+MS_TILT_PROJECTION_PER_STEP, MS_TILT_PROJECTION_PER_PASS = 0, 1
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
 MS_BEND_HELFRICH, MS_BEND_WILLMORE = 0, 1
 MS_GRAD_ANALYTIC, MS_GRAD_APPROX = 0, 1
@@ -95,6 +96,10 @@ class ms_rim_source_params(ctypes.Structure):
 class ms_thetab_contact_params(ctypes.Structure):
     _fields_ = [("center", ctypes.c_double * 3), ("normal", ctypes.c_double * 3), ("k", ctypes.c_double),
                 ("gamma", ctypes.c_double), ("work_mode", ctypes.c_int), ("penalty_mode", ctypes.c_int)]
+
+
+class ms_thetab_boundary_params(ctypes.Structure):
+    _fields_ = [("center", ctypes.c_double * 3), ("normal", ctypes.c_double * 3)]
 
 
 class ms_disk_target_params(ctypes.Structure):
@@ -194,6 +199,14 @@ SIGNATURES = {
     "ms_get_thetab_contact_scalars": (ctypes.c_int, [_P, _D]),
     "ms_update_thetab_value": (ctypes.c_int, [_P, _D, ctypes.POINTER(ctypes.c_int)]),
     "ms_thetab_contact_stats": (ctypes.c_int, [_P, _D]),
+    "ms_set_thetab_boundary": (ctypes.c_int, [_P, ctypes.c_int, _I32, ctypes.POINTER(ms_thetab_boundary_params)]),
+    "ms_set_tilt_projection": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    "ms_thetab_boundary_enforce": (ctypes.c_int, [_P]),
+    "ms_thetab_boundary_directions": (ctypes.c_int, [_P, _D, _U8]),
+    "ms_thetab_boundary_projected_gradient": (ctypes.c_int, [_P, _D, _D, _D]),
+    "ms_thetab_boundary_stats": (ctypes.c_int, [_P, _D]),
+    "ms_thetab_boundary_tables_host": (ctypes.c_int, [ctypes.c_int, _I32, ctypes.c_int, _I32, ctypes.c_int, _I32, _I32,
+                                                      _I32]),
     "ms_set_tilt_coupling": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int]),
     "ms_get_tilt_coupling_energy": (ctypes.c_int, [_P, _D]),
     "ms_tilt_coupling_stats": (ctypes.c_int, [_P, _D]),

@@ -33,6 +33,7 @@ std::string g_last_error;  // for failures that have no context yet
 #include "ms_api_pins.inc"  // pin_to_plane / pin_to_circle: tables, the enforcement program, the project lane
 #include "ms_api_context.inc"  // create / destroy, setters and getters, curvature fields
 #include "ms_api_tilt.inc"  // tilt-module evaluation, the relaxations (host-driven, device program, fused), leaflet fields
+#include "ms_api_thetab_bnd.inc"  // tilt_thetaB_boundary_in: the constraint's ring and row -> facet CSR, the geometry / apply launches of the relaxation, the cadence
 #include "ms_api_step.inc"  // energy / gradient entry points, line-search rounds, ms_step, volume projection, the resident step, ms_minimize
 #include "ms_api_shard.inc"  // phase API, boundary exchange, the sharded drivers (RCCL, peer-to-peer), ms_shard_step
 #include "ms_api_misc.inc"  // state rebinding, statistics, profiling, the tiling planner, the kernel-provider seam

@@ -173,6 +173,17 @@ struct ms_ctx {
   bool tb_relax = false;        // a relaxation is running: x is frozen ...
   bool tb_geom_valid = false;   // ... and the table holds its ring (the first evaluation's geometry pass)
   long tb_launches[2] = {0, 0};  // k_thetab_geom, k_thetab_apply
+  // tilt_thetaB_boundary_in (ms_set_thetab_boundary): one allocation holds the per-row table (d, N_v, keep), the rows
+  // and the row -> facet CSR; theta_B is tb_theta.  The constraint acts on the inner leaflet's field only.
+  void* d_tbb = nullptr;
+  TbbArgs tbb{};
+  bool tbb_set = false;
+  bool tbb_geom_valid = false;   // a relaxation is running (x frozen) and the table holds its directions
+  long tbb_launches[3] = {0, 0, 0};  // k_tbb_geom, k_tbb_apply<0/1>, k_tbb_apply<2>
+  // tilt_projection_cadence / tilt_projection_interval (ms_set_tilt_projection): when a relaxation re-enforces the tilt
+  // constraint after an accepted step
+  int tilt_proj_cadence = 0;     // 0 per_step, 1 per_pass
+  int tilt_proj_interval = 1;
   // tilt_splay_twist_in (ms_set_tilt_splay_twist): the two moduli; d_st holds the per-workgroup sums of the last launch
   double st_k_splay = 0.0, st_k_twist = 0.0;
   bool st_set = false;

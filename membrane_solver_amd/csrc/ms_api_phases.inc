@@ -42,6 +42,12 @@ int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gr
 enum { TB_CELL_AUTO = -1, TB_CELL_ADD = 0, TB_CELL_DEFINE = 1 };
 int thetab_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const double* tilts, double* tilt_grad,
                 int cell = TB_CELL_AUTO);
+// tilt_thetaB_boundary_in (ms_api_thetab_bnd.inc): the ring's table on x (nullptr: the context's positions) or on
+// x + alpha d, kept while `frozen` holds; and k_tbb_apply<mode> on it (0 enforce in place, 1 P(enforce(t)) into out,
+// 2 project the gradient `field`).  Both return at once when no table with a row is set.
+int tbb_geom_run(ms_ctx* c, const double* x, bool use_dir, double alpha, bool frozen);
+int tbb_apply_run(ms_ctx* c, int mode, double* field, double* out, bool project);
+bool tbb_active(const ms_ctx* c);
 // tilt_splay_twist_in: 1/2 A_f (k_splay div^2 + k_twist curl_n^2) of x (+ alpha d) and `tilts` into the inner leaflet's
 // smoothness partials, behind the smoothness pass where both run (ms_api_splay.inc).  tilt_grad: dE/dt ADDED there, or
 // nullptr (energy only).  The cells are ADDED to when tilt_smoothness_in's pass defined them, DEFINED otherwise

@@ -680,6 +680,8 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   const bool enforce_pin = sp->enforce_pins != 0 && pins_set(c);
   const bool enforce_tilt = pin_tilt;
   const bool enforce = enforce_vol || enforce_pin;
+  bool tbb_lane = false;  // the tilt constraint's ring is set and the inner leaflet's field is among the active ones
+  for (int k = 0; k < n_tf; ++k) tbb_lane = tbb_lane || (tfl[k] == &c->tf[1] && tbb_active(c));
   const bool can_chain = c->speculate && carry_mode && !tilt &&
                          !(c->params.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY | MS_EDGE_MODS)) && !enforce && !precond;
   // a round queued by the step before (while its gradient pass was running): the round of THIS search's first
@@ -749,6 +751,13 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
         // which takes the field's place for the evaluation -- the tilts of x stay where they are, bit for bit
         for (int k = 0; k < n_tf && rc == MS_OK && enforce_tilt; ++k)
           rc = tilt_pass_f(c, *tfl[k], 2, false, 0.0, tfl[k]->tilts, tfl[k]->trial);
+        // tilt_thetaB_boundary_in behind the pins (minimizer.py:1103-1120, then energy_fn's projection): the directions
+        // of the enforced trial, then P(enforce(t)) of the ring rows over what the projection above left there; the
+        // tilts of x are read, never written
+        if (rc == MS_OK && enforce_tilt && tbb_lane) {
+          rc = tbb_geom_run(c, nullptr, false, 0.0, false);
+          if (rc == MS_OK) rc = tbb_apply_run(c, 1, c->tf[1].tilts, c->tf[1].trial, true);
+        }
         for (int k = 0; k < n_tf && enforce_tilt; ++k) std::swap(tfl[k]->tilts, tfl[k]->trial);
         if (rc == MS_OK) rc = phase_energy(c, c->params.modules, false, 0.0, false, false, carry_mode);
         if (rc == MS_OK) rc = fetch(c);

@@ -538,6 +538,21 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
   int iters = 0, evals = 0;
   int rc = ensure_bt_record(c);
   if (rc) return rc;
+  // tilt_thetaB_boundary_in: the constraint acts on the inner leaflet's field (the single-field driver never sees it).
+  // x is frozen: the directions are formed once, here; the stored tilts are enforced before the set-up launch projects
+  // them (tilt_relaxation.py:612-616)
+  bool tbb_on = false;
+  for (int k = 0; k < nf; ++k) tbb_on = tbb_on || (fl[k] == &c->tf[1] && tbb_active(c));
+  c->tbb_geom_valid = false;
+  // enforce (+ P on the ring rows: every other row of both fields is a projected row already)
+  auto tbb_enforce = [&](bool project) -> int {
+    if (!tbb_on) return MS_OK;
+    int r = tbb_geom_run(c, nullptr, false, 0.0, /*frozen=*/true);
+    if (r) return r;
+    return tbb_apply_run(c, 0, c->tf[1].tilts, nullptr, project);
+  };
+  rc = tbb_enforce(false);
+  if (rc) return rc;
   auto tvec = [&](TiltField& f, int mode, const double* src, double* out, double coef, int flag) -> int {
     ProfScope ps(c, 6);
     HIPCHK(c, launch_tvec(mode, c->tile0, c->tile1, t.nv, t.own, c->d_vflags, f.grad, f.minv, f.dir, f.tilts, src,
@@ -633,6 +648,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
       for (int l = 0; l < 3; ++l) c->tf[l].dt_target_valid = c->tf[l].rs_coef_valid = false;
       c->rb_coef_valid = false;
       c->tb_relax = c->tb_geom_valid = false;
+      c->tbb_geom_valid = false;
     }
   } va_scope{c};
   c->relax_va_valid = jacobi_smooth_by_param;  // leaflet driver only (the single field has no such form)
@@ -655,7 +671,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     int r = MS_OK;
     TgradArgs ga;
     uint32_t gmask = 0;
-    if (tgrad_plan(c, fl, nf, &ga, &gmask)) {
+    if (!tbb_on && tgrad_plan(c, fl, nf, &ga, &gmask)) {  // (the constraint's projection sits between the gradient and its norms)
       // every module of every field, the clamped rows and the norms in ONE pass and one fold
       {
         ProfScope ps(c, 12);
@@ -666,6 +682,10 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     } else {
       r = tilt_eval(c, false, true);
       if (r) return r;
+      if (tbb_on) {  // tilt_relaxation.py:826-853: the projection, then the fixed rows' zeroing and the norms below
+        r = tbb_apply_run(c, 2, c->tf[1].grad, nullptr, false);
+        if (r) return r;
+      }
       for (int k = 0; k < nf; ++k) {
         r = tvec(*fl[k], 0, nullptr, nullptr, 0.0, 0);
         if (r) return r;
@@ -781,7 +801,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     return search(along_dir, sign, E0, E_acc, accepted);
   };
   // (the rim source's, the coupling's, the splay / twist term's and the theta_B contact term's kernels are not recorded)
-  if (c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_THETAB_CONTACT_IN))) {
+  if (!tbb_on && c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_THETAB_CONTACT_IN))) {
     // one-tile context: the whole solve below as ONE launch (ms_internal.h: ExecRelaxHead)
     bool used = false;
     rc = relax_program(c, rp, fl, nf, norm_mask, &iters, &evals, &used);
@@ -796,6 +816,13 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
   }
   const double tol = rp->tol > 0.0 ? rp->tol : 0.0;
   double E0 = 0.0, gnorm = 0.0, rz_old = 0.0;
+  // behind an accepted step (:1048-1052 / :1372-1378): the constraint enforced on the accepted field, then P
+  int accepted = 0;
+  auto tbb_after_accept = [&]() -> int {
+    ++accepted;
+    if (c->tilt_proj_cadence != MS_TILT_PROJECTION_PER_STEP || accepted % c->tilt_proj_interval != 0) return MS_OK;
+    return tbb_enforce(true);
+  };
   if (rp->solver == 0) {  // gradient descent (:312-351 / :892-1058)
     for (int it = 0; it < rp->max_iters; ++it) {
       rc = grad_at(&E0, &gnorm, &rz_old);
@@ -807,6 +834,8 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
       if (rc) return rc;
       ++iters;
       if (!acc) break;
+      rc = tbb_after_accept();
+      if (rc) return rc;
     }
   } else {  // (preconditioned) Fletcher-Reeves CG (:352-421 / :1059-1398)
     rc = grad_at(&E0, &gnorm, &rz_old);
@@ -822,6 +851,8 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
         if (rc) return rc;
         ++iters;
         if (!acc) break;
+        rc = tbb_after_accept();
+        if (rc) return rc;
         double rz_new = 0.0;
         rc = grad_at(&E0, &gnorm, &rz_new);
         if (rc) return rc;
@@ -834,6 +865,12 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
       }
     }
   }
+  if (c->tilt_proj_cadence == MS_TILT_PROJECTION_PER_PASS) {  // :1416-1417
+    rc = tbb_enforce(true);
+    if (rc) return rc;
+  }
+  rc = tbb_enforce(false);  // :1474-1478, the stored field
+  if (rc) return rc;
   if (iters_out) *iters_out = iters;
   if (evals_out) *evals_out = evals;
   // the tilt-dependent energies in the mailbox belong to whatever was evaluated last

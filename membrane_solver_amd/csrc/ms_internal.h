@@ -465,6 +465,32 @@ struct ThetabArgs {
 };
 hipError_t launch_thetab_geom(const ThetabArgs& a, hipStream_t s);
 hipError_t launch_thetab_apply(const ThetabArgs& a, hipStream_t s);
+// tilt_thetaB_boundary_in (ms_thetab_bnd.hip): the constraint t_in . d = theta_B on a ring of rows.  k_tbb_geom writes
+// the per-row table (d, the unit vertex normal N_v, keep) from x (+ alpha d), or from a trial buffer handed in as x;
+// k_tbb_apply<0/1/2> enforces in place, writes P(enforce(t)) into another buffer, or projects a gradient.  Rows are
+// the library's (til.iperm applied), in the setter's order.
+struct TbbArgs {
+  const double* x;
+  const double* d;        // trial direction or nullptr, alpha: exactly what EnergyArgs hands k_energy
+  double alpha;
+  const uint8_t* vflags;  // (a fixed row does not move in a trial; the field's fixed bit skips a row of an apply)
+  int n;                  // ring rows, any number
+  const int32_t* rows;
+  const int32_t* off;     // n + 1: CSR over the rows' incident facets, ascending facet order
+  const int32_t* fv;      // three rows per CSR entry: the facet's corners in its own order
+  double center[3];       // tilt_thetaB_center
+  double normal[3];       // unit normal of the ring's plane
+  double* dir;            // [3 n] d, 0 where the row is dropped
+  double* nrm;            // [3 n] N_v
+  uint8_t* keep;          // [n]
+  double* field;          // apply: the inner tilts (modes 0 / 1) or the inner tilt gradient (mode 2)
+  double* out;            // mode 1: where P(enforce(t)) of the ring rows goes
+  double theta_b;
+  int project;            // mode 0: t <- t - (t . N_v) N_v behind the enforcement
+  uint8_t fixed_bit;      // the inner field's
+};
+hipError_t launch_tbb_geom(const TbbArgs& a, hipStream_t s);
+hipError_t launch_tbb_apply(int mode, const TbbArgs& a, hipStream_t s);
 // tilt_coupling (ms_couple.hip): E = 1/2 k_c int |t_out + s t_in|^2 dA, k_tilt's lumped arithmetic on the field
 // d = t_out + s t_in.  k_couple<0/1> per tile on x (+ alpha d); k_couple_vec per vertex on the frozen surface's areas.
 struct CoupleArgs {

@@ -462,6 +462,62 @@ class DeviceMesh:
         self._chk(L.lib().ms_thetab_contact_stats(self._h, _pd(v)), "ms_thetab_contact_stats")
         return {"geom_launches": int(v[0]), "apply_launches": int(v[1])}
 
+    def set_thetab_boundary(self, rows=None, *, center=(0.0, 0.0, 0.0), normal=(0.0, 0.0, 1.0)):
+        """tilt_thetaB_boundary_in: the constraint's ring (external rows, in vertex_ids order) and frame
+        (ms_set_thetab_boundary); no rows clear the table.  theta_B is set_thetab_value's."""
+        if self.shard_count != 1:  # (the library refuses it as well)
+            raise L.MembraneHipError("the tilt_thetaB_boundary_in constraint is not sharded (single GPU only)")
+        if rows is None:
+            self._chk(L.lib().ms_set_thetab_boundary(self._h, 0, None, None), "ms_set_thetab_boundary")
+            self._thetab_boundary_rows = 0
+            return
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        n = len(r)
+        if n == 0:  # (a non-NULL pointer: a table that holds no row)
+            r = np.zeros(1, np.int32)
+        p = L.ms_thetab_boundary_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)))
+        self._chk(L.lib().ms_set_thetab_boundary(self._h, n, r.ctypes.data_as(L._I32), ctypes.byref(p)),
+                  "ms_set_thetab_boundary")
+        self._thetab_boundary_rows = n
+
+    def set_tilt_projection(self, cadence: str = "per_step", interval: int = 1):
+        """tilt_projection_cadence / tilt_projection_interval of the leaflet relaxation (ms_set_tilt_projection)."""
+        codes = {"per_step": L.MS_TILT_PROJECTION_PER_STEP, "per_pass": L.MS_TILT_PROJECTION_PER_PASS}
+        if cadence not in codes:
+            raise ValueError("tilt_projection_cadence must be 'per_step' or 'per_pass'.")
+        if int(interval) < 1:
+            raise ValueError("tilt_projection_interval must be >= 1.")
+        self._chk(L.lib().ms_set_tilt_projection(self._h, codes[cadence], int(interval)), "ms_set_tilt_projection")
+
+    def thetab_boundary_enforce(self):
+        """t_in <- t_in + (theta_B - t_in . d) d on the ring's kept, free rows, on the context's positions and stored
+        inner tilts (ms_thetab_boundary_enforce)."""
+        self._chk(L.lib().ms_thetab_boundary_enforce(self._h), "ms_thetab_boundary_enforce")
+
+    def thetab_boundary_directions(self):
+        """-> (d (n_rows,3), keep (n_rows,) bool) of the table's rows on the context's positions
+        (ms_thetab_boundary_directions)."""
+        n = int(getattr(self, "_thetab_boundary_rows", 0))
+        d, keep = np.zeros((max(n, 1), 3)), np.zeros(max(n, 1), dtype=np.uint8)
+        self._chk(L.lib().ms_thetab_boundary_directions(self._h, _pd(d), keep.ctypes.data_as(L._U8)),
+                  "ms_thetab_boundary_directions")
+        return d[:n], keep[:n].astype(bool)
+
+    def thetab_boundary_projected_gradient(self):
+        """-> (tilt-dependent energy, dE/dt_in, dE/dt_out) as the relaxation sees them: the inner gradient projected
+        against the constraint's rows, fixed rows zeroed (ms_thetab_boundary_projected_gradient)."""
+        e = ctypes.c_double(0.0)
+        gi, go = np.empty((self.nv, 3), dtype=np.float64), np.empty((self.nv, 3), dtype=np.float64)
+        self._chk(L.lib().ms_thetab_boundary_projected_gradient(self._h, ctypes.byref(e), _pd(gi), _pd(go)),
+                  "ms_thetab_boundary_projected_gradient")
+        return float(e.value), gi, go
+
+    def thetab_boundary_stats(self):
+        """Launch counts of the constraint's kernels (ms_thetab_boundary_stats)."""
+        v = np.zeros(3)
+        self._chk(L.lib().ms_thetab_boundary_stats(self._h, _pd(v)), "ms_thetab_boundary_stats")
+        return {"geom_launches": int(v[0]), "enforce_launches": int(v[1]), "project_launches": int(v[2])}
+
     def get_leaflet_tilts(self, leaflet: str) -> np.ndarray:
         out = np.empty((self.nv, 3), dtype=np.float64)
         lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]

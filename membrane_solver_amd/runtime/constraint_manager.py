@@ -1,7 +1,8 @@
 """Constraint plugin loader (runtime/constraint_manager.py, reduced to the
-in-scope ``volume``, ``pin_to_plane`` and ``pin_to_circle`` modules) and the KKT
-projection of the gradient (:174-315): the k == 1 dense row alone, or the mixed
-dense + sparse-row solve with the pins."""
+in-scope ``volume``, ``pin_to_plane``, ``pin_to_circle`` and ``tilt_thetaB_boundary_in``
+modules), the KKT projection of the gradient (:174-315): the k == 1 dense row alone, or the
+mixed dense + sparse-row solve with the pins -- and the two tilt-space seams (:651-841) for
+constraints that act on the leaflet tilts only."""
 
 from __future__ import annotations
 
@@ -73,6 +74,49 @@ class ConstraintModuleManager:
             lam = float(np.sum(grad_arr * gC)) / norm_sq
             grad_arr -= lam * gC
 
+    def apply_tilt_gradient_modifications_array(self, tilt_in_grad_arr, tilt_out_grad_arr, mesh, global_params, *,
+                                                positions=None, tilts_in=None, tilts_out=None):
+        """Host-array variant of constraint_manager.py:651-828: the leaflet tilt gradients projected against the sparse
+        rows of every module that has ``constraint_gradients_tilt_rows_array``.  In scope: rows that touch one vertex
+        of one leaflet each and are pairwise disjoint (tilt_thetaB_boundary_in), so C C^T is diagonal and the
+        projection is g_i <- g_i - ((g_i . d_i) / (d_i . d_i)) d_i row by row.  (On the device the relaxation does
+        this itself: ms_relax_leaflet_tilts with a table set, DeviceMesh.thetab_boundary_projected_gradient.)"""
+        if tilt_in_grad_arr.shape != tilt_out_grad_arr.shape:
+            raise ValueError("tilt gradient arrays must have matching shapes")
+        if positions is None:
+            positions = mesh.positions_view()
+        seen = [set(), set()]
+        for module in self.modules.values():
+            fn = getattr(module, "constraint_gradients_tilt_rows_array", None)
+            if fn is None:
+                continue
+            payload = fn(mesh, global_params, positions=positions, index_map=mesh.vertex_index_to_row,
+                         tilts_in=tilts_in, tilts_out=tilts_out)
+            for parts in payload or []:
+                for leaflet, (part, grad) in enumerate(zip(parts, (tilt_in_grad_arr, tilt_out_grad_arr))):
+                    if part is None:
+                        continue
+                    rows, vecs = np.asarray(part[0], dtype=int), np.asarray(part[1], dtype=float)
+                    if len(rows) != 1 or int(rows[0]) in seen[leaflet] or sum(p is not None for p in parts) != 1:
+                        raise NotImplementedError("only disjoint one-vertex, one-leaflet tilt constraint rows are in scope")
+                    seen[leaflet].add(int(rows[0]))
+                    d = vecs.reshape(3)
+                    g = grad[int(rows[0])]
+                    grad[int(rows[0])] = g - (float(g @ d) / float(d @ d)) * d
+
+    def enforce_tilt_constraints(self, mesh, *, device=None, **kwargs):
+        """Tilt-only projections of every loaded module that has ``enforce_tilt_constraint``
+        (constraint_manager.py:830-841), on the mesh's arrays -- or, with ``device`` (a DeviceMesh whose table is set),
+        on the device's positions and stored inner tilts (ms_thetab_boundary_enforce)."""
+        for module in self.modules.values():
+            fn = getattr(module, "enforce_tilt_constraint", None)
+            if fn is None:
+                continue
+            if device is not None:
+                device.thetab_boundary_enforce()
+            else:
+                fn(mesh, **kwargs)
+
     def enforce_all(self, mesh, *, context="minimize", global_params=None, **options):
         """Hard projection of every loaded constraint that has one -- here: ``volume`` -- onto its target
         (interface of constraint_manager.py:843-905).
@@ -86,6 +130,8 @@ class ConstraintModuleManager:
             global_params.get("volume_projection_during_minimization", True))
         options.pop("force_projection", None)
         for name, module in self.modules.items():  # in the listed order (:857-905); the pins in every context
+            if not hasattr(module, "enforce_constraint"):  # (a tilt-only module: enforce_tilt_constraints)
+                continue
             if name != "volume":
                 module.enforce_constraint(mesh, context=context, global_params=global_params, **options)
             elif not (during_step and not step_projection):

@@ -53,6 +53,7 @@ from ..geometry.mesh import mirror_for
 from ..modules.energy import leaflet_common as _lc
 from ..modules.energy._common import bending_gradient_mode, bending_model
 from ..modules.constraints import pins as _pins
+from ..modules.constraints import tilt_thetaB_boundary_in as _tbb
 from ..modules.energy.body_area_penalty import body_area_params
 from ..modules.energy import edge_length_penalty as _edgepen
 from ..modules.energy import line_tension as _line
@@ -103,6 +104,10 @@ _LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN 
                  | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING
                  | L.MS_MOD_TILT_SPLAY_TWIST_IN | L.MS_MOD_TILT_RIM_SOURCE_BILAYER | L.MS_MOD_TILT_THETAB_CONTACT_IN)
 _TILT_BITS = _SINGLE_TILT_BITS | _LEAFLET_BITS
+# every module that reads the inner leaflet's field (a relaxation with one of them relaxes that field)
+_INNER_LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_TILT_DISK_TARGET_IN
+                       | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_COUPLING | L.MS_MOD_TILT_SPLAY_TWIST_IN
+                       | L.MS_MOD_TILT_RIM_SOURCE_BILAYER | L.MS_MOD_TILT_THETAB_CONTACT_IN)
 # scalar slot of every module that shares energies[3]
 _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": L.MS_S_ETILT_IN,
                 "tilt_out": L.MS_S_ETILT_OUT, "tilt_smoothness_in": L.MS_S_ETS_IN,
@@ -223,9 +228,9 @@ class Minimizer:
         self.constraint_modules = [self.constraint_manager.get_constraint(c)
                                    for c in self.constraint_module_names]
         for name in self.constraint_module_names:
-            if name not in ("volume",) + _PIN_MODULES:
+            if name not in ("volume", _tbb.NAME) + _PIN_MODULES:
                 raise L.MembraneHipError(f"constraint module {name!r} is outside the HIP hot path "
-                                         "(volume, pin_to_plane, pin_to_circle)")
+                                         "(volume, pin_to_plane, pin_to_circle, tilt_thetaB_boundary_in)")
         self._pin_names = [n for n in self.constraint_module_names if n in _PIN_MODULES]
         if self._pin_names and "volume" in self.constraint_module_names and \
                 self.constraint_module_names.index("volume") < self.constraint_module_names.index(self._pin_names[0]):
@@ -234,6 +239,8 @@ class Minimizer:
                                      "path enforces the pins first; list the pin modules before volume")
         self._pin_key = None
         self._pins_active = False
+        self._tbb_active = False  # (set by _device(): tilt_thetaB_boundary_in is listed and has a ring)
+        # (tilt_thetaB_boundary_in has no enforce_constraint: alone it switches no enforcer on, minimizer.py:1103-1106)
         self._has_enforceable_constraints = any(hasattr(m, "enforce_constraint")
                                                 for m in self.constraint_modules)
         self._configured_key = None
@@ -356,6 +363,8 @@ class Minimizer:
             raise L.MembraneHipError("tilt_thetaB_contact_in together with a single-field tilt module is outside the "
                                      "HIP hot path")
         self._thetab_update = thetab is not None and thetab["penalty_mode"] == "legacy" and thetab["k"] > 0.0
+        tbb = self._thetab_boundary_params(mods)
+        self._tbb_active = tbb is not None
         target = 0.0
         stiffness = float(gp.get("volume_stiffness") or 0.0)
         body = mir.body
@@ -440,6 +449,19 @@ class Minimizer:
                     dm.set_thetab_contact(**thetab)
                     mir._leaflet_keys["bend_thetab"] = key
                 dm.set_thetab_value(_lc.thetab_value(gp))
+            # tilt_thetaB_boundary_in: keyed like the other ring tables; theta_B and the relaxation's cadence go with every
+            # configuration; a table of an earlier configuration is cleared
+            key = None if tbb is None else (mir._topo_key, id(dm), _tbb.device_key(tbb))
+            old = mir._leaflet_keys.get("bend_tbb")
+            if old != key:
+                if tbb is not None:
+                    dm.set_thetab_boundary(**tbb)
+                elif old is not None and old[1] == id(dm):
+                    dm.set_thetab_boundary(None)
+                mir._leaflet_keys["bend_tbb"] = key
+            if tbb is not None:
+                dm.set_thetab_value(_lc.thetab_value(gp))
+                dm.set_tilt_projection(*_tbb.projection_schedule(gp))
             if coupling is not None:  # keyed on modulus and sign ("bend_": not a tilt upload, mark_device_leaflets_current)
                 key = (id(dm), coupling)
                 if mir._leaflet_keys.get("bend_coupling") != key:
@@ -502,6 +524,42 @@ class Minimizer:
         if self._edgepen_key is None or self._edgepen_key[:5] != key:
             self._edgepen_key = key + (_edgepen.upload(self.mesh, self.global_params, dm, (tail, head, target, num)),)
         return self._edgepen_key[5]
+
+    def _thetab_boundary_params(self, mods):
+        """tilt_thetaB_boundary_in: kwargs of DeviceMesh.set_thetab_boundary, or None where the module is not listed or
+        does nothing (no group, no tagged row).  Everything the device path does not take is refused here, before
+        anything is uploaded."""
+        if _tbb.NAME not in self.constraint_module_names:
+            return None
+        gp = self.global_params
+        prm = _tbb.device_params(self.mesh, gp)  # (a missing normal, non-finite parameters, the grown "disk" ring,
+        if prm is None:                          # tilt_thetaB_optimize: refused there)
+            return None
+        _tbb.projection_schedule(gp)  # ValueError on the values the reference rejects
+        if mods & _SINGLE_TILT_BITS:
+            raise L.MembraneHipError("tilt_thetaB_boundary_in together with a single-field tilt module is outside the "
+                                     "HIP hot path")
+        if not mods & _INNER_LEAFLET_BITS:
+            raise L.MembraneHipError("tilt_thetaB_boundary_in without an active inner-leaflet tilt module (tilt_in, "
+                                     "bending_tilt_in, ...) is outside the HIP hot path: nothing relaxes the field it "
+                                     "constrains")
+        if "volume" in self.constraint_module_names:
+            raise L.MembraneHipError("tilt_thetaB_boundary_in next to the volume constraint's enforcer is outside the "
+                                     "HIP hot path")
+        if self._pin_names:
+            X = np.asarray(self.mesh.positions_view(), dtype=np.float64)
+            if not _pins.device_tables(X, _pins.programs(self.mesh, self._pin_names), []).params:
+                # the reference's line search then has an enforcer that moves nothing but the ring's tilts; the device
+                # switches its enforcer lane on with the pin program
+                raise L.MembraneHipError("tilt_thetaB_boundary_in next to a pin module that pins nothing is outside the "
+                                         "HIP hot path")
+            if self._target_volume() is not None and gp.get("volume_constraint_mode", "lagrange") == "lagrange" \
+                    and not gp.get("volume_projection_during_minimization", True):
+                # the volume drift check of a step (minimizer.py:1478-1513) then runs the mesh-operation enforcement
+                # inside ms_minimize, whose lane does not run the tilt constraint between the pins and the projection
+                raise L.MembraneHipError("tilt_thetaB_boundary_in next to pins and the volume drift check of a body with "
+                                         "a target volume is outside the HIP hot path")
+        return prm
 
     def _upload_pins(self, mir, dm, mods):
         """Resolve the pin tags once per mesh topology, fixed mask and row set (call refresh_modules() after
@@ -621,6 +679,11 @@ class Minimizer:
         moved = False
         if self._pins_active:  # constraint_manager.enforce_all: the pins in every context, listed before volume
             dm.enforce_pins()
+            moved = True
+        if self._tbb_active:
+            # minimizer.py:1112-1120, :1165-1171: enforce_tilt_constraints behind enforce_all, on the pinned surface; the
+            # tangent projection of the finalize / mesh-operation contexts below comes after it
+            dm.thetab_boundary_enforce()
             moved = True
         gp = self.global_params
         if context == "minimize" and not gp.get("volume_projection_during_minimization", True):
