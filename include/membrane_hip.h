@@ -826,6 +826,14 @@ int ms_search_trials(ms_ctx *ctx, double *rows, int max_rows, int *n_rows, int64
  * kernel writes it from the stored gradient and history first.  *skipped: steps whose gradient pass left the store out;
  * *materialized: directions written out afterwards.  Since ms_create.  (MS_BUF_D after ms_reset_stepper is unspecified until the next step.) */
 int ms_direction_stats(ms_ctx *ctx, int64_t *skipped, int64_t *materialized);
+/* The energy kernel has a lean instance for the headline case: surface + Helfrich bending with uniform surface tension,
+ * bending modulus and spontaneous curvature on a closed surface of more than one tile, LDS-atomic vertex sums (not
+ * ms_set_deterministic), no volume term and no bending_tilt records.  Every other case runs the general instance.
+ * The lean instance performs the general instance's arithmetic operation for operation; what the general one decides
+ * from its arguments at run time is compiled out.  MS_KA_LEAN=0 in the environment at ms_create forces the general
+ * instance.
+ * *lean / *general: energy launches (or k_exec records) of either kind since ms_create.  No reference counterpart. */
+int ms_energy_stats(ms_ctx *ctx, int64_t *lean, int64_t *general);
 /* One-tile meshes (every mesh the reference's own benchmarks and decks use: <= 256 vertices): the library records its
  * kernel launches and runs them pack by pack in ONE workgroup (k_exec) instead of launching each -- same device code,
  * same results bit for bit, a few launches per step instead of dozens.  MS_EXEC=0 in the environment switches it off.

@@ -269,6 +269,7 @@ SIGNATURES = {
     "ms_queue_stats": (ctypes.c_int, [_P, _I64]),
     "ms_search_trials": (ctypes.c_int, [_P, _D, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _I64]),
     "ms_direction_stats": (ctypes.c_int, [_P, _I64, _I64]),
+    "ms_energy_stats": (ctypes.c_int, [_P, _I64, _I64]),
     "ms_exec_stats": (ctypes.c_int, [_P, _I64]),
     "ms_resident_stats": (ctypes.c_int, [_P, _I64]),
     "ms_set_pins": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.c_int, _I32, _I32, _I32, _I32, _I32, ctypes.c_int,

@@ -203,6 +203,10 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
   c->no_fast = variant_env("MS_NO_FAST") != nullptr && atoi(variant_env("MS_NO_FAST")) != 0;
   c->pair_lean_enable = !(getenv("MS_PAIR_LEAN") != nullptr && atoi(getenv("MS_PAIR_LEAN")) == 0);
   c->deterministic = getenv("MS_DETERMINISTIC") != nullptr && atoi(getenv("MS_DETERMINISTIC")) != 0;
+  // MS_KA_LEAN=0: the general k_energy instance everywhere (the A/B switch, and how the tests set the two instances
+  // against each other).  A one-tile mesh never takes the lean instance: its launches are k_exec's, and stay the same
+  // kernel code whether the recorder is attached or not (MS_EXEC=0, profiling)
+  c->ka_lean_off = ((getenv("MS_KA_LEAN") != nullptr && atoi(getenv("MS_KA_LEAN")) == 0) || t.n_tiles == 1) ? 1u : 0u;
   c->resident_enable = !(getenv("MS_RESIDENT") != nullptr && atoi(getenv("MS_RESIDENT")) == 0);
   c->params.modules = MS_MOD_SURFACE;
   c->params.bending_model = MS_BEND_HELFRICH;

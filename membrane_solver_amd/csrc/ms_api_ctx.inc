@@ -237,6 +237,8 @@ struct ms_ctx {
   // it: the queueing code restores the carried state, the step that adopts the pass takes the flag from here)
   bool kc_dir_unwritten[2] = {false, false};
   long dir_skipped = 0, dir_materialized = 0;  // ms_direction_stats
+  long ka_lean = 0, ka_general = 0;            // ms_energy_stats: k_energy launches (or k_exec records) by instance
+  uint32_t ka_lean_off = 0;                    // EnergyArgs::lean_off of this context (MS_KA_LEAN=0 at ms_create, a one-tile mesh)
   // Decision records (ms_internal.h DEC_*): one 128-byte line each, written by the head workgroup of the fold that
   // closes a line-search stage, read by every kernel queued behind that stage.  Record k belongs to stage k of the
   // round being queued; the stream orders a record's readers between its writers.

@@ -117,6 +117,13 @@ int ms_direction_stats(ms_ctx* c, int64_t* skipped, int64_t* materialized) {
   return MS_OK;
 }
 
+int ms_energy_stats(ms_ctx* c, int64_t* lean, int64_t* general) {
+  if (!c || !lean || !general) return MS_ERR_INVALID;
+  *lean = c->ka_lean;
+  *general = c->ka_general;
+  return MS_OK;
+}
+
 int ms_resident_stats(ms_ctx* c, int64_t stats[4]) {
   if (!c || !stats) return MS_ERR_INVALID;
   stats[0] = c->resident_ok;

@@ -643,6 +643,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   a.gate = st.cur_gate_fold_only ? nullptr : st.cur_gate;
   a.gate_want = st.cur_gate_want;
   a.atomic = c->deterministic ? 0 : 1;
+  a.lean_off = c->ka_lean_off;
   a.pair = 0;
   for (int j = 0; j < MS_MAX_TRIALS - 1; ++j) {
     a.alpha_side[j] = 0.0;
@@ -687,7 +688,9 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   } else if (!lbt) {
     ProfScope ps(c, a.pair > 3 ? 10 : (a.pair == 3 ? 8 : (a.pair ? 7 : 0)), a.gate, a.gate_want);
     const double t_l0 = g_host_timing.on ? HostTiming::now() : 0.0;
-    HIPCHK(c, launch_energy(a, guard && use_dir, c->cap, c->til.max_ent, c->stream));
+    EnergyInst ran{};
+    HIPCHK(c, launch_energy(a, guard && use_dir, c->cap, c->til.max_ent, c->stream, &ran));
+    ++(ran.lean ? c->ka_lean : c->ka_general);
     if (g_host_timing.on && g_host_timing.armed) {
       const double t1 = HostTiming::now();
       g_host_timing.armed = false;
@@ -767,6 +770,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
       {
         ProfScope ps(c, 0);
         HIPCHK(c, launch_energy(al, guard && use_dir, c->cap, c->til.max_ent, c->stream));
+        ++c->ka_general;  // (bt_vert / bt_normals: never lean)
       }
       if (fused_tilt) continue;  // (its facet pass rides in the one launch below)
       int rc = bt_pass_f(c, f, write_factors ? 1 : 0, use_dir, alpha, use_dir ? f.trial : f.tilts);

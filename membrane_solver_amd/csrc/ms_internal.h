@@ -141,6 +141,9 @@ struct EnergyArgs {
   // queued stage (nullptr: unconditional): run only if the decision word holds `gate_want` (see DEC_*)
   const uint32_t* gate;
   uint32_t gate_want;
+  // nonzero: never the lean instance (MS_KA_LEAN=0 at ms_create, a one-tile mesh; launch_energy sets it under a
+  // k_exec recorder)
+  uint32_t lean_off = 0;
   const double* bt_normals;  // leaflet bending_tilt: unit vertex normals of the evaluated positions (signed H, K_dir = n)
   // energy-only evaluation of BOTH leaflets' bending_tilt in one launch: the second leaflet's record from the same
   // curvature sums with its own (kappa, c0) (no factor outputs: fK / fA serve one leaflet at a time)
@@ -579,19 +582,26 @@ static_assert(sizeof(ExecCmdHead) == 32, "ExecCmdHead is 32 bytes");
 struct EnergyInst {
   bool bend, guard, atomic, area, fast;  // fast: the T = 256 instances
   int multi;                             // trial positions per launch: 0 (one), 2, 3 or 8
+  bool lean = false;                     // the headline instances (energy_body's LEANE), every multi
   constexpr bool valid() const {
-    return (bend || !atomic) && (multi == 0 || ((multi == 2 || multi == 3 || multi == 8) && bend && !guard && !area));
+    return (bend || !atomic) && (multi == 0 || ((multi == 2 || multi == 3 || multi == 8) && bend && !guard && !area)) &&
+           (!lean || (bend && !guard && atomic && fast && !area));
   }
-  constexpr bool in_exec() const { return valid() && fast && multi == 0; }
+  // (k_exec keeps the general instances: a lean one has no code())
+  constexpr bool in_exec() const { return valid() && fast && multi == 0 && !lean; }
   // bit 0 bending, bit 1 guard, bit 2 LDS-atomic vertex sums, bit 3 body area (body_area_penalty)
   constexpr uint32_t code() const { return (bend ? 1u : 0u) | (guard ? 2u : 0u) | (atomic ? 4u : 0u) | (area ? 8u : 0u); }
   static constexpr EnergyInst from_code(uint32_t c) {
     return {(c & 1u) != 0, (c & 2u) != 0, (c & 4u) != 0, (c & 8u) != 0, true, c < 16u ? 0 : -1};
   }
   constexpr bool operator==(const EnergyInst& o) const {
-    return bend == o.bend && guard == o.guard && atomic == o.atomic && area == o.area && fast == o.fast && multi == o.multi;
+    return bend == o.bend && guard == o.guard && atomic == o.atomic && area == o.area && fast == o.fast && multi == o.multi &&
+           lean == o.lean;
   }
 };
+static_assert(EnergyInst{true, false, true, false, true, 3, true}.valid() && !EnergyInst{true, false, true, false, true, 0, true}.in_exec() &&
+                  !EnergyInst{true, false, false, false, true, 0, true}.valid() && !EnergyInst{true, true, true, false, true, 0, true}.valid(),
+              "EnergyInst: lean goes with the T = 256 LDS-atomic bending instances only and is never one of k_exec's");
 struct GradientInst {
   int mode;  // bending: 0 none, 1 analytic, 2 approx, 3 leaflet bending_tilt (generic-size instances only)
   bool volrow, atomic, lean, area, fast;
@@ -756,7 +766,8 @@ hipError_t launch_resident(const ResidentArgs& a, size_t lds, hipStream_t s);
 // max_ent = largest per-tile vertex->corner entry count.
 size_t energy_lds_bytes(int T, int cap, int max_ent, bool bend, bool guard, bool flags, bool atomic = false);
 size_t gradient_lds_bytes(int T, int cap, int max_ent, bool bend, bool volrow, bool atomic = false, bool leaf = false);
-hipError_t launch_energy(const EnergyArgs& a, bool guard, int cap, int max_ent, hipStream_t s);
+// (*ran, when given: the instance that was launched or recorded)
+hipError_t launch_energy(const EnergyArgs& a, bool guard, int cap, int max_ent, hipStream_t s, EnergyInst* ran = nullptr);
 hipError_t launch_gradient(const GradientArgs& a, int cap, int max_ent, hipStream_t s);
 // which instantiation the launchers pick; !valid() for arguments they refuse (hipErrorInvalidValue)
 EnergyInst energy_instance(const EnergyArgs& a, bool guard);

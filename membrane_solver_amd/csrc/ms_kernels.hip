@@ -506,8 +506,16 @@ __device__ unsigned long long g_stamps[8 * 16384];
 // AREA: also sum the area of the body's facets into MS_S_AREA (body_area_penalty).  A template flag, not a runtime one:
 // the accumulator and the sixth reduced value would cost existing instances registers, some of them occupancy
 // (tools/kernel_resources.py).  Only the k_energy_area instances carry it; never combined with MULTI.
-template <bool BEND, bool GUARD, int TT, int CAPC, bool ATOMIC, int MULTI = 0, bool AREA = false>
+// LEANE: the instance of the headline loop (energy_instance: surface + Helfrich bending, uniform gamma / kappa / c0, closed
+// surface, no volume term, no bending_tilt records).  What the general code decides per launch from its arguments is
+// decided here by the compiler: no module tests, no gamma register, no per-vertex parameter loads, no flag bytes in LDS,
+// no boundary redistribution, and one facet-level test in front of the fifth accumulator column.  Item by item the same
+// operations on the same doubles as the general instance.  (Letting two edges carry the facet as gradient_body does
+// saved four VALU instructions of 564 and nothing measurable, at the price of last bits: measured and taken out,
+// DESIGN.md section 5.)
+template <bool BEND, bool GUARD, int TT, int CAPC, bool ATOMIC, int MULTI = 0, bool AREA = false, bool LEANE = false>
 __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_ent, double* lds, int block_id) {
+  static_assert(!LEANE || (BEND && !GUARD && ATOMIC && TT == 256 && !AREA), "LEANE: the T = 256 LDS-atomic bending instances");
   int bid = block_id;
   double* const ran_row = a.partials + (size_t)MS_P_RAN * a.m.n_tiles;  // (of the ordinary partials)
   bool last_trial = true;  // this workgroup evaluates the launch's last trial (ordinary outputs)
@@ -546,7 +554,7 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
   // ATOMIC: stg holds the five per-vertex accumulators K(3), A_vor, A_eff - A_vor (ds_add_f64), no CSR
   uint16_t* vent = reinterpret_cast<uint16_t*>(stg + (BEND ? (ATOMIC ? 5 : 9) * T : 6 * 16));
   uint8_t* lfl = reinterpret_cast<uint8_t*>(vent + ((BEND && !ATOMIC) ? ((max_ent + 3) & ~3) : 0));
-  const bool stage_flags = a.m.has_boundary || GUARD;
+  const bool stage_flags = !LEANE && (a.m.has_boundary || GUARD);
   // queued line-search stage: runs only if the decision word says so (DEC_CONTINUE: every trial before it was rejected)
   const int my_tile = a.tile0 + xcd_tile(bid, a.tile1 - a.tile0);
   if (a.gate != nullptr && !gate_open(a.gate, a.gate_want, last_trial ? ran_row + my_tile : nullptr)) return;
@@ -566,12 +574,12 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
   double gam_nx = 0.0;
   if (t.f0 + tid < t.f1) {
     tf_nx = facet_load<PACKED>(a.m, (size_t)(t.f0 + tid));
-    gam_nx = a.m.gamma_uniform ? a.m.gamma_const : a.m.tf_gamma[t.f0 + tid];
+    if (!LEANE) gam_nx = a.m.gamma_uniform ? a.m.gamma_const : a.m.tf_gamma[t.f0 + tid];
   }
 
   // per-vertex parameters of the epilogue are requested now, used ~all the way down
   double kappa_v = 0.0, c0_v = 0.0;
-  if (BEND && tid < t.n_owned) {
+  if (BEND && !LEANE && tid < t.n_owned) {
     kappa_v = a.m.kc_uniform ? a.m.kappa_const : a.m.kappa[t.v_lo + tid];
     c0_v = a.m.kc_uniform ? a.m.c0_const : a.m.c0[t.v_lo + tid];
   }
@@ -671,8 +679,8 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
   MS_STAMP(1);
 
   double e_surf = 0.0, vol = 0.0, min_e2 = 1.0e300, guard = 0.0;
-  const bool want_surf = a.modules & MS_MOD_SURFACE;
-  const bool want_vol = a.modules & (MS_MOD_VOLUME_PENALTY | MS_CON_VOLUME | MS_TRACK_VOLUME);
+  const bool want_surf = LEANE || (a.modules & MS_MOD_SURFACE);
+  const bool want_vol = !LEANE && (a.modules & (MS_MOD_VOLUME_PENALTY | MS_CON_VOLUME | MS_TRACK_VOLUME));
   // body_area_penalty (modules/energy/body_area_penalty.py:125-137): the body's area, for K_C's effective tension and the
   // host's 1/2 k (A - A0)^2
   constexpr bool want_area = AREA;
@@ -685,10 +693,10 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
   for (int c0 = t.f0; c0 < t.f1; c0 += T) {
     const int p = c0 + tid;
     const TileFacet tf = facet_unpack<PACKED>(tf_nx);
-    const double gam = gam_nx;
+    const double gam = LEANE ? a.m.gamma_const : gam_nx;  // (uniform: a kernel argument)
     if (p + T < t.f1) {
       tf_nx = facet_load<PACKED>(a.m, (size_t)(p + T));
-      gam_nx = a.m.gamma_uniform ? a.m.gamma_const : a.m.tf_gamma[p + T];
+      if (!LEANE) gam_nx = a.m.gamma_uniform ? a.m.gamma_const : a.m.tf_gamma[p + T];
     }
     double va0 = 0, va1 = 0, va2 = 0, ve0 = 0, ve1 = 0, ve2 = 0;
     if (p < t.f1) {
@@ -741,9 +749,12 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
           ve1 = va1;
           ve2 = va2;
           const double ta_eff = fmax(0.5 * A2, 1.0e-12);
-          if (ta_eff != tri_area) corner_areas(c0, c1, c2, l0, l1, l2, ta_eff, ve0, ve1, ve2);
+          // (lean: without a boundary nothing else makes A_eff differ from A_vor, so this one test stands for the three
+          // per-corner compares in front of the fifth column)
+          const bool clamped = ta_eff != tri_area;
+          if (clamped) corner_areas(c0, c1, c2, l0, l1, l2, ta_eff, ve0, ve1, ve2);
           // bending_utils.py:121-153 boundary -> interior redistribution
-          if (a.m.has_boundary) {  // uniform: closed surfaces skip the whole block
+          if (!LEANE && a.m.has_boundary) {  // uniform: closed surfaces skip the whole block
             const int b0 = (lfl[tf.l0] & VF_BOUNDARY) ? 1 : 0;
             const int b1 = (lfl[tf.l1] & VF_BOUNDARY) ? 1 : 0;
             const int b2 = (lfl[tf.l2] & VF_BOUNDARY) ? 1 : 0;
@@ -767,17 +778,17 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
             if (tf.l0 < no) {
               atomicAdd(&stg[tf.l0], K0.x); atomicAdd(&stg[T + tf.l0], K0.y); atomicAdd(&stg[2 * T + tf.l0], K0.z);
               atomicAdd(&stg[3 * T + tf.l0], va0);
-              if (ve0 != va0) atomicAdd(&stg[4 * T + tf.l0], ve0 - va0);
+              if (LEANE ? clamped : ve0 != va0) atomicAdd(&stg[4 * T + tf.l0], ve0 - va0);
             }
             if (tf.l1 < no) {
               atomicAdd(&stg[tf.l1], K1.x); atomicAdd(&stg[T + tf.l1], K1.y); atomicAdd(&stg[2 * T + tf.l1], K1.z);
               atomicAdd(&stg[3 * T + tf.l1], va1);
-              if (ve1 != va1) atomicAdd(&stg[4 * T + tf.l1], ve1 - va1);
+              if (LEANE ? clamped : ve1 != va1) atomicAdd(&stg[4 * T + tf.l1], ve1 - va1);
             }
             if (tf.l2 < no) {
               atomicAdd(&stg[tf.l2], K2.x); atomicAdd(&stg[T + tf.l2], K2.y); atomicAdd(&stg[2 * T + tf.l2], K2.z);
               atomicAdd(&stg[3 * T + tf.l2], va2);
-              if (ve2 != va2) atomicAdd(&stg[4 * T + tf.l2], ve2 - va2);
+              if (LEANE ? clamped : ve2 != va2) atomicAdd(&stg[4 * T + tf.l2], ve2 - va2);
             }
           } else {
             double* s = stg + tid;
@@ -839,7 +850,7 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
     // modules/energy/bending.py:111-161 on this thread's owned vertex
     const int v = t.v_lo + tid;
     const V3 K = mk(aKx, aKy, aKz);
-    const double kappa = kappa_v, c0 = c0_v;
+    const double kappa = LEANE ? a.m.kappa_const : kappa_v, c0 = LEANE ? a.m.c0_const : c0_v;
     const bool interior = !(own_fl & VF_BOUNDARY);
     const double safe = fmax(aAv, 1.0e-12);
     // |K| and 1/|K| from one refined rsqrt (as for the facet normals); |K| <= 1e-15 gives (0, 0) and the rare path
@@ -850,7 +861,7 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
     double H = k_mag * (0.5 * inv_safe);
     // leaflet bending_tilt (bending_tilt_leaflet.py:455-459): oriented curvature H = (K . n)/(2 A) with
     // the unit vertex normal, and K_dir = n (:574-575)
-    const bool signed_h = a.bt_normals != nullptr;
+    const bool signed_h = !LEANE && a.bt_normals != nullptr;
     V3 nh = mk(0, 0, 0);
     if (signed_h) {
       nh = mk(a.bt_normals[3 * (size_t)v], a.bt_normals[3 * (size_t)v + 1], a.bt_normals[3 * (size_t)v + 2]);
@@ -858,7 +869,7 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
     }
     const double ratio = safe > 1.0e-15 ? aAe * inv_safe : 0.0;
     double scale_K, fe, fv;
-    if (a.bt_vert) {
+    if (!LEANE && a.bt_vert) {
       // bending_tilt.py:217-233: the energy and the factors need div t, which k_bt adds;
       // leave the per-vertex pieces: base term, A_eff, kappa*ratio*H and K_dir*kappa*ratio
       double base = (2.0 * H) - c0;
@@ -880,7 +891,7 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
         rec_b[2] = kappa_b * ratio * H;
         rec_b[3] = 0.0;
       }
-    } else if (a.bending_model == MS_BEND_HELFRICH) {
+    } else if (LEANE || a.bending_model == MS_BEND_HELFRICH) {
       double term = (2.0 * H) - c0;
       if (!interior) term = 0.0;
       e_bend = 0.5 * (kappa * (term * term) * aAe);
@@ -975,10 +986,18 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
 #endif
 }
 
+// The T = 256 LDS-atomic bending instances of k_energy are the LEAN ones -- the headline launches, under the names they
+// always had; the general code for those template arguments is k_energy_general.
 template <bool BEND, bool GUARD, int TT, int CAPC, bool ATOMIC, int MULTI = 0>
 __global__ __launch_bounds__(TT ? TT : 512, (TT == 256 && BEND && !GUARD && ATOMIC) ? MS_KA_SLOTS : 1) MS_WPE_ENERGY void k_energy(EnergyArgs a, int cap_rt, int max_ent) {
   extern __shared__ double lds[];
-  energy_body<BEND, GUARD, TT, CAPC, ATOMIC, MULTI>(a, cap_rt, max_ent, lds, (int)blockIdx.x);
+  constexpr bool HEAD = TT == 256 && BEND && !GUARD && ATOMIC;
+  energy_body<BEND, GUARD, TT, CAPC, ATOMIC, MULTI, false, HEAD>(a, cap_rt, max_ent, lds, (int)blockIdx.x);
+}
+template <int MULTI>
+__global__ __launch_bounds__(256, MS_KA_SLOTS) MS_WPE_ENERGY void k_energy_general(EnergyArgs a, int cap_rt, int max_ent) {
+  extern __shared__ double lds[];
+  energy_body<true, false, 256, 0, true, MULTI>(a, cap_rt, max_ent, lds, (int)blockIdx.x);
 }
 
 static size_t u16_bytes(int T, int max_ent) { return 2 * ((size_t)((max_ent + 3) & ~3)); }
@@ -1054,9 +1073,9 @@ static int abl_ntiles() {
 // The instance descriptors as types, and the one place that maps a runtime descriptor onto them: f(tag) runs for the
 // instance d names, the return value says whether there is one (EXEC: among those k_exec has).  Only what valid() /
 // in_exec() lists is ever instantiated.
-template <bool BEND, bool GUARD, bool ATOMIC, bool AREA, bool FAST, int MULTI>
+template <bool BEND, bool GUARD, bool ATOMIC, bool AREA, bool FAST, int MULTI, bool LEAN>
 struct EnergyTag {
-  static constexpr EnergyInst d{BEND, GUARD, ATOMIC, AREA, FAST, MULTI};
+  static constexpr EnergyInst d{BEND, GUARD, ATOMIC, AREA, FAST, MULTI, LEAN};
 };
 template <int MODE, bool VOLROW, bool ATOMIC, bool LEAN, bool AREA, bool FAST>
 struct GradientTag {
@@ -1080,8 +1099,10 @@ __host__ __device__ __forceinline__ bool visit_instance(const EnergyInst& d, F&&
         return pick(d.area, [&](auto AR) {
           return pick(d.fast, [&](auto FA) {
             return pick_int<0, 2, 3, 8>(d.multi, [&](auto NM) {
-              return visit_tag<EXEC, EnergyTag<decltype(B)::value, decltype(G)::value, decltype(AT)::value,
-                                               decltype(AR)::value, decltype(FA)::value, decltype(NM)::value>>(f);
+              return pick(d.lean, [&](auto LE) {
+                return visit_tag<EXEC, EnergyTag<decltype(B)::value, decltype(G)::value, decltype(AT)::value, decltype(AR)::value,
+                                                 decltype(FA)::value, decltype(NM)::value, decltype(LE)::value>>(f);
+              });
             });
           });
         });
@@ -1119,16 +1140,24 @@ EnergyInst energy_instance(const EnergyArgs& a, bool guard) {
   // pair launch: bending factors on, no guard (the caller checked both), never with body_area_penalty (multi-trial
   // launches belong to the device-decided queue), 2..MS_MAX_TRIALS trials -- valid() refuses the rest
   const int multi = !a.pair ? 0 : ((a.pair < 2 || a.pair > MS_MAX_TRIALS) ? -1 : (a.pair == 2 ? 2 : (a.pair == 3 ? 3 : 8)));
-  return {bend, guard, atomic, area, fast, multi};
+  // the lean instances (see energy_body): surface + Helfrich bending with uniform parameters on a closed surface, no
+  // volume term, no bending_tilt records; lean_off is the caller's veto (MS_KA_LEAN=0, one tile, a recorder for k_exec)
+  const bool lean = fast && bend && atomic && !guard && !area && a.m.gamma_uniform && a.m.kc_uniform &&
+                    a.bending_model == MS_BEND_HELFRICH && !a.m.has_boundary && (a.modules & MS_MOD_SURFACE) &&
+                    !(a.modules & (MS_MOD_VOLUME_PENALTY | MS_CON_VOLUME | MS_TRACK_VOLUME)) && !a.bt_vert && !a.bt_vert2 &&
+                    !a.bt_normals && !a.kappa2 && !a.lean_off;
+  return {bend, guard, atomic, area, fast, multi, lean};
 }
 
-hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_ent, hipStream_t s) {
+hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_ent, hipStream_t s, EnergyInst* ran) {
   EnergyArgs a = a_in;
   if (abl_ntiles() > 0) a.tile1 = std::min(a.tile1, a.tile0 + abl_ntiles());
   const int nb = a.tile1 - a.tile0;
   if (nb <= 0) return hipSuccess;
+  if (exec_find(s) != nullptr) a.lean_off = 1;  // (k_exec has the general instances only)
   const EnergyInst d = energy_instance(a, guard);
   if (!d.valid()) return hipErrorInvalidValue;
+  if (ran) *ran = d;
   // MS_KA_LDS_MIN=<bytes> (variant builds only): request at least this much LDS per workgroup (caps the workgroups per CU)
   static const size_t lds_min = variant_env("MS_KA_LDS_MIN") ? (size_t)atol(variant_env("MS_KA_LDS_MIN")) : 0;
   const size_t lds = std::max(lds_min, energy_lds_bytes(a.m.T, cap, max_ent, d.bend, guard, a.m.has_boundary != 0, d.atomic));
@@ -1143,8 +1172,11 @@ hipError_t launch_energy(const EnergyArgs& a_in, bool guard, int cap, int max_en
   visit_instance<false>(d, [&](auto tag) {
     using I = decltype(tag);
     constexpr int TT = I::d.fast ? FAST_T : 0, CC = I::d.fast ? FAST_CAP : 0;
+    constexpr bool head = I::d.fast && I::d.bend && !I::d.guard && I::d.atomic;  // (k_energy's lean template arguments)
     if constexpr (I::d.area)
       e = launch(k_energy_area<I::d.bend, I::d.guard, TT, CC, I::d.atomic>, grid, a.m.T, lds, s, a, cap, max_ent);
+    else if constexpr (head && !I::d.lean)
+      e = launch(k_energy_general<I::d.multi>, grid, a.m.T, lds, s, a, cap, max_ent);
     else
       e = launch(k_energy<I::d.bend, I::d.guard, TT, CC, I::d.atomic, I::d.multi>, grid, a.m.T, lds, s, a, cap, max_ent);
   });

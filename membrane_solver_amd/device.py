@@ -844,6 +844,13 @@ class DeviceMesh:
                   "ms_direction_stats")
         return {"skipped": int(v[0]), "materialized": int(v[1])}
 
+    def energy_stats(self):
+        """Energy launches that ran the lean instance and the general one (include/membrane_hip.h, ms_energy_stats)."""
+        v = np.zeros(2, dtype=np.int64)
+        self._chk(L.lib().ms_energy_stats(self._h, v[0:1].ctypes.data_as(L._I64), v[1:2].ctypes.data_as(L._I64)),
+                  "ms_energy_stats")
+        return {"lean": int(v[0]), "general": int(v[1])}
+
     def exec_stats(self):
         """One-workgroup interpreter of one-tile meshes (include/membrane_hip.h, ms_exec_stats)."""
         v = np.zeros(4, dtype=np.int64)
