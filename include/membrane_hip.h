@@ -123,6 +123,11 @@ extern "C" {
  * (tilt_in, tilt_rim_source_in): no reduction slot of its own.  Single context only; not together with a single-field
  * tilt module. */
 #define MS_MOD_TILT_THETAB_CONTACT_IN 16777216u
+/* constraint row of the hard body-area constraint (modules/constraints/body_area.py:28-84): dA/dx over the body's
+ * facets takes part in the KKT projection of the gradient -- alone (constraint_manager.py:293-301), or behind the
+ * volume row in the 2 x 2 solve of runtime/constraint_projection.py:101-129.  Needs ms_set_area_constraint(MS_AREA_BODY);
+ * without it the bit does nothing.  ms_set_params keeps the bit out of the word the kernels read. */
+#define MS_CON_BODY_AREA 33554432u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -240,6 +245,14 @@ typedef struct ms_stepper_params {
                               Refused: pins next to tilt modules together with the volume
                               constraint (row or enforcer); a rim source in follow mode
                               with any enforcer; sharded contexts.                  */
+  int enforce_area;        /* body_area / global_area loaded (minimizer.py:1379): every
+                              trial that passed the guard runs ms_project_area behind the
+                              pin program and the volume projection before its energy is
+                              taken.  Needs ms_set_area_constraint; unqueued trials, every
+                              Armijo decision on the host.  Refused next to tilt-family
+                              modules, pins, body_area_penalty; sharded contexts.     */
+  int enforce_area_iters;  /* max_iter of that projection: body_area 20, global_area 3
+                              (0: 20)                                               */
 } ms_stepper_params;
 
 typedef struct ms_step_result {
@@ -296,6 +309,34 @@ int ms_set_area_penalty(ms_ctx *ctx, double stiffness, double target_area);
 /* the body's area as the last energy pass folded it (MS_S_AREA; synchronises): the module's own energy is
  * 1/2 k (area - A0)^2 */
 int ms_get_body_area(ms_ctx *ctx, double *area);
+/* The hard area constraints (modules/constraints/body_area.py, global_area.py).  kind MS_AREA_BODY: the facets of the
+ * body (ms_create's body_facets), target = body.options["target_area"]; MS_AREA_GLOBAL: every facet, target = the
+ * global target_surface_area; MS_AREA_NONE (or ms_clear_area_constraint) clears it.  The target must be finite and
+ * positive (MS_ERR_INVALID).  Single GPU.  With MS_AREA_BODY and MS_CON_BODY_AREA in ms_params.modules the row dA/dx is
+ * projected out of the gradient of ms_energy_and_gradient / ms_step on the device: one pass over G for the dot products,
+ * lambda from the 1 x 1 (<gA,gA> > 1e-18) or the ridged 2 x 2 system (Cholesky, LU, else the gradient is left alone),
+ * G -= lambda_V gV + lambda_A gA, then the fixed rows are zeroed.  global_area has no row. */
+#define MS_AREA_NONE 0
+#define MS_AREA_BODY 1
+#define MS_AREA_GLOBAL 2
+int ms_set_area_constraint(ms_ctx *ctx, int kind, double target_area);
+int ms_clear_area_constraint(ms_ctx *ctx);
+/* enforce_constraint of the module that is set (body_area.py:87-139, global_area.py:8-51) on the context's positions:
+ * up to max_iter steps x -= (dA / (|gA|^2 + 1e-18)) gA on the movable rows, |gA|^2 over all rows, until |A - target| <
+ * tol (absolute) or |gA|^2 < 1e-18.  *iters: steps taken; *area: the area of the last evaluation (synchronises). */
+int ms_project_area(ms_ctx *ctx, double tol, int max_iter, int *iters, double *area);
+/* The same with Body's cache (geometry/body.py:347-384): body_area's loop takes area and gradient from
+ * compute_area_and_gradient, which answers from the body's cache when the cached version is the mesh's.  The volume
+ * module's projection, when it ends on an evaluation (fewer steps than its max_iter), leaves that version current
+ * without refreshing the cached area: the first pass of a body_area projection right behind it then works on the area
+ * and the gradient of the last FRESH evaluation inside an earlier ms_project_area call.  first_step_cached != 0 asks
+ * for that (ignored until a fresh evaluation has happened, and for MS_AREA_GLOBAL, which keeps no cache). */
+int ms_project_area_cached(ms_ctx *ctx, double tol, int max_iter, int first_step_cached, int *iters, double *area);
+/* the row dA/dx of the constraint that is set at the context's positions (row: nv x 3 in the caller's order, may be
+ * NULL), its area and <gA,gA> (synchronises).  body_area.py:28-84 for MS_AREA_BODY. */
+int ms_area_row(ms_ctx *ctx, double *row, double *area, double *norm2);
+/* stats: launches of {k_area_row, k_area_dots, k_area_fold, k_area_apply} since ms_create.  No reference counterpart. */
+int ms_area_stats(ms_ctx *ctx, double stats[4]);
 /* line_tension (modules/energy/line_tension.py:24-34 selects the edges, :117-123 their gamma: the edge's own
  * "line_tension" option or else the global parameter; an edge whose gamma is 0 is skipped): n_edges tagged edges as
  * EXTERNAL rows (the order of ms_set_positions) in ascending edge order, gamma per edge.  Every row is validated

@@ -38,6 +38,8 @@ MS_MOD_TILT_COUPLING = 2097152
 MS_MOD_TILT_RIM_SOURCE_BILAYER = 8388608
 MS_MOD_TILT_SPLAY_TWIST_IN = 4194304
 MS_MOD_TILT_THETAB_CONTACT_IN = 16777216
+MS_CON_BODY_AREA = 33554432
+MS_AREA_NONE, MS_AREA_BODY, MS_AREA_GLOBAL = 0, 1, 2
 MS_THETAB_MAX_ROWS = 4096
 MS_THETAB_WORK_SCALAR, MS_THETAB_WORK_FIELD_LINEAR = 0, 1
 MS_TILT_PROJECTION_PER_STEP, MS_TILT_PROJECTION_PER_PASS = 0, 1
@@ -76,7 +78,8 @@ class ms_stepper_params(ctypes.Structure):
                 ("c", ctypes.c_double), ("gamma", ctypes.c_double),
                 ("alpha_max_factor", ctypes.c_double), ("restart_interval", ctypes.c_int),
                 ("edge_fraction", ctypes.c_double), ("reuse_energy0", ctypes.c_int), ("enforce_volume", ctypes.c_int),
-                ("precondition", ctypes.c_int), ("enforce_pins", ctypes.c_int)]
+                ("precondition", ctypes.c_int), ("enforce_pins", ctypes.c_int),
+                ("enforce_area", ctypes.c_int), ("enforce_area_iters", ctypes.c_int)]
 
 
 class ms_tilt_relax_params(ctypes.Structure):
@@ -156,6 +159,13 @@ SIGNATURES = {
     "ms_set_params": (ctypes.c_int, [_P, ctypes.POINTER(ms_params)]),
     "ms_set_area_penalty": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_double]),
     "ms_get_body_area": (ctypes.c_int, [_P, _D]),
+    "ms_set_area_constraint": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_double]),
+    "ms_clear_area_constraint": (ctypes.c_int, [_P]),
+    "ms_project_area": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _D]),
+    "ms_project_area_cached": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int), _D]),
+    "ms_area_row": (ctypes.c_int, [_P, _D, _D, _D]),
+    "ms_area_stats": (ctypes.c_int, [_P, _D]),
     "ms_set_line_tension": (ctypes.c_int, [_P, ctypes.c_int, _I32, _I32, _D]),
     "ms_get_line_energy": (ctypes.c_int, [_P, _D]),
     "ms_line_stats": (ctypes.c_int, [_P, _D]),

@@ -267,7 +267,8 @@ void ms_destroy(ms_ctx* c) {
                   c->tf[1].disk, c->tf[1].diff, c->tf[2].disk, c->tf[2].diff, c->tf[0].va, c->tf[1].va, c->tf[2].va,
                   c->state, c->d_partials, c->d_scal, c->d_stage, c->d_bnd_rows, c->d_bnd_off,
                   c->d_halo_rows, c->d_scal_all, c->d_pins, c->edge[0].d_blob, c->edge[1].d_blob, c->tf[1].d_rim, c->tf[2].d_rim,
-                  c->d_cpl, c->d_st, c->d_rimb, c->d_tb, c->d_tbb};
+                  c->d_cpl, c->d_st, c->d_rimb, c->d_tb, c->d_tbb,
+                  c->d_area_ga, c->d_area_part, c->d_area_res, c->d_area_cache};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& lane : c->edge)
@@ -444,7 +445,16 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_bt_vert), bytes));
     HIPCHK(c, hipMemset(c->d_bt_vert, 0, bytes));
   }
+  if ((p->modules & MS_CON_BODY_AREA) && c->shard_count != 1)
+    return fail(c, MS_ERR_STATE, "the body_area constraint row is not sharded (single GPU only)");
+  if ((p->modules & MS_CON_BODY_AREA) && (p->modules & MS_ANY_TILT_MODS))
+    return fail(c, MS_ERR_STATE, "the body_area constraint row together with a tilt-family module is outside the device path");
+  if ((p->modules & MS_CON_BODY_AREA) && (p->modules & MS_MOD_AREA_PENALTY))
+    return fail(c, MS_ERR_STATE, "the body_area constraint row together with body_area_penalty is outside the device path");
   c->params = *p;
+  // (no kernel reads the bit: the row is the area lane's own, ms_api_area_con.inc)
+  c->area_row = (p->modules & MS_CON_BODY_AREA) != 0;
+  c->params.modules &= ~MS_CON_BODY_AREA;
   c->carry.factors_valid = false;
   c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
   c->sh_carry_valid = c->sh_grad_valid = false;

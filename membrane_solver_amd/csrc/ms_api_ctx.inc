@@ -430,6 +430,21 @@ struct ms_ctx {
   PinEnforceArgs pin_enf{};
   PinGradArgs pin_grad{};
   int pin_lane = -1;
+  // the hard area constraints (ms_api_area_con.inc): kind and target of ms_set_area_constraint; area_row: MS_CON_BODY_AREA
+  // was in the module word of the last ms_set_params (the row takes part in the gradient projection); gA, the lane's
+  // partial rows and its result cells (AP_*), allocated on first use
+  int area_con_kind = MS_AREA_NONE;
+  double area_con_target = 0.0;
+  bool area_row = false;
+  double* d_area_ga = nullptr;
+  double* d_area_part = nullptr;
+  double* d_area_res = nullptr;
+  // Body's cached area and area gradient (geometry/body.py:347-384): what the last fresh evaluation inside
+  // ms_project_area computed
+  double* d_area_cache = nullptr;
+  double area_cache_area = 0.0, area_cache_norm2 = 0.0;
+  bool area_cache_valid = false;
+  long area_launches[4] = {0, 0, 0, 0};  // k_area_row, k_area_dots, k_area_fold, k_area_apply
   long pin_enforce_launches = 0, pin_grad_launches = 0, pin_trials = 0;
   // the edge lane (ms_api_edge.inc): edge[t] is the state of kEdgeTerms[t] -- line_tension, then edge_length_penalty.
   // One allocation holds every table of a term, the per-workgroup sums and the module's energy

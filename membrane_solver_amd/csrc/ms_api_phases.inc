@@ -9,6 +9,8 @@ inline hipStream_t S(ms_ctx* c) {
   return c->stream;
 }
 int pin_grad_run(ms_ctx* c, bool volrow);  // (ms_api_pins.inc)
+int area_project_gradient(ms_ctx* c);      // (ms_api_area_con.inc: the area row projected out of G, with the volume row if set)
+inline bool area_row_active(const ms_ctx* c);
 // the edge lane (ms_api_edge.inc): its terms in launch order, kEdgeTerms[t] going with c->edge[t]
 struct EdgeTableMsgs {
   const char *row, *first, *second, *perm;
@@ -1024,7 +1026,8 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
 
 int phase_direction(ms_ctx* c, int stepper, bool use_history, bool g_finalized = false) {
   // (pins in the skip lane: the reference's KKT solve returned before touching g, the volume row included)
-  const bool use_con = (c->params.modules & MS_CON_VOLUME) != 0 && c->pin_lane != MS_PIN_LANE_SKIP;
+  // (the area lane: G was projected against every row behind the gradient pass, area_project_gradient)
+  const bool use_con = (c->params.modules & MS_CON_VOLUME) != 0 && c->pin_lane != MS_PIN_LANE_SKIP && !area_row_active(c);
   const StageCtl& st = c->stage();
   c->carry.dir_implicit = false;
   c->carry.dir_unwritten = false;
@@ -1218,7 +1221,7 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
   // (and a preconditioned direction -- conjugate_gradient.py:74-76 -- is the direction kernel's)
   // (the edge modules add into g after K_C as well: |g|^2, <g,d> and max|g_i|^2 are taken over the completed G)
   const bool constraint = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS | MS_EDGE_MODS)) != 0 ||
-                          (stepper == MS_STEPPER_CG && c->precond) || c->pin_lane == MS_PIN_LANE_PROJECT;
+                          (stepper == MS_STEPPER_CG && c->precond) || c->pin_lane == MS_PIN_LANE_PROJECT || area_row_active(c);
   // K_C reads the reduced volume / body area (already reduced when the energy pass is skipped)
   const bool penalty = skip_energy || (mods & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) != 0;
   int rc = MS_OK;
@@ -1235,6 +1238,10 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
   if (rc) return rc;
   rc = pin_grad_run(c, (mods & MS_CON_VOLUME) != 0);  // (project lane only)
   if (rc) return rc;
+  if (area_row_active(c)) {  // (the area lane: one or two rows projected out here, none by k_direction)
+    rc = area_project_gradient(c);
+    if (rc) return rc;
+  }
   // (<g,gC> / <gC,gC> exist only with a row or a tilt module behind K_C)
   const uint32_t gmask = (mods & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS)) ? MASK_GRAD : 0u;
   const uint32_t fmask = (penalty ? 0u : energy_mask(mods)) | gmask;

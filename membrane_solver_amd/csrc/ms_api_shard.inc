@@ -20,6 +20,8 @@ int ms_phase_gradient(ms_ctx* c) {
 int ms_phase_direction(ms_ctx* c, int stepper, int use_history) {
   if (!c) return MS_ERR_INVALID;
   c->precond = false;  // (the phase API has no preconditioned lane: never inherit one from an earlier ms_step)
+  if (area_row_active(c))  // (its projection sits between the gradient pass and the direction kernel of ms_step)
+    return fail(c, MS_ERR_STATE, "the phase API has no area constraint row (ms_step / ms_energy_and_gradient project it)");
   return phase_direction(c, stepper, use_history != 0);
 }
 
@@ -68,7 +70,7 @@ int ms_phase_commit_trial(ms_ctx* c, double alpha, int keep_history) {
 
 int ms_phase_gradient_direction(ms_ctx* c, int stepper, int use_history) {
   if (!c) return MS_ERR_INVALID;
-  if (c->params.modules & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS))
+  if ((c->params.modules & (MS_CON_VOLUME | MS_TILT_SHAPE_MODS)) || area_row_active(c))
     return fail(c, MS_ERR_STATE, "fused gradient+direction needs no constraint row and no tilt module");
   c->carry.grad_valid = false;
   const int dir_mode = (stepper == MS_STEPPER_CG && use_history) ? 2 : 1;
@@ -591,6 +593,8 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
     return fail(c, MS_ERR_STATE, "volume_projection_during_minimization (the enforcer lane of the line search) is not sharded (single GPU only)");
   if (sp->enforce_pins || pins_set(c))
     return fail(c, MS_ERR_STATE, "pin_to_plane / pin_to_circle are not sharded (single GPU only)");
+  if (sp->enforce_area || area_con_set(c) || c->area_row)
+    return fail(c, MS_ERR_STATE, "the body_area / global_area constraints are not sharded (single GPU only)");
   c->precond = false;
   memset(out, 0, sizeof(*out));
   const bool cg = sp->stepper == MS_STEPPER_CG;

@@ -465,6 +465,17 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   if (pin_tilt && ((c->params.modules & MS_CON_VOLUME) || sp->enforce_volume))
     return fail(c, MS_ERR_STATE, "pin_to_plane / pin_to_circle next to tilt modules together with the volume constraint "
                                  "are outside the device path");
+  // the area lane (ms_api_area_con.inc): the row is projected out behind the gradient pass, the enforcer runs behind the
+  // pins' and the volume's on every trial; what has no reference fixture next to it is refused
+  const bool area_lane = area_row_active(c) || sp->enforce_area != 0;
+  if (sp->enforce_area != 0 && !area_con_set(c))
+    return fail(c, MS_ERR_STATE, "ms_stepper_params.enforce_area without an area constraint (ms_set_area_constraint)");
+  if (area_lane && tilt)
+    return fail(c, MS_ERR_STATE, "the body_area / global_area constraints together with a tilt-family module are outside the device path");
+  if (area_lane && pins_set(c))
+    return fail(c, MS_ERR_STATE, "the body_area / global_area constraints next to pin_to_plane / pin_to_circle are outside the device path");
+  if (area_lane && (c->params.modules & MS_MOD_AREA_PENALTY))
+    return fail(c, MS_ERR_STATE, "the body_area / global_area constraints together with body_area_penalty are outside the device path");
   // reuse_energy0 == 2: an accepted trial doubles as the next step's energy/factor pass
   const bool carry_mode = sp->reuse_energy0 >= 2 && !tilt;
   if (c->ahead.valid && !c->ahead.go_known && !(c->carry.kc_pending && carry_mode && c->carry.carry_valid)) {
@@ -679,11 +690,14 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   const bool enforce_vol = sp->enforce_volume != 0 && volrow && !tilt;
   const bool enforce_pin = sp->enforce_pins != 0 && pins_set(c);
   const bool enforce_tilt = pin_tilt;
-  const bool enforce = enforce_vol || enforce_pin;
+  // (ms_stepper_params.enforce_area: behind both, constraint_manager.enforce_all's order pins -> volume -> area)
+  const bool enforce_area = sp->enforce_area != 0;
+  const bool enforce = enforce_vol || enforce_pin || enforce_area;
   bool tbb_lane = false;  // the tilt constraint's ring is set and the inner leaflet's field is among the active ones
   for (int k = 0; k < n_tf; ++k) tbb_lane = tbb_lane || (tfl[k] == &c->tf[1] && tbb_active(c));
   const bool can_chain = c->speculate && carry_mode && !tilt &&
-                         !(c->params.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY | MS_EDGE_MODS)) && !enforce && !precond;
+                         !(c->params.modules & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY | MS_EDGE_MODS)) && !enforce && !precond &&
+                         !area_lane;  // (its kernels are not gated: every Armijo decision of the lane is the host's)
   // a round queued by the step before (while its gradient pass was running): the round of THIS search's first
   // iteration if it was queued for exactly what this step has computed by itself
   bool adopted = false;
@@ -746,7 +760,12 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
           rc = pin_enforce_run(c);
           ++c->pin_trials;
         }
-        if (rc == MS_OK && enforce_vol) rc = ms_project_volume_cached(c, c->params.target_volume, 1e-12, 3, 0, nullptr, nullptr);
+        int vol_iters = 3;
+        if (rc == MS_OK && enforce_vol) rc = ms_project_volume_cached(c, c->params.target_volume, 1e-12, 3, 0, &vol_iters, nullptr);
+        // (a volume projection that ended on an evaluation leaves Body's cache looking current: ms_project_area_cached)
+        if (rc == MS_OK && enforce_area)
+          rc = ms_project_area_cached(c, 1e-12, sp->enforce_area_iters > 0 ? sp->enforce_area_iters : 20,
+                                      enforce_vol && vol_iters < 3, nullptr, nullptr);
         // energy_fn on the enforced trial projects the stored tilts onto it first (minimizer.py:581-588): into `trial`,
         // which takes the field's place for the evaluation -- the tilts of x stay where they are, bit for bit
         for (int k = 0; k < n_tf && rc == MS_OK && enforce_tilt; ++k)
@@ -1002,6 +1021,7 @@ bool resident_eligible(ms_ctx* c, const ms_minimize_params* mp) {
   if (sp.stepper != MS_STEPPER_GD || sp.precondition || sp.enforce_volume || sp.reuse_energy0 < 2 || sp.edge_fraction > 0.0)
     return false;
   if (pins_set(c)) return false;  // (the pin program and the project lane run outside the resident kernel)
+  if (area_row_active(c) || sp.enforce_area) return false;  // (so do the area row and its enforcer)
   if (mp->relax_tilts || mp->fixed_step_mode) return false;
   if (c->resident_ok < 0) {
     c->resident_lds = resident_lds_bytes(c->cap, c->til.max_ent, c->til.max_tile_facets, false);
@@ -1244,6 +1264,11 @@ int ms_minimize(ms_ctx* c, const ms_minimize_params* mp, int n_steps, ms_minimiz
             if (rc) return rc;
             rc = ms_project_volume_cached(c, mp->target_volume, 1e-12, 12, 1, &iters, nullptr);
             if (rc) return rc;
+            if (mp->stepper.enforce_area) {  // (body_area / global_area: listed behind volume)
+              rc = ms_project_area_cached(c, 1e-12, mp->stepper.enforce_area_iters > 0 ? mp->stepper.enforce_area_iters : 20,
+                                          iters < 12, nullptr, nullptr);
+              if (rc) return rc;
+            }
             out->volume_cache_current = 0;  // enforce_constraints_after_mesh_ops bumps the mesh version
             // minimizer.py:1505-1507: enforce, then mesh.project_tilts_to_tangent() on the projected surface
             if (c->params.modules & MS_ANY_TILT_MODS) {

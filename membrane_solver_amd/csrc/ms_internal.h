@@ -535,6 +535,33 @@ struct SplayArgs {
 };
 size_t splay_lds_bytes(int T, int cap, int max_ent, int mode);
 hipError_t launch_splay(const SplayArgs& a, int mode, int cap, int max_ent, hipStream_t s);
+// The hard area constraints (ms_area.hip): body_area's KKT row and the enforcers of body_area / global_area.  The lane's
+// sums live in partial rows and result cells of its own (the mailbox has one slot left): part[AP_ROWS][n_tiles], written
+// by k_area_row (AP_A, AP_GAGA) and k_area_dots (the rest), folded in tile order by k_area_fold into res[0 .. AP_ROWS),
+// which also leaves the multipliers of the projection in res[AP_LAMV], res[AP_LAMA].
+enum : int { AP_A = 0, AP_GAGA, AP_GGV, AP_GGA, AP_GVGV, AP_GVGA, AP_ROWS, AP_LAMV = AP_ROWS, AP_LAMA, AP_RES };
+struct AreaRowArgs {
+  DeviceMesh m;
+  int tile0, tile1;
+  const double* x;
+  double* ga;             // (nvp,3) out: dA/dx of the owned rows
+  double* part;
+  int all_facets;         // global_area: every facet; else the facets that carry TF_BODY
+  int cap;
+};
+struct AreaProjArgs {
+  int tile0, tile1, nv, own, n_tiles;
+  double* g;
+  const double* gv;       // the volume row K_C wrote, or nullptr
+  const double* ga;
+  double* part;
+  const double* res;
+};
+size_t area_row_lds_bytes(int T, int cap, bool atomic);
+hipError_t launch_area_row(const AreaRowArgs& a, bool atomic, hipStream_t s);
+hipError_t launch_area_dots(const AreaProjArgs& a, hipStream_t s);
+hipError_t launch_area_fold(const double* part, double* res, int n_tiles, int tile0, int tile1, int rows, hipStream_t s);
+hipError_t launch_area_apply(const AreaProjArgs& a, hipStream_t s);
 struct RowDotArgs {
   int tile0, nv, T;
   const double* g;

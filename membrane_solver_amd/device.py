@@ -117,6 +117,40 @@ class DeviceMesh:
         self._area_penalty = (float(stiffness), float(target_area))
         self._chk(L.lib().ms_set_area_penalty(self._h, float(stiffness), float(target_area)), "ms_set_area_penalty")
 
+    def set_area_constraint(self, kind: int, target_area: float = 0.0):
+        """body_area (L.MS_AREA_BODY: the body's facets) or global_area (L.MS_AREA_GLOBAL: every facet) with its target;
+        L.MS_AREA_NONE clears it (ms_set_area_constraint)."""
+        self._chk(L.lib().ms_set_area_constraint(self._h, int(kind), float(target_area)), "ms_set_area_constraint")
+        self._area_constraint = (int(kind), float(target_area)) if kind != L.MS_AREA_NONE else None
+
+    @property
+    def area_constraint(self):
+        """(kind, target) of the area constraint that is set, or None."""
+        return self.__dict__.get("_area_constraint")
+
+    def project_area(self, tol: float = 1e-12, max_iter: int = 20, first_step_cached: bool = False):
+        """enforce_constraint of the area constraint that is set, on the device positions; ``first_step_cached``: Body's
+        cached-area quirk (include/membrane_hip.h, ms_project_area_cached).  -> (steps taken, area of the last evaluation)"""
+        it = ctypes.c_int(0)
+        a = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_project_area_cached(self._h, float(tol), int(max_iter), int(bool(first_step_cached)),
+                                                 ctypes.byref(it), ctypes.byref(a)), "ms_project_area_cached")
+        return int(it.value), float(a.value)
+
+    def area_row(self):
+        """dA/dx of the area constraint that is set at the device positions -> (row (nv,3), area, <gA,gA>)."""
+        row = np.zeros((self.nv, 3))
+        a = ctypes.c_double(0.0)
+        n2 = ctypes.c_double(0.0)
+        self._chk(L.lib().ms_area_row(self._h, _pd(row), ctypes.byref(a), ctypes.byref(n2)), "ms_area_row")
+        return row, float(a.value), float(n2.value)
+
+    def area_stats(self) -> dict:
+        """Launch counts of the area lane's kernels (ms_area_stats)."""
+        s = np.zeros(4)
+        self._chk(L.lib().ms_area_stats(self._h, _pd(s)), "ms_area_stats")
+        return {"row": int(s[0]), "dots": int(s[1]), "fold": int(s[2]), "apply": int(s[3])}
+
     def body_area(self) -> float:
         """Area of the body's facets as the last energy pass folded it (MS_S_AREA)."""
         a = ctypes.c_double(0.0)
@@ -586,17 +620,17 @@ class DeviceMesh:
              beta: float = 0.7, c: float = 1e-4, gamma: float = 1.5, alpha_max_factor: float = 10.0,
              restart_interval: int = 10, edge_fraction: float = 0.0,
              reuse_energy0: int = 0, enforce_volume: int = 0, precondition: int = 0,
-             enforce_pins: int = 0) -> StepResult:
+             enforce_pins: int = 0, enforce_area: int = 0) -> StepResult:
         # the parameter block and the result struct are reused between calls: at ~140 us per
         # step every microsecond of ctypes marshalling shows
         key = (stepper, max_iter, beta, c, gamma, alpha_max_factor, restart_interval, edge_fraction,
-               reuse_energy0, enforce_volume, precondition, enforce_pins)
+               reuse_energy0, enforce_volume, precondition, enforce_pins, enforce_area)
         cache = self.__dict__.get("_step_cache")
         if cache is None or cache[0] != key:
             sp = L.ms_stepper_params(int(stepper), int(max_iter), float(beta), float(c), float(gamma),
                                      float(alpha_max_factor), int(restart_interval), float(edge_fraction),
                                      int(reuse_energy0), int(enforce_volume), int(precondition),
-                                     int(enforce_pins))
+                                     int(enforce_pins), int(enforce_area > 0), int(enforce_area))
             r = L.ms_step_result()
             cache = (key, sp, r, ctypes.byref(sp), ctypes.byref(r), L.lib().ms_step)
             self._step_cache = cache

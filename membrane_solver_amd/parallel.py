@@ -331,6 +331,9 @@ class HipShardBackend:
         if modules & L.MS_MOD_AREA_PENALTY:
             raise L.MembraneHipError("the body_area_penalty module is not sharded (single GPU only; ms_shard_step "
                                      "refuses it as well)")
+        if modules & L.MS_CON_BODY_AREA:
+            raise L.MembraneHipError("the body_area constraint is not sharded (single GPU only; ms_set_params and "
+                                     "ms_shard_step refuse it as well)")
         if modules & L.MS_MOD_LINE_TENSION:
             raise L.MembraneHipError("the line_tension module is not sharded (single GPU only; ms_shard_step "
                                      "refuses it as well)")

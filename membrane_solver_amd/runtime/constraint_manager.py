@@ -1,7 +1,8 @@
 """Constraint plugin loader (runtime/constraint_manager.py, reduced to the
-in-scope ``volume``, ``pin_to_plane``, ``pin_to_circle`` and ``tilt_thetaB_boundary_in``
-modules), the KKT projection of the gradient (:174-315): the k == 1 dense row alone, or the
-mixed dense + sparse-row solve with the pins -- and the two tilt-space seams (:651-841) for
+in-scope ``volume``, ``body_area``, ``global_area``, ``pin_to_plane``, ``pin_to_circle`` and
+``tilt_thetaB_boundary_in`` modules), the KKT projection of the gradient (:174-315): the k == 1 dense row alone, the
+volume and area rows together, or the mixed dense + sparse-row solve with the pins -- and the two tilt-space seams
+(:651-841) for
 constraints that act on the leaflet tilts only."""
 
 from __future__ import annotations
@@ -66,8 +67,24 @@ class ConstraintModuleManager:
                 rows.extend(g_list)
         if not rows:
             return
+        if len(rows) == 2:
+            # the dense KKT solve (constraint_projection.py:101-129) on C = [volume row; area row], in the listed order
+            C = np.stack([np.asarray(r, dtype=float).reshape(-1) for r in rows])
+            g = grad_arr.reshape(-1)
+            A = C @ C.T
+            A[np.diag_indices_from(A)] += 1e-18
+            b = C @ g
+            try:
+                lam = np.linalg.solve(np.linalg.cholesky(A).T, np.linalg.solve(np.linalg.cholesky(A), b))
+            except np.linalg.LinAlgError:
+                try:
+                    lam = np.linalg.solve(A, b)
+                except np.linalg.LinAlgError:
+                    return
+            g -= C.T @ lam
+            return
         if len(rows) != 1:
-            raise NotImplementedError("only the single dense constraint row (volume) is in scope")
+            raise NotImplementedError("only one dense constraint row (volume or body_area) or the two together are in scope")
         gC = rows[0]
         norm_sq = float(np.sum(gC * gC))
         if norm_sq > 1e-18:

@@ -27,13 +27,16 @@ modules (``tilt``, ``bending_tilt``, ``tilt_smoothness`` and their ``_in`` /
 ``_out`` leaflet forms, ``tilt_disk_target_in/out``), ``gaussian_curvature``
 and the switched-off ``rim_slope_match_out`` as host-side constants.
 
-Constraints: ``volume`` and the pins (``pin_to_plane`` / ``pin_to_circle``: the pin program on every
+Constraints: ``volume``, the hard area constraints ``body_area`` (its row in the KKT projection next to the volume row,
+its projection on every line-search trial and in every enforce context) and ``global_area`` (the projection alone), and
+the pins (``pin_to_plane`` / ``pin_to_circle``: the pin program on every
 line-search trial and in every enforce context, their rows removed from the gradient in the project lane).  Next to
 the tilt modules, single field or leaflets, a trial is: positions, pin program, the stored tilts projected onto the
 pinned surface, energy there; a rejected trial puts the tilts back with the positions.
 
 Out of scope here (raises MembraneHipError): every other energy module,
-constraints other than ``volume``, ``pin_to_plane`` and ``pin_to_circle``, pins next to tilt modules together with the
+constraints other than ``volume``, ``body_area``, ``global_area``, ``pin_to_plane``, ``pin_to_circle`` and
+``tilt_thetaB_boundary_in``, the area constraints next to tilt modules, pins or ``body_area_penalty``, pins next to tilt modules together with the
 ``volume`` constraint, the benchmark toggles of the leaflet modules
 (modules/energy/leaflet_common._UNSUPPORTED_KEYS), the reference's auto
 mesh-quality repair hook.
@@ -54,6 +57,8 @@ from ..modules.energy import leaflet_common as _lc
 from ..modules.energy._common import bending_gradient_mode, bending_model
 from ..modules.constraints import pins as _pins
 from ..modules.constraints import tilt_thetaB_boundary_in as _tbb
+from ..modules.constraints import body_area as _body_area
+from ..modules.constraints import global_area as _global_area
 from ..modules.energy.body_area_penalty import body_area_params
 from ..modules.energy import edge_length_penalty as _edgepen
 from ..modules.energy import line_tension as _line
@@ -114,6 +119,7 @@ _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": 
                 "tilt_smoothness_out": L.MS_S_ETS_OUT, "tilt_disk_target_in": L.MS_S_EDT_IN,
                 "tilt_disk_target_out": L.MS_S_EDT_OUT}
 _PIN_MODULES = ("pin_to_plane", "pin_to_circle")
+_AREA_CONSTRAINTS = ("body_area", "global_area")  # the area lane: the row (body_area) and the enforcer on every trial
 _BEND_SCALAR = {"bending": L.MS_S_EBEND, "bending_tilt": L.MS_S_EBT, "bending_tilt_in": L.MS_S_EBT_IN,
                 "bending_tilt_out": L.MS_S_EBT_OUT}
 
@@ -228,15 +234,18 @@ class Minimizer:
         self.constraint_modules = [self.constraint_manager.get_constraint(c)
                                    for c in self.constraint_module_names]
         for name in self.constraint_module_names:
-            if name not in ("volume", _tbb.NAME) + _PIN_MODULES:
+            if name not in ("volume", _tbb.NAME) + _PIN_MODULES + _AREA_CONSTRAINTS:
                 raise L.MembraneHipError(f"constraint module {name!r} is outside the HIP hot path "
-                                         "(volume, pin_to_plane, pin_to_circle, tilt_thetaB_boundary_in)")
+                                         "(volume, body_area, global_area, pin_to_plane, pin_to_circle, "
+                                         "tilt_thetaB_boundary_in)")
         self._pin_names = [n for n in self.constraint_module_names if n in _PIN_MODULES]
         if self._pin_names and "volume" in self.constraint_module_names and \
                 self.constraint_module_names.index("volume") < self.constraint_module_names.index(self._pin_names[0]):
             # enforce_all runs the modules in their listed order; the device runs the pins first
             raise L.MembraneHipError("constraint_modules lists volume before pin_to_plane / pin_to_circle: the HIP "
                                      "path enforces the pins first; list the pin modules before volume")
+        self._check_area_constraints()
+        self._area_con = None  # (set by _device(): (kind, target) of the area constraint that is listed and has a target)
         self._pin_key = None
         self._pins_active = False
         self._tbb_active = False  # (set by _device(): tilt_thetaB_boundary_in is listed and has a ring)
@@ -245,6 +254,44 @@ class Minimizer:
                                                 for m in self.constraint_modules)
         self._configured_key = None
         self._device_ahead = False
+
+    def _check_area_constraints(self):
+        """What the area lane does not take, by the names alone (the targets are checked by _device()): the lane enforces
+        pins -> volume -> area and has no fixture next to the tilt families, the pins or the soft penalty."""
+        names = self.constraint_module_names
+        area = [n for n in names if n in _AREA_CONSTRAINTS]
+        if not area:
+            return
+        if len(area) > 1:
+            raise L.MembraneHipError("body_area and global_area together are outside the HIP hot path: the device "
+                                     "holds one area constraint")
+        what = area[0]
+        if "volume" in names and names.index("volume") > names.index(what):
+            raise L.MembraneHipError(f"constraint_modules lists volume after {what}: the HIP path enforces the volume "
+                                     f"first; list volume before {what}")
+        if len(getattr(self.mesh, "bodies", None) or {}) > 1:
+            raise L.MembraneHipError(f"{what} on a mesh with more than one body is outside the HIP hot path "
+                                     "(one body per mesh, SURVEY 8a row a7)")
+        if any(_ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names) or _tbb.NAME in names:
+            raise L.MembraneHipError(f"{what} together with tilt modules is outside the HIP hot path")
+        if "body_area_penalty" in self.energy_module_names:
+            raise L.MembraneHipError(f"{what} together with body_area_penalty is outside the HIP hot path: hold the area "
+                                     "with the constraint or with the penalty")
+        if self._pin_names:
+            raise L.MembraneHipError(f"{what} next to pin_to_plane / pin_to_circle is outside the HIP hot path")
+
+    def _area_constraint_params(self):
+        """(kind, target, max_iter) of the listed area constraint, or None where it does nothing (no body, no
+        ``target_area`` / ``target_surface_area``: body_area.py:40-41, global_area.py:11-15).  A target that is not finite
+        and positive is refused by the module's ``target_area``."""
+        names = self.constraint_module_names
+        if "body_area" in names:
+            t = _body_area.target_area(self.mesh)
+            return None if t is None else (L.MS_AREA_BODY, t, 20)
+        if "global_area" in names:
+            t = _global_area.target_area(self.mesh, self.global_params)
+            return None if t is None else (L.MS_AREA_GLOBAL, t, 3)
+        return None
 
     def sync_mesh_from_device(self):
         """Write device positions back into the mesh (after minimize(sync_mesh=False))."""
@@ -270,6 +317,7 @@ class Minimizer:
     def _device(self):
         gp = self.global_params
         mir = mirror_for(self.mesh, device=self.device, tile_vertices=self.tile_vertices)
+        area_con = self._area_constraint_params()  # (refused before anything is uploaded)
         dm = mir.sync()
         if self.deterministic is not None:
             dm.set_deterministic(self.deterministic)
@@ -381,6 +429,9 @@ class Minimizer:
         if body is not None and self._target_volume() is not None and vol_mode == "lagrange" \
                 and not gp.get("volume_projection_during_minimization", True):
             mods |= L.MS_TRACK_VOLUME  # drift check of minimizer.py:1478-1513
+        if area_con is not None and area_con[0] == L.MS_AREA_BODY:
+            mods |= L.MS_CON_BODY_AREA  # its row takes part in the KKT projection (global_area has none)
+        self._area_con = area_con
         model = bending_model(gp)
         if (mods & L.MS_MOD_BENDING) and (mods & L.MS_MOD_BENDING_TILT):
             raise L.MembraneHipError("bending and bending_tilt together are outside the HIP hot path")
@@ -495,6 +546,11 @@ class Minimizer:
             dm.set_tilt_smoothness(float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0))
         if self._pin_names:
             self._upload_pins(mir, dm, mods)
+        if area_con is not None or getattr(self, "_area_set_on", None) is dm:
+            # (the constraint of an earlier configuration of this minimizer is replaced or cleared)
+            if (None if area_con is None else area_con[:2]) != dm.area_constraint:
+                dm.set_area_constraint(*(area_con[:2] if area_con is not None else (L.MS_AREA_NONE, 0.0)))
+            self._area_set_on = dm if area_con is not None else None
         key = (mods, model, mode, stiffness, target, area_params, self._line_key, self._edgepen_key, id(dm))
         if key != self._configured_key:
             if area_params is not None:
@@ -676,6 +732,18 @@ class Minimizer:
         current mesh version has made that cache look current (ms_project_volume_cached)."""
         if not self._has_enforceable_constraints:
             return False
+        self._vol_ended_on_eval = False
+        moved = self._enforce_pins_volume(dm, context, first_step_cached)
+        if self._area_con is not None:
+            # body_area / global_area behind them, in every context (enforce_all's order; body_area.py:87, global_area.py:8:
+            # tol 1e-12, max_iter 20 / 3 whatever the context).  A volume projection that ended on an evaluation leaves
+            # Body's cache looking current: body_area's first pass then reads the cached area (ms_project_area_cached)
+            iters, _a = dm.project_area(tol=1e-12, max_iter=self._area_con[2],
+                                        first_step_cached=self._vol_ended_on_eval)
+            moved = moved or iters > 0
+        return moved
+
+    def _enforce_pins_volume(self, dm, context: str, first_step_cached: bool = False) -> bool:
         moved = False
         if self._pins_active:  # constraint_manager.enforce_all: the pins in every context, listed before volume
             dm.enforce_pins()
@@ -700,6 +768,7 @@ class Minimizer:
             return moved
         max_iter = 12 if context in ("finalize", "mesh_operation") else 3
         iters, _v = dm.project_volume(target, tol=1e-12, max_iter=max_iter, first_step_cached=first_step_cached)
+        self._vol_ended_on_eval = iters < max_iter
         moved = moved or iters > 0
         if context in ("finalize", "mesh_operation") and dm.modules & _TILT_BITS:
             # minimizer.py:1186, :1224, :1506: every enforce outside the line search is followed by
@@ -797,7 +866,8 @@ class Minimizer:
                                          float(st.c), float(st.gamma), float(st.alpha_max_factor),
                                          int(extra.get("restart_interval", 10)), edge_fraction,
                                          int(st.reuse_energy0), int(getattr(st, "enforce_volume", 0)),
-                                         int(extra.get("precondition", 0)), int(getattr(st, "enforce_pins", 0)))
+                                         int(extra.get("precondition", 0)), int(getattr(st, "enforce_pins", 0)),
+                                         int(getattr(st, "enforce_area", 0) > 0), int(getattr(st, "enforce_area", 0)))
         step_mode = str(gp.get("step_size_mode", "adaptive") or "adaptive").lower()
         mp.step_size = float(self.step_size)
         mp.tol = float(self.tol)
@@ -840,6 +910,8 @@ class Minimizer:
             and gp.get("volume_constraint_mode", "lagrange") == "lagrange" and self._target_volume() is not None
             and (dm.modules & L.MS_CON_VOLUME)))
         self.stepper.enforce_pins = int(self._pins_active)  # (pins always have enforce_constraint)
+        # (so do body_area / global_area: the projection on every trial, with the module's own max_iter)
+        self.stepper.enforce_area = int(self._area_con[2]) if self._area_con is not None else 0
         if n_steps <= 0:
             E, g = self.compute_energy_and_gradient_array()
             moved = self._enforce(dm, "minimize")

@@ -53,6 +53,9 @@ class BaseStepper(ABC):
         self.enforce_volume = 0
         # set by the Minimizer when pin_to_plane / pin_to_circle are loaded: every trial runs the pin program first
         self.enforce_pins = 0
+        # set by the Minimizer when body_area / global_area are loaded: max_iter of the area projection every trial runs
+        # behind the pins and the volume projection (20 / 3; 0: off)
+        self.enforce_area = 0
         self._dm = None
 
     @abstractmethod
@@ -72,7 +75,8 @@ class BaseStepper(ABC):
                        max_iter=self._max_iter_for(mesh), beta=self.beta, c=self.c, gamma=self.gamma,
                        alpha_max_factor=self.alpha_max_factor, edge_fraction=edge_fraction,
                        reuse_energy0=self.reuse_energy0, enforce_volume=int(self.enforce_volume),
-                       **({"enforce_pins": 1} if self.enforce_pins else {}), **self._extra())
+                       **({"enforce_pins": 1} if self.enforce_pins else {}),
+                       **({"enforce_area": int(self.enforce_area)} if self.enforce_area else {}), **self._extra())
 
     def step(self, mesh, grad, step_size, energy_fn=None, constraint_enforcer=None,
              trial_energy_fn=None):
