@@ -245,6 +245,17 @@ typedef struct ms_stepper_params {
                               Refused: pins next to tilt modules together with the volume
                               constraint (row or enforcer); a rim source in follow mode
                               with any enforcer; sharded contexts.                  */
+  int enforce_fixed_plane; /* fixed_plane loaded: every trial that passed the guard runs
+                              the plane projection FIRST, in front of the pin program
+                              (the device's enforce order: fixed_plane -> pins ->
+                              perimeter -> volume -> area).  Needs ms_set_fixed_plane
+                              (else MS_ERR_STATE).  Next to a tilt family it takes the
+                              lane of the pins next to tilt modules.  Unqueued trials,
+                              every Armijo decision on the host, no resident steps.    */
+  int enforce_perimeter;   /* perimeter loaded: every trial runs ms_project_perimeter
+                              (tol 1e-10, 3 passes) behind the pin program, in front of
+                              the volume projection.  Needs ms_set_perimeter (else
+                              MS_ERR_STATE).  Refused next to tilt-family modules.      */
   int enforce_area;        /* body_area / global_area loaded (minimizer.py:1379): every
                               trial that passed the guard runs ms_project_area behind the
                               pin program and the volume projection before its energy is
@@ -337,6 +348,44 @@ int ms_project_area_cached(ms_ctx *ctx, double tol, int max_iter, int first_step
 int ms_area_row(ms_ctx *ctx, double *row, double *area, double *norm2);
 /* stats: launches of {k_area_row, k_area_dots, k_area_fold, k_area_apply} since ms_create.  No reference counterpart. */
 int ms_area_stats(ms_ctx *ctx, double stats[4]);
+/* The enforce-only shape constraints (modules/constraints/fixed_plane.py, perimeter.py): no KKT row, they only move
+ * positions inside ConstraintModuleManager.enforce_all.  Single GPU (MS_ERR_STATE on a sharded context).  Every call
+ * below that moves positions invalidates what ms_project_area_cached invalidates.
+ *
+ * fixed_plane (fixed_plane.py:25-53): every row that is not fixed becomes x - ((x - point) . n) n.  The library divides
+ * the normal by its norm; a normal or point that is not finite, or |normal| < 1e-15 (where the module warns and skips),
+ * is MS_ERR_INVALID.  normal == NULL clears the plane. */
+int ms_set_fixed_plane(ms_ctx *ctx, const double normal[3], const double point[3]);
+/* the projection on the context's positions, in place (synchronises); MS_ERR_STATE without a plane */
+int ms_enforce_fixed_plane(ms_ctx *ctx);
+/* perimeter (perimeter.py:27-74): n_loops edge lists, loop l owning the entries loop_off[l] .. loop_off[l + 1) of tail /
+ * head (EXTERNAL rows, the order of ms_set_positions, in list order; duplicates stay, the sign of a reference edge index
+ * is already resolved into tail / head), with its target length.  A row out of range or a target that is not finite is
+ * MS_ERR_INVALID.  An empty loop is legal and does nothing.  n_loops == 0 clears. */
+int ms_set_perimeter(ms_ctx *ctx, int n_loops, const int32_t *loop_off, const int32_t *tail, const int32_t *head,
+                     const double *target);
+/* Host only, no context: the tables ms_set_perimeter uploads, built by the same code from external rows and a row
+ * permutation iperm (external row -> library row): counts = {entries, distinct vertices summed over the loops}; the
+ * entries in library rows (e_tail, e_head: loop_off[n_loops]); per loop its distinct vertices in order of first
+ * appearance, an entry's tail before its head (vert_off: n_loops + 1, vrow: 2 entries at most); and the vertex -> entry
+ * CSR (csr_off: one more than vrow, csr_ent: 2 entries) whose items are -(entry + 1) where the vertex is the entry's tail
+ * and +(entry + 1) where it is the head, in list order.  No reference counterpart. */
+int ms_perimeter_tables_host(int nv, const int32_t *iperm, int n_loops, const int32_t *loop_off, const int32_t *tail,
+                             const int32_t *head, int32_t counts[2], int32_t *e_tail, int32_t *e_head, int32_t *vert_off,
+                             int32_t *vrow, int32_t *csr_off, int32_t *csr_ent);
+/* perimeter.enforce_constraint on the context's positions, one kernel launch: the loops in list order, per loop up to
+ * max_iter passes {P = sum of the listed lengths; stop when |P - target| < tol; g_v = the listed edges' -dir at the tail,
+ * +dir at the head (edges shorter than 1e-12 add nothing); stop when sum |g_v|^2 < 1e-18 (all rows); x_v -= ((P - target)
+ * / (sum |g_v|^2 + 1e-18)) g_v on the movable rows}.  passes[l]: passes of loop l that moved something; perimeter[l]: P of
+ * its last evaluation (n_loops entries each).  Either may be NULL; with both NULL nothing is copied back and the call
+ * does not synchronise.  The reference's call is tol 1e-10, max_iter 3 in every context. */
+int ms_project_perimeter(ms_ctx *ctx, double tol, int max_iter, int32_t *passes, double *perimeter);
+/* The padding rows nv .. nvp of the position buffer, which no kernel may move (*n_rows: how many; rows: n_rows x 3, or
+ * NULL to ask for the count alone; synchronises).  For tests.  No reference counterpart. */
+int ms_get_padded_rows(ms_ctx *ctx, int64_t *n_rows, double *rows);
+/* stats: {k_fixed_plane launches, k_perimeter launches, line-search trials that ran either, loops set}.  No reference
+ * counterpart. */
+int ms_enforce_only_stats(ms_ctx *ctx, int64_t stats[4]);
 /* line_tension (modules/energy/line_tension.py:24-34 selects the edges, :117-123 their gamma: the edge's own
  * "line_tension" option or else the global parameter; an edge whose gamma is 0 is skipped): n_edges tagged edges as
  * EXTERNAL rows (the order of ms_set_positions) in ascending edge order, gamma per edge.  Every row is validated

@@ -79,6 +79,7 @@ class ms_stepper_params(ctypes.Structure):
                 ("alpha_max_factor", ctypes.c_double), ("restart_interval", ctypes.c_int),
                 ("edge_fraction", ctypes.c_double), ("reuse_energy0", ctypes.c_int), ("enforce_volume", ctypes.c_int),
                 ("precondition", ctypes.c_int), ("enforce_pins", ctypes.c_int),
+                ("enforce_fixed_plane", ctypes.c_int), ("enforce_perimeter", ctypes.c_int),
                 ("enforce_area", ctypes.c_int), ("enforce_area_iters", ctypes.c_int)]
 
 
@@ -166,6 +167,14 @@ SIGNATURES = {
                                               ctypes.POINTER(ctypes.c_int), _D]),
     "ms_area_row": (ctypes.c_int, [_P, _D, _D, _D]),
     "ms_area_stats": (ctypes.c_int, [_P, _D]),
+    "ms_set_fixed_plane": (ctypes.c_int, [_P, _D, _D]),
+    "ms_enforce_fixed_plane": (ctypes.c_int, [_P]),
+    "ms_set_perimeter": (ctypes.c_int, [_P, ctypes.c_int, _I32, _I32, _I32, _D]),
+    "ms_perimeter_tables_host": (ctypes.c_int, [ctypes.c_int, _I32, ctypes.c_int, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
+                                                _I32, _I32, _I32]),
+    "ms_project_perimeter": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int, _I32, _D]),
+    "ms_enforce_only_stats": (ctypes.c_int, [_P, _I64]),
+    "ms_get_padded_rows": (ctypes.c_int, [_P, _I64, _D]),
     "ms_set_line_tension": (ctypes.c_int, [_P, ctypes.c_int, _I32, _I32, _D]),
     "ms_get_line_energy": (ctypes.c_int, [_P, _D]),
     "ms_line_stats": (ctypes.c_int, [_P, _D]),

@@ -32,6 +32,7 @@ std::string g_last_error;  // for failures that have no context yet
 #include "ms_api_splay.inc"  // tilt_splay_twist_in: its setter and getters, the pass behind the inner leaflet's smoothness pass
 #include "ms_api_pins.inc"  // pin_to_plane / pin_to_circle: tables, the enforcement program, the project lane
 #include "ms_api_area_con.inc"  // body_area / global_area: the setter, the area row's part in the gradient projection, the enforcer loop
+#include "ms_api_enforce.inc"  // fixed_plane / perimeter: the setters, perimeter's table builder, the two enforcer launches
 #include "ms_api_context.inc"  // create / destroy, setters and getters, curvature fields
 #include "ms_api_tilt.inc"  // tilt-module evaluation, the relaxations (host-driven, device program, fused), leaflet fields
 #include "ms_api_thetab_bnd.inc"  // tilt_thetaB_boundary_in: the constraint's ring and row -> facet CSR, the geometry / apply launches of the relaxation, the cadence

@@ -268,7 +268,7 @@ void ms_destroy(ms_ctx* c) {
                   c->state, c->d_partials, c->d_scal, c->d_stage, c->d_bnd_rows, c->d_bnd_off,
                   c->d_halo_rows, c->d_scal_all, c->d_pins, c->edge[0].d_blob, c->edge[1].d_blob, c->tf[1].d_rim, c->tf[2].d_rim,
                   c->d_cpl, c->d_st, c->d_rimb, c->d_tb, c->d_tbb,
-                  c->d_area_ga, c->d_area_part, c->d_area_res, c->d_area_cache};
+                  c->d_area_ga, c->d_area_part, c->d_area_res, c->d_area_cache, c->d_perim};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& lane : c->edge)

@@ -445,6 +445,13 @@ struct ms_ctx {
   double area_cache_area = 0.0, area_cache_norm2 = 0.0;
   bool area_cache_valid = false;
   long area_launches[4] = {0, 0, 0, 0};  // k_area_row, k_area_dots, k_area_fold, k_area_apply
+  // the enforce-only constraints (ms_api_enforce.inc): fixed_plane's plane (ms_set_fixed_plane), perimeter's tables, targets,
+  // scratch and result cells in one allocation (ms_set_perimeter); launches of the two kernels, trials that ran either
+  bool fplane_set = false;
+  double fplane_n[3] = {0.0, 0.0, 1.0}, fplane_q[3] = {0.0, 0.0, 0.0};
+  void* d_perim = nullptr;
+  PerimeterArgs perim{};
+  long enforce_only_launches[2] = {0, 0}, enforce_only_trials = 0;
   long pin_enforce_launches = 0, pin_grad_launches = 0, pin_trials = 0;
   // the edge lane (ms_api_edge.inc): edge[t] is the state of kEdgeTerms[t] -- line_tension, then edge_length_penalty.
   // One allocation holds every table of a term, the per-workgroup sums and the module's energy

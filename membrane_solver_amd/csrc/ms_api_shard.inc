@@ -595,6 +595,8 @@ int ms_shard_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, doub
     return fail(c, MS_ERR_STATE, "pin_to_plane / pin_to_circle are not sharded (single GPU only)");
   if (sp->enforce_area || area_con_set(c) || c->area_row)
     return fail(c, MS_ERR_STATE, "the body_area / global_area constraints are not sharded (single GPU only)");
+  if (sp->enforce_fixed_plane || sp->enforce_perimeter || fplane_set(c) || perimeter_set(c))
+    return fail(c, MS_ERR_STATE, "the fixed_plane / perimeter constraints are not sharded (single GPU only)");
   c->precond = false;
   memset(out, 0, sizeof(*out));
   const bool cg = sp->stepper == MS_STEPPER_CG;

@@ -450,21 +450,32 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   // A rim source in follow mode takes its center from x when this step's energy pass at x runs, and the trials reuse it
   // (tilt_rim_source_in.py:318 reads the mesh, not the trial positions: without an enforcer the mesh stays at x through
   // the search).  With an enforcer the reference moves the mesh to every trial: that lane is not built.
+  // the enforce-only constraints (ms_api_enforce.inc): a flag without its setter is an error, as enforce_area's is
+  if (sp->enforce_fixed_plane != 0 && !fplane_set(c))
+    return fail(c, MS_ERR_STATE, "ms_stepper_params.enforce_fixed_plane without a plane (ms_set_fixed_plane)");
+  if (sp->enforce_perimeter != 0 && !perimeter_set(c))
+    return fail(c, MS_ERR_STATE, "ms_stepper_params.enforce_perimeter without loops (ms_set_perimeter)");
+  if (sp->enforce_perimeter != 0 && (tilt || tbb_active(c)))
+    return fail(c, MS_ERR_STATE, "perimeter together with tilt modules is outside the device path");
+  const bool enforce_only = sp->enforce_fixed_plane != 0 || sp->enforce_perimeter != 0;
   for (int k = 0; k < n_tf; ++k)
-    if ((c->params.modules & tfl[k]->mod_rs) && tfl[k]->rs_follow && (sp->enforce_volume || sp->enforce_pins))
+    if ((c->params.modules & tfl[k]->mod_rs) && tfl[k]->rs_follow && (sp->enforce_volume || sp->enforce_pins || enforce_only))
       return fail(c, MS_ERR_STATE, "tilt_rim_source in follow mode (pin_to_circle_mode: fit) with a constraint enforcer "
                                    "on the line search is outside the device path");
-  if ((c->params.modules & MS_MOD_TILT_RIM_SOURCE_BILAYER) && c->rb_follow && (sp->enforce_volume || sp->enforce_pins))
+  if ((c->params.modules & MS_MOD_TILT_RIM_SOURCE_BILAYER) && c->rb_follow && (sp->enforce_volume || sp->enforce_pins || enforce_only))
     return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer in follow mode (pin_to_circle_mode: fit) with a constraint "
                                  "enforcer on the line search is outside the device path");
   // (no reference fixture for the enforcers next to the splay / twist term yet)
   if ((c->params.modules & MS_MOD_TILT_SPLAY_TWIST_IN) && (sp->enforce_volume || (sp->enforce_pins != 0 && pins_set(c))))
     return fail(c, MS_ERR_STATE, "tilt_splay_twist_in together with pin_to_plane / pin_to_circle or the volume enforcer on "
                                  "the line search is outside the device path");
-  const bool pin_tilt = sp->enforce_pins != 0 && pins_set(c) && tilt;  // (the lane of pins next to a tilt family)
+  if ((c->params.modules & MS_MOD_TILT_SPLAY_TWIST_IN) && sp->enforce_fixed_plane != 0)
+    return fail(c, MS_ERR_STATE, "tilt_splay_twist_in together with fixed_plane on the line search is outside the device path");
+  // (the lane of pins next to a tilt family: a pin program or a fixed plane)
+  const bool pin_tilt = ((sp->enforce_pins != 0 && pins_set(c)) || sp->enforce_fixed_plane != 0) && tilt;
   if (pin_tilt && ((c->params.modules & MS_CON_VOLUME) || sp->enforce_volume))
-    return fail(c, MS_ERR_STATE, "pin_to_plane / pin_to_circle next to tilt modules together with the volume constraint "
-                                 "are outside the device path");
+    return fail(c, MS_ERR_STATE, "pin_to_plane / pin_to_circle / fixed_plane next to tilt modules together with the volume "
+                                 "constraint are outside the device path");
   // the area lane (ms_api_area_con.inc): the row is projected out behind the gradient pass, the enforcer runs behind the
   // pins' and the volume's on every trial; what has no reference fixture next to it is refused
   const bool area_lane = area_row_active(c) || sp->enforce_area != 0;
@@ -692,7 +703,10 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
   const bool enforce_tilt = pin_tilt;
   // (ms_stepper_params.enforce_area: behind both, constraint_manager.enforce_all's order pins -> volume -> area)
   const bool enforce_area = sp->enforce_area != 0;
-  const bool enforce = enforce_vol || enforce_pin || enforce_area;
+  // (enforce_fixed_plane / enforce_perimeter: the device's one order is fixed_plane -> pins -> perimeter -> volume -> area,
+  // enforce_all's listed order for the lists the reference's decks and parser produce)
+  const bool enforce_fplane = sp->enforce_fixed_plane != 0, enforce_perim = sp->enforce_perimeter != 0;
+  const bool enforce = enforce_vol || enforce_pin || enforce_area || enforce_only;
   bool tbb_lane = false;  // the tilt constraint's ring is set and the inner leaflet's field is among the active ones
   for (int k = 0; k < n_tf; ++k) tbb_lane = tbb_lane || (tfl[k] == &c->tf[1] && tbb_active(c));
   const bool can_chain = c->speculate && carry_mode && !tilt &&
@@ -756,10 +770,14 @@ int ms_step(ms_ctx* c, const ms_stepper_params* sp, double step_size, double tol
         // projection works on buffer X: the trial takes that place for its duration.
         std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
         rc = MS_OK;
-        if (enforce_pin) {
+        if (enforce_only) ++c->enforce_only_trials;
+        if (enforce_fplane) rc = fplane_run(c);
+        if (rc == MS_OK && enforce_pin) {
           rc = pin_enforce_run(c);
           ++c->pin_trials;
         }
+        // (perimeter.enforce_constraint's defaults, which enforce_all never overrides: tol 1e-10, 3 passes)
+        if (rc == MS_OK && enforce_perim) rc = perimeter_run(c, 1e-10, 3);
         int vol_iters = 3;
         if (rc == MS_OK && enforce_vol) rc = ms_project_volume_cached(c, c->params.target_volume, 1e-12, 3, 0, &vol_iters, nullptr);
         // (a volume projection that ended on an evaluation leaves Body's cache looking current: ms_project_area_cached)
@@ -1022,6 +1040,8 @@ bool resident_eligible(ms_ctx* c, const ms_minimize_params* mp) {
     return false;
   if (pins_set(c)) return false;  // (the pin program and the project lane run outside the resident kernel)
   if (area_row_active(c) || sp.enforce_area) return false;  // (so do the area row and its enforcer)
+  // (and the enforce-only constraints: inside the kernel their projections would be dropped without a word)
+  if (sp.enforce_fixed_plane || sp.enforce_perimeter || fplane_set(c) || perimeter_set(c)) return false;
   if (mp->relax_tilts || mp->fixed_step_mode) return false;
   if (c->resident_ok < 0) {
     c->resident_lds = resident_lds_bytes(c->cap, c->til.max_ent, c->til.max_tile_facets, false);
@@ -1260,8 +1280,17 @@ int ms_minimize(ms_ctx* c, const ms_minimize_params* mp, int n_steps, ms_minimiz
           if (mp->project_on_drift) {
             int iters = 0;
             drop_ahead(c, /*ran=*/2);  // (the projection moves x: a round queued for the next step is void)
-            rc = pin_enforce_run(c);  // enforce_all(context="mesh_operation"): the pins, then the volume
+            // enforce_all(context="mesh_operation"): fixed_plane, the pins, perimeter, then the volume
+            if (mp->stepper.enforce_fixed_plane) {
+              rc = fplane_run(c);
+              if (rc) return rc;
+            }
+            rc = pin_enforce_run(c);
             if (rc) return rc;
+            if (mp->stepper.enforce_perimeter) {
+              rc = perimeter_run(c, 1e-10, 3);
+              if (rc) return rc;
+            }
             rc = ms_project_volume_cached(c, mp->target_volume, 1e-12, 12, 1, &iters, nullptr);
             if (rc) return rc;
             if (mp->stepper.enforce_area) {  // (body_area / global_area: listed behind volume)

@@ -562,6 +562,31 @@ hipError_t launch_area_row(const AreaRowArgs& a, bool atomic, hipStream_t s);
 hipError_t launch_area_dots(const AreaProjArgs& a, hipStream_t s);
 hipError_t launch_area_fold(const double* part, double* res, int n_tiles, int tile0, int tile1, int rows, hipStream_t s);
 hipError_t launch_area_apply(const AreaProjArgs& a, hipStream_t s);
+// The enforce-only constraints (ms_enforce.hip): fixed_plane's projection of a position buffer and perimeter's loops.
+struct FixedPlaneArgs {
+  int64_t nv;             // the real rows: nv .. nvp are never touched
+  const uint8_t* vflags;
+  double* x;
+  double n[3], q[3];      // unit normal, point of the plane
+};
+// perimeter's tables (ms_api_enforce.inc builds them): loop l owns the entries loop_off[l] .. loop_off[l + 1) (tail / head
+// in library rows, list order, duplicates kept) and the distinct vertices vert_off[l] .. vert_off[l + 1) (vrow, in order of
+// first appearance); vertex j's incident entries are csr_ent[csr_off[j] .. csr_off[j + 1)) in list order, -(entry + 1) where
+// it is the tail and +(entry + 1) where it is the head.  ent / gv: scratch of 4 x the longest loop's entries / vertices.
+struct PerimeterArgs {
+  int n_loops;
+  const int32_t *loop_off, *tail, *head, *vert_off, *vrow, *csr_off, *csr_ent;
+  const double* target;
+  const uint8_t* vflags;
+  double* x;
+  double *ent, *gv;
+  int max_ent, max_verts;
+  double* res;            // [2 n_loops]: passes that moved something, P of the last evaluation
+  double tol;
+  int max_iter;
+};
+hipError_t launch_fixed_plane(const FixedPlaneArgs& a, hipStream_t s);
+hipError_t launch_perimeter(const PerimeterArgs& a, hipStream_t s);
 struct RowDotArgs {
   int tile0, nv, T;
   const double* g;

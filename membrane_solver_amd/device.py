@@ -620,17 +620,20 @@ class DeviceMesh:
              beta: float = 0.7, c: float = 1e-4, gamma: float = 1.5, alpha_max_factor: float = 10.0,
              restart_interval: int = 10, edge_fraction: float = 0.0,
              reuse_energy0: int = 0, enforce_volume: int = 0, precondition: int = 0,
-             enforce_pins: int = 0, enforce_area: int = 0) -> StepResult:
+             enforce_pins: int = 0, enforce_area: int = 0, enforce_fixed_plane: int = 0,
+             enforce_perimeter: int = 0) -> StepResult:
         # the parameter block and the result struct are reused between calls: at ~140 us per
         # step every microsecond of ctypes marshalling shows
         key = (stepper, max_iter, beta, c, gamma, alpha_max_factor, restart_interval, edge_fraction,
-               reuse_energy0, enforce_volume, precondition, enforce_pins, enforce_area)
+               reuse_energy0, enforce_volume, precondition, enforce_pins, enforce_area, enforce_fixed_plane,
+               enforce_perimeter)
         cache = self.__dict__.get("_step_cache")
         if cache is None or cache[0] != key:
             sp = L.ms_stepper_params(int(stepper), int(max_iter), float(beta), float(c), float(gamma),
                                      float(alpha_max_factor), int(restart_interval), float(edge_fraction),
                                      int(reuse_energy0), int(enforce_volume), int(precondition),
-                                     int(enforce_pins), int(enforce_area > 0), int(enforce_area))
+                                     int(enforce_pins), int(bool(enforce_fixed_plane)), int(bool(enforce_perimeter)),
+                                     int(enforce_area > 0), int(enforce_area))
             r = L.ms_step_result()
             cache = (key, sp, r, ctypes.byref(sp), ctypes.byref(r), L.lib().ms_step)
             self._step_cache = cache
@@ -921,6 +924,87 @@ class DeviceMesh:
         v = np.zeros(4, dtype=np.int64)
         self._chk(L.lib().ms_pin_stats(self._h, v.ctypes.data_as(L._I64)), "ms_pin_stats")
         return {"lane": int(v[0]), "enforce_launches": int(v[1]), "grad_launches": int(v[2]), "trials": int(v[3])}
+
+    def set_fixed_plane(self, normal=None, point=None):
+        """fixed_plane's plane {normal (the library normalises it), point}; no normal clears it (ms_set_fixed_plane)."""
+        if normal is None:
+            self._chk(L.lib().ms_set_fixed_plane(self._h, None, None), "ms_set_fixed_plane")
+            self._fixed_plane = None
+            return
+        n = np.ascontiguousarray(np.asarray(normal, dtype=np.float64).reshape(3))
+        q = np.ascontiguousarray(np.zeros(3) if point is None else np.asarray(point, dtype=np.float64).reshape(3))
+        self._chk(L.lib().ms_set_fixed_plane(self._h, _pd(n), _pd(q)), "ms_set_fixed_plane")
+        self._fixed_plane = (tuple(n.tolist()), tuple(q.tolist()))
+
+    @property
+    def fixed_plane(self):
+        """(normal, point) as handed to set_fixed_plane, or None."""
+        return self.__dict__.get("_fixed_plane")
+
+    def enforce_fixed_plane(self):
+        """fixed_plane.enforce_constraint on the device positions (ms_enforce_fixed_plane)."""
+        self._chk(L.lib().ms_enforce_fixed_plane(self._h), "ms_enforce_fixed_plane")
+
+    def set_perimeter(self, loop_off=None, tail=None, head=None, target=None):
+        """perimeter's loops: entries loop_off[l] .. loop_off[l + 1) of tail / head (external rows, list order) and the
+        target length of each; nothing clears them (ms_set_perimeter).  The same tables are not uploaded twice."""
+        if loop_off is None or len(loop_off) <= 1:
+            if self.__dict__.get("_perimeter_key") is not None:
+                self._chk(L.lib().ms_set_perimeter(self._h, 0, None, None, None, None), "ms_set_perimeter")
+            self._perimeter_key = None
+            return
+        lo = np.ascontiguousarray(np.asarray(loop_off, dtype=np.int32).reshape(-1))
+        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
+        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
+        tg = np.ascontiguousarray(np.asarray(target, dtype=np.float64).reshape(-1))
+        if len(tg) != len(lo) - 1 or len(t) != len(h) or (len(lo) and int(lo[-1]) != len(t)):
+            raise L.MembraneHipError("set_perimeter: loop_off, tail / head and target do not fit together")
+        key = (lo.tobytes(), t.tobytes(), h.tobytes(), tg.tobytes())
+        if key == self.__dict__.get("_perimeter_key"):
+            return
+        self._perimeter_key = None
+        i32 = lambda a: (a if len(a) else np.zeros(1, np.int32)).ctypes.data_as(L._I32)  # noqa: E731
+        self._chk(L.lib().ms_set_perimeter(self._h, len(lo) - 1, i32(lo), i32(t), i32(h), _pd(tg)), "ms_set_perimeter")
+        self._perimeter_key = key
+
+    @property
+    def perimeter_key(self):
+        """What identifies the tables set_perimeter uploaded last (None: none)."""
+        return self.__dict__.get("_perimeter_key")
+
+    @property
+    def perimeter_loops(self) -> int:
+        """Loops set by set_perimeter (0: none)."""
+        key = self.__dict__.get("_perimeter_key")
+        return 0 if key is None else len(key[3]) // 8
+
+    def project_perimeter(self, tol: float = 1e-10, max_iter: int = 3, fetch: bool = True):
+        """perimeter.enforce_constraint on the device positions, one launch (ms_project_perimeter) -> (passes per loop that
+        moved something, P per loop at its last evaluation); ``fetch=False``: nothing comes back, no synchronise."""
+        if not fetch:
+            self._chk(L.lib().ms_project_perimeter(self._h, float(tol), int(max_iter), None, None), "ms_project_perimeter")
+            return None, None
+        n = max(1, self.perimeter_loops)
+        passes = np.zeros(n, dtype=np.int32)
+        per = np.zeros(n)
+        self._chk(L.lib().ms_project_perimeter(self._h, float(tol), int(max_iter), passes.ctypes.data_as(L._I32), _pd(per)),
+                  "ms_project_perimeter")
+        return passes[: self.perimeter_loops], per[: self.perimeter_loops]
+
+    def enforce_only_stats(self) -> dict:
+        """Launch counts of fixed_plane's and perimeter's kernels (ms_enforce_only_stats)."""
+        v = np.zeros(4, dtype=np.int64)
+        self._chk(L.lib().ms_enforce_only_stats(self._h, v.ctypes.data_as(L._I64)), "ms_enforce_only_stats")
+        return {"fixed_plane_launches": int(v[0]), "perimeter_launches": int(v[1]), "trials": int(v[2]), "loops": int(v[3])}
+
+    def padded_positions(self) -> np.ndarray:
+        """The padding rows nv .. nvp of the position buffer (ms_get_padded_rows): no kernel may move them."""
+        n = ctypes.c_int64(0)
+        self._chk(L.lib().ms_get_padded_rows(self._h, ctypes.byref(n), None), "ms_get_padded_rows")
+        out = np.zeros((max(int(n.value), 0), 3))
+        if len(out):
+            self._chk(L.lib().ms_get_padded_rows(self._h, ctypes.byref(n), _pd(out)), "ms_get_padded_rows")
+        return out
 
     def resident_stats(self):
         """The resident step kernel (include/membrane_hip.h, ms_resident_stats)."""

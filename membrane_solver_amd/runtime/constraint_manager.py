@@ -1,6 +1,7 @@
 """Constraint plugin loader (runtime/constraint_manager.py, reduced to the
-in-scope ``volume``, ``body_area``, ``global_area``, ``pin_to_plane``, ``pin_to_circle`` and
-``tilt_thetaB_boundary_in`` modules), the KKT projection of the gradient (:174-315): the k == 1 dense row alone, the
+in-scope ``volume``, ``body_area``, ``global_area``, ``pin_to_plane``, ``pin_to_circle``,
+``tilt_thetaB_boundary_in`` and the enforce-only ``fixed_plane`` / ``perimeter`` modules, which have no row and take no
+part in it), the KKT projection of the gradient (:174-315): the k == 1 dense row alone, the
 volume and area rows together, or the mixed dense + sparse-row solve with the pins -- and the two tilt-space seams
 (:651-841) for
 constraints that act on the leaflet tilts only."""

@@ -32,11 +32,16 @@ its projection on every line-search trial and in every enforce context) and ``gl
 the pins (``pin_to_plane`` / ``pin_to_circle``: the pin program on every
 line-search trial and in every enforce context, their rows removed from the gradient in the project lane).  Next to
 the tilt modules, single field or leaflets, a trial is: positions, pin program, the stored tilts projected onto the
-pinned surface, energy there; a rejected trial puts the tilts back with the positions.
+pinned surface, energy there; a rejected trial puts the tilts back with the positions.  The enforce-only constraints
+``fixed_plane`` (every movable vertex onto a plane; next to the tilt modules it takes the pins' lane) and ``perimeter``
+(listed edge loops held at a target length) have no row: they run on every trial and in every enforce context, in the
+device's one order fixed_plane -> pins -> perimeter -> volume -> area.
 
 Out of scope here (raises MembraneHipError): every other energy module,
-constraints other than ``volume``, ``body_area``, ``global_area``, ``pin_to_plane``, ``pin_to_circle`` and
-``tilt_thetaB_boundary_in``, the area constraints next to tilt modules, pins or ``body_area_penalty``, pins next to tilt modules together with the
+constraints other than ``volume``, ``body_area``, ``global_area``, ``pin_to_plane``, ``pin_to_circle``,
+``tilt_thetaB_boundary_in``, ``fixed_plane`` and ``perimeter``, a listed order of the enforcers other than the device's,
+``perimeter`` next to tilt modules, ``volume``, ``global_area`` or a ``body_area`` whose facets its loops touch,
+``fixed_plane`` next to ``volume`` or the area constraints, the area constraints next to tilt modules, pins or ``body_area_penalty``, pins next to tilt modules together with the
 ``volume`` constraint, the benchmark toggles of the leaflet modules
 (modules/energy/leaflet_common._UNSUPPORTED_KEYS), the reference's auto
 mesh-quality repair hook.
@@ -52,13 +57,15 @@ import numpy as np
 from .. import _lib as L
 from ..core.parameters import ParameterResolver
 from .steppers.base import BaseStepper
-from ..geometry.mesh import mirror_for
+from ..geometry.mesh import _body_facet_mask, mirror_for
 from ..modules.energy import leaflet_common as _lc
 from ..modules.energy._common import bending_gradient_mode, bending_model
 from ..modules.constraints import pins as _pins
 from ..modules.constraints import tilt_thetaB_boundary_in as _tbb
 from ..modules.constraints import body_area as _body_area
 from ..modules.constraints import global_area as _global_area
+from ..modules.constraints import fixed_plane as _fplane
+from ..modules.constraints import perimeter as _perimeter
 from ..modules.energy.body_area_penalty import body_area_params
 from ..modules.energy import edge_length_penalty as _edgepen
 from ..modules.energy import line_tension as _line
@@ -120,6 +127,14 @@ _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": 
                 "tilt_disk_target_out": L.MS_S_EDT_OUT}
 _PIN_MODULES = ("pin_to_plane", "pin_to_circle")
 _AREA_CONSTRAINTS = ("body_area", "global_area")  # the area lane: the row (body_area) and the enforcer on every trial
+# The reference's fixed_plane and perimeter write vertex.position without Mesh.increment_version(), and volume.py:109 /
+# body_area.py:98 / global_area take their first evaluation from Mesh.positions_view(), a copy keyed on that version: right
+# behind an enforce-only module their first pass is evaluated at the positions from BEFORE it and applied to the moved
+# ones.  The device evaluates where it applies; the reference's trajectories of these pairs differ from it by 1e-5 .. 1e-1
+# in the accepted energies, so the pairs are refused until that first pass is reproduced.
+_STALE_CACHE = ("the reference evaluates that module's first pass at the positions cached before the enforce-only module "
+                "moved them (Mesh.positions_view is not invalidated), which the device path does not reproduce")
+_ENFORCE_ONLY = (_fplane.NAME, _perimeter.NAME)  # no KKT row: they only move the positions of a trial / an enforce context
 _BEND_SCALAR = {"bending": L.MS_S_EBEND, "bending_tilt": L.MS_S_EBT, "bending_tilt_in": L.MS_S_EBT_IN,
                 "bending_tilt_out": L.MS_S_EBT_OUT}
 
@@ -234,10 +249,10 @@ class Minimizer:
         self.constraint_modules = [self.constraint_manager.get_constraint(c)
                                    for c in self.constraint_module_names]
         for name in self.constraint_module_names:
-            if name not in ("volume", _tbb.NAME) + _PIN_MODULES + _AREA_CONSTRAINTS:
+            if name not in ("volume", _tbb.NAME) + _PIN_MODULES + _AREA_CONSTRAINTS + _ENFORCE_ONLY:
                 raise L.MembraneHipError(f"constraint module {name!r} is outside the HIP hot path "
                                          "(volume, body_area, global_area, pin_to_plane, pin_to_circle, "
-                                         "tilt_thetaB_boundary_in)")
+                                         "tilt_thetaB_boundary_in, fixed_plane, perimeter)")
         self._pin_names = [n for n in self.constraint_module_names if n in _PIN_MODULES]
         if self._pin_names and "volume" in self.constraint_module_names and \
                 self.constraint_module_names.index("volume") < self.constraint_module_names.index(self._pin_names[0]):
@@ -245,6 +260,10 @@ class Minimizer:
             raise L.MembraneHipError("constraint_modules lists volume before pin_to_plane / pin_to_circle: the HIP "
                                      "path enforces the pins first; list the pin modules before volume")
         self._check_area_constraints()
+        self._check_enforce_only()
+        self._fplane_active = False  # (set by _device(): fixed_plane is listed and its normal is not zero)
+        self._perim_active = False   # (set by _device(): perimeter is listed and some entry has edges and a target)
+        self._perim_key = None
         self._area_con = None  # (set by _device(): (kind, target) of the area constraint that is listed and has a target)
         self._pin_key = None
         self._pins_active = False
@@ -279,6 +298,77 @@ class Minimizer:
                                      "with the constraint or with the penalty")
         if self._pin_names:
             raise L.MembraneHipError(f"{what} next to pin_to_plane / pin_to_circle is outside the HIP hot path")
+
+    def _check_enforce_only(self):
+        """What the lane of fixed_plane / perimeter does not take, by the names alone.  The device enforces in ONE order,
+        fixed_plane -> pin program -> perimeter -> volume -> area: enforce_all's listed order for the lists the
+        reference's decks and parser produce (explicitly listed modules first, body_area / volume appended from the
+        bodies last); a list whose relative order differs is refused."""
+        names = self.constraint_module_names
+        enforcers = [n for n in names if n in ("volume",) + _PIN_MODULES + _AREA_CONSTRAINTS + _ENFORCE_ONLY]
+        tilt = any(_ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names)
+        if _fplane.NAME in names:
+            if enforcers[0] != _fplane.NAME:
+                raise L.MembraneHipError(f"constraint_modules lists fixed_plane after {enforcers[0]}: the HIP path "
+                                         "enforces fixed_plane first; list fixed_plane before every other enforcer")
+            for other in ("volume",) + _AREA_CONSTRAINTS:
+                if other in names:
+                    raise L.MembraneHipError(f"fixed_plane next to {other} is outside the HIP hot path: " + _STALE_CACHE)
+        if _perimeter.NAME in names:
+            at = names.index(_perimeter.NAME)
+            later_pins = [n for n in names[at + 1:] if n in _PIN_MODULES]
+            if later_pins:
+                raise L.MembraneHipError(f"constraint_modules lists perimeter before {later_pins[0]}: the HIP path "
+                                         "enforces the pins first; list the pin modules before perimeter")
+            earlier = [n for n in names[:at] if n in ("volume",) + _AREA_CONSTRAINTS]
+            if earlier:
+                raise L.MembraneHipError(f"constraint_modules lists perimeter after {earlier[0]}: the HIP path enforces "
+                                         f"perimeter first; list perimeter before {earlier[0]}")
+            if tilt or _tbb.NAME in names:
+                raise L.MembraneHipError("perimeter together with tilt modules is outside the HIP hot path")
+            for other in ("volume", "global_area"):
+                if other in names:
+                    raise L.MembraneHipError(f"perimeter next to {other} is outside the HIP hot path: " + _STALE_CACHE)
+            # (body_area behind perimeter: where the loops touch no vertex of the body's facets, checked at upload)
+            if not _line.has_edge_table(self.mesh):
+                raise L.MembraneHipError("perimeter is listed but the mesh has no edge table (ArrayMesh(edges=...)): its "
+                                         "signed edge indices cannot be resolved")
+
+    def _upload_enforce_only(self, mir, dm):
+        """fixed_plane's plane and perimeter's loops on the device, keyed like the pins: resolved once per mesh topology,
+        context and parameter values (call refresh_modules() after changing them).  A module that is not listed leaves
+        nothing set: a plane or loops that the module's own ``enforce_constraint`` (or another minimizer) left on the
+        mesh's context are cleared, so that the lanes that decline with them (the resident kernel) stay open."""
+        names = self.constraint_module_names
+        gp = self.global_params
+        if _fplane.NAME not in names and dm.fixed_plane is not None:
+            dm.set_fixed_plane()
+        if _perimeter.NAME not in names and dm.perimeter_loops:
+            dm.set_perimeter()
+        if _fplane.NAME in names:
+            pl = _fplane.plane(self.mesh, gp)
+            want = None if pl is None else (tuple(pl[0].tolist()), tuple(pl[1].tolist()))
+            if want != dm.fixed_plane:
+                dm.set_fixed_plane(*(pl if pl is not None else ()))
+            self._fplane_active = pl is not None
+        if _perimeter.NAME in names:
+            cons = gp.get("perimeter_constraints") or []
+            key = (mir._topo_key, id(dm), repr([(list(c.get("edges") or []), c.get("target_perimeter")) for c in cons]))
+            # (the tables this minimizer uploaded must still be the context's: the module's own entry point may have
+            # replaced them in between)
+            if self._perim_key is None or self._perim_key[:3] != key or self._perim_key[3] != dm.perimeter_key:
+                self._perim_active = bool(_perimeter.upload(self.mesh, gp, dm))
+                self._perim_key = key + (dm.perimeter_key,)
+                if self._perim_active and "body_area" in names:
+                    # body_area.py:98 reads the cached positions: exact only where perimeter moved no vertex of the body
+                    tri, _ = self.mesh.triangle_row_cache()
+                    mask, body = _body_facet_mask(self.mesh, len(tri))
+                    rows = np.asarray(tri)[np.flatnonzero(mask)] if mask is not None else np.asarray(tri)
+                    _n, _off, tail, head, _t = _perimeter.loops(self.mesh, gp)
+                    if body is not None and np.intersect1d(np.concatenate([tail, head]), rows.reshape(-1)).size:
+                        self._perim_key = None  # (refused again on the next call)
+                        raise L.MembraneHipError("perimeter next to body_area with a listed edge on the body's facets is "
+                                                 "outside the HIP hot path: " + _STALE_CACHE)
 
     def _area_constraint_params(self):
         """(kind, target, max_iter) of the listed area constraint, or None where it does nothing (no body, no
@@ -469,6 +559,8 @@ class Minimizer:
             if self._pin_names:
                 raise L.MembraneHipError("tilt_splay_twist_in next to pin_to_plane / pin_to_circle is outside the HIP "
                                          "hot path")
+            if _fplane.NAME in self.constraint_module_names:
+                raise L.MembraneHipError("tilt_splay_twist_in next to fixed_plane is outside the HIP hot path")
             if "volume" in self.constraint_module_names:
                 raise L.MembraneHipError("tilt_splay_twist_in next to the volume constraint's enforcer is outside the "
                                          "HIP hot path")
@@ -546,6 +638,14 @@ class Minimizer:
             dm.set_tilt_smoothness(float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0))
         if self._pin_names:
             self._upload_pins(mir, dm, mods)
+        if _fplane.NAME in self.constraint_module_names:
+            if mods & _TILT_BITS and ((mods & L.MS_CON_VOLUME) or "volume" in self.constraint_module_names):
+                raise L.MembraneHipError("fixed_plane next to tilt modules together with the volume constraint is "
+                                         "outside the HIP hot path")
+            if rim_bilayer is not None and rim_bilayer["follow"]:  # (ms_step refuses the one-leaflet sources' follow mode)
+                raise L.MembraneHipError("tilt_rim_source_bilayer in follow mode (pin_to_circle_mode: fit) next to "
+                                         "fixed_plane's enforcer on the line search is outside the HIP hot path")
+        self._upload_enforce_only(mir, dm)
         if area_con is not None or getattr(self, "_area_set_on", None) is dm:
             # (the constraint of an earlier configuration of this minimizer is replaced or cleared)
             if (None if area_con is None else area_con[:2]) != dm.area_constraint:
@@ -745,9 +845,15 @@ class Minimizer:
 
     def _enforce_pins_volume(self, dm, context: str, first_step_cached: bool = False) -> bool:
         moved = False
+        if self._fplane_active:  # fixed_plane.py:25-53: in every context, listed in front of every other enforcer
+            dm.enforce_fixed_plane()
+            moved = True
         if self._pins_active:  # constraint_manager.enforce_all: the pins in every context, listed before volume
             dm.enforce_pins()
             moved = True
+        if self._perim_active:  # perimeter.py:27-74: tol 1e-10, 3 passes whatever the context; behind the pins
+            passes, _p = dm.project_perimeter(tol=1e-10, max_iter=3)
+            moved = moved or int(passes.sum()) > 0
         if self._tbb_active:
             # minimizer.py:1112-1120, :1165-1171: enforce_tilt_constraints behind enforce_all, on the pinned surface; the
             # tangent projection of the finalize / mesh-operation contexts below comes after it
@@ -758,7 +864,8 @@ class Minimizer:
             return moved
         target = self._target_volume()
         if target is None or "volume" not in self.constraint_module_names:
-            if self._pin_names and context in ("finalize", "mesh_operation") and dm.modules & _TILT_BITS:
+            if (self._pin_names or _fplane.NAME in self.constraint_module_names) \
+                    and context in ("finalize", "mesh_operation") and dm.modules & _TILT_BITS:
                 # minimizer.py:1186, :1224: the pins alone are an enforcer as well -- the tilts go onto the tangent
                 # planes of the pinned surface before the next evaluation reads them.  Keyed on the LISTED pin modules,
                 # not on _pins_active: the reference projects whenever a constraint module with enforce_constraint is
@@ -867,6 +974,8 @@ class Minimizer:
                                          int(extra.get("restart_interval", 10)), edge_fraction,
                                          int(st.reuse_energy0), int(getattr(st, "enforce_volume", 0)),
                                          int(extra.get("precondition", 0)), int(getattr(st, "enforce_pins", 0)),
+                                         int(getattr(st, "enforce_fixed_plane", 0)),
+                                         int(getattr(st, "enforce_perimeter", 0)),
                                          int(getattr(st, "enforce_area", 0) > 0), int(getattr(st, "enforce_area", 0)))
         step_mode = str(gp.get("step_size_mode", "adaptive") or "adaptive").lower()
         mp.step_size = float(self.step_size)
@@ -912,6 +1021,9 @@ class Minimizer:
         self.stepper.enforce_pins = int(self._pins_active)  # (pins always have enforce_constraint)
         # (so do body_area / global_area: the projection on every trial, with the module's own max_iter)
         self.stepper.enforce_area = int(self._area_con[2]) if self._area_con is not None else 0
+        # (fixed_plane / perimeter have enforce_constraint as well: minimizer.py:114-116 switches the enforcer lane on)
+        self.stepper.enforce_fixed_plane = int(self._fplane_active)
+        self.stepper.enforce_perimeter = int(self._perim_active)
         if n_steps <= 0:
             E, g = self.compute_energy_and_gradient_array()
             moved = self._enforce(dm, "minimize")

@@ -56,6 +56,10 @@ class BaseStepper(ABC):
         # set by the Minimizer when body_area / global_area are loaded: max_iter of the area projection every trial runs
         # behind the pins and the volume projection (20 / 3; 0: off)
         self.enforce_area = 0
+        # set by the Minimizer when fixed_plane / perimeter are loaded: every trial runs the plane projection in front of
+        # the pin program / the perimeter loops behind it
+        self.enforce_fixed_plane = 0
+        self.enforce_perimeter = 0
         self._dm = None
 
     @abstractmethod
@@ -76,7 +80,9 @@ class BaseStepper(ABC):
                        alpha_max_factor=self.alpha_max_factor, edge_fraction=edge_fraction,
                        reuse_energy0=self.reuse_energy0, enforce_volume=int(self.enforce_volume),
                        **({"enforce_pins": 1} if self.enforce_pins else {}),
-                       **({"enforce_area": int(self.enforce_area)} if self.enforce_area else {}), **self._extra())
+                       **({"enforce_area": int(self.enforce_area)} if self.enforce_area else {}),
+                       **({"enforce_fixed_plane": 1} if self.enforce_fixed_plane else {}),
+                       **({"enforce_perimeter": 1} if self.enforce_perimeter else {}), **self._extra())
 
     def step(self, mesh, grad, step_size, energy_fn=None, constraint_enforcer=None,
              trial_energy_fn=None):
