@@ -1004,6 +1004,29 @@ int ms_plan_tiling(int nv, int nf, const double *positions, const int32_t *tri,
  * model[2], model[3] = fraction of lane groups that are conflict-free for each. */
 int ms_plan_tiling_conflicts(int nv, int nf, const double *positions,
                              const int32_t *tri, int tile_vertices, double model[4]);
+/* Host-only: the lane order of the lean k_energy instances (no GPU needed).  They
+ * read each tile's facet records in an order of their own (the records themselves
+ * are the common ones), chosen by a greedy for the LDS instructions they issue per
+ * aligned lane group and corner slot k:
+ *   A16  ds_add_f64: groups of 16 lanes, OWNED targets only (a halo corner issues
+ *        none), ways = most targets in one residue mod 16 (same slot twice = 2)
+ *   R16  ds_read2_b64 halves: groups of 16, distinct slots by residue mod 16
+ *   R32  ds_read_b64: groups of 32, distinct slots by residue mod 32
+ * model[0..7] scores the common order, model[8..15] the lean one:
+ *   {mean A16 ways per group with an owned target, mean R16, mean R32,
+ *    sum over groups of 7.4 A16 + 2 R16 + R32 (the energy kernel's mix),
+ *    sum of 5.55 A16 + 4 R16 + 3 R32 (the lean gradient kernel's mix, which reads
+ *    the common order: reported for comparison),
+ *    A16 groups, R16 groups, R32 groups}.
+ * facet_off_out (n_tiles + 1), common_out and lean_out (facet_instances x 4:
+ * l0, l1, l2, flags) may each be NULL; sizes as ms_plan_tiling reports them. */
+int ms_plan_lane_order(int nv, int nf, const double *positions, const int32_t *tri,
+                       int tile_vertices, double model[16], int32_t *facet_off_out,
+                       int32_t *common_out, int32_t *lean_out);
+/* stats[0]: 1 if the lean k_energy instances of this context read their own lane order
+ * (0: MS_LANE_ORDER=0 at ms_create, or a tile of more than 1024 slots);
+ * stats[1]: 1 if they stage from a halo list of their own (not built: always 0). */
+int ms_lane_order_stats(ms_ctx *ctx, int64_t stats[2]);
 
 /* ---- kernel-provider seam: the five procedures under fortran_kernels/ ----
  * Host arrays in, host arrays out (H2D/D2H per call: for parity, not speed).

@@ -80,6 +80,15 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
       packed[i] = (uint32_t)f.l0 | ((uint32_t)f.l1 << 10) | ((uint32_t)f.l2 << 20) | ((uint32_t)(f.flags & 3u) << 30);
     }
     CREATE_CHK(upload(c, &c->d_tile_facets32, packed));
+    // MS_LANE_ORDER=0: the lean k_energy instances read the common array too (the A/B switch)
+    if (!(getenv("MS_LANE_ORDER") != nullptr && atoi(getenv("MS_LANE_ORDER")) == 0)) {
+      for (size_t i = 0; i < packed.size(); ++i) {
+        const TileFacet& f = t.tile_facets_lean[i];
+        packed[i] = (uint32_t)f.l0 | ((uint32_t)f.l1 << 10) | ((uint32_t)f.l2 << 20) | ((uint32_t)(f.flags & 3u) << 30);
+      }
+      CREATE_CHK(upload(c, &c->d_tile_facets_lean, packed));
+      c->lane_order_on = true;
+    }
   }
   CREATE_CHK(upload(c, &c->d_tile_halo_off, t.tile_halo_off));
   CREATE_CHK(upload(c, &c->d_halo_ids, t.halo_ids));
@@ -258,7 +267,7 @@ void ms_destroy(ms_ctx* c) {
   }
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (!c->own_state) c->state = nullptr;
-  void* ptrs[] = {c->d_perm, c->d_tile_facet_off, c->d_tile_facets, c->d_tile_facets32, c->d_tf_gamma, c->d_volgrad_cache,
+  void* ptrs[] = {c->d_perm, c->d_tile_facet_off, c->d_tile_facets, c->d_tile_facets32, c->d_tile_facets_lean, c->d_tf_gamma, c->d_volgrad_cache,
                   c->d_tile_halo_off, c->d_halo_ids, c->d_tile_ent_off, c->d_tile_voff, c->d_vent,
                   c->d_vflags, c->d_kappa, c->d_c0, c->tf[0].tilts, c->tf[0].grad, c->tf[0].trial, c->d_bt_vert, c->d_tn, c->tf[0].dir, c->tf[0].minv,
                   c->tf[1].tilts, c->tf[1].grad, c->tf[1].trial, c->tf[1].dir, c->tf[1].minv,

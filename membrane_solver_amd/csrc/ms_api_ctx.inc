@@ -71,6 +71,8 @@ struct ms_ctx {
   int32_t* d_tile_facet_off = nullptr;
   TileFacet* d_tile_facets = nullptr;
   uint32_t* d_tile_facets32 = nullptr;  // packed copy (DeviceMesh::tile_facets32), or nullptr
+  uint32_t* d_tile_facets_lean = nullptr;  // packed Tiling::tile_facets_lean (the lean k_energy instances' lane order), or nullptr
+  bool lane_order_on = false;           // they read it (MS_LANE_ORDER=0 at ms_create: they read the common array)
   double* d_tf_gamma = nullptr;
   // Body's cached volume gradient (geometry/body.py:386-407): what the last fresh evaluation inside
   // ms_project_volume computed, and its squared norm

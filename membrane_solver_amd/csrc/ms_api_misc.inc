@@ -324,6 +324,48 @@ int ms_plan_tiling_conflicts(int nv, int nf, const double* positions, const int3
   return MS_OK;
 }
 
+int ms_plan_lane_order(int nv, int nf, const double* positions, const int32_t* tri, int tile_vertices, double model[16],
+                       int32_t* facet_off_out, int32_t* common_out, int32_t* lean_out) {
+  if (!model) return fail(nullptr, MS_ERR_INVALID, "ms_plan_lane_order: model is NULL");
+  Tiling t;
+  std::string err;
+  int rc = build_tiling(nv, nf, positions, tri, nullptr, tile_vertices, 1, t, err);
+  if (rc != MS_OK) return fail(nullptr, rc, err);
+  const LaneModel* ms[2] = {&t.model_common, &t.model_lean};
+  for (int i = 0; i < 2; ++i) {
+    const LaneModel& m = *ms[i];
+    double* o = model + 8 * i;
+    o[0] = m.a16_groups > 0 ? m.a16_sum / m.a16_groups : 0.0;
+    o[1] = m.r16_groups > 0 ? m.r16_sum / m.r16_groups : 0.0;
+    o[2] = m.r32_groups > 0 ? m.r32_sum / m.r32_groups : 0.0;
+    o[3] = m.ka();
+    o[4] = m.kc();
+    o[5] = m.a16_groups;
+    o[6] = m.r16_groups;
+    o[7] = m.r32_groups;
+  }
+  if (facet_off_out) memcpy(facet_off_out, t.tile_facet_off.data(), sizeof(int32_t) * t.tile_facet_off.size());
+  const std::vector<TileFacet>* src[2] = {&t.tile_facets, &t.tile_facets_lean};
+  int32_t* dst[2] = {common_out, lean_out};
+  for (int i = 0; i < 2; ++i)
+    if (dst[i])
+      for (size_t p = 0; p < src[i]->size(); ++p) {
+        const TileFacet& f = (*src[i])[p];
+        dst[i][4 * p] = f.l0;
+        dst[i][4 * p + 1] = f.l1;
+        dst[i][4 * p + 2] = f.l2;
+        dst[i][4 * p + 3] = f.flags;
+      }
+  return MS_OK;
+}
+
+int ms_lane_order_stats(ms_ctx* c, int64_t stats[2]) {
+  if (!c || !stats) return MS_ERR_INVALID;
+  stats[0] = c->lane_order_on ? 1 : 0;
+  stats[1] = 0;
+  return MS_OK;
+}
+
 // ---- kernel-provider seam ---------------------------------------------------
 
 int ms_surface_energy_and_gradient_host(int nv, int nf, const double* pos, const int32_t* tri,

@@ -108,6 +108,7 @@ DeviceMesh device_mesh(const ms_ctx* c) {
   m.tile_facet_off = c->d_tile_facet_off;
   m.tile_facets = c->d_tile_facets;
   m.tile_facets32 = c->d_tile_facets32;
+  m.tile_facets_lean = c->lane_order_on ? c->d_tile_facets_lean : c->d_tile_facets32;
   m.no_fast = c->no_fast ? 1 : 0;
   m.tf_gamma = c->d_tf_gamma;
   m.gamma_uniform = c->gamma_uniform ? 1 : 0;

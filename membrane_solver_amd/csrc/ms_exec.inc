@@ -341,6 +341,7 @@ std::atomic<int> g_exec_count{0};
 bool same_mesh(const DeviceMesh& a, const DeviceMesh& b) {
   return a.nv == b.nv && a.T == b.T && a.n_tiles == b.n_tiles && a.own == b.own && a.has_boundary == b.has_boundary &&
          a.tile_facet_off == b.tile_facet_off && a.tile_facets == b.tile_facets && a.tile_facets32 == b.tile_facets32 &&
+         a.tile_facets_lean == b.tile_facets_lean &&
          a.no_fast == b.no_fast && a.tf_gamma == b.tf_gamma && a.gamma_uniform == b.gamma_uniform &&
          a.kc_uniform == b.kc_uniform && a.gamma_const == b.gamma_const && a.kappa_const == b.kappa_const &&
          a.c0_const == b.c0_const && a.tile_halo_off == b.tile_halo_off && a.halo_ids == b.halo_ids &&

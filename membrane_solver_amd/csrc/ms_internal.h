@@ -65,6 +65,24 @@ constexpr uint8_t VF_TILT_FIXED = 4;  // vertex.tilt_fixed (runtime/minimizer_he
 constexpr uint8_t VF_TILT_FIXED_IN = 8;    // vertex.tilt_fixed_in  (minimizer.py:460-472)
 constexpr uint8_t VF_TILT_FIXED_OUT = 16;  // vertex.tilt_fixed_out (minimizer.py:474-486)
 
+// LDS bank model of one lane order (lane_order_model): per aligned lane group and corner slot k, the number of "ways"
+// (serialised passes) of the instruction the group issues.
+//   a16: ds_add_f64, groups of 16, OWNED targets only, by slot mod 16; the same slot twice is two ways
+//   r16: ds_read2_b64 halves, groups of 16, distinct slots by slot mod 16 (24-byte rows: bank 6 l mod 32); same slot broadcasts
+//   r32: ds_read_b64, groups of 32, distinct slots by slot mod 32
+// *_sum: ways summed over the groups; *_groups: groups counted (a16: groups with an owned target only).
+// ka, kc: the two headline kernels' instruction mixes per corner, summed over groups (cycles of the model)
+struct LaneModel {
+  double a16_sum = 0, r16_sum = 0, r32_sum = 0;
+  double a16_groups = 0, r16_groups = 0, r32_groups = 0;
+  double ka() const { return LANE_W_KA[0] * a16_sum + LANE_W_KA[1] * r16_sum + LANE_W_KA[2] * r32_sum; }
+  double kc() const { return LANE_W_KC[0] * a16_sum + LANE_W_KC[1] * r16_sum + LANE_W_KC[2] * r32_sum; }
+  // per group-way: an atomic 1.85 (7.4 cycles per extra way of a wave = four groups), a ds_read2_b64 2, a ds_read_b64 1.
+  // K_A per corner: 4 atomics, 1 read2, 1 read; K_C: 3 atomics, 2 read2 (px, fk), 3 reads (px, fk, fa)
+  static constexpr double LANE_W_KA[3] = {7.4, 2.0, 1.0};
+  static constexpr double LANE_W_KC[3] = {5.55, 4.0, 3.0};
+};
+
 // Host-side result of the tiling pass.
 struct Tiling {
   int nv = 0, nf = 0, T = 256;
@@ -78,6 +96,10 @@ struct Tiling {
   std::vector<int32_t> tile_facet_off;  // n_tiles+1
   std::vector<TileFacet> tile_facets;   // facet instances
   std::vector<int32_t> tile_facet_ext;  // external facet row of each instance
+  // the lean k_energy instances' own lane order: per tile a permutation of tile_facets' records; tiles below the
+  // ordering threshold are copies
+  std::vector<TileFacet> tile_facets_lean;
+  LaneModel model_common, model_lean;   // lane_order_model of the two arrays
   std::vector<int32_t> tile_halo_off;   // n_tiles+1
   std::vector<int32_t> halo_ids;        // internal vertex ids
   // per-tile vertex -> corner CSR (deterministic gather order): for owned vertex i of
@@ -97,6 +119,9 @@ int build_tiling(int nv, int nf, const double* positions, const int32_t* tri,
                  const uint8_t* body_facets, int T, int shard_count, Tiling& out,
                  std::string& err);
 
+// Scores `recs` (the tiling's tile_facet_off ranges) with the LDS bank model above.
+LaneModel lane_order_model(const Tiling& t, const TileFacet* recs, int tile0, int tile1);
+
 // ---- device-side view handed to kernels ---------------------------------
 struct DeviceMesh {
   int nv, T, n_tiles;
@@ -107,6 +132,9 @@ struct DeviceMesh {
   // the same records in 4 bytes (10 bits per corner slot | 2 flag bits) for the T = 256 instances of the two tile
   // kernels; nullptr when some tile needs more than 1024 LDS slots (those instances are not used then)
   const uint32_t* tile_facets32;
+  // what the lean k_energy instances (energy_body's LEANE) read instead: the same records per tile in a lane order
+  // chosen for the LDS atomics and gathers they issue -- or tile_facets32 itself (MS_LANE_ORDER=0)
+  const uint32_t* tile_facets_lean;
   int no_fast;            // MS_NO_FAST at ms_create: never pick the T = 256 instances (A/B switch)
   const double* tf_gamma;  // surface tension per facet instance
   // uniform-parameter shortcuts: when every facet carries the same surface tension (every vertex the same kappa and

@@ -365,10 +365,13 @@ template <>
 struct FacetRec<true> {
   uint32_t v;
 };
-template <bool PACKED>
+// LEANORD: the lean k_energy instances' own lane order of the same records (DeviceMesh::tile_facets_lean)
+template <bool PACKED, bool LEANORD = false>
 __device__ __forceinline__ FacetRec<PACKED> facet_load(const DeviceMesh& m, size_t i) {
+  static_assert(PACKED || !LEANORD, "the lean lane order exists in packed form only");
   FacetRec<PACKED> r;
-  if constexpr (PACKED) r.v = m.tile_facets32[i];
+  if constexpr (LEANORD) r.v = m.tile_facets_lean[i];
+  else if constexpr (PACKED) r.v = m.tile_facets32[i];
   else r.v = m.tile_facets[i];
   return r;
 }
@@ -573,7 +576,7 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
   FacetRec<PACKED> tf_nx = facet_null<PACKED>();
   double gam_nx = 0.0;
   if (t.f0 + tid < t.f1) {
-    tf_nx = facet_load<PACKED>(a.m, (size_t)(t.f0 + tid));
+    tf_nx = facet_load<PACKED, LEANE>(a.m, (size_t)(t.f0 + tid));
     if (!LEANE) gam_nx = a.m.gamma_uniform ? a.m.gamma_const : a.m.tf_gamma[t.f0 + tid];
   }
 
@@ -695,7 +698,7 @@ __device__ __forceinline__ void energy_body(EnergyArgs& a, int cap_rt, int max_e
     const TileFacet tf = facet_unpack<PACKED>(tf_nx);
     const double gam = LEANE ? a.m.gamma_const : gam_nx;  // (uniform: a kernel argument)
     if (p + T < t.f1) {
-      tf_nx = facet_load<PACKED>(a.m, (size_t)(p + T));
+      tf_nx = facet_load<PACKED, LEANE>(a.m, (size_t)(p + T));
       if (!LEANE) gam_nx = a.m.gamma_uniform ? a.m.gamma_const : a.m.tf_gamma[p + T];
     }
     double va0 = 0, va1 = 0, va2 = 0, ve0 = 0, ve1 = 0, ve2 = 0;

@@ -11,7 +11,10 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
+#include <atomic>
 #include <numeric>
+#include <system_error>
+#include <thread>
 
 #include "ms_internal.h"
 
@@ -46,7 +49,123 @@ inline uint64_t hilbert3(uint32_t x, uint32_t y, uint32_t z, int bits) {
   return h;
 }
 
+inline uint16_t corner_slot(const TileFacet& f, int k) { return k == 0 ? f.l0 : (k == 1 ? f.l1 : f.l2); }
+
+// Integer weights of the lean lane order's greedy: the energy kernel's mix per corner (LaneModel::LANE_W_KA), times 10
+constexpr int LANE_WA = 74, LANE_WR16 = 20, LANE_WR32 = 10;
+constexpr int LANE_SCAN = 400;  // free candidates looked at per lane
+
+// Scratch of lean_lane_order, kept across tiles.
+struct LaneScratch {
+  std::vector<int32_t> seq;
+  std::vector<uint8_t> taken;
+  std::vector<uint32_t> seen16, seen32;  // [3][n_slots]: id of the last half / group that holds this slot at corner k
+  uint32_t half_id = 0, group_id = 0;
+};
+
+// The lean k_energy instances' lane order of one tile: `walk` (n records, walk order) -> `dst`, a permutation of the
+// records.  The greedy of the common order (stride-permuted candidates, groups of 32 filled half by half, bounded
+// scan), charged with the model of LaneModel instead: atomics on OWNED targets only (a halo corner issues none), reads
+// on distinct slots.  The records keep their corners as they are (a rotated record would be the same triangle, but its
+// arithmetic rounds differently: the lean launches would leave the general instance's run-to-run scatter).
+void lean_lane_order(const TileFacet* walk, size_t n, int n_owned, int n_slots, size_t S, TileFacet* dst, LaneScratch& w) {
+  w.seq.resize(n);
+  for (size_t i = 0; i < n; ++i) w.seq[i] = (int32_t)((i * S) % n);
+  w.taken.assign(n, 0);
+  if (w.seen16.size() < 3 * (size_t)n_slots || w.half_id > 0xfff00000u) {
+    w.seen16.assign(3 * (size_t)n_slots, 0);
+    w.seen32.assign(3 * (size_t)n_slots, 0);
+    w.half_id = w.group_id = 0;
+  }
+  size_t placed = 0, first_free = 0;
+  while (placed < n) {
+    int r32[3][32] = {};
+    const uint32_t gid = ++w.group_id;
+    const size_t group_end = std::min(n, placed + 32);
+    for (int half = 0; half < 2 && placed < group_end; ++half) {
+      int a16[3][16] = {}, r16[3][16] = {};
+      const uint32_t hid = ++w.half_id;
+      const size_t half_end = std::min(group_end, placed + 16);
+      while (placed < half_end) {
+        size_t best = n;
+        int best_cost = INT32_MAX, seen = 0;
+        for (size_t q = first_free; q < n && seen < LANE_SCAN && best_cost > 0; ++q) {
+          if (w.taken[q]) continue;
+          ++seen;
+          const TileFacet& f = walk[w.seq[q]];
+          int cost = 0;
+          for (int k = 0; k < 3; ++k) {
+            const uint32_t s = corner_slot(f, k);
+            if ((int)s < n_owned) cost += LANE_WA * a16[k][s & 15];
+            if (w.seen16[(size_t)k * n_slots + s] != hid) cost += LANE_WR16 * r16[k][s & 15];
+            if (w.seen32[(size_t)k * n_slots + s] != gid) cost += LANE_WR32 * r32[k][s & 31];
+          }
+          if (cost < best_cost) {
+            best_cost = cost;
+            best = q;
+          }
+        }
+        const TileFacet& f = walk[w.seq[best]];
+        for (int k = 0; k < 3; ++k) {
+          const uint32_t s = corner_slot(f, k);
+          if ((int)s < n_owned) ++a16[k][s & 15];
+          uint32_t& h16 = w.seen16[(size_t)k * n_slots + s];
+          if (h16 != hid) ++r16[k][s & 15];
+          h16 = hid;
+          uint32_t& h32 = w.seen32[(size_t)k * n_slots + s];
+          if (h32 != gid) ++r32[k][s & 31];
+          h32 = gid;
+        }
+        w.taken[best] = 1;
+        dst[placed++] = f;
+        while (first_free < n && w.taken[first_free]) ++first_free;
+      }
+    }
+  }
+}
+
 }  // namespace
+
+LaneModel lane_order_model(const Tiling& t, const TileFacet* recs, int tile0, int tile1) {
+  LaneModel m;
+  std::vector<uint32_t> seen((size_t)t.own + (size_t)t.max_halo + 1, 0);
+  uint32_t id = 0;
+  for (int tile = tile0; tile < tile1; ++tile) {
+    const int n_owned = std::min(t.own, t.nv - tile * t.own);
+    const int f0 = t.tile_facet_off[tile], f1 = t.tile_facet_off[tile + 1];
+    for (int k = 0; k < 3; ++k)
+      for (int width = 16; width <= 32; width += 16)
+        for (int g0 = f0; g0 < f1; g0 += width) {
+          int rd[32] = {0}, at[16] = {0};
+          bool any = false;
+          ++id;
+          for (int p = g0; p < std::min(f1, g0 + width); ++p) {
+            const uint32_t s = corner_slot(recs[p], k);
+            if (width == 16 && (int)s < n_owned) {
+              ++at[s & 15];
+              any = true;
+            }
+            if (seen[s] != id) ++rd[s & (uint32_t)(width - 1)];
+            seen[s] = id;
+          }
+          int mr = 1, ma = 1;
+          for (int q = 0; q < width; ++q) mr = std::max(mr, rd[q]);
+          for (int q = 0; q < 16; ++q) ma = std::max(ma, at[q]);
+          if (width == 16) {
+            m.r16_sum += mr;
+            m.r16_groups += 1;
+            if (any) {
+              m.a16_sum += ma;
+              m.a16_groups += 1;
+            }
+          } else {
+            m.r32_sum += mr;
+            m.r32_groups += 1;
+          }
+        }
+  }
+  return m;
+}
 
 int build_tiling(int nv, int nf, const double* positions, const int32_t* tri,
                  const uint8_t* body_facets, int T, int shard_count, Tiling& out,
@@ -182,6 +301,7 @@ int build_tiling(int nv, int nf, const double* positions, const int32_t* tri,
   const size_t n_inst = (size_t)out.tile_facet_off[out.n_tiles];
   out.tile_facets.resize(n_inst);
   out.tile_facet_ext.resize(n_inst);
+  out.tile_facets_lean.resize(n_inst);
   std::vector<int32_t> cursor(out.tile_facet_off.begin(), out.tile_facet_off.end() - 1);
   // temporary: internal vertex ids per instance
   std::vector<int32_t> inst_v(3 * n_inst);
@@ -232,6 +352,7 @@ int build_tiling(int nv, int nf, const double* positions, const int32_t* tri,
   std::vector<int32_t> ext_tmp;
   std::vector<int32_t> order;
   std::vector<uint8_t> taken;
+  std::vector<int32_t> lean_tiles;  // tiles whose lanes are ordered
   for (int t = 0; t < out.n_tiles; ++t) {
     const int v_lo = t * R;
     const int v_hi = std::min(nv, v_lo + R);
@@ -274,7 +395,11 @@ int build_tiling(int nv, int nf, const double* positions, const int32_t* tri,
     // Bank-aware order: fill every group of 32 lanes greedily with facets whose three corner slots are free in
     // the group's three residue sets (mod 32 over the group, mod 16 over each half); what does not fit anywhere
     // goes to the end.  Same-vertex corners (same address) are the special case "same residue".
-    if (n >= 128 && order_mode != 0) {
+    const bool reorder = n >= 128 && order_mode != 0;
+    if (reorder) {
+      // (the walk order, for step 4: the lean k_energy instances' own order starts from it too)
+      std::copy(out.tile_facets.begin() + b, out.tile_facets.begin() + e, out.tile_facets_lean.begin() + b);
+      lean_tiles.push_back(t);
       tf_tmp.assign(out.tile_facets.begin() + b, out.tile_facets.begin() + e);
       ext_tmp.assign(out.tile_facet_ext.begin() + b, out.tile_facet_ext.begin() + e);
       order.clear();
@@ -334,6 +459,7 @@ int build_tiling(int nv, int nf, const double* positions, const int32_t* tri,
         out.tile_facet_ext[b + i] = ext_tmp[order[i]];
       }
     }
+    if (!reorder) std::copy(out.tile_facets.begin() + b, out.tile_facets.begin() + e, out.tile_facets_lean.begin() + b);
 
     // vertex -> corner CSR of this tile (counting sort keeps facet_local ascending)
     {
@@ -374,6 +500,40 @@ int build_tiling(int nv, int nf, const double* positions, const int32_t* tri,
     out.max_halo = std::max(out.max_halo, (int)halo_tmp.size());
     out.max_tile_facets = std::max(out.max_tile_facets, (int)(e - b));
   }
+
+  // ---- 4. the lean k_energy instances' lane order (tile_facets_lean) -------------
+  // Tiles are independent, so they are shared out over up to 16 threads (MS_TILE_THREADS, default: the CPUs of the
+  // machine); every tile's result is a function of that tile alone, whatever the thread count.
+  {
+    int n_thr = (int)std::thread::hardware_concurrency();
+    if (const char* e = getenv("MS_TILE_THREADS")) n_thr = atoi(e);
+    n_thr = std::max(1, std::min({n_thr, 16, (int)lean_tiles.size()}));
+    std::atomic<size_t> next{0};
+    auto work = [&]() {
+      LaneScratch scratch;
+      std::vector<TileFacet> walk;
+      for (size_t i = next.fetch_add(1); i < lean_tiles.size(); i = next.fetch_add(1)) {
+        const int t = lean_tiles[i];
+        const size_t b = (size_t)out.tile_facet_off[t], n = (size_t)out.tile_facet_off[t + 1] - b;
+        const int n_owned = std::min(nv, (t + 1) * R) - t * R;
+        const int n_slots = n_owned + (out.tile_halo_off[t + 1] - out.tile_halo_off[t]);
+        size_t S = std::max<size_t>(stride_mode > 1 ? (size_t)stride_mode : 7, (n + 63) / 64);
+        while (std::gcd(S, n) != 1) ++S;
+        walk.assign(out.tile_facets_lean.begin() + b, out.tile_facets_lean.begin() + b + n);
+        lean_lane_order(walk.data(), n, n_owned, n_slots, S, &out.tile_facets_lean[b], scratch);
+      }
+    };
+    std::vector<std::thread> pool;
+    try {
+      for (int i = 1; i < n_thr; ++i) pool.emplace_back(work);
+    } catch (const std::system_error&) {
+      // (no more threads to be had: the ones that started, and this one, share the tiles)
+    }
+    work();
+    for (auto& th : pool) th.join();
+  }
+  out.model_common = lane_order_model(out, out.tile_facets.data(), 0, out.n_tiles);
+  out.model_lean = lane_order_model(out, out.tile_facets_lean.data(), 0, out.n_tiles);
   return MS_OK;
 }
 

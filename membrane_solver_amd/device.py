@@ -1042,5 +1042,8 @@ class DeviceMesh:
     def tile_stats(self):
         v = [ctypes.c_int64(0) for _ in range(5)]
         self._chk(L.lib().ms_tile_stats(self._h, *[ctypes.byref(x) for x in v]), "ms_tile_stats")
+        lo = np.zeros(2, dtype=np.int64)
+        self._chk(L.lib().ms_lane_order_stats(self._h, lo.ctypes.data_as(L._I64)), "ms_lane_order_stats")
         return {"n_tiles": v[0].value, "facet_instances": v[1].value, "max_halo": v[2].value,
-                "lds_bytes_energy": v[3].value, "lds_bytes_gradient": v[4].value}
+                "lds_bytes_energy": v[3].value, "lds_bytes_gradient": v[4].value,
+                "lane_order": bool(lo[0]), "lane_halo": bool(lo[1])}
