@@ -983,6 +983,24 @@ int ms_pin_stats(ms_ctx *ctx, int64_t stats[4]);
  * does not cover (disk targets, a lone tilt module on the single field, consistent mass there) and MS_TSEARCH=0 keep
  * one launch per module, field and trial.  stats: {search passes launched, step sizes evaluated by them}. */
 int ms_tsearch_stats(ms_ctx *ctx, int64_t stats[2]);
+/* Diagnostic, changes nothing: which lane the tilt family takes on this context.  The size of a tile's vertex patch,
+ * cap = owned rows + largest halo, decides it: the fused tilt passes step aside above 150 KiB of LDS (the
+ * launch-per-module kernels run instead, same results), a workgroup may ask for 160 KiB at the most.
+ * stats[0..11] = {cap, max_ent (largest vertex -> corner list of a tile),
+ *   one field:  8-step-size search pass fits, gradient pass fits, energy-only pass fits (each 0 / 1),
+ *   two fields: the same three,
+ *   LDS bytes of the leaflet bending_tilt instance of the shape-gradient kernel in the context's current summation
+ *   mode and module mask, whether that instance fits (0: an evaluation that needs it -- a shape gradient with
+ *   bending_tilt_in/out in the mask -- returns MS_ERR_TILE_CAPACITY before it launches anything; everything else on the
+ *   context works), threads per workgroup, rows a tile owns}.
+ * The values come from the functions and limits the library's own planners read. */
+int ms_tilt_lane_stats(ms_ctx *ctx, int64_t stats[12]);
+/* Host-only (no GPU needed): the same for a mesh as ms_create would tile it (fixed_order != 0: the fixed-order
+ * summation mode of ms_set_deterministic; no constraint row) ... */
+int ms_plan_tilt_lanes(int nv, int nf, const double *positions, const int32_t *tri, int tile_vertices,
+                       int fixed_order, int64_t stats[12]);
+/* ... and for a patch of `cap` rows outright (threads = rows a tile owns = tile size): where the thresholds lie. */
+int ms_tilt_lane_plan(int threads, int cap, int max_ent, int fixed_order, int64_t stats[12]);
 /* Diagnostic of the same interpreter: on != 0 arms a device buffer to which every record run appends its duration
  * (s_memrealtime); a call also returns what has accumulated since the last one, per (kind, mode) pair: rows of
  * {kind, mode | instance << 16, count, total microseconds} (max_rows rows of 4 doubles; NULL: just arm / disarm). */

@@ -296,6 +296,9 @@ SIGNATURES = {
     "ms_enforce_pins": (ctypes.c_int, [_P]),
     "ms_pin_stats": (ctypes.c_int, [_P, _I64]),
     "ms_tsearch_stats": (ctypes.c_int, [_P, _I64]),
+    "ms_tilt_lane_stats": (ctypes.c_int, [_P, _I64]),
+    "ms_plan_tilt_lanes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _D, _I32, ctypes.c_int, ctypes.c_int, _I64]),
+    "ms_tilt_lane_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _I64]),
     "ms_exec_trace": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "ms_shard_peer_export": (ctypes.c_int, [_P, _P]),
     "ms_shard_peer_open": (ctypes.c_int, [_P, _P]),

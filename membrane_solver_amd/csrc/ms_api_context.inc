@@ -42,7 +42,7 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
   {
     const size_t le = energy_lds_bytes(t.T, c->cap, t.max_ent, true, true, true);
     const size_t lg = gradient_lds_bytes(t.T, c->cap, t.max_ent, true, true);
-    if (le > 160 * 1024 || lg > 160 * 1024) {
+    if (le > MS_LDS_CU || lg > MS_LDS_CU) {
       delete c;
       return fail(nullptr, MS_ERR_TILE_CAPACITY,
                   "ms_create: a vertex patch (tile + halo) exceeds the 160 KiB LDS of a CU; "

@@ -140,6 +140,49 @@ int ms_tsearch_stats(ms_ctx* c, int64_t stats[2]) {
   return MS_OK;
 }
 
+namespace {
+// (the functions and limits the planners decide by -- ms_internal.h -- not a second copy of them)
+void tilt_lane_fill(int T, int own, int cap, int max_ent, bool volrow, bool atomic, int64_t stats[12]) {
+  stats[0] = cap;
+  stats[1] = max_ent;
+  for (int nf = 1; nf <= 2; ++nf) {
+    int64_t* s = stats + 2 + 3 * (nf - 1);
+    s[0] = tsearch_fits(cap, nf, MS_MAX_TRIALS) ? 1 : 0;                          // tsearch_plan
+    s[1] = (s[0] && tgrad_fits(T, cap, max_ent, nf)) ? 1 : 0;                     // tgrad_plan
+    s[2] = tsearch_fits(cap, nf, 1) ? 1 : 0;                                      // tilt_energy_pass
+  }
+  const size_t leaf = leaflet_gradient_lds_bytes(T, cap, max_ent, volrow, atomic);
+  stats[8] = (int64_t)leaf;
+  stats[9] = leaf <= MS_LDS_CU ? 1 : 0;                                           // leaflet_gradient_admit
+  stats[10] = T;
+  stats[11] = own;
+}
+}  // namespace
+
+int ms_tilt_lane_stats(ms_ctx* c, int64_t stats[12]) {
+  if (!c || !stats) return MS_ERR_INVALID;
+  const Tiling& t = c->til;
+  tilt_lane_fill(t.T, t.own, c->cap, t.max_ent, (c->params.modules & MS_CON_VOLUME) != 0, !c->deterministic, stats);
+  return MS_OK;
+}
+
+int ms_plan_tilt_lanes(int nv, int nf, const double* positions, const int32_t* tri, int tile_vertices,
+                       int fixed_order, int64_t stats[12]) {
+  if (!stats) return fail(nullptr, MS_ERR_INVALID, "ms_plan_tilt_lanes: stats is NULL");
+  Tiling t;
+  std::string err;
+  int rc = build_tiling(nv, nf, positions, tri, nullptr, tile_vertices, 1, t, err);
+  if (rc != MS_OK) return fail(nullptr, rc, err);
+  tilt_lane_fill(t.T, t.own, t.own + t.max_halo, t.max_ent, false, fixed_order == 0, stats);
+  return MS_OK;
+}
+
+int ms_tilt_lane_plan(int threads, int cap, int max_ent, int fixed_order, int64_t stats[12]) {
+  if (!stats || threads < 1 || cap < 1 || max_ent < 0) return fail(nullptr, MS_ERR_INVALID, "ms_tilt_lane_plan: bad argument");
+  tilt_lane_fill(threads, threads, cap, max_ent, false, fixed_order == 0, stats);
+  return MS_OK;
+}
+
 int ms_exec_stats(ms_ctx* c, int64_t stats[4]) {
   if (!c || !stats) return MS_ERR_INVALID;
   stats[0] = c->exec_on ? 1 : 0;

@@ -601,7 +601,7 @@ int tilt_energy_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bo
     a.coef[j] = 0.0;
     a.partials[j] = j == 0 ? c->d_partials : nullptr;
   }
-  if (tsearch_lds_bytes(c->cap, nf, 1) > 150 * 1024) return MS_OK;
+  if (!tsearch_fits(c->cap, nf, 1)) return MS_OK;
   if (dry) {  // (the caller only asks whether the pass will cover this evaluation)
     *used = true;
     return MS_OK;
@@ -869,6 +869,21 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   return MS_OK;
 }
 
+// The leaflet bending_tilt instance of k_gradient stages 12 doubles per patch row where the instances ms_create admits
+// stage 8: on a patch that large the shape gradient of bending_tilt_in/out is refused here, by every entry point that
+// would run it and before its first launch (the runtime would refuse the launch itself).  Everything else on the
+// context -- energies, tilt gradients, the relaxations, other module sets -- does not use the instance and stays.
+int leaflet_gradient_admit(ms_ctx* c, uint32_t modules) {
+  if (!(modules & MS_LEAFLET_BT)) return MS_OK;
+  const size_t need =
+      leaflet_gradient_lds_bytes(c->til.T, c->cap, c->til.max_ent, (modules & MS_CON_VOLUME) != 0, !c->deterministic);
+  if (need <= MS_LDS_CU) return MS_OK;
+  return fail(c, MS_ERR_TILE_CAPACITY,
+              "bending_tilt_in/out shape gradient: a vertex patch (tile + halo) of " + std::to_string(c->cap) +
+                  " rows needs " + std::to_string(need) + " bytes of LDS, above the 160 KiB of a CU; "
+                  "use a smaller tile_vertices");
+}
+
 // dir_mode: 0 = plain gradient pass (+ <g,gC> partials); 1/2 = fused direction (GD / CG history)
 // may_skip_d: the caller reads D only after it has seen the direction scalars (ms_step) -- the pass may leave D unstored
 int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulate, int dir_mode = 0,
@@ -886,6 +901,7 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
     if (modules & MS_MOD_BENDING) return fail(c, MS_ERR_STATE, "bending together with bending_tilt_in/out is outside the device path");
     if (c->params.bending_grad_mode != MS_GRAD_ANALYTIC)
       return fail(c, MS_ERR_STATE, "bending_tilt_in/out: only bending_gradient_mode=analytic is on the device path");
+    if (int rc_a = leaflet_gradient_admit(c, modules)) return rc_a;
     for (int l = 2; l >= 1; --l)
       if (modules & c->tf[l].mod_bt) lbt_order[n_lbt++] = l;
     if (n_lbt == 2 && c->factors_leaflet == lbt_order[1]) std::swap(lbt_order[0], lbt_order[1]);
@@ -1225,7 +1241,8 @@ int queue_energy_and_gradient(ms_ctx* c, int stepper, bool use_history, bool ski
                           (stepper == MS_STEPPER_CG && c->precond) || c->pin_lane == MS_PIN_LANE_PROJECT || area_row_active(c);
   // K_C reads the reduced volume / body area (already reduced when the energy pass is skipped)
   const bool penalty = skip_energy || (mods & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) != 0;
-  int rc = MS_OK;
+  int rc = leaflet_gradient_admit(c, mods);  // (before the energy pass: a refusal launches nothing)
+  if (rc) return rc;
   if (!skip_energy) rc = phase_energy(c, mods, false, 0.0, false, false, true, /*reduce_now=*/penalty);
   if (rc) return rc;
   if (!constraint) {

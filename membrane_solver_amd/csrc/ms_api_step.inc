@@ -56,7 +56,9 @@ int ms_energy_and_raw_gradient(ms_ctx* c, double energies[4], double* grad) {
     return fail(c, MS_ERR_STATE, "ms_energy_and_raw_gradient: sharded contexts use the phase API");
   const uint32_t mods = c->params.modules;
   const bool penalty = (mods & (MS_MOD_VOLUME_PENALTY | MS_MOD_AREA_PENALTY)) != 0;  // K_C reads the reduced volume / body area
-  int rc = phase_energy(c, mods, false, 0.0, false, false, true, /*reduce_now=*/penalty);
+  int rc = leaflet_gradient_admit(c, mods);
+  if (rc) return rc;
+  rc = phase_energy(c, mods, false, 0.0, false, false, true, /*reduce_now=*/penalty);
   if (rc) return rc;
   c->carry.grad_valid = false;  // G receives the raw gradient: no fixed-row zeroing, no KKT projection
   rc = phase_gradient(c, mods, c->buf[MS_BUF_G], false, 0, /*reduce_now=*/false);

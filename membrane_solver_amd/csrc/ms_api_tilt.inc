@@ -187,7 +187,7 @@ bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs
   a->plain = 0;
   a->n_fields = nf;
   if (nf == 1) a->f[1] = a->f[0];
-  return tsearch_lds_bytes(c->cap, nf, MS_MAX_TRIALS) <= 150 * 1024;
+  return tsearch_fits(c->cap, nf, MS_MAX_TRIALS);
 }
 
 // The gradient pass of a relaxation (ms_tsearch.inc: k_tgrad) covers what the search pass covers
@@ -225,7 +225,7 @@ bool tgrad_plan(ms_ctx* c, TiltField** fl, int nf, TgradArgs* a, uint32_t* mask)
   a->x = sa.x;
   a->n_fields = nf;
   a->partials = c->d_partials;
-  return tgrad_lds_bytes(c->til.T, c->cap, c->til.max_ent, nf, false, true) <= 150 * 1024;
+  return tgrad_fits(c->til.T, c->cap, c->til.max_ent, nf);
 }
 
 // n step sizes of one ladder in one pass + one fold, queued; `second`: a pass queued BEHIND one whose results have not
@@ -355,7 +355,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
            (!q.has_dt || (f.dt_target && f.disk && f.dt_target_valid));
     }
     const size_t need = relax_fused_lds_bytes(c->cap, t.max_ent, t.max_tile_facets);
-    if (ok && need <= (size_t)150 * 1024) {
+    if (ok && need <= MS_LDS_TILT_PASS) {
       const hipError_t he = R.push(CK_RELAX_FUSED, 0, c->cap, t.max_ent, 1, 0, need, &a, sizeof(a), &a.m);
       if (he != hipSuccess) return fail_hip(c, he, "k_exec (fused relaxation)");
       rc = exec_flush(c);

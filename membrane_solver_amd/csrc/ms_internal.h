@@ -930,6 +930,24 @@ size_t tgrad_lds_bytes(int T, int cap, int max_ent, int n_fields, bool atomic, b
 // combine: a corner's module terms are added and accumulated per vertex by LDS atomics (default mode); false: staged and gathered module by module, the per-module launches' sums
 hipError_t launch_tgrad(const TgradArgs& a, int cap, int max_ent, bool combine, hipStream_t s);
 
+// The LDS limits the host's size checks read (ms_create, the planners of the tilt passes, ms_tilt_lane_stats), in one
+// place.  MS_LDS_CU: what one workgroup may ask for, the 160 KiB of a CU -- a launch above it is refused by the runtime.
+// MS_LDS_TILT_PASS: the fused tilt passes (k_tsearch, k_tgrad, the fused relaxation) step aside above 150 KiB and the
+// launch-per-module kernels, whose patches are smaller, run instead.
+constexpr size_t MS_LDS_CU = (size_t)160 * 1024;
+constexpr size_t MS_LDS_TILT_PASS = (size_t)150 * 1024;
+// (what tsearch_plan, tilt_energy_pass and tgrad_plan decide by)
+inline bool tsearch_fits(int cap, int n_fields, int n_trials) {
+  return tsearch_lds_bytes(cap, n_fields, n_trials) <= MS_LDS_TILT_PASS;
+}
+inline bool tgrad_fits(int T, int cap, int max_ent, int n_fields) {
+  return tgrad_lds_bytes(T, cap, max_ent, n_fields, false, true) <= MS_LDS_TILT_PASS;
+}
+// the leaflet bending_tilt instance of k_gradient (12 doubles per patch row, not 8): nothing at ms_create admits it
+inline size_t leaflet_gradient_lds_bytes(int T, int cap, int max_ent, bool volrow, bool atomic) {
+  return gradient_lds_bytes(T, cap, max_ent, true, volrow, atomic, true);
+}
+
 hipError_t launch_tvec2(const TvecArgs& a, const TvecArgs& b, int n_blocks, hipStream_t s);
 // One fold launch.  set[]: the trials of a multi-trial launch in TRIAL order (the last one = the ordinary outputs); a
 // plain fold has one set.

@@ -1018,6 +1018,38 @@ class DeviceMesh:
         self._chk(L.lib().ms_tsearch_stats(self._h, v.ctypes.data_as(L._I64)), "ms_tsearch_stats")
         return {"passes": int(v[0]), "step_sizes": int(v[1])}
 
+    @staticmethod
+    def _tilt_lanes(v) -> dict:
+        fits = lambda k: {"search": bool(v[k]), "gradient": bool(v[k + 1]), "energy_only": bool(v[k + 2])}  # noqa: E731
+        return {"cap": int(v[0]), "max_ent": int(v[1]), 1: fits(2), 2: fits(5), "leaflet_gradient_lds": int(v[8]),
+                "leaflet_gradient_fits": bool(v[9]), "threads": int(v[10]), "own": int(v[11])}
+
+    def tilt_lane_stats(self) -> dict:
+        """Which lane the tilt family takes on this context (include/membrane_hip.h, ms_tilt_lane_stats): the patch size
+        ``cap``, per number of fields (keys 1 and 2) whether the search, gradient and energy-only passes fit, and the
+        leaflet bending_tilt gradient instance's LDS bytes in the current summation mode."""
+        v = np.zeros(12, dtype=np.int64)
+        self._chk(L.lib().ms_tilt_lane_stats(self._h, v.ctypes.data_as(L._I64)), "ms_tilt_lane_stats")
+        return self._tilt_lanes(v)
+
+    @classmethod
+    def plan_tilt_lanes(cls, positions, tri_rows, tile_vertices: int = 0, fixed_order: bool = False) -> dict:
+        """The same for a mesh, on the host (ms_plan_tilt_lanes: no GPU needed)."""
+        pos = _f64(positions, name="positions")
+        tri = np.ascontiguousarray(tri_rows, dtype=np.int32)
+        v = np.zeros(12, dtype=np.int64)
+        L.check(L.lib().ms_plan_tilt_lanes(len(pos), len(tri), _pd(pos), tri.ctypes.data_as(L._I32), int(tile_vertices),
+                                           1 if fixed_order else 0, v.ctypes.data_as(L._I64)), None, "ms_plan_tilt_lanes")
+        return cls._tilt_lanes(v)
+
+    @classmethod
+    def tilt_lane_plan(cls, threads: int, cap: int, max_ent: int, fixed_order: bool = False) -> dict:
+        """... and for a patch of ``cap`` rows outright (ms_tilt_lane_plan): where the thresholds lie."""
+        v = np.zeros(12, dtype=np.int64)
+        L.check(L.lib().ms_tilt_lane_plan(int(threads), int(cap), int(max_ent), 1 if fixed_order else 0,
+                                          v.ctypes.data_as(L._I64)), None, "ms_tilt_lane_plan")
+        return cls._tilt_lanes(v)
+
     EXEC_KINDS = {1: "energy", 2: "gradient", 3: "tilt", 4: "bt", 5: "tsmooth", 6: "tvec", 7: "disk_target", 8: "reduce",
                   9: "direction", 10: "row_dot", 11: "axpy_masked", 12: "memset", 13: "relax", 14: "relax_fused", 15: "tsearch"}
 
