@@ -128,6 +128,16 @@ extern "C" {
  * volume row in the 2 x 2 solve of runtime/constraint_projection.py:101-129.  Needs ms_set_area_constraint(MS_AREA_BODY);
  * without it the bit does nothing.  ms_set_params keeps the bit out of the word the kernels read. */
 #define MS_CON_BODY_AREA 33554432u
+/* rim matching of the outer leaflet (modules/energy/rim_slope_match_out.py:352-629, modes pointwise_radial_v1 and
+ * ring_average_radial_v1): three tagged rings (rim, outer, optional disk) are ordered by angle from the positions of
+ * EVERY evaluation and rim and outer entries paired by index (unequal counts: the outer positions interpolated at the
+ * rim's arc-length parameters); phi = (h_out - h_rim) / (r_out - r_rim), E = 1/2 k sum w (t_out . r_hat - phi)^2 and,
+ * with a disk ring, + 1/2 k sum w (t_in . r_hat - (theta_disk - phi))^2.  Tilt gradients on the rim rows of both
+ * leaflets and on the disk rows of the inner one; a shape gradient along the normal on the rim and outer rows.  Rows,
+ * frame and strength come from ms_set_rim_match.  The out term is added into the outer leaflet's tilt-magnitude slot
+ * (MS_S_ETILT_OUT), the in term into the inner one's (MS_S_ETILT_IN), behind every pass that writes them: no reduction
+ * slot of its own.  Single context only; not together with a single-field tilt module. */
+#define MS_MOD_RIM_SLOPE_MATCH_OUT 67108864u
 #define MS_LEAFLET_IN 0
 #define MS_LEAFLET_OUT 1
 
@@ -578,6 +588,32 @@ int ms_get_thetab_contact_scalars(ms_ctx *ctx, double out[3]);
 int ms_update_thetab_value(ms_ctx *ctx, double *theta_b, int *changed);
 /* launches so far: {k_thetab_geom, k_thetab_apply} */
 int ms_thetab_contact_stats(ms_ctx *ctx, double stats[2]);
+/* rim_slope_match_out with a non-zero strength: the rim, outer and optional disk rows
+ * (modules/energy/rim_slope_match_out.py:160-169, each in vertex_ids order; :86-102 a disk group equal to the rim group is
+ * the caller's to drop), the frame (:110-114 center, :141-149 normal -- the fitted-plane branch :152-153, :422-425 stays
+ * host work: a normal is required; geometry/plane_ops.py:8-41 the in-plane axes) and the strength (:105-107).  rows are
+ * external rows, validated: in range, unique within a table and the three tables pairwise disjoint; at most
+ * MS_RIM_MATCH_MAX_ROWS per ring (one workgroup orders a ring in LDS), more is refused; n_rim and n_outer at least 1
+ * (:420-421 an empty ring is a host constant 0.0: no table), n_disk 0 for no disk term.  Every parameter must be finite
+ * and the normal non-zero (it is normalised here).  A refused call leaves the tables in use as they were.  Takes effect
+ * when MS_MOD_RIM_SLOPE_MATCH_OUT is in ms_params.modules.  Single context only. */
+#define MS_RIM_MATCH_MAX_ROWS MS_THETAB_MAX_ROWS
+typedef struct ms_rim_match_params {
+  double center[3];  /* rim_slope_match_center */
+  double normal[3];  /* rim_slope_match_normal */
+  double strength;   /* rim_slope_match_strength */
+} ms_rim_match_params;
+int ms_set_rim_match(ms_ctx *ctx, int n_rim, const int32_t *rim, int n_outer, const int32_t *outer, int n_disk,
+                     const int32_t *disk, const ms_rim_match_params *params);
+/* drops the tables (the module bit is refused again until the next ms_set_rim_match) */
+int ms_clear_rim_match(ms_ctx *ctx);
+/* the module's own energy at the last evaluation and its two terms {E, E_out, E_in}: E_out is also part of the outer
+ * leaflet's tilt-magnitude sum, E_in of the inner one's (both in energies[3]) */
+int ms_get_rim_match_energy(ms_ctx *ctx, double energy[3]);
+/* launches so far: {k_rsm_geom, k_rsm_apply}.  The reference evaluates the module once at x and once per trial put to
+ * the Armijo test (runtime/minimizer.py line search -> compute_energy_array); every such evaluation orders the rings,
+ * while the evaluations of a relaxation (positions frozen) share one geometry launch. */
+int ms_rim_match_stats(ms_ctx *ctx, double stats[2]);
 /* tilt_thetaB_boundary_in, the constraint t_in . d = theta_B on a ring of vertices
  * (modules/constraints/tilt_thetaB_boundary_in.py:162-236): the ring rows (:89-109, in vertex_ids order) and the frame
  * (:70-74 center, :77-86 normal -- the fitted-plane branch stays host work: a normal is required).  Per row

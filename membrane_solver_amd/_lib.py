@@ -39,8 +39,10 @@ MS_MOD_TILT_RIM_SOURCE_BILAYER = 8388608
 MS_MOD_TILT_SPLAY_TWIST_IN = 4194304
 MS_MOD_TILT_THETAB_CONTACT_IN = 16777216
 MS_CON_BODY_AREA = 33554432
+MS_MOD_RIM_SLOPE_MATCH_OUT = 67108864
 MS_AREA_NONE, MS_AREA_BODY, MS_AREA_GLOBAL = 0, 1, 2
 MS_THETAB_MAX_ROWS = 4096
+MS_RIM_MATCH_MAX_ROWS = MS_THETAB_MAX_ROWS
 MS_THETAB_WORK_SCALAR, MS_THETAB_WORK_FIELD_LINEAR = 0, 1
 MS_TILT_PROJECTION_PER_STEP, MS_TILT_PROJECTION_PER_PASS = 0, 1
 MS_LEAFLET_IN, MS_LEAFLET_OUT = 0, 1
@@ -100,6 +102,10 @@ class ms_rim_source_params(ctypes.Structure):
 class ms_thetab_contact_params(ctypes.Structure):
     _fields_ = [("center", ctypes.c_double * 3), ("normal", ctypes.c_double * 3), ("k", ctypes.c_double),
                 ("gamma", ctypes.c_double), ("work_mode", ctypes.c_int), ("penalty_mode", ctypes.c_int)]
+
+
+class ms_rim_match_params(ctypes.Structure):
+    _fields_ = [("center", ctypes.c_double * 3), ("normal", ctypes.c_double * 3), ("strength", ctypes.c_double)]
 
 
 class ms_thetab_boundary_params(ctypes.Structure):
@@ -218,6 +224,11 @@ SIGNATURES = {
     "ms_get_thetab_contact_scalars": (ctypes.c_int, [_P, _D]),
     "ms_update_thetab_value": (ctypes.c_int, [_P, _D, ctypes.POINTER(ctypes.c_int)]),
     "ms_thetab_contact_stats": (ctypes.c_int, [_P, _D]),
+    "ms_set_rim_match": (ctypes.c_int, [_P, ctypes.c_int, _I32, ctypes.c_int, _I32, ctypes.c_int, _I32,
+                                        ctypes.POINTER(ms_rim_match_params)]),
+    "ms_clear_rim_match": (ctypes.c_int, [_P]),
+    "ms_get_rim_match_energy": (ctypes.c_int, [_P, _D]),
+    "ms_rim_match_stats": (ctypes.c_int, [_P, _D]),
     "ms_set_thetab_boundary": (ctypes.c_int, [_P, ctypes.c_int, _I32, ctypes.POINTER(ms_thetab_boundary_params)]),
     "ms_set_tilt_projection": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
     "ms_thetab_boundary_enforce": (ctypes.c_int, [_P]),

@@ -27,6 +27,7 @@ std::string g_last_error;  // for failures that have no context yet
 #include "ms_api_phases.inc"  // pass launchers, folds, mailboxes, the energy / gradient / direction phases
 #include "ms_api_edge.inc"  // line_tension and edge_length_penalty: the edge / vertex tables, each term's two launches behind the energy and the gradient pass
 #include "ms_api_rim.inc"  // tilt_rim_source_in/out: the rim tables, the frame / coefficient / apply launches next to the disk-target pass
+#include "ms_api_rimmatch.inc"  // rim_slope_match_out: the three rings' rows and frame, the geometry / apply launches behind every other leaflet pass
 #include "ms_api_thetab.inc"  // tilt_thetaB_contact_in: the ring's rows and frame, theta_B, the geometry / apply launches behind the inner rim source, the scalar update
 #include "ms_api_couple.inc"  // tilt_coupling: its setter and getters, the pass behind the rim source's
 #include "ms_api_splay.inc"  // tilt_splay_twist_in: its setter and getters, the pass behind the inner leaflet's smoothness pass

@@ -199,6 +199,7 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
     f2.mod_rs = MS_MOD_TILT_RIM_SOURCE_OUT;
     f2.mod_cpl = f2.mod_cpl_slot = MS_MOD_TILT_COUPLING;
     f2.mod_rb = f2.mod_rb_slot = MS_MOD_TILT_RIM_SOURCE_BILAYER;
+    f2.mod_rsm = MS_MOD_RIM_SLOPE_MATCH_OUT;  // (the inner field's: ms_set_rim_match, with a disk ring)
   }
   if (const char* pe = getenv("MS_PAIR")) {
     c->pair_enable = atoi(pe) != 0;
@@ -276,7 +277,7 @@ void ms_destroy(ms_ctx* c) {
                   c->tf[1].disk, c->tf[1].diff, c->tf[2].disk, c->tf[2].diff, c->tf[0].va, c->tf[1].va, c->tf[2].va,
                   c->state, c->d_partials, c->d_scal, c->d_stage, c->d_bnd_rows, c->d_bnd_off,
                   c->d_halo_rows, c->d_scal_all, c->d_pins, c->edge[0].d_blob, c->edge[1].d_blob, c->tf[1].d_rim, c->tf[2].d_rim,
-                  c->d_cpl, c->d_st, c->d_rimb, c->d_tb, c->d_tbb,
+                  c->d_cpl, c->d_st, c->d_rimb, c->d_tb, c->d_tbb, c->d_rsm,
                   c->d_area_ga, c->d_area_part, c->d_area_res, c->d_area_cache, c->d_perim};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -441,6 +442,10 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
     return fail(c, MS_ERR_STATE, "the tilt_thetaB_contact_in module is not sharded (single GPU only)");
   if ((p->modules & MS_MOD_TILT_THETAB_CONTACT_IN) && (p->modules & MS_TILT_MODS))
     return fail(c, MS_ERR_STATE, "tilt_thetaB_contact_in together with a single-field tilt module is outside the device path");
+  if ((p->modules & MS_MOD_RIM_SLOPE_MATCH_OUT) && c->shard_count != 1)
+    return fail(c, MS_ERR_STATE, "the rim_slope_match_out module is not sharded (single GPU only)");
+  if ((p->modules & MS_MOD_RIM_SLOPE_MATCH_OUT) && (p->modules & MS_TILT_MODS))
+    return fail(c, MS_ERR_STATE, "rim_slope_match_out together with a single-field tilt module is outside the device path");
   if ((p->modules & MS_MOD_TILT_COUPLING) && c->shard_count != 1)
     return fail(c, MS_ERR_STATE, "the tilt_coupling module is not sharded (single GPU only)");
   if ((p->modules & MS_MOD_TILT_COUPLING) && (p->modules & MS_TILT_MODS))

@@ -140,11 +140,15 @@ struct ms_ctx {
     // tilt_thetaB_contact_in reads the inner leaflet's field and rides in its tilt-magnitude slot behind the rim source;
     // its tables are the context's (ms_ctx::tb)
     uint32_t mod_tb = 0;
-    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl | mod_st | mod_rb | mod_tb; }
+    // rim_slope_match_out reads the outer leaflet's field and, with a disk ring, the inner one's (ms_set_rim_match sets
+    // the inner field's bit only then); each term rides in its leaflet's tilt-magnitude slot behind every other pass;
+    // its tables are the context's (ms_ctx::rsm)
+    uint32_t mod_rsm = 0;
+    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl | mod_st | mod_rb | mod_tb | mod_rsm; }
     // every module bit whose sums land in this field's tilt-magnitude slot (s_etilt)
     uint32_t etilt_mods() const { return mod_tilt | mod_rs | mod_cpl_slot | mod_rb_slot; }
     // ... and the theta_B contact term on top of them: what the readers of the slot ask
-    uint32_t etilt_all() const { return etilt_mods() | mod_tb; }
+    uint32_t etilt_all() const { return etilt_mods() | mod_tb | mod_rsm; }
     // every module bit whose sums land in this field's smoothness slot (s_ets)
     uint32_t ets_mods() const { return mod_smooth | mod_st; }
     bool any_free = true;     // some row of this field is not clamped (kept current by the flag setters)
@@ -175,6 +179,14 @@ struct ms_ctx {
   bool tb_relax = false;        // a relaxation is running: x is frozen ...
   bool tb_geom_valid = false;   // ... and the table holds its ring (the first evaluation's geometry pass)
   long tb_launches[2] = {0, 0};  // k_thetab_geom, k_thetab_apply
+  // rim_slope_match_out (ms_set_rim_match): one allocation holds the three row tables, the tables k_rsm_geom writes, the
+  // record and the module's energy.  While a relaxation runs (tb_relax: x is frozen) the first evaluation's geometry
+  // pass serves the others
+  void* d_rsm = nullptr;
+  RsmArgs rsm{};
+  bool rsm_set = false;
+  bool rsm_geom_valid = false;
+  long rsm_launches[2] = {0, 0};  // k_rsm_geom, k_rsm_apply
   // tilt_thetaB_boundary_in (ms_set_thetab_boundary): one allocation holds the per-row table (d, N_v, keep), the rows
   // and the row -> facet CSR; theta_B is tb_theta.  The constraint acts on the inner leaflet's field only.
   void* d_tbb = nullptr;

@@ -44,6 +44,13 @@ int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gr
 enum { TB_CELL_AUTO = -1, TB_CELL_ADD = 0, TB_CELL_DEFINE = 1 };
 int thetab_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const double* tilts, double* tilt_grad,
                 int cell = TB_CELL_AUTO);
+// rim_slope_match_out: the rings ordered on x (+ alpha d) and both terms of `t_in` / `t_out` (the leaflets' rows belonging
+// to those positions) into cell 0 of the leaflets' tilt-magnitude partials, behind EVERY other pass that writes those
+// slots (ms_api_rimmatch.inc).  tilt_gradients: the rows added into both fields' grad; g_out: the shape gradient's rows
+// added there, or nullptr; cell: RSM_CELL_* (AUTO: defined where no module in front of it writes the slot)
+enum { RSM_CELL_AUTO = -1, RSM_CELL_ADD = 0, RSM_CELL_LEAVE = 2 };
+int rim_match_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool trial_tilts, bool tilt_gradients,
+                   double* g_out, int cell = RSM_CELL_AUTO);
 // tilt_thetaB_boundary_in (ms_api_thetab_bnd.inc): the ring's table on x (nullptr: the context's positions) or on
 // x + alpha d, kept while `frozen` holds; and k_tbb_apply<mode> on it (0 enforce in place, 1 P(enforce(t)) into out,
 // 2 project the gradient `field`).  Both return at once when no table with a row is set.
@@ -197,13 +204,13 @@ constexpr uint32_t MS_LEAFLET_DT = MS_MOD_TILT_DISK_TARGET_IN | MS_MOD_TILT_DISK
 constexpr uint32_t MS_LEAFLET_RS = MS_MOD_TILT_RIM_SOURCE_IN | MS_MOD_TILT_RIM_SOURCE_OUT;
 // (tilt_rim_source_bilayer is NOT part of MS_LEAFLET_RS: that mask selects the per-field tables and passes; the lanes
 // that decline a rim source name both)
-constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_THETAB_CONTACT_IN;
+constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_THETAB_CONTACT_IN | MS_MOD_RIM_SLOPE_MATCH_OUT;
 constexpr uint32_t MS_ANY_TILT_MODS = MS_TILT_MODS | MS_LEAFLET_MODS;
 // the edge modules: energy added into the MS_S_ESURF partials behind the energy pass, gradient into G behind K_C; they
 // share one lane of the step (one trial per launch, every Armijo decision the host's, the separate direction pass)
 constexpr uint32_t MS_EDGE_MODS = MS_MOD_LINE_TENSION | MS_MOD_EDGE_LENGTH_PENALTY;
 // modules whose shape gradient is added into g by a pass after K_C (so the direction cannot be fused)
-constexpr uint32_t MS_TILT_SHAPE_MODS = MS_MOD_TILT | MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_MOD_TILT_COUPLING;
+constexpr uint32_t MS_TILT_SHAPE_MODS = MS_MOD_TILT | MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_MOD_TILT_COUPLING | MS_MOD_RIM_SLOPE_MATCH_OUT;
 using TiltField = ms_ctx::TiltField;
 using RoundPlan = ms_ctx::RoundPlanT;
 
@@ -556,6 +563,7 @@ int tilt_energy_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bo
                      bool skip_bt = false) {
   *used = false;
   if (!c->tenergy_enable) return MS_OK;
+  if (modules & MS_MOD_RIM_SLOPE_MATCH_OUT) return MS_OK;  // (the rim matching term keeps the launch-per-module evaluation)
   TsearchArgs a;
   int nf = 0;
   for (int l = 0; l < 3; ++l) {
@@ -813,7 +821,7 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   for (int l = 1; l <= 2 && (modules & MS_LEAFLET_MODS); ++l) {  // leaflet fields, same protocol
     TiltField& f = c->tf[l];
     // (the coupling alone is reason enough: its trial energy is taken with BOTH leaflets projected onto the trial surface)
-    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb | f.mod_tb))) continue;
+    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb | f.mod_tb | f.mod_rsm))) continue;
     int rc = MS_OK;
     const double* tilts = f.tilts;
     if (use_dir) {
@@ -852,6 +860,10 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   // tilt_coupling: behind the rim sources of the outer leaflet (the order of the adds into a cell is fixed)
   if (modules & MS_MOD_TILT_COUPLING)
     if (int rc_c = couple_pass(c, modules, use_dir, alpha, false, false, /*trial_tilts=*/use_dir)) return rc_c;
+  // rim_slope_match_out: behind everything that writes the two leaflets' tilt-magnitude cells; the rings are ordered on
+  // THIS evaluation's positions (the reference takes the module once at x and once per trial put to the Armijo test)
+  if (modules & MS_MOD_RIM_SLOPE_MATCH_OUT)
+    if (int rc_m = rim_match_pass(c, modules, use_dir, alpha, /*trial_tilts=*/use_dir, false, nullptr)) return rc_m;
   // tilt_splay_twist_in: behind the inner leaflet's smoothness pass (k_tsmooth<0> above, or the one launch of
   // tilt_energy_pass), at x and at every trial with the tilts projected onto it
   if (modules & c->tf[1].mod_st)
@@ -1028,6 +1040,13 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
   if ((modules & MS_MOD_TILT_COUPLING) && g_out) {
     int rc = couple_pass(c, modules, false, 0.0, true, false, false,
                          (modules & c->tf[2].mod_tilt) ? CPL_CELL_ADD : CPL_CELL_LEAVE, g_out);
+    if (rc) return rc;
+    added_after = true;
+  }
+  // rim_slope_match_out: its shape gradient behind the coupling's; each of its energies goes into its leaflet's cells once
+  // more when k_tilt<1> above has rewritten them (behind every re-add above), and nowhere when nobody has
+  if ((modules & MS_MOD_RIM_SLOPE_MATCH_OUT) && g_out) {
+    int rc = rim_match_pass(c, modules, false, 0.0, false, false, g_out, RSM_CELL_ADD);
     if (rc) return rc;
     added_after = true;
   }

@@ -103,6 +103,13 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
     if (rc) return rc;
     mask |= 1u << c->tf[2].s_etilt;
   }
+  if (mods & MS_MOD_RIM_SLOPE_MATCH_OUT) {
+    // behind every pass above: it adds into both tilt gradients and into cell 0 of both leaflets' magnitude partials
+    rc = rim_match_pass(c, mods, false, 0.0, trial, gradient, nullptr);
+    if (rc) return rc;
+    mask |= 1u << c->tf[2].s_etilt;
+    if (mods & c->tf[1].mod_rsm) mask |= 1u << c->tf[1].s_etilt;
+  }
   return mask ? reduce_slots(c, mask) : MS_OK;
 }
 double tilt_energy_from(const ms_ctx* c, const double* hs) {
@@ -137,6 +144,7 @@ bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs
     // (the disk target, the rim sources, the coupling and the splay / twist term keep their own passes)
     if (!single && (mods & (f.mod_rb | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st))) return false;
     if (!single && (mods & f.mod_tb)) return false;  // (and so does the theta_B contact term)
+    if (mods & MS_MOD_RIM_SLOPE_MATCH_OUT) return false;  // (... and the rim matching term, whichever fields are relaxed)
     o.tilts = f.tilts;
     o.src = along_dir ? f.dir : f.grad;
     o.bt_vert = nullptr;
@@ -351,7 +359,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
       q.has_ts = (mods & f.mod_smooth) ? 1 : 0;
       q.has_dt = (mods & f.mod_dt) ? 1 : 0;
       q.fixed_bit = f.fixed_bit;
-      ok = ok && !(mods & (f.mod_tb | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
+      ok = ok && !(mods & (f.mod_tb | f.mod_rsm | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
            (!q.has_dt || (f.dt_target && f.disk && f.dt_target_valid));
     }
     const size_t need = relax_fused_lds_bytes(c->cap, t.max_ent, t.max_tile_facets);
@@ -647,7 +655,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
       c->relax_va_valid = false;
       for (int l = 0; l < 3; ++l) c->tf[l].dt_target_valid = c->tf[l].rs_coef_valid = false;
       c->rb_coef_valid = false;
-      c->tb_relax = c->tb_geom_valid = false;
+      c->tb_relax = c->tb_geom_valid = c->rsm_geom_valid = false;
       c->tbb_geom_valid = false;
     }
   } va_scope{c};
@@ -655,7 +663,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
   // tilt_thetaB_contact_in: x is frozen from here on whatever the preconditioner -- the ring is ordered by the first
   // evaluation of this relaxation and the others only apply its table
   c->tb_relax = true;
-  c->tb_geom_valid = false;
+  c->tb_geom_valid = c->rsm_geom_valid = false;
   for (int k = 0; k < nf && c->relax_va_valid; ++k) {
     // prime the frozen-surface caches of the disk target (radius, theta(r) r_hat) before the loop: every evaluation of
     // the relaxation -- and the device program's captured lists -- then only take differences
@@ -801,7 +809,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     return search(along_dir, sign, E0, E_acc, accepted);
   };
   // (the rim source's, the coupling's, the splay / twist term's and the theta_B contact term's kernels are not recorded)
-  if (!tbb_on && c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_THETAB_CONTACT_IN))) {
+  if (!tbb_on && c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_THETAB_CONTACT_IN | MS_MOD_RIM_SLOPE_MATCH_OUT))) {
     // one-tile context: the whole solve below as ONE launch (ms_internal.h: ExecRelaxHead)
     bool used = false;
     rc = relax_program(c, rp, fl, nf, norm_mask, &iters, &evals, &used);

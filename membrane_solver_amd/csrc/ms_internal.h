@@ -496,6 +496,61 @@ struct ThetabArgs {
 };
 hipError_t launch_thetab_geom(const ThetabArgs& a, hipStream_t s);
 hipError_t launch_thetab_apply(const ThetabArgs& a, hipStream_t s);
+// rim_slope_match_out (ms_rimmatch.hip): the rim, outer and optional disk rings ordered by angle on x (+ alpha d) by ONE
+// workgroup (k_rsm_geom: the ordered rows, the rim table r_hat / w / phi / 1/dr / valid, the pairing idx0 / w0 / w1 with
+// the outer ring -- identity or arc-length interpolation --, the first rim entry of every outer row, the disk table
+// r_hat_d / w_d and the record {n_valid, contributes, local_disk, sum w_d}), then k_rsm_apply on those tables: both
+// energies into cell 0 of the leaflets' tilt-magnitude partials (added or defined), the rows of the two tilt gradients
+// and of the shape gradient on request.  Rows are the library's (til.iperm applied), in the setter's order (ties of the
+// angular order are broken by that order); the three tables are pairwise disjoint.
+struct RsmArgs {
+  const double* x;
+  const double* d;        // trial direction or nullptr, alpha: exactly what EnergyArgs hands k_energy
+  double alpha;
+  const uint8_t* vflags;  // (a fixed row does not move in a trial)
+  int n_rim, n_out, n_disk;  // ring rows, each 0 .. MS_RIM_MATCH_MAX_ROWS (n_rim, n_out >= 1; n_disk == 0: no disk term)
+  const int32_t* rows_rim;
+  const int32_t* rows_out;
+  const int32_t* rows_disk;
+  double center[3];       // rim_slope_match_center
+  double normal[3];       // unit normal of the rings' plane
+  double u[3], v[3];      // in-plane axes (geometry/plane_ops.py:21-41)
+  double k;               // rim_slope_match_strength
+  // k_rsm_geom writes, k_rsm_apply reads; indexed by the position in the ring's angular order
+  int32_t* orow_rim;      // [n_rim] the rim's rows in angular order
+  int32_t* orow_out;      // [n_out]
+  int32_t* orow_disk;     // [n_disk]
+  double* rhat;           // [3 n_rim] in-plane unit vector from the center, 0 where |r| <= 1e-12
+  double* w;              // [n_rim] arc-length weight on the ordered rim, 0 where the entry is not valid
+  double* phi;            // [n_rim] (h_out - h_rim) / (r_out - r_rim), 0 where not valid
+  double* inv_dr;         // [n_rim] 1 / dr, 0 where not valid
+  int32_t* valid;         // [n_rim]
+  int32_t* idx0;          // [n_rim] the outer entry below the rim entry's arc-length parameter (idx1 = idx0 + 1 mod n_out) ...
+  double* w0;             // [n_rim] ... and the two interpolation weights; identity pairing: idx0 = i, w0 = 1, w1 = 0
+  double* w1;
+  int32_t* first0;        // [n_out + 1] first rim entry with idx0 >= j: idx0 is monotone, so the entries of an outer row are a range
+  double* s_out;          // [n_out] arc-length knots of the ordered outer ring (interpolation only)
+  double* rhat_d;         // [3 n_disk] the disk rows' r_hat, 0 where |r| <= 1e-12
+  double* w_d;            // [n_disk] arc-length weight on the ordered disk ring, 0 where |r| <= 1e-12
+  double* dif;            // [n_rim] k_rsm_apply's scratch: diff, ...
+  double* dif_in;         // [n_rim] ... diff_in of the launch
+  double* rec;            // {n_valid, 1 when the rings contribute / 0 for the early returns, local_disk, sum w_d} and
+                          // k_rsm_apply's {E_out, E_in}
+  const double* t_in;     // inner leaflet (read only when n_disk > 0)
+  const double* t_out;    // outer leaflet
+  double* tg_in;          // the rows' gradients added here, or nullptr
+  double* tg_out;
+  double* g;              // the shape gradient's rows added here, or nullptr (grad_arr=None of the reference)
+  double* partials;       // E_out -> [slot_out * n_tiles + tile0], E_in -> [slot_in * n_tiles + tile0]
+  int n_tiles, tile0, n_cells;  // n_cells: tiles of the context (define: the cells past the first are zeroed)
+  int slot_out, slot_in;
+  int define_out, define_in;  // store (no pass before this one wrote the slot) instead of add; -1: leave the slot alone
+  double* wg_sums;        // [1] the workgroup's sum ...
+  uint32_t* done;         // ... counted here (publish_wg_sum, one workgroup) ...
+  double* energy;         // ... into the module's own energy (ms_get_rim_match_energy)
+};
+hipError_t launch_rsm_geom(const RsmArgs& a, hipStream_t s);
+hipError_t launch_rsm_apply(const RsmArgs& a, hipStream_t s);
 // tilt_thetaB_boundary_in (ms_thetab_bnd.hip): the constraint t_in . d = theta_B on a ring of rows.  k_tbb_geom writes
 // the per-row table (d, the unit vertex normal N_v, keep) from x (+ alpha d), or from a trial buffer handed in as x;
 // k_tbb_apply<0/1/2> enforces in place, writes P(enforce(t)) into another buffer, or projects a gradient.  Rows are

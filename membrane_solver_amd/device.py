@@ -496,6 +496,39 @@ class DeviceMesh:
         self._chk(L.lib().ms_thetab_contact_stats(self._h, _pd(v)), "ms_thetab_contact_stats")
         return {"geom_launches": int(v[0]), "apply_launches": int(v[1])}
 
+    def set_rim_match(self, rim=None, outer=None, disk=None, *, center=(0.0, 0.0, 0.0), normal=(0.0, 0.0, 1.0),
+                      strength: float = 0.0):
+        """rim_slope_match_out: the rim, outer and optional disk rows (external, each in vertex_ids order), frame and
+        strength (ms_set_rim_match); no rim rows clear the tables (ms_clear_rim_match)."""
+        if self.shard_count != 1:  # (the library refuses it as well)
+            raise L.MembraneHipError("the rim_slope_match_out module is not sharded (single GPU only)")
+        if rim is None:
+            self._chk(L.lib().ms_clear_rim_match(self._h), "ms_clear_rim_match")
+            return
+        tabs = [np.ascontiguousarray(np.asarray([] if t is None else t, dtype=np.int32).reshape(-1))
+                for t in (rim, outer, disk)]
+        ptr = [(t if len(t) else np.zeros(1, np.int32)).ctypes.data_as(L._I32) for t in tabs]
+        p = L.ms_rim_match_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)),
+                                  float(strength))
+        self._chk(L.lib().ms_set_rim_match(self._h, len(tabs[0]), ptr[0], len(tabs[1]), ptr[1], len(tabs[2]), ptr[2],
+                                           ctypes.byref(p)), "ms_set_rim_match")
+
+    def rim_match_energy(self) -> float:
+        """The rim matching term's own energy as the last evaluation summed it (ms_get_rim_match_energy)."""
+        return self.rim_match_energies()[0]
+
+    def rim_match_energies(self):
+        """(E, E_out, E_in) of the last evaluation: the module's energy and its outer- and inner-leaflet terms."""
+        v = np.zeros(3)
+        self._chk(L.lib().ms_get_rim_match_energy(self._h, _pd(v)), "ms_get_rim_match_energy")
+        return float(v[0]), float(v[1]), float(v[2])
+
+    def rim_match_stats(self):
+        """Launch counts of the rim matching term's two kernels (ms_rim_match_stats)."""
+        v = np.zeros(2)
+        self._chk(L.lib().ms_rim_match_stats(self._h, _pd(v)), "ms_rim_match_stats")
+        return {"geom_launches": int(v[0]), "apply_launches": int(v[1])}
+
     def set_thetab_boundary(self, rows=None, *, center=(0.0, 0.0, 0.0), normal=(0.0, 0.0, 1.0)):
         """tilt_thetaB_boundary_in: the constraint's ring (external rows, in vertex_ids order) and frame
         (ms_set_thetab_boundary); no rows clear the table.  theta_B is set_thetab_value's."""

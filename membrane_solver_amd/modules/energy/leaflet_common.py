@@ -719,6 +719,298 @@ def _set_param(global_params, key, value) -> None:
         global_params[key] = value
 
 
+# --- rim_slope_match_out ----------------------------------------------------------------------------------------------
+_RIM_MATCH_MODES = ("pointwise_radial_v1", "ring_average_radial_v1", "shared_rim_staggered_v1",
+                    "physical_edge_staggered_v1")
+_RIM_MATCH_WARNED = False
+
+
+def rim_match_group(param_resolver, global_params, key: str):
+    """A group name of rim_slope_match_out (:78-83): stripped, None when absent or empty."""
+    raw = _get(param_resolver, global_params, key)
+    if raw is None:
+        return None
+    group = str(raw).strip()
+    return group if group else None
+
+
+def rim_match_sanitize_disk_group(rim_group, disk_group):
+    """_sanitize_disk_group (:86-102): a disk group equal to the rim group is dropped, with one warning per process."""
+    if rim_group is None or disk_group is None or disk_group != rim_group:
+        return disk_group
+    global _RIM_MATCH_WARNED
+    if not _RIM_MATCH_WARNED:
+        import logging
+
+        logging.getLogger("membrane_solver").warning(
+            "rim_slope_match_disk_group matches rim_slope_match_group (%s); skipping disk-side coupling to avoid "
+            "degenerate constraints.", rim_group)
+        _RIM_MATCH_WARNED = True
+    return None
+
+
+def rim_match_mode(param_resolver, global_params) -> str:
+    """rim_slope_match_mode (:117-131): default pointwise_radial_v1, an unknown mode raises ValueError."""
+    raw = _get(param_resolver, global_params, "rim_slope_match_mode")
+    mode = "pointwise_radial_v1" if raw is None else str(raw).strip().lower()
+    if mode not in _RIM_MATCH_MODES:
+        raise ValueError("rim_slope_match_mode must be 'pointwise_radial_v1' or 'ring_average_radial_v1' or "
+                         "'shared_rim_staggered_v1' or 'physical_edge_staggered_v1'.")
+    return mode
+
+
+def rim_match_strength(param_resolver, global_params) -> float:
+    return float(_get(param_resolver, global_params, "rim_slope_match_strength") or 0.0)
+
+
+def rim_match_rows(mesh, group: str) -> np.ndarray:
+    """Rows whose options carry ``rim_slope_match_group == group``, in vertex_ids order (:160-169): vertex options of a
+    reference Mesh, or ``vertex_options`` of an array mesh."""
+    verts = getattr(mesh, "vertices", None)
+    rows = []
+    if isinstance(verts, dict):
+        for vid in mesh.vertex_ids:
+            if (getattr(verts[int(vid)], "options", None) or {}).get("rim_slope_match_group") == group:
+                row = mesh.vertex_index_to_row.get(int(vid))
+                if row is not None:
+                    rows.append(int(row))
+    else:
+        vopts = getattr(mesh, "vertex_options", None) or {}
+        row_of = mesh.vertex_index_to_row
+        for vid in mesh.vertex_ids:
+            row = row_of.get(int(vid))
+            if row is not None and (vopts.get(int(row)) or {}).get("rim_slope_match_group") == group:
+                rows.append(int(row))
+    return np.asarray(rows, dtype=np.int64)
+
+
+def rim_match_params(mesh, param_resolver, global_params):
+    """Resolved parameters of rim_slope_match_out as kwargs of DeviceMesh.set_rim_match, or None where the reference
+    returns 0.0 before it looks at a position: strength 0 (:380-382), no rim or outer group (:377-378), an empty rim or
+    outer ring (:420-421).  The other early returns depend on the positions: the device takes them.  Refused, each with
+    its own text: the staggered modes, a missing or zero ``rim_slope_match_normal`` (the SVD plane fit, :422-423), a ring
+    above the device's size and non-finite parameters."""
+    mode = rim_match_mode(param_resolver, global_params)
+    k = rim_match_strength(param_resolver, global_params)
+    if k == 0.0:
+        return None
+    if not np.isfinite(k):
+        raise L.MembraneHipError("rim_slope_match_out: rim_slope_match_strength must be finite")
+    if mode in ("shared_rim_staggered_v1", "physical_edge_staggered_v1"):
+        raise L.MembraneHipError(f"rim_slope_match_out with rim_slope_match_mode={mode} and a non-zero "
+                                 "rim_slope_match_strength (vertex normals and local interface shells) is outside the "
+                                 "HIP hot path")
+    group = rim_match_group(param_resolver, global_params, "rim_slope_match_group")
+    outer_group = rim_match_group(param_resolver, global_params, "rim_slope_match_outer_group")
+    disk_group = rim_match_sanitize_disk_group(group, rim_match_group(param_resolver, global_params,
+                                                                      "rim_slope_match_disk_group"))
+    if group is None or outer_group is None:
+        return None
+    rim, outer = rim_match_rows(mesh, group), rim_match_rows(mesh, outer_group)
+    if rim.size == 0 or outer.size == 0:
+        return None
+    disk = rim_match_rows(mesh, disk_group) if disk_group is not None else np.zeros(0, np.int64)
+    center = _get(param_resolver, global_params, "rim_slope_match_center")
+    center = np.asarray([0.0, 0.0, 0.0] if center is None else center, dtype=float).reshape(3)
+    raw = _get(param_resolver, global_params, "rim_slope_match_normal")
+    normal = None if raw is None else np.asarray(raw, dtype=float).reshape(3)
+    if not np.all(np.isfinite(center)) or (normal is not None and not np.all(np.isfinite(normal))):
+        raise L.MembraneHipError("rim_slope_match_out: rim_slope_match_center and rim_slope_match_normal must be finite")
+    if normal is None or float(np.linalg.norm(normal)) < 1e-15:
+        raise L.MembraneHipError("rim_slope_match_out with a non-zero rim_slope_match_strength and without a non-zero "
+                                 "rim_slope_match_normal (SVD plane fit of the rim rows) is outside the HIP hot path")
+    for name, rows in (("a rim", rim), ("an outer", outer), ("a disk", disk)):
+        if rows.size > L.MS_RIM_MATCH_MAX_ROWS:
+            raise L.MembraneHipError(f"rim_slope_match_out: {name} ring of {rows.size} rows is above the "
+                                     f"{L.MS_RIM_MATCH_MAX_ROWS} the device orders")
+    return {"rim": rim.astype(np.int32), "outer": outer.astype(np.int32), "disk": disk.astype(np.int32),
+            "center": tuple(float(v) for v in center), "normal": tuple(float(v) for v in normal), "strength": k}
+
+
+def rim_match_key(prm):
+    """Hashable identity of rim_match_params' result (the Minimizer re-uploads when it changes)."""
+    if prm is None:
+        return None
+    return (prm["rim"].tobytes(), prm["outer"].tobytes(), prm["disk"].tobytes(), prm["center"], prm["normal"],
+            prm["strength"])
+
+
+def evaluate_rim_match(mesh, global_params, param_resolver, *, positions, tilts_in, tilts_out, grad_arr,
+                       tilt_in_grad_arr, tilt_out_grad_arr) -> float:
+    """rim_slope_match_out on caller arrays (H2D/D2H per call: the parity seam, not the hot loop): energy; shape gradient
+    ADDED into ``grad_arr``, tilt gradients ADDED into ``tilt_in_grad_arr`` / ``tilt_out_grad_arr`` (each optional).
+    0.0 with nothing written exactly where the reference returns early."""
+    prm = rim_match_params(mesh, param_resolver, global_params)
+    if prm is None:
+        return 0.0
+    nv = len(mesh.vertex_ids)
+    fields = {}
+    for lf, t in (("in", tilts_in), ("out", tilts_out)):
+        if t is None:
+            t = mesh.tilts_in_view() if lf == "in" else mesh.tilts_out_view()
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        if t.shape != (nv, 3):
+            raise ValueError(f"tilts_{lf} must have shape (N_vertices, 3)")
+        fields[lf] = t
+    for name, arr in (("tilt_in_grad_arr", tilt_in_grad_arr), ("tilt_out_grad_arr", tilt_out_grad_arr)):
+        if arr is not None and np.shape(arr) != (nv, 3):
+            raise ValueError(f"{name} must have shape (N_vertices, 3)")
+    mir = mirror_for(mesh)
+    dm = mir.sync(positions=None if positions is mesh.positions_view() else positions)
+    for lf in ("in", "out"):
+        dm.set_leaflet_tilts(lf, fields[lf], tilt_modulus=0.0, smoothness=0.0)
+    mir._leaflet_keys = {}  # foreign arrays were uploaded
+    dm.set_rim_match(**prm)
+    dm.set_params(modules=L.MS_MOD_RIM_SLOPE_MATCH_OUT)
+    if grad_arr is not None:
+        e, g = dm.energy_and_gradient(want_grad=True, raw=True)
+        grad_arr += g
+        E = float(e[3])
+    else:
+        E = float(dm.energy()[3])
+    if tilt_in_grad_arr is not None or tilt_out_grad_arr is not None:
+        _e, gi, go = dm.leaflet_tilt_energy_and_gradient(want_gradient=True)
+        if tilt_in_grad_arr is not None:
+            tilt_in_grad_arr += gi
+        if tilt_out_grad_arr is not None:
+            tilt_out_grad_arr += go
+    return E
+
+
+def rim_match_numpy(positions, tilts_in, tilts_out, *, rim, outer, disk, center, normal, strength, shape_gradient=True):
+    """The module's tables and sums restated in NumPy, the way k_rsm_geom / k_rsm_apply form them (rank-by-counting for
+    the order, a binary search for the pairing, the first rim entry of every outer row, a row's terms added in np.add.at's
+    order) -> dict with E, E_out, E_in, grad, tilt_in_grad, tilt_out_grad, the ordered rows and the record.  Host-side
+    check of the device's scheme against the fixtures; not on any hot path."""
+    x = np.asarray(positions, dtype=np.float64)
+    c = np.asarray(center, dtype=np.float64).reshape(3)
+    n = np.asarray(normal, dtype=np.float64).reshape(3)
+    n = n / np.linalg.norm(n)
+    trial = np.array([0.0, 1.0, 0.0]) if abs(n[0]) > 0.9 else np.array([1.0, 0.0, 0.0])
+    u = trial - float(trial @ n) * n
+    u = u / np.linalg.norm(u)
+    v = np.cross(n, u)
+    v = v / np.linalg.norm(v)
+
+    def order(rows):
+        rows = np.asarray(rows, dtype=np.int64)
+        rel = x[rows] - c
+        key = np.arctan2(rel @ v, rel @ u)
+        idx = np.arange(len(rows))
+        before = (key[None, :] < key[:, None]) | ((key[None, :] == key[:, None]) & (idx[None, :] < idx[:, None]))
+        out = np.empty(len(rows), np.int64)
+        out[before.sum(axis=1)] = rows
+        return out
+
+    def in_plane(p):
+        r = p - c
+        return r - (r @ n)[:, None] * n
+
+    def arc_weight(p):
+        return 0.5 * (np.linalg.norm(np.roll(p, -1, axis=0) - p, axis=1) + np.linalg.norm(p - np.roll(p, 1, axis=0), axis=1))
+
+    def arc_params(p):
+        seg = np.linalg.norm(np.roll(p, -1, axis=0) - p, axis=1)
+        run, s = 0.0, np.zeros(len(p))
+        for q in range(len(p)):
+            s[q] = run
+            run += seg[q]
+        return (s / run if run > 0.0 else np.zeros(len(p))), run
+
+    orim, oout = order(rim), order(outer)
+    odisk = order(disk) if len(disk) else np.zeros(0, np.int64)
+    nr, no, nd = len(orim), len(oout), len(odisk)
+    nv = len(x)
+    out = {"E": 0.0, "E_out": 0.0, "E_in": 0.0, "grad": np.zeros((nv, 3)), "tilt_in_grad": np.zeros((nv, 3)),
+           "tilt_out_grad": np.zeros((nv, 3)), "rim_order": orim, "outer_order": oout, "disk_order": odisk,
+           "n_valid": 0, "contributes": False, "local_disk": nd > 0 and nd == nr, "sum_wd": 0.0}
+    p_rim, p_out = x[orim], x[oout]
+    idx0, w0, w1 = np.arange(nr), np.ones(nr), np.zeros(nr)
+    paired, interp = True, nr != no
+    if interp:
+        s_out, total_out = arc_params(p_out)
+        s_rim, total_rim = arc_params(p_rim)
+        paired = total_rim > 0.0 and total_out > 0.0 and no >= 2
+        if paired:
+            for q in range(nr):
+                lo, hi = 0, no
+                while lo < hi:
+                    mid = (lo + hi) >> 1
+                    if s_out[mid] <= s_rim[q]:
+                        lo = mid + 1
+                    else:
+                        hi = mid
+                i1 = lo % no
+                i0 = (i1 + no - 1) % no
+                s0, s1, st = s_out[i0], s_out[i1], s_rim[q]
+                if s1 <= s0:
+                    s1 += 1.0
+                if st < s0:
+                    st += 1.0
+                t = (st - s0) / (s1 - s0) if s1 - s0 > 1e-12 else 0.0
+                idx0[q], w0[q], w1[q] = i0, 1.0 - t, t
+    if not paired:
+        return out
+    idx1 = (idx0 + 1) % no if interp else idx0
+    po = p_out[idx0] * w0[:, None] + p_out[idx1] * w1[:, None] if interp else p_out[idx0]
+    r = in_plane(p_rim)
+    rl = np.linalg.norm(r, axis=1)
+    good = rl > 1e-12
+    rhat = np.where(good[:, None], r / np.where(good, rl, 1.0)[:, None], 0.0)
+    dr = np.linalg.norm(in_plane(po), axis=1) - rl
+    ok = np.abs(dr) > 1e-8
+    phi = np.where(ok, ((po - c) @ n - (p_rim - c) @ n) / np.where(ok, dr, 1.0), 0.0)
+    valid = ok & good & np.isfinite(phi)
+    out["n_valid"] = int(valid.sum())
+    if not valid.any():
+        return out
+    out["contributes"] = True
+    w = np.where(valid, arc_weight(p_rim), 0.0)
+    phi = np.where(valid, phi, 0.0)
+    inv_dr = np.where(valid, 1.0 / np.where(valid, dr, 1.0), 0.0)
+    k = float(strength)
+    tin, tout = np.asarray(tilts_in, dtype=np.float64), np.asarray(tilts_out, dtype=np.float64)
+    dif = np.where(valid, np.einsum("ij,ij->i", tout[orim], rhat) - phi, 0.0)
+    dif_in = np.zeros(nr)
+    has_in = False
+    if nd:
+        rd = in_plane(x[odisk])
+        rdl = np.linalg.norm(rd, axis=1)
+        gd = rdl > 1e-12
+        rhat_d = np.where(gd[:, None], rd / np.where(gd, rdl, 1.0)[:, None], 0.0)
+        th_d = np.einsum("ij,ij->i", tin[odisk], rhat_d)
+        if out["local_disk"]:
+            theta, has_in = th_d, True
+        else:
+            w_d = np.where(gd, arc_weight(x[odisk]), 0.0)
+            out["sum_wd"] = float(w_d.sum())
+            if out["sum_wd"] > 0.0:
+                theta, has_in = float((w_d * th_d).sum() / out["sum_wd"]), True
+        if has_in:
+            dif_in = np.where(valid, np.einsum("ij,ij->i", tin[orim], rhat) - (theta - phi), 0.0)
+    out["E_out"] = 0.5 * k * float((w * dif * dif).sum())
+    out["E_in"] = 0.5 * k * float((w * dif_in * dif_in).sum()) if has_in else 0.0
+    out["E"] = out["E_out"] + out["E_in"]
+    out["tilt_out_grad"][orim] += (k * w * dif)[:, None] * rhat
+    if has_in:
+        out["tilt_in_grad"][orim] += (k * w * dif_in)[:, None] * rhat
+        if out["local_disk"]:
+            out["tilt_in_grad"][odisk] += (-k * w * dif_in)[:, None] * rhat_d
+        else:
+            out["tilt_in_grad"][odisk] += (-k * float((w * dif_in).sum())) * (w_d / out["sum_wd"])[:, None] * rhat_d
+    if shape_gradient:
+        gc = k * w * (dif - dif_in) * inv_dr
+        out["grad"][orim] += gc[:, None] * n
+        first0 = np.searchsorted(idx0, np.arange(no + 1), side="left")  # idx0 is monotone
+        assert np.all(np.diff(idx0) >= 0)
+        for j in range(no):
+            for ps in range(2 if interp else 1):
+                jj = j if ps == 0 else (j + no - 1) % no
+                for q in range(first0[jj], first0[jj + 1]):
+                    out["grad"][oout[j]] += (-gc[q] * n) * (w0[q] if ps == 0 else w1[q])
+    return out
+
+
 def splay_twist_params(param_resolver, global_params):
     """(k_splay, k_twist, divergence mode) of tilt_splay_twist_in (modules/energy/tilt_splay_twist_in.py:16-50), in the
     reference's order: ``tilt_splay_modulus_in`` else ``bending_modulus_in`` else ``bending_modulus`` (the fallback is

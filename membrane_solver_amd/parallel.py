@@ -349,6 +349,9 @@ class HipShardBackend:
         if modules & L.MS_MOD_TILT_THETAB_CONTACT_IN:
             raise L.MembraneHipError("the tilt_thetaB_contact_in module is not sharded (single GPU only; ms_set_params "
                                      "refuses it on a sharded context as well)")
+        if modules & L.MS_MOD_RIM_SLOPE_MATCH_OUT:
+            raise L.MembraneHipError("the rim_slope_match_out module with a non-zero rim_slope_match_strength is not "
+                                     "sharded (single GPU only; ms_set_params refuses it on a sharded context as well)")
         if modules & L.MS_MOD_TILT_COUPLING:
             raise L.MembraneHipError("the tilt_coupling module is not sharded (single GPU only; ms_set_params refuses "
                                      "it on a sharded context as well)")

@@ -24,8 +24,9 @@ On the device as well: the tilt relaxation at the top of every iteration
 (``tilt_solve_mode`` nested / coupled, single field and two leaflets:
 ms_relax_tilts / ms_relax_leaflet_tilts, minimizer.py:1237-1307), the tilt
 modules (``tilt``, ``bending_tilt``, ``tilt_smoothness`` and their ``_in`` /
-``_out`` leaflet forms, ``tilt_disk_target_in/out``), ``gaussian_curvature``
-and the switched-off ``rim_slope_match_out`` as host-side constants.
+``_out`` leaflet forms, ``tilt_disk_target_in/out``), ``rim_slope_match_out`` with a
+non-zero strength (k_rsm_geom / k_rsm_apply), and ``gaussian_curvature`` and the
+switched-off ``rim_slope_match_out`` as host-side constants.
 
 Constraints: ``volume``, the hard area constraints ``body_area`` (its row in the KKT projection next to the volume row,
 its projection on every line-search trial and in every enforce context) and ``global_area`` (the projection alone), and
@@ -88,9 +89,12 @@ _ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volum
                 "tilt_coupling": L.MS_MOD_TILT_COUPLING, "tilt_splay_twist_in": L.MS_MOD_TILT_SPLAY_TWIST_IN,
                 "tilt_rim_source_bilayer": L.MS_MOD_TILT_RIM_SOURCE_BILAYER,
                 "tilt_thetaB_contact_in": L.MS_MOD_TILT_THETAB_CONTACT_IN,
-                # host-side constants, no kernel: a topological constant on closed surfaces; a module that is only
-                # accepted in its switched-off state (strength 0, as in the caveolin decks)
-                "gaussian_curvature": 0, "rim_slope_match_out": 0}
+                # (the bit is set only with a non-zero strength and both rings: strength 0, as in most caveolin decks, and
+                # a missing group or ring stay a host-side constant 0.0; the bit is left out of _LEAFLET_BITS: the module is
+                # admitted only next to leaflet modules that are in it)
+                "rim_slope_match_out": L.MS_MOD_RIM_SLOPE_MATCH_OUT,
+                # host-side constant, no kernel: a topological constant on closed surfaces
+                "gaussian_curvature": 0}
 _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_tilt": 1, "tilt_smoothness": 3,
                 "tilt_in": 3, "tilt_out": 3, "tilt_smoothness_in": 3, "tilt_smoothness_out": 3,
                 "bending_tilt_in": 1, "bending_tilt_out": 1, "tilt_disk_target_in": 3, "tilt_disk_target_out": 3,
@@ -108,6 +112,7 @@ _ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_til
 _RIM_MODULES = ("tilt_rim_source_in", "tilt_rim_source_out")
 _RIM_BILAYER = "tilt_rim_source_bilayer"  # one table for both leaflet fields (DeviceMesh.set_rim_source_bilayer)
 _THETAB = "tilt_thetaB_contact_in"  # the ring's table of the context (DeviceMesh.set_thetab_contact)
+_RIM_MATCH = "rim_slope_match_out"  # the three rings' tables of the context (DeviceMesh.set_rim_match)
 _EDGE_MODULES = ("line_tension", "edge_length_penalty")  # they share the lane behind the energy and the gradient pass
 _SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
 _LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
@@ -120,6 +125,10 @@ _TILT_BITS = _SINGLE_TILT_BITS | _LEAFLET_BITS
 _INNER_LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_TILT_DISK_TARGET_IN
                        | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_COUPLING | L.MS_MOD_TILT_SPLAY_TWIST_IN
                        | L.MS_MOD_TILT_RIM_SOURCE_BILAYER | L.MS_MOD_TILT_THETAB_CONTACT_IN)
+# the modules whose tilt gradient relaxes the outer leaflet's field / the inner one's (rim_slope_match_out couples to a
+# field that one of them must relax)
+_OUTER_RELAX_BITS = (L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_OUT | L.MS_MOD_BENDING_TILT_OUT | L.MS_MOD_TILT_DISK_TARGET_OUT
+                     | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING | L.MS_MOD_TILT_RIM_SOURCE_BILAYER)
 # scalar slot of every module that shares energies[3]
 _TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": L.MS_S_ETILT_IN,
                 "tilt_out": L.MS_S_ETILT_OUT, "tilt_smoothness_in": L.MS_S_ETS_IN,
@@ -235,10 +244,10 @@ class Minimizer:
                     "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
                     "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
                     "body_area_penalty, line_tension, edge_length_penalty, tilt_rim_source_in, tilt_rim_source_out, "
-                    "tilt_rim_source_bilayer, tilt_thetaB_contact_in, "
+                    "tilt_rim_source_bilayer, tilt_thetaB_contact_in, rim_slope_match_out, "
                     "tilt_coupling, tilt_splay_twist_in)")
         if "body_area_penalty" in self.energy_module_names and any(
-                _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
+                _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):  # (not rim_slope_match_out: see _ENERGY_BITS)
             raise L.MembraneHipError("body_area_penalty together with tilt modules is outside the HIP hot path")
         for edge_mod in _EDGE_MODULES:
             if edge_mod in self.energy_module_names and any(
@@ -417,6 +426,7 @@ class Minimizer:
         rim_params = {}
         rim_bilayer = None
         thetab = None
+        rim_match = False  # (then: rim_slope_match_out is listed with a non-zero strength; below: its tables, or None)
         coupling = None
         splay_twist = None
         vol_mode = gp.get("volume_constraint_mode", "lagrange")
@@ -451,10 +461,10 @@ class Minimizer:
                 from ..modules.energy import gaussian_curvature as _gc
 
                 self._const_energy[name] = _gc.constant_energy(self.mesh, gp)  # gaussian_curvature.py:117-134
-            elif name == "rim_slope_match_out":
-                from ..modules.energy import rim_slope_match_out as _rs
-
-                self._const_energy[name] = _rs.constant_energy(self.mesh, gp, self.param_resolver)
+            elif name == _RIM_MATCH:
+                # rim_slope_match_out.py:380-382: strength 0 is 0.0 whatever else is set
+                rim_match = _lc.rim_match_strength(self.param_resolver, gp) != 0.0
+                self._const_energy[name] = 0.0
             elif name in ("tilt_disk_target_in", "tilt_disk_target_out"):
                 prm = _lc.disk_target_params(self.mesh, self.param_resolver, gp, name[17:])
                 if prm is not None:  # tilt_disk_target_in.py:175-191
@@ -501,6 +511,10 @@ class Minimizer:
             raise L.MembraneHipError("tilt_thetaB_contact_in together with a single-field tilt module is outside the "
                                      "HIP hot path")
         self._thetab_update = thetab is not None and thetab["penalty_mode"] == "legacy" and thetab["k"] > 0.0
+        rim_match = self._rim_match_params(mods) if rim_match else None  # (refused before anything is uploaded)
+        if rim_match is not None:
+            mods |= _ENERGY_BITS[_RIM_MATCH]
+            del self._const_energy[_RIM_MATCH]
         tbb = self._thetab_boundary_params(mods)
         self._tbb_active = tbb is not None
         target = 0.0
@@ -592,6 +606,11 @@ class Minimizer:
                     dm.set_thetab_contact(**thetab)
                     mir._leaflet_keys["bend_thetab"] = key
                 dm.set_thetab_value(_lc.thetab_value(gp))
+            if rim_match is not None:  # keyed like the pins: topology, context and parameters
+                key = (mir._topo_key, id(dm), _lc.rim_match_key(rim_match))
+                if mir._leaflet_keys.get("bend_rim_match") != key:
+                    dm.set_rim_match(**rim_match)
+                    mir._leaflet_keys["bend_rim_match"] = key
             # tilt_thetaB_boundary_in: keyed like the other ring tables; theta_B and the relaxation's cadence go with every
             # configuration; a table of an earlier configuration is cleared
             key = None if tbb is None else (mir._topo_key, id(dm), _tbb.device_key(tbb))
@@ -680,6 +699,30 @@ class Minimizer:
         if self._edgepen_key is None or self._edgepen_key[:5] != key:
             self._edgepen_key = key + (_edgepen.upload(self.mesh, self.global_params, dm, (tail, head, target, num)),)
         return self._edgepen_key[5]
+
+    def _rim_match_params(self, mods):
+        """rim_slope_match_out with a non-zero strength: kwargs of DeviceMesh.set_rim_match, or None where the module is
+        a constant 0.0 (no rim / outer group, an empty ring).  Refused here: no active outer-leaflet tilt module -- checked
+        first, whatever the groups hold --, a single-field tilt module next to it, a disk ring without an active
+        inner-leaflet module (the sharded drivers refuse the bit themselves); in leaflet_common.rim_match_params: the staggered modes, a missing
+        normal, a ring above the device's size, non-finite parameters."""
+        if not mods & _OUTER_RELAX_BITS:
+            raise L.MembraneHipError("rim_slope_match_out with a non-zero rim_slope_match_strength and without an active "
+                                     "outer-leaflet tilt module (tilt_out, bending_tilt_out, tilt_smoothness_out, "
+                                     "tilt_disk_target_out, tilt_rim_source_out, tilt_coupling, tilt_rim_source_bilayer) is "
+                                     "outside the HIP hot path: nothing relaxes the field it couples")
+        if mods & _SINGLE_TILT_BITS:
+            raise L.MembraneHipError("rim_slope_match_out with a non-zero rim_slope_match_strength together with a "
+                                     "single-field tilt module is outside the HIP hot path")
+        prm = _lc.rim_match_params(self.mesh, self.param_resolver, self.global_params)
+        if prm is None:
+            return None
+        if len(prm["disk"]) and not mods & _INNER_LEAFLET_BITS:
+            raise L.MembraneHipError("rim_slope_match_out with a non-zero rim_slope_match_strength and a disk group, "
+                                     "without an active inner-leaflet tilt module (tilt_in, bending_tilt_in, "
+                                     "tilt_smoothness_in, ...), is outside the HIP hot path: nothing relaxes the inner field "
+                                     "it couples")
+        return prm
 
     def _thetab_boundary_params(self, mods):
         """tilt_thetaB_boundary_in: kwargs of DeviceMesh.set_thetab_boundary, or None where the module is not listed or
@@ -806,6 +849,10 @@ class Minimizer:
         tb_e = dm.thetab_contact_energy() if dm.modules & L.MS_MOD_TILT_THETAB_CONTACT_IN else 0.0
         if _THETAB in out:
             out[_THETAB] = tb_e
+        # ... and the rim matching term, one part in each leaflet's slot
+        rm_e = dm.rim_match_energies() if dm.modules & L.MS_MOD_RIM_SLOPE_MATCH_OUT else (0.0, 0.0, 0.0)
+        if _RIM_MATCH in out and dm.modules & L.MS_MOD_RIM_SLOPE_MATCH_OUT:
+            out[_RIM_MATCH] = rm_e[0]
         # the splay / twist term rides in the inner leaflet's smoothness slot in the same way
         st_e = dm.tilt_splay_twist_energy() if dm.modules & L.MS_MOD_TILT_SPLAY_TWIST_IN else 0.0
         if "tilt_splay_twist_in" in out:
@@ -817,12 +864,12 @@ class Minimizer:
                 for n in sharing:
                     out[n] = float(sc[table[n]]) if dm.modules & _ENERGY_BITS[n] else 0.0
                     if n in ("tilt_in", "tilt_out") and dm.modules & _ENERGY_BITS[n]:
-                        out[n] -= rim_e[n[5:]] + ((cpl_e + rb_e) if n == "tilt_out" else tb_e)
+                        out[n] -= rim_e[n[5:]] + ((cpl_e + rb_e + rm_e[1]) if n == "tilt_out" else (tb_e + rm_e[2]))
                     if n == "tilt_smoothness_in" and dm.modules & _ENERGY_BITS[n]:
                         out[n] -= st_e
             elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e or st_e or rb_e
-                                                                     or tb_e):
-                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e - st_e - rb_e - tb_e
+                                                                     or tb_e or rm_e[0]):
+                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e - st_e - rb_e - tb_e - rm_e[0]
         return out
 
     # -- constraint enforcement (minimizer.py:1103-1188) ---------------------------
