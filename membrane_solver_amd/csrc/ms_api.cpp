@@ -14,6 +14,7 @@
 #include <dlfcn.h>
 
 #include "ms_internal.h"
+#include "ms_table_blob.h"
 
 static void shard_comm_destroy(void* comm);  // (RCCL binding further down)
 
@@ -25,6 +26,7 @@ std::string g_last_error;  // for failures that have no context yet
 
 #include "ms_api_ctx.inc"  // the context: everything a ms_ctx holds
 #include "ms_api_phases.inc"  // pass launchers, folds, mailboxes, the energy / gradient / direction phases
+#include "ms_api_tables.inc"  // what the ring and rim setters share: the plane check and its axes, a ring's external rows
 #include "ms_api_edge.inc"  // line_tension and edge_length_penalty: the edge / vertex tables, each term's two launches behind the energy and the gradient pass
 #include "ms_api_rim.inc"  // tilt_rim_source_in/out: the rim tables, the frame / coefficient / apply launches next to the disk-target pass
 #include "ms_api_rimmatch.inc"  // rim_slope_match_out: the three rings' rows and frame, the geometry / apply launches behind every other leaflet pass

@@ -84,7 +84,7 @@ int ms_set_area_constraint(ms_ctx* c, int kind, double target_area) {
   c->area_con_kind = kind;
   c->area_con_target = kind == MS_AREA_NONE ? 0.0 : target_area;
   // (the gradient held may have been projected against the old row set)
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate();
   return MS_OK;
 }
 
@@ -135,7 +135,7 @@ int ms_project_area_cached(ms_ctx* c, double tol, int max_iter, int first_step_c
     const double lam = delta / (res[AP_GAGA] + 1e-18);
     HIPCHK(c, launch_axpy_masked(c->til.nv, c->d_vflags, c->buf[MS_BUF_X], g, -lam, c->stream));
     c->carry.factors_valid = false;
-    c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+    c->carry.invalidate_with_bt();
     ++it;
   }
   if (iters_out) *iters_out = it;

@@ -385,7 +385,7 @@ int ms_set_surface_tension(ms_ctx* c, const double* gamma) {
   for (int f = 1; f < t.nf && c->gamma_uniform; ++f) c->gamma_uniform = gamma[f] == c->gamma_const;
   if (!g.empty())
     HIPCHK(c, hipMemcpy(c->d_tf_gamma, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->sh_carry_valid = c->sh_grad_valid = false;
   return MS_OK;
 }
@@ -406,7 +406,7 @@ int ms_set_bending_params(ms_ctx* c, const double* kappa, const double* c0) {
   HIPCHK(c, hipMemcpy(c->d_kappa, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_c0, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice));
   c->carry.factors_valid = false;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->sh_carry_valid = c->sh_grad_valid = false;
   return MS_OK;
 }
@@ -470,7 +470,7 @@ int ms_set_params(ms_ctx* c, const ms_params* p) {
   c->area_row = (p->modules & MS_CON_BODY_AREA) != 0;
   c->params.modules &= ~MS_CON_BODY_AREA;
   c->carry.factors_valid = false;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->sh_carry_valid = c->sh_grad_valid = false;
   return MS_OK;
 }
@@ -481,7 +481,7 @@ int ms_set_area_penalty(ms_ctx* c, double stiffness, double target_area) {
     return fail(c, MS_ERR_INVALID, "ms_set_area_penalty: stiffness and target area must be finite");
   c->area_stiffness = stiffness;
   c->target_area = target_area;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies and the gradient held are the old term's)
+  c->carry.invalidate();  // (the energies and the gradient held are the old term's)
   c->sh_carry_valid = c->sh_grad_valid = false;
   return MS_OK;
 }
@@ -508,7 +508,7 @@ int ms_set_tilts(ms_ctx* c, const double* tilts, double tilt_rigidity) {
     HIPCHK(c, hipMemset(c->tf[0].grad, 0, bytes));
   }
   c->tf[0].k_tilt = tilt_rigidity;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->sh_carry_valid = c->sh_grad_valid = false;
   return ext_to_patch(c, tilts, c->tf[0].tilts, 3);
 }
@@ -621,7 +621,7 @@ int ms_set_deterministic(ms_ctx* c, int on) {
   if (!c) return MS_ERR_INVALID;
   if (c->deterministic == (on != 0)) return MS_OK;
   c->deterministic = on != 0;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->carry.factors_valid = false;
   return MS_OK;
 }
@@ -629,7 +629,7 @@ int ms_set_deterministic(ms_ctx* c, int on) {
 int ms_set_tilt_smoothness(ms_ctx* c, double k_smooth) {
   if (!c) return MS_ERR_INVALID;
   c->tf[0].k_smooth = k_smooth;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   return MS_OK;
 }
 

@@ -75,7 +75,7 @@ int ms_set_tilt_coupling(ms_ctx* c, double modulus, int sign) {
   c->cpl_k = modulus;
   c->cpl_sign = sign;
   if (const char* e = getenv("MS_COUPLE_VEC")) c->cpl_force_tile = atoi(e) == 0;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies held are the old term's)
+  c->carry.invalidate();  // (the energies held are the old term's)
   return MS_OK;
 }
 

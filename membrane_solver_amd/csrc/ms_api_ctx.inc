@@ -57,6 +57,10 @@ struct CarryState {
   // gradient pass, survives a failed line search, cleared together with carry_valid)
   bool grad_valid = false;
   bool maxg2_valid = false;  // the mailbox holds |g|^2 and max|g_i|^2 of the gradient in buffer G
+  // a mutator's part: the energies, the gradient and its reductions held describe what was there before ...
+  void invalidate() { carry_valid = grad_valid = maxg2_valid = false; }
+  // ... and, where positions or tilts moved, so does d_bt_vert
+  void invalidate_with_bt() { carry_valid = grad_valid = bt_valid = maxg2_valid = false; }
 };
 struct ms_ctx {
   int device = 0;

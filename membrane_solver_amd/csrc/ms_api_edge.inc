@@ -87,57 +87,35 @@ const char* build_edge_tables(int nv, const int32_t* iperm, int n_edges, const i
   return nullptr;
 }
 
-// the tables on the device, one allocation: doubles first (the per-edge column, the CSR column, the energy kernel's
-// workgroup sums, the module's energy, the arrival counter's cell), then the int tables
-struct EdgeBlob {
-  int ne = 0, nt = 0, grid_e = 0, grid_g = 0;
-  const double *ecol = nullptr, *ccol = nullptr;
-  double *wg_sums = nullptr, *energy = nullptr;
-  uint32_t* done = nullptr;
-  const int32_t *tail = nullptr, *head = nullptr, *vrow = nullptr, *off = nullptr, *other = nullptr;
-};
+// the tables on the device, one allocation (ms_table_blob.h): the term's column per edge (ecol) and per CSR entry (ccol),
+// the energy kernel's workgroup sums, the module's energy, the arrival counter's cell; the int tables.  The lane's two
+// argument records point into it.
 int upload_edge_tables(ms_ctx* c, const char* who, const EdgeTables& tb, const std::vector<double>& ecol,
-                       const std::vector<double>& ccol, void** d_blob, EdgeBlob& out) {
+                       const std::vector<double>& ccol, ms_ctx::EdgeLane& l) {
   const int tiles = c->tile1 - c->tile0;
   const int ne = (int)tb.et.size(), nt = (int)tb.vrow.size();
   if (ne > 0 && tiles <= 0) return fail(c, MS_ERR_STATE, std::string(who) + ": the context has no tiles");
   const int grid_e = ne > 0 ? std::min(tiles, (ne + 255) / 256) : 0;
   const int grid_g = nt > 0 ? std::min(tiles, (nt + 255) / 256) : 0;
-  const size_t n_dbl = (size_t)ne + 2 * (size_t)ne + (size_t)std::max(1, grid_e) + 2;
-  const size_t n_int = 2 * (size_t)ne + (size_t)nt + (size_t)nt + 1 + 2 * (size_t)ne;
-  std::vector<double> blob(n_dbl + (n_int + 1) / 2 + 1, 0.0);
-  double* bp = blob.data();
-  if (ne) {
-    memcpy(bp, ecol.data(), sizeof(double) * ne);
-    memcpy(bp + ne, ccol.data(), sizeof(double) * 2 * (size_t)ne);
-  }
-  int32_t* ip = reinterpret_cast<int32_t*>(bp + n_dbl);
-  size_t at = 0;
-  auto put = [&](const std::vector<int32_t>& v) {
-    const size_t o = at;
-    if (!v.empty()) memcpy(ip + at, v.data(), sizeof(int32_t) * v.size());
-    at += v.size();
-    return o;
-  };
-  const size_t o_t = put(tb.et), o_h = put(tb.eh), o_v = put(tb.vrow), o_o = put(tb.off), o_x = put(tb.other);
-  HIPCHK(c, hipMalloc(d_blob, blob.size() * sizeof(double)));
-  HIPCHK(c, hipMemcpy(*d_blob, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-  double* dp = static_cast<double*>(*d_blob);
-  const int32_t* di = reinterpret_cast<const int32_t*>(dp + n_dbl);
-  out.ne = ne;
-  out.nt = nt;
-  out.grid_e = grid_e;
-  out.grid_g = grid_g;
-  out.ecol = dp;
-  out.ccol = dp + ne;
-  out.wg_sums = dp + 3 * (size_t)ne;
-  out.energy = out.wg_sums + std::max(1, grid_e);
-  out.done = reinterpret_cast<uint32_t*>(out.energy + 1);
-  out.tail = di + o_t;
-  out.head = di + o_h;
-  out.vrow = di + o_v;
-  out.off = di + o_o;
-  out.other = di + o_x;
+  TableBlob b;
+  const auto h_ecol = b.f64((size_t)ne, ecol.data()), h_ccol = b.f64(2 * (size_t)ne, ccol.data());
+  const auto h_wg = b.f64((size_t)std::max(1, grid_e)), h_en = b.f64(1), h_done = b.f64(1);
+  const auto h_t = b.i32(tb.et), h_h = b.i32(tb.eh), h_v = b.i32(tb.vrow), h_o = b.i32(tb.off), h_x = b.i32(tb.other);
+  if (int rc = upload_table(c, b, &l.d_blob)) return rc;
+  l.en.n_edges = ne;
+  l.en.grid = grid_e;
+  l.en.col = b.at(l.d_blob, h_ecol);
+  l.en.wg_sums = b.at(l.d_blob, h_wg);
+  l.en.energy = b.at(l.d_blob, h_en);
+  l.en.done = b.u32(l.d_blob, h_done);
+  l.en.tail = b.at(l.d_blob, h_t);
+  l.en.head = b.at(l.d_blob, h_h);
+  l.gr.n_touch = nt;
+  l.gr.grid = grid_g;
+  l.gr.vrow = b.at(l.d_blob, h_v);
+  l.gr.off = b.at(l.d_blob, h_o);
+  l.gr.other = b.at(l.d_blob, h_x);
+  l.gr.col = b.at(l.d_blob, h_ccol);
   return MS_OK;
 }
 
@@ -200,39 +178,18 @@ int edge_lane_set(ms_ctx* c, int term, int n_edges, const int32_t* tail, const i
   const EdgeTerm& T = kEdgeTerms[term];
   ms_ctx::EdgeLane& l = c->edge[term];
   if (c->shard_count != 1) return fail(c, MS_ERR_STATE, std::string(T.setter) + ": " + edge_not_sharded(T));
-  if (l.d_blob) {
-    HIPCHK(c, hipStreamSynchronize(S(c)));
-    HIPCHK(c, hipFree(l.d_blob));
-    l.d_blob = nullptr;
-  }
+  if (int rc = drop_table(c, l.d_blob)) return rc;
   l.en = EdgeEnergyArgs{};
   l.gr = EdgeGradArgs{};
   l.set = false;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (energies and G held are the old term's)
+  c->carry.invalidate();  // (energies and G held are the old term's)
   if (!tail) return MS_OK;
   if (n_edges < 0 || !head || !col) return fail(c, MS_ERR_INVALID, std::string(T.setter) + ": bad argument");
   EdgeTables tb;
   if (const char* why = build_term_tables(term, c->til.nv, c->til.iperm.data(), n_edges, tail, head, col, k, tb))
     return fail(c, MS_ERR_INVALID, why);
-  EdgeBlob bl;
-  if (int rc = upload_edge_tables(c, T.setter, tb, T.second ? tb.el0 : tb.eg, T.second ? tb.ol0 : tb.og, &l.d_blob, bl))
-    return rc;
-  l.en.k = k;
-  l.en.n_edges = bl.ne;
-  l.en.col = bl.ecol;
-  l.en.wg_sums = bl.wg_sums;
-  l.en.energy = bl.energy;
-  l.en.done = bl.done;
-  l.en.tail = bl.tail;
-  l.en.head = bl.head;
-  l.en.grid = bl.grid_e;
-  l.gr.k = k;
-  l.gr.n_touch = bl.nt;
-  l.gr.vrow = bl.vrow;
-  l.gr.off = bl.off;
-  l.gr.other = bl.other;
-  l.gr.col = bl.ccol;
-  l.gr.grid = bl.grid_g;
+  if (int rc = upload_edge_tables(c, T.setter, tb, T.second ? tb.el0 : tb.eg, T.second ? tb.ol0 : tb.og, l)) return rc;
+  l.en.k = l.gr.k = k;
   l.set = true;
   return MS_OK;
 }

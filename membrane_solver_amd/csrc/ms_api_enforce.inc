@@ -10,7 +10,7 @@ inline bool perimeter_set(const ms_ctx* c) { return c->d_perim != nullptr; }
 // every call that moves positions: what ms_project_area_cached invalidates
 inline void enforce_only_moved(ms_ctx* c) {
   c->carry.factors_valid = false;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
 }
 
 // fixed_plane.enforce_constraint (fixed_plane.py:25-53) on buffer X
@@ -108,11 +108,7 @@ const char* build_perimeter_tables(int nv, const int32_t* iperm, int n_loops, co
 }
 
 int perimeter_clear(ms_ctx* c) {
-  if (c->d_perim) {
-    HIPCHK(c, hipStreamSynchronize(S(c)));
-    HIPCHK(c, hipFree(c->d_perim));
-    c->d_perim = nullptr;
-  }
+  if (int rc = drop_table(c, c->d_perim)) return rc;
   c->perim = PerimeterArgs{};
   return MS_OK;
 }
@@ -185,42 +181,28 @@ int ms_set_perimeter(ms_ctx* c, int n_loops, const int32_t* loop_off, const int3
   PerimTables t;
   if (const char* why = build_perimeter_tables(c->til.nv, c->til.iperm.data(), n_loops, loop_off, tail, head, t))
     return fail(c, MS_ERR_INVALID, why);
-  // one blob: the doubles (targets, result cells, the two scratch arrays), then the int tables
-  const size_t n_dbl = (size_t)n_loops + 2 * (size_t)n_loops + 4 * (size_t)t.max_ent + 4 * (size_t)t.max_verts;
-  const size_t n_int = (size_t)(n_loops + 1) + 2 * t.et.size() + (size_t)(n_loops + 1) + t.vrow.size() + t.csr_off.size() +
-                       t.csr_ent.size();
-  std::vector<double> blob(n_dbl + (n_int + 1) / 2 + 1, 0.0);
-  std::copy(target, target + n_loops, blob.begin());
-  int32_t* ip = reinterpret_cast<int32_t*>(blob.data() + n_dbl);
-  size_t at = 0;
-  auto put = [&](const int32_t* src, size_t n) {
-    const size_t o = at;
-    if (n) memcpy(ip + at, src, sizeof(int32_t) * n);
-    at += n;
-    return o;
-  };
-  const size_t o_lo = put(loop_off, (size_t)n_loops + 1), o_et = put(t.et.data(), t.et.size()), o_eh = put(t.eh.data(), t.eh.size());
-  const size_t o_vo = put(t.vert_off.data(), t.vert_off.size()), o_vr = put(t.vrow.data(), t.vrow.size());
-  const size_t o_co = put(t.csr_off.data(), t.csr_off.size()), o_ce = put(t.csr_ent.data(), t.csr_ent.size());
-  HIPCHK(c, hipMalloc(&c->d_perim, blob.size() * sizeof(double)));
-  HIPCHK(c, hipMemcpy(c->d_perim, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-  double* dp = static_cast<double*>(c->d_perim);
-  const int32_t* di = reinterpret_cast<const int32_t*>(dp + n_dbl);
+  // one allocation (ms_table_blob.h): the targets, the result cells, the two scratch arrays; the int tables
+  TableBlob b;
+  const auto h_tg = b.f64((size_t)n_loops, target), h_res = b.f64(2 * (size_t)n_loops), h_ent = b.f64(4 * (size_t)t.max_ent),
+             h_gv = b.f64(4 * (size_t)t.max_verts);
+  const auto h_lo = b.i32((size_t)n_loops + 1, loop_off), h_et = b.i32(t.et), h_eh = b.i32(t.eh), h_vo = b.i32(t.vert_off),
+             h_vr = b.i32(t.vrow), h_co = b.i32(t.csr_off), h_ce = b.i32(t.csr_ent);
+  if (int rc = upload_table(c, b, &c->d_perim)) return rc;
   PerimeterArgs& a = c->perim;
   a.n_loops = n_loops;
-  a.target = dp;
-  a.res = dp + n_loops;
-  a.ent = a.res + 2 * (size_t)n_loops;
-  a.gv = a.ent + 4 * (size_t)t.max_ent;
+  a.target = b.at(c->d_perim, h_tg);
+  a.res = b.at(c->d_perim, h_res);
+  a.ent = b.at(c->d_perim, h_ent);
+  a.gv = b.at(c->d_perim, h_gv);
   a.max_ent = t.max_ent;
   a.max_verts = t.max_verts;
-  a.loop_off = di + o_lo;
-  a.tail = di + o_et;
-  a.head = di + o_eh;
-  a.vert_off = di + o_vo;
-  a.vrow = di + o_vr;
-  a.csr_off = di + o_co;
-  a.csr_ent = di + o_ce;
+  a.loop_off = b.at(c->d_perim, h_lo);
+  a.tail = b.at(c->d_perim, h_et);
+  a.head = b.at(c->d_perim, h_eh);
+  a.vert_off = b.at(c->d_perim, h_vo);
+  a.vrow = b.at(c->d_perim, h_vr);
+  a.csr_off = b.at(c->d_perim, h_co);
+  a.csr_ent = b.at(c->d_perim, h_ce);
   return MS_OK;
 }
 

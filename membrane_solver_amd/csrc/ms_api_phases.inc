@@ -625,7 +625,7 @@ int tilt_energy_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bo
 int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool write_trial,
                  bool guard, bool write_factors, bool reduce_now = true) {
   const StageCtl& st = c->stage();
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->sh_carry_valid = c->sh_grad_valid = false;
   EnergyArgs a;
   a.m = device_mesh(c);
@@ -1293,6 +1293,22 @@ int upload(ms_ctx* c, Tp** dst, const std::vector<Tp>& src, size_t min_elems = 1
   HIPCHK(c, hipMalloc(reinterpret_cast<void**>(dst), n * sizeof(Tp)));
   if (!src.empty())
     HIPCHK(c, hipMemcpy(*dst, src.data(), src.size() * sizeof(Tp), hipMemcpyHostToDevice));
+  return MS_OK;
+}
+
+// a setter's table (ms_table_blob.h) as one allocation; the sections' pointers are b.at(*dst, handle)
+int upload_table(ms_ctx* c, TableBlob& b, void** dst) {
+  HIPCHK(c, hipMalloc(dst, b.bytes()));
+  HIPCHK(c, hipMemcpy(*dst, b.image(), b.bytes(), hipMemcpyHostToDevice));
+  return MS_OK;
+}
+
+// ... and the end of one: no launch still reads it once the stream has drained
+int drop_table(ms_ctx* c, void*& d_table) {
+  if (!d_table) return MS_OK;
+  HIPCHK(c, hipStreamSynchronize(S(c)));
+  HIPCHK(c, hipFree(d_table));
+  d_table = nullptr;
   return MS_OK;
 }
 

@@ -15,7 +15,7 @@ int pin_enforce_run(ms_ctx* c) {
   HIPCHK(c, launch_pin_enforce(a, c->stream, c->exec_pins));  // (a record of the pack, or a launch behind a flush)
   ++c->pin_enforce_launches;
   c->carry.factors_valid = false;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   return MS_OK;
 }
 
@@ -46,11 +46,7 @@ int ms_set_pins(ms_ctx* c, int n_params, const double* params, int n_stages, con
                 const int32_t* avg_row) {
   if (!c) return MS_ERR_INVALID;
   if (c->shard_count != 1) return fail(c, MS_ERR_STATE, "ms_set_pins: pin constraints are single-shard only");
-  if (c->d_pins) {
-    HIPCHK(c, hipStreamSynchronize(S(c)));
-    HIPCHK(c, hipFree(c->d_pins));
-    c->d_pins = nullptr;
-  }
+  if (int rc = drop_table(c, c->d_pins)) return rc;
   c->pin_enf = PinEnforceArgs{};
   c->pin_grad = PinGradArgs{};
   c->pin_lane = -1;
@@ -115,53 +111,39 @@ int ms_set_pins(ms_ctx* c, int n_params, const double* params, int n_stages, con
       note(arow[i]);
     }
   }
-  // one blob: params, then the int tables
-  const size_t n_int = (size_t)3 * n_stages + 1 + 2 * (size_t)n_items + 3 * (size_t)n_grad + 2 * (size_t)n_avg + 1 +
-                       (size_t)n_avg_rows + touch.size();
-  std::vector<double> blob((size_t)7 * n_params + (n_int + 1) / 2 + 1, 0.0);
-  memcpy(blob.data(), params, sizeof(double) * 7 * (size_t)n_params);
-  int32_t* ip = reinterpret_cast<int32_t*>(blob.data() + 7 * (size_t)n_params);
-  size_t at = 0;
-  auto put = [&](const int32_t* src, size_t n) {
-    const size_t o = at;
-    if (n) memcpy(ip + at, src, sizeof(int32_t) * n);
-    at += n;
-    return o;
-  };
-  const int32_t zero = 0;
-  const size_t o_sk = put(stage_kind, n_stages), o_sp = put(stage_param, n_stages);
-  const size_t o_so = n_stages > 0 ? put(stage_off, n_stages + 1) : put(&zero, 1);
-  const size_t o_ir = put(irow.data(), n_items), o_ia = put(item_arg, n_items);
-  const size_t o_gr = put(grow.data(), n_grad), o_gk = put(grad_kind, n_grad), o_gp = put(grad_param, n_grad);
-  const size_t o_ap = put(avg_param, n_avg);
-  const size_t o_ao = n_avg > 0 ? put(avg_off, n_avg + 1) : put(&zero, 1);
-  const size_t o_ar = put(arow.data(), n_avg_rows), o_t = put(touch.data(), touch.size());
-  HIPCHK(c, hipMalloc(&c->d_pins, blob.size() * sizeof(double)));
-  HIPCHK(c, hipMemcpy(c->d_pins, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-  const double* dp = static_cast<const double*>(c->d_pins);
-  const int32_t* di = reinterpret_cast<const int32_t*>(dp + 7 * (size_t)n_params);
+  // one allocation (ms_table_blob.h): params, then the int tables (an offset table without a stage / support is one 0)
+  TableBlob b;
+  const auto h_prm = b.f64(7 * (size_t)n_params, params);
+  const auto h_sk = b.i32(n_stages, stage_kind), h_sp = b.i32(n_stages, stage_param);
+  const auto h_so = n_stages > 0 ? b.i32(n_stages + 1, stage_off) : b.i32(1);
+  const auto h_ir = b.i32(irow), h_ia = b.i32(n_items, item_arg);
+  const auto h_gr = b.i32(grow), h_gk = b.i32(n_grad, grad_kind), h_gp = b.i32(n_grad, grad_param);
+  const auto h_ap = b.i32(n_avg, avg_param);
+  const auto h_ao = n_avg > 0 ? b.i32(n_avg + 1, avg_off) : b.i32(1);
+  const auto h_ar = b.i32(arow), h_t = b.i32(touch);
+  if (int rc = upload_table(c, b, &c->d_pins)) return rc;
   PinEnforceArgs& e = c->pin_enf;
-  e.params = dp;
+  e.params = b.at(c->d_pins, h_prm);
   e.n_stages = n_stages;
-  e.stage_kind = di + o_sk;
-  e.stage_param = di + o_sp;
-  e.stage_off = di + o_so;
-  e.item_row = di + o_ir;
-  e.item_arg = di + o_ia;
+  e.stage_kind = b.at(c->d_pins, h_sk);
+  e.stage_param = b.at(c->d_pins, h_sp);
+  e.stage_off = b.at(c->d_pins, h_so);
+  e.item_row = b.at(c->d_pins, h_ir);
+  e.item_arg = b.at(c->d_pins, h_ia);
   PinGradArgs& g = c->pin_grad;
-  g.params = dp;
+  g.params = e.params;
   g.n_grad = n_grad;
-  g.grad_row = di + o_gr;
-  g.grad_kind = di + o_gk;
-  g.grad_param = di + o_gp;
+  g.grad_row = b.at(c->d_pins, h_gr);
+  g.grad_kind = b.at(c->d_pins, h_gk);
+  g.grad_param = b.at(c->d_pins, h_gp);
   g.n_avg = n_avg;
-  g.avg_param = di + o_ap;
-  g.avg_off = di + o_ao;
-  g.avg_row = di + o_ar;
+  g.avg_param = b.at(c->d_pins, h_ap);
+  g.avg_off = b.at(c->d_pins, h_ao);
+  g.avg_row = b.at(c->d_pins, h_ar);
   g.n_touch = (int)touch.size();
-  g.touch_row = di + o_t;
+  g.touch_row = b.at(c->d_pins, h_t);
   c->pin_lane = lane;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (G no longer describes this row set)
+  c->carry.invalidate();  // (G no longer describes this row set)
   return MS_OK;
 }
 

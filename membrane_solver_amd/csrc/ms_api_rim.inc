@@ -132,25 +132,16 @@ int rim_upload(ms_ctx* c, const char* who, const RimState& st, int n_edges, cons
   const std::string w(who);
   if (c->shard_count != 1)
     return fail(c, MS_ERR_STATE, w + ": the tilt_rim_source modules are not sharded (single GPU only)");
-  if (st.d_rim) {
-    HIPCHK(c, hipStreamSynchronize(S(c)));
-    HIPCHK(c, hipFree(st.d_rim));
-    st.d_rim = nullptr;
-  }
+  if (int rc = drop_table(c, st.d_rim)) return rc;
   st.rs = RimArgs{};
   st.set = st.follow = st.coef_valid = false;
   st.center = nullptr;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies held are the old term's)
+  c->carry.invalidate();  // (the energies held are the old term's)
   if (!tail) return MS_OK;
   if (n_edges < 0 || !head || !gamma || !p) return fail(c, MS_ERR_INVALID, w + ": bad argument");
-  double nn = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    if (!std::isfinite(p->center[k]) || !std::isfinite(p->normal[k]))
-      return fail(c, MS_ERR_INVALID, w + ": center and normal must be finite");
-    nn += p->normal[k] * p->normal[k];
-  }
-  nn = std::sqrt(nn);
-  if (!(nn >= 1e-15)) return fail(c, MS_ERR_INVALID, w + ": a non-zero plane normal is required");
+  double unit[3];
+  if (int rc = plane_finite(c, who, p->center, p->normal)) return rc;
+  if (int rc = plane_frame(c, who, p->normal, unit)) return rc;  // tilt_rim_source_in.py:150-159
   EdgeTables tb;
   if (const char* why = build_rim_tables(c->til.nv, c->til.iperm.data(), n_edges, tail, head, gamma, tb)) {
     // (the builder's texts name the leaflet setter)
@@ -162,45 +153,29 @@ int rim_upload(ms_ctx* c, const char* who, const RimState& st, int n_edges, cons
   const int ne = (int)tb.et.size(), nt = (int)tb.vrow.size();
   if (nt > 0 && tiles <= 0) return fail(c, MS_ERR_STATE, w + ": the context has no tiles");
   const int grid = nt > 0 ? std::min(tiles, (nt + 255) / 256) : 0;
-  // one allocation: doubles first (gamma per CSR entry, the coefficients, the workgroup sums, the module's energy, the
-  // follow mode's center, the arrival counter's cell), then the int tables
-  const size_t n_dbl = 2 * (size_t)ne + 3 * (size_t)nt + (size_t)std::max(1, grid) + 1 + 3 + 1;
-  const size_t n_int = (size_t)nt + (size_t)nt + 1 + 2 * (size_t)ne;
-  std::vector<double> blob(n_dbl + (n_int + 1) / 2 + 1, 0.0);
-  double* bp = blob.data();
-  if (ne) memcpy(bp, tb.ol0.data(), sizeof(double) * 2 * (size_t)ne);
-  const size_t o_coef = 2 * (size_t)ne, o_wg = o_coef + 3 * (size_t)nt, o_en = o_wg + (size_t)std::max(1, grid);
-  const size_t o_cen = o_en + 1, o_done = o_cen + 3;
-  for (int k = 0; k < 3; ++k) bp[o_cen + k] = p->center[k];  // (until the first evaluation at x)
-  int32_t* ip = reinterpret_cast<int32_t*>(bp + n_dbl);
-  size_t at = 0;
-  auto put = [&](const std::vector<int32_t>& v) {
-    const size_t o = at;
-    if (!v.empty()) memcpy(ip + at, v.data(), sizeof(int32_t) * v.size());
-    at += v.size();
-    return o;
-  };
-  const size_t o_v = put(tb.vrow), o_o = put(tb.off), o_x = put(tb.other);
-  HIPCHK(c, hipMalloc(&st.d_rim, blob.size() * sizeof(double)));
-  HIPCHK(c, hipMemcpy(st.d_rim, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-  double* dp = static_cast<double*>(st.d_rim);
-  const int32_t* di = reinterpret_cast<const int32_t*>(dp + n_dbl);
+  // one allocation (ms_table_blob.h): gamma per CSR entry, the coefficients, the workgroup sums, the module's energy,
+  // the follow mode's center (the given one until the first evaluation at x), the arrival counter's cell; the int tables
+  TableBlob b;
+  const auto h_gamma = b.f64(2 * (size_t)ne, tb.ol0.data()), h_coef = b.f64(3 * (size_t)nt);
+  const auto h_wg = b.f64((size_t)std::max(1, grid)), h_en = b.f64(1), h_cen = b.f64(3, p->center), h_done = b.f64(1);
+  const auto h_v = b.i32(tb.vrow), h_o = b.i32(tb.off), h_x = b.i32(tb.other);
+  if (int rc = upload_table(c, b, &st.d_rim)) return rc;
   RimArgs& a = st.rs;
   a.n_touch = nt;
-  a.vrow = di + o_v;
-  a.off = di + o_o;
-  a.other = di + o_x;
-  a.gamma = dp;
-  a.coef = dp + o_coef;
-  a.wg_sums = dp + o_wg;
-  a.energy = dp + o_en;
-  a.done = reinterpret_cast<uint32_t*>(dp + o_done);
+  a.vrow = b.at(st.d_rim, h_v);
+  a.off = b.at(st.d_rim, h_o);
+  a.other = b.at(st.d_rim, h_x);
+  a.gamma = b.at(st.d_rim, h_gamma);
+  a.coef = b.at(st.d_rim, h_coef);
+  a.wg_sums = b.at(st.d_rim, h_wg);
+  a.energy = b.at(st.d_rim, h_en);
+  a.done = b.u32(st.d_rim, h_done);
   a.grid = grid;
   for (int k = 0; k < 3; ++k) {
     a.center[k] = p->center[k];
-    a.normal[k] = p->normal[k] / nn;  // tilt_rim_source_in.py:150-159
+    a.normal[k] = unit[k];
   }
-  st.center = dp + o_cen;
+  st.center = b.at(st.d_rim, h_cen);
   st.follow = p->follow != 0;
   st.set = true;
   return MS_OK;

@@ -59,15 +59,11 @@ int rim_match_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool
 }
 
 int rim_match_drop(ms_ctx* c) {
-  if (c->d_rsm) {
-    HIPCHK(c, hipStreamSynchronize(S(c)));
-    HIPCHK(c, hipFree(c->d_rsm));
-    c->d_rsm = nullptr;
-  }
+  if (int rc = drop_table(c, c->d_rsm)) return rc;
   c->rsm = RsmArgs{};
   c->rsm_set = c->rsm_geom_valid = false;
   c->tf[1].mod_rsm = 0;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies held are the old term's)
+  c->carry.invalidate();  // (the energies held are the old term's)
   return MS_OK;
 }
 
@@ -90,109 +86,68 @@ int ms_set_rim_match(ms_ctx* c, int n_rim, const int32_t* rim, int n_outer, cons
     if (counts[k] > MS_RIM_MATCH_MAX_ROWS)
       return fail(c, MS_ERR_INVALID, std::string("ms_set_rim_match: ") + a_names[k] + " ring of " + std::to_string(counts[k]) +
                                          " rows is above the " + std::to_string(MS_RIM_MATCH_MAX_ROWS) + " one workgroup orders");
-  double nn = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    if (!std::isfinite(p->center[k]) || !std::isfinite(p->normal[k]))
-      return fail(c, MS_ERR_INVALID, "ms_set_rim_match: center and normal must be finite");
-    nn += p->normal[k] * p->normal[k];
-  }
-  nn = std::sqrt(nn);
+  const char* who = "ms_set_rim_match";
+  double unit[3], u[3], v[3];  // rim_slope_match_out.py:141-149 the unit normal, geometry/plane_ops.py:21-41 the in-plane axes
+  if (int rc = plane_finite(c, who, p->center, p->normal)) return rc;
   if (!std::isfinite(p->strength)) return fail(c, MS_ERR_INVALID, "ms_set_rim_match: the strength must be finite");
-  if (!(nn >= 1e-15)) return fail(c, MS_ERR_INVALID, "ms_set_rim_match: a non-zero plane normal is required");
-  const int nv = c->til.nv;
+  if (int rc = plane_frame(c, who, p->normal, unit, u, v)) return rc;
   std::vector<int32_t> lib[3];
   {
-    std::vector<uint8_t> seen((size_t)nv, 0);  // one map for the three tables: a thread of k_rsm_apply owns a row
+    std::vector<uint8_t> seen((size_t)c->til.nv, 0);  // one map for the three tables: a thread of k_rsm_apply owns a row
     for (int k = 0; k < 3; ++k) {
       lib[k].assign((size_t)std::max(counts[k], 1), 0);
-      for (int i = 0; i < counts[k]; ++i) {
-        const int32_t r = tabs[k][i];
-        if (r < 0 || r >= nv) return fail(c, MS_ERR_INVALID, std::string("ms_set_rim_match: ") + names[k] + " row out of range");
-        if (seen[(size_t)r])
-          return fail(c, MS_ERR_INVALID, std::string("ms_set_rim_match: ") + a_names[k] + " row is listed twice (within its ring or in another one)");
-        seen[(size_t)r] = 1;
-        lib[k][(size_t)i] = c->til.iperm[(size_t)r];
-      }
+      if (int rc = ring_rows(c, who, names[k], a_names[k], c->til.nv, c->til.iperm.data(), counts[k], tabs[k], seen,
+                             lib[k].data(), " (within its ring or in another one)"))
+        return rc;
     }
   }
   if (c->tile1 - c->tile0 <= 0) return fail(c, MS_ERR_STATE, "ms_set_rim_match: the context has no tiles");
-  // one allocation: doubles first, then the int tables
+  // one allocation (ms_table_blob.h); a ring without a disk keeps one slot in each of the disk's tables
   const size_t nr = (size_t)n_rim, no = (size_t)n_outer, nd = (size_t)std::max(n_disk, 1);
-  size_t od = 0;
-  auto dbl = [&od](size_t n) { const size_t o = od; od += n; return o; };
-  const size_t o_rh = dbl(3 * nr), o_w = dbl(nr), o_phi = dbl(nr), o_idr = dbl(nr), o_w0 = dbl(nr), o_w1 = dbl(nr),
-               o_dif = dbl(nr), o_dfi = dbl(nr), o_so = dbl(no), o_rhd = dbl(3 * nd), o_wd = dbl(nd), o_rec = dbl(6),
-               o_wg = dbl(1), o_en = dbl(1), o_done = dbl(1);
-  const size_t n_dbl = od;
-  size_t oi = 0;
-  auto i32 = [&oi](size_t n) { const size_t o = oi; oi += n; return o; };
-  const size_t i_rr = i32(nr), i_ro = i32(no), i_rd = i32(nd), i_or = i32(nr), i_oo = i32(no), i_od = i32(nd),
-               i_val = i32(nr), i_i0 = i32(nr), i_f0 = i32(no + 1);
-  std::vector<double> blob(n_dbl + (oi + 1) / 2, 0.0);
-  int32_t* bi = reinterpret_cast<int32_t*>(blob.data() + n_dbl);
-  memcpy(bi + i_rr, lib[0].data(), sizeof(int32_t) * nr);
-  memcpy(bi + i_ro, lib[1].data(), sizeof(int32_t) * no);
-  memcpy(bi + i_rd, lib[2].data(), sizeof(int32_t) * nd);
+  TableBlob b;
+  const auto h_rh = b.f64(3 * nr), h_w = b.f64(nr), h_phi = b.f64(nr), h_idr = b.f64(nr), h_w0 = b.f64(nr), h_w1 = b.f64(nr),
+             h_dif = b.f64(nr), h_dfi = b.f64(nr), h_so = b.f64(no), h_rhd = b.f64(3 * nd), h_wd = b.f64(nd),
+             h_rec = b.f64(6), h_wg = b.f64(1), h_en = b.f64(1), h_done = b.f64(1);
   // (the ordered tables start as the rows themselves: every slot holds a row of its ring before the first geometry pass)
-  memcpy(bi + i_or, lib[0].data(), sizeof(int32_t) * nr);
-  memcpy(bi + i_oo, lib[1].data(), sizeof(int32_t) * no);
-  memcpy(bi + i_od, lib[2].data(), sizeof(int32_t) * nd);
+  const auto h_rr = b.i32(lib[0]), h_ro = b.i32(lib[1]), h_rd = b.i32(lib[2]), h_or = b.i32(lib[0]), h_oo = b.i32(lib[1]),
+             h_od = b.i32(lib[2]), h_val = b.i32(nr), h_i0 = b.i32(nr), h_f0 = b.i32(no + 1);
   if (int rc = rim_match_drop(c)) return rc;  // (only now: a refused call leaves the tables in use as they were)
-  HIPCHK(c, hipMalloc(&c->d_rsm, blob.size() * sizeof(double)));
-  HIPCHK(c, hipMemcpy(c->d_rsm, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-  double* dp = static_cast<double*>(c->d_rsm);
-  int32_t* di = reinterpret_cast<int32_t*>(dp + n_dbl);
+  if (int rc = upload_table(c, b, &c->d_rsm)) return rc;
+  void* d = c->d_rsm;
   RsmArgs& a = c->rsm;
   a.n_rim = n_rim;
   a.n_out = n_outer;
   a.n_disk = n_disk;
-  a.rows_rim = di + i_rr;
-  a.rows_out = di + i_ro;
-  a.rows_disk = di + i_rd;
-  a.orow_rim = di + i_or;
-  a.orow_out = di + i_oo;
-  a.orow_disk = di + i_od;
-  a.valid = di + i_val;
-  a.idx0 = di + i_i0;
-  a.first0 = di + i_f0;
-  a.rhat = dp + o_rh;
-  a.w = dp + o_w;
-  a.phi = dp + o_phi;
-  a.inv_dr = dp + o_idr;
-  a.w0 = dp + o_w0;
-  a.w1 = dp + o_w1;
-  a.dif = dp + o_dif;
-  a.dif_in = dp + o_dfi;
-  a.s_out = dp + o_so;
-  a.rhat_d = dp + o_rhd;
-  a.w_d = dp + o_wd;
-  a.rec = dp + o_rec;
-  a.wg_sums = dp + o_wg;
-  a.energy = dp + o_en;
-  a.done = reinterpret_cast<uint32_t*>(dp + o_done);
+  a.rows_rim = b.at(d, h_rr);
+  a.rows_out = b.at(d, h_ro);
+  a.rows_disk = b.at(d, h_rd);
+  a.orow_rim = b.at(d, h_or);
+  a.orow_out = b.at(d, h_oo);
+  a.orow_disk = b.at(d, h_od);
+  a.valid = b.at(d, h_val);
+  a.idx0 = b.at(d, h_i0);
+  a.first0 = b.at(d, h_f0);
+  a.rhat = b.at(d, h_rh);
+  a.w = b.at(d, h_w);
+  a.phi = b.at(d, h_phi);
+  a.inv_dr = b.at(d, h_idr);
+  a.w0 = b.at(d, h_w0);
+  a.w1 = b.at(d, h_w1);
+  a.dif = b.at(d, h_dif);
+  a.dif_in = b.at(d, h_dfi);
+  a.s_out = b.at(d, h_so);
+  a.rhat_d = b.at(d, h_rhd);
+  a.w_d = b.at(d, h_wd);
+  a.rec = b.at(d, h_rec);
+  a.wg_sums = b.at(d, h_wg);
+  a.energy = b.at(d, h_en);
+  a.done = b.u32(d, h_done);
   a.k = p->strength;
   for (int k = 0; k < 3; ++k) {
     a.center[k] = p->center[k];
-    a.normal[k] = p->normal[k] / nn;  // rim_slope_match_out.py:141-149
-  }
-  // the in-plane axes (geometry/plane_ops.py:21-41)
-  double trial[3] = {1.0, 0.0, 0.0};
-  if (std::fabs(a.normal[0]) > 0.9) {
-    trial[0] = 0.0;
-    trial[1] = 1.0;
-  }
-  const double tn = trial[0] * a.normal[0] + trial[1] * a.normal[1] + trial[2] * a.normal[2];
-  double u[3], v[3];
-  for (int k = 0; k < 3; ++k) u[k] = trial[k] - tn * a.normal[k];
-  const double un = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-  for (int k = 0; k < 3; ++k) u[k] = un < 1e-15 ? (k == 0 ? 1.0 : 0.0) : u[k] / un;
-  v[0] = a.normal[1] * u[2] - a.normal[2] * u[1];
-  v[1] = a.normal[2] * u[0] - a.normal[0] * u[2];
-  v[2] = a.normal[0] * u[1] - a.normal[1] * u[0];
-  const double vn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  for (int k = 0; k < 3; ++k) {
+    a.normal[k] = unit[k];
     a.u[k] = u[k];
-    a.v[k] = vn < 1e-15 ? (k == 1 ? 1.0 : 0.0) : v[k] / vn;
+    a.v[k] = v[k];
   }
   c->tf[1].mod_rsm = n_disk > 0 ? MS_MOD_RIM_SLOPE_MATCH_OUT : 0;  // (the inner leaflet is read only with a disk ring)
   c->rsm_set = true;

@@ -30,7 +30,7 @@ int ms_phase_accept(ms_ctx* c, int keep_history) {
   if (int rc = materialize_direction(c)) return rc;  // (D becomes PD below: never unwritten)
   std::swap(c->buf[MS_BUF_X], c->buf[MS_BUF_XT]);
   c->carry.factors_valid = false;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->sh_carry_valid = c->sh_grad_valid = false;
   c->sh_maxg2_valid = false;
   if (keep_history) {

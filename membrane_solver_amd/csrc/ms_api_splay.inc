@@ -57,7 +57,7 @@ int ms_set_tilt_splay_twist(ms_ctx* c, double k_splay, double k_twist) {
   c->st_k_splay = k_splay;
   c->st_k_twist = k_twist;
   c->st_set = true;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies held are the old term's)
+  c->carry.invalidate();  // (the energies held are the old term's)
   return MS_OK;
 }
 

@@ -2,7 +2,7 @@
 int ms_set_positions(ms_ctx* c, const double* positions) {
   if (!c || !positions) return fail(c, MS_ERR_INVALID, "ms_set_positions: NULL argument");
   c->carry.factors_valid = false;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->sh_carry_valid = c->sh_grad_valid = false;
   return ext_to_patch(c, positions, c->buf[MS_BUF_X], 3);
 }
@@ -355,7 +355,7 @@ void drop_ahead(ms_ctx* c, int ran) {
   ++c->q_dropped;
   if (ran >= 1) c->carry.factors_valid = false;
   if (ran >= 2) {
-    c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;
+    c->carry.invalidate();
     c->carry.kc_pending = false;
     c->carry.cg_have_history = false;
     c->carry.cg_iter_count = 0;
@@ -1014,7 +1014,7 @@ int ms_project_volume_cached(ms_ctx* c, double target, double tol, int max_iter,
     const double lam = delta / (norm2 + 1e-12);
     HIPCHK(c, launch_axpy_masked(c->til.nv, c->d_vflags, c->buf[MS_BUF_X], g, -lam, c->stream));
     c->carry.factors_valid = false;
-    c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+    c->carry.invalidate_with_bt();
   }
   if (iters_out) *iters_out = it;
   if (volume_out) *volume_out = V;

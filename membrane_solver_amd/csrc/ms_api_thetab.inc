@@ -61,14 +61,10 @@ int ms_set_thetab_contact(ms_ctx* c, int n_rows, const int32_t* rows, const ms_t
     return fail(c, MS_ERR_STATE, "ms_set_thetab_contact: the tilt_thetaB_contact_in module is not sharded (single GPU only)");
   // the table in use is dropped only once the new arguments have passed every check: a refused call leaves it as it was
   auto drop_old = [c]() -> int {
-    if (c->d_tb) {
-      HIPCHK(c, hipStreamSynchronize(S(c)));
-      HIPCHK(c, hipFree(c->d_tb));
-      c->d_tb = nullptr;
-    }
+    if (int rc = drop_table(c, c->d_tb)) return rc;
     c->tb = ThetabArgs{};
     c->tb_set = c->tb_geom_valid = false;
-    c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies held are the old term's)
+    c->carry.invalidate();  // (the energies held are the old term's)
     return MS_OK;
   };
   if (!rows) return drop_old();
@@ -76,82 +72,49 @@ int ms_set_thetab_contact(ms_ctx* c, int n_rows, const int32_t* rows, const ms_t
   if (n_rows > MS_THETAB_MAX_ROWS)
     return fail(c, MS_ERR_INVALID, "ms_set_thetab_contact: a ring of " + std::to_string(n_rows) + " rows is above the " +
                                        std::to_string(MS_THETAB_MAX_ROWS) + " one workgroup orders");
-  double nn = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    if (!std::isfinite(p->center[k]) || !std::isfinite(p->normal[k]))
-      return fail(c, MS_ERR_INVALID, "ms_set_thetab_contact: center and normal must be finite");
-    nn += p->normal[k] * p->normal[k];
-  }
-  nn = std::sqrt(nn);
+  const char* who = "ms_set_thetab_contact";
+  double unit[3], u[3], v[3];  // tilt_thetaB_contact_in.py:63-67 the unit normal, :97-111 the in-plane axes
+  if (int rc = plane_finite(c, who, p->center, p->normal)) return rc;
   if (!std::isfinite(p->k) || !std::isfinite(p->gamma))
     return fail(c, MS_ERR_INVALID, "ms_set_thetab_contact: k and gamma must be finite");
-  if (!(nn >= 1e-15)) return fail(c, MS_ERR_INVALID, "ms_set_thetab_contact: a non-zero plane normal is required");
+  if (int rc = plane_frame(c, who, p->normal, unit, u, v)) return rc;
   if (p->work_mode != MS_THETAB_WORK_SCALAR && p->work_mode != MS_THETAB_WORK_FIELD_LINEAR)
     return fail(c, MS_ERR_INVALID, "ms_set_thetab_contact: work_mode must be MS_THETAB_WORK_SCALAR or MS_THETAB_WORK_FIELD_LINEAR");
-  const int nv = c->til.nv;
-  std::vector<int32_t> lib((size_t)std::max(n_rows, 1), 0), keep((size_t)std::max(n_rows, 1), 0);
+  const size_t n = (size_t)n_rows, n_pad = (size_t)std::max(n_rows, 1);
+  std::vector<int32_t> lib(n_pad, 0);
   {
-    std::vector<uint8_t> seen((size_t)nv, 0);
-    for (int i = 0; i < n_rows; ++i) {
-      const int32_t r = rows[i];
-      if (r < 0 || r >= nv) return fail(c, MS_ERR_INVALID, "ms_set_thetab_contact: ring row out of range");
-      if (seen[(size_t)r]) return fail(c, MS_ERR_INVALID, "ms_set_thetab_contact: a ring row is listed twice");
-      seen[(size_t)r] = 1;
-      lib[(size_t)i] = c->til.iperm[(size_t)r];
-    }
+    std::vector<uint8_t> seen((size_t)c->til.nv, 0);
+    if (int rc = ring_rows(c, who, "ring", "a ring", c->til.nv, c->til.iperm.data(), n_rows, rows, seen, lib.data())) return rc;
   }
   if (n_rows > 0 && c->tile1 - c->tile0 <= 0) return fail(c, MS_ERR_STATE, "ms_set_thetab_contact: the context has no tiles");
-  // one allocation: doubles first (w, r_hat, the record, the scalars, the workgroup's sum, the module's energy, the
-  // arrival counter's cell), then the int tables (rows, keep)
-  const size_t n = (size_t)n_rows;
-  const size_t o_w = 0, o_rh = o_w + n, o_rec = o_rh + 3 * n, o_sc = o_rec + 4, o_wg = o_sc + 3, o_en = o_wg + 1,
-               o_done = o_en + 1, n_dbl = o_done + 1;
-  std::vector<double> blob(n_dbl + (2 * lib.size() + 1) / 2, 0.0);
-  int32_t* bi = reinterpret_cast<int32_t*>(blob.data() + n_dbl);
-  memcpy(bi, lib.data(), sizeof(int32_t) * lib.size());
-  memcpy(bi + lib.size(), keep.data(), sizeof(int32_t) * keep.size());
+  // one allocation (ms_table_blob.h): w, r_hat, the record, the scalars, the workgroup's sum, the module's energy, the
+  // arrival counter's cell; the int tables (rows, keep: one slot each for a ring without a row)
+  TableBlob b;
+  const auto h_w = b.f64(n), h_rh = b.f64(3 * n), h_rec = b.f64(4), h_sc = b.f64(3), h_wg = b.f64(1), h_en = b.f64(1),
+             h_done = b.f64(1);
+  const auto h_rows = b.i32(lib), h_keep = b.i32(n_pad);
   if (int rc = drop_old()) return rc;
-  HIPCHK(c, hipMalloc(&c->d_tb, blob.size() * sizeof(double)));
-  HIPCHK(c, hipMemcpy(c->d_tb, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-  double* dp = static_cast<double*>(c->d_tb);
-  int32_t* di = reinterpret_cast<int32_t*>(dp + n_dbl);
+  if (int rc = upload_table(c, b, &c->d_tb)) return rc;
   ThetabArgs& a = c->tb;
   a.n = n_rows;
-  a.rows = di;
-  a.keep = di + lib.size();
-  a.w = dp + o_w;
-  a.rhat = dp + o_rh;
-  a.rec = dp + o_rec;
-  a.scalars = dp + o_sc;
-  a.wg_sums = dp + o_wg;
-  a.energy = dp + o_en;
-  a.done = reinterpret_cast<uint32_t*>(dp + o_done);
+  a.rows = b.at(c->d_tb, h_rows);
+  a.keep = b.at(c->d_tb, h_keep);
+  a.w = b.at(c->d_tb, h_w);
+  a.rhat = b.at(c->d_tb, h_rh);
+  a.rec = b.at(c->d_tb, h_rec);
+  a.scalars = b.at(c->d_tb, h_sc);
+  a.wg_sums = b.at(c->d_tb, h_wg);
+  a.energy = b.at(c->d_tb, h_en);
+  a.done = b.u32(c->d_tb, h_done);
   a.k = p->k;
   a.gamma = p->gamma;
   a.field_linear = p->work_mode == MS_THETAB_WORK_FIELD_LINEAR ? 1 : 0;
   a.penalty = p->penalty_mode != 0 ? 1 : 0;
   for (int k = 0; k < 3; ++k) {
     a.center[k] = p->center[k];
-    a.normal[k] = p->normal[k] / nn;  // tilt_thetaB_contact_in.py:63-67
-  }
-  // the in-plane axes (tilt_thetaB_contact_in.py:97-111)
-  double trial[3] = {1.0, 0.0, 0.0};
-  if (std::fabs(a.normal[0]) > 0.9) {
-    trial[0] = 0.0;
-    trial[1] = 1.0;
-  }
-  const double tn = trial[0] * a.normal[0] + trial[1] * a.normal[1] + trial[2] * a.normal[2];
-  double u[3], v[3];
-  for (int k = 0; k < 3; ++k) u[k] = trial[k] - tn * a.normal[k];
-  const double un = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-  for (int k = 0; k < 3; ++k) u[k] = un < 1e-15 ? (k == 0 ? 1.0 : 0.0) : u[k] / un;
-  v[0] = a.normal[1] * u[2] - a.normal[2] * u[1];
-  v[1] = a.normal[2] * u[0] - a.normal[0] * u[2];
-  v[2] = a.normal[0] * u[1] - a.normal[1] * u[0];
-  const double vn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  for (int k = 0; k < 3; ++k) {
+    a.normal[k] = unit[k];
     a.u[k] = u[k];
-    a.v[k] = vn < 1e-15 ? (k == 1 ? 1.0 : 0.0) : v[k] / vn;
+    a.v[k] = v[k];
   }
   c->tb_set = true;
   return MS_OK;
@@ -161,7 +124,7 @@ int ms_set_thetab_value(ms_ctx* c, double theta_b) {
   if (!c) return MS_ERR_INVALID;
   if (!std::isfinite(theta_b)) return fail(c, MS_ERR_INVALID, "ms_set_thetab_value: theta_B must be finite");
   if (theta_b != c->tb_theta)
-    c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;  // (the energies held are the old value's)
+    c->carry.invalidate();  // (the energies held are the old value's)
   c->tb_theta = theta_b;
   return MS_OK;
 }

@@ -114,37 +114,23 @@ int ms_set_thetab_boundary(ms_ctx* c, int n_rows, const int32_t* rows, const ms_
     return fail(c, MS_ERR_STATE, "ms_set_thetab_boundary: the tilt_thetaB_boundary_in constraint is not sharded (single GPU only)");
   // the table in use is dropped only once the new arguments have passed every check: a refused call leaves it as it was
   auto drop_old = [c]() -> int {
-    if (c->d_tbb) {
-      HIPCHK(c, hipStreamSynchronize(S(c)));
-      HIPCHK(c, hipFree(c->d_tbb));
-      c->d_tbb = nullptr;
-    }
+    if (int rc = drop_table(c, c->d_tbb)) return rc;
     c->tbb = TbbArgs{};
     c->tbb_set = c->tbb_geom_valid = false;
     return MS_OK;
   };
   if (!rows) return drop_old();
   if (n_rows < 0 || !p) return fail(c, MS_ERR_INVALID, "ms_set_thetab_boundary: bad argument");
-  double nn = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    if (!std::isfinite(p->center[k]) || !std::isfinite(p->normal[k]))
-      return fail(c, MS_ERR_INVALID, "ms_set_thetab_boundary: center and normal must be finite");
-    nn += p->normal[k] * p->normal[k];
-  }
-  nn = std::sqrt(nn);
+  const char* who = "ms_set_thetab_boundary";
+  double unit[3];  // tilt_thetaB_boundary_in.py:41-45, :79-82
+  if (int rc = plane_finite(c, who, p->center, p->normal)) return rc;
   // tilt_thetaB_boundary_in.py:77-86: the fitted-plane branch stays host work
-  if (!(nn >= 1e-15)) return fail(c, MS_ERR_INVALID, "ms_set_thetab_boundary: a non-zero plane normal is required");
+  if (int rc = plane_frame(c, who, p->normal, unit)) return rc;
   const int nv = c->til.nv;
   std::vector<int32_t> lib((size_t)n_rows, 0);
   {
     std::vector<uint8_t> seen((size_t)nv, 0);
-    for (int i = 0; i < n_rows; ++i) {
-      const int32_t r = rows[i];
-      if (r < 0 || r >= nv) return fail(c, MS_ERR_INVALID, "ms_set_thetab_boundary: ring row out of range");
-      if (seen[(size_t)r]) return fail(c, MS_ERR_INVALID, "ms_set_thetab_boundary: a ring row is listed twice");
-      seen[(size_t)r] = 1;
-      lib[(size_t)i] = c->til.iperm[(size_t)r];
-    }
+    if (int rc = ring_rows(c, who, "ring", "a ring", nv, c->til.iperm.data(), n_rows, rows, seen, lib.data())) return rc;
   }
   std::vector<int32_t> off, fv;
   {
@@ -152,30 +138,25 @@ int ms_set_thetab_boundary(ms_ctx* c, int n_rows, const int32_t* rows, const ms_
     tbb_context_facets(c, tri);
     build_tbb_csr(nv, c->til.nf, tri.data(), n_rows, lib.data(), off, fv);
   }
-  // one allocation: doubles first (d, N_v), then the int tables (rows, off, fv), then keep
+  // one allocation (ms_table_blob.h): d, N_v; the int tables (rows, off, fv); keep
   const size_t n = (size_t)n_rows;
-  const size_t n_dbl = 6 * n, n_int = n + off.size() + fv.size();
-  std::vector<double> blob(n_dbl + (n_int + 1) / 2 + (n + 7) / 8 + 1, 0.0);
-  int32_t* bi = reinterpret_cast<int32_t*>(blob.data() + n_dbl);
-  if (n) memcpy(bi, lib.data(), sizeof(int32_t) * n);
-  memcpy(bi + n, off.data(), sizeof(int32_t) * off.size());
-  if (!fv.empty()) memcpy(bi + n + off.size(), fv.data(), sizeof(int32_t) * fv.size());
+  TableBlob b;
+  const auto h_dir = b.f64(3 * n), h_nrm = b.f64(3 * n);
+  const auto h_rows = b.i32(lib), h_off = b.i32(off), h_fv = b.i32(fv);
+  const auto h_keep = b.u8(n);
   if (int rc = drop_old()) return rc;
-  HIPCHK(c, hipMalloc(&c->d_tbb, blob.size() * sizeof(double)));
-  HIPCHK(c, hipMemcpy(c->d_tbb, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice));
-  double* dp = static_cast<double*>(c->d_tbb);
-  int32_t* di = reinterpret_cast<int32_t*>(dp + n_dbl);
+  if (int rc = upload_table(c, b, &c->d_tbb)) return rc;
   TbbArgs& a = c->tbb;
   a.n = n_rows;
-  a.dir = dp;
-  a.nrm = dp + 3 * n;
-  a.rows = di;
-  a.off = di + n;
-  a.fv = di + n + off.size();
-  a.keep = reinterpret_cast<uint8_t*>(dp + n_dbl + (n_int + 1) / 2);
+  a.dir = b.at(c->d_tbb, h_dir);
+  a.nrm = b.at(c->d_tbb, h_nrm);
+  a.rows = b.at(c->d_tbb, h_rows);
+  a.off = b.at(c->d_tbb, h_off);
+  a.fv = b.at(c->d_tbb, h_fv);
+  a.keep = b.at(c->d_tbb, h_keep);
   for (int k = 0; k < 3; ++k) {
     a.center[k] = p->center[k];
-    a.normal[k] = p->normal[k] / nn;  // tilt_thetaB_boundary_in.py:41-45, :79-82
+    a.normal[k] = unit[k];
   }
   c->tbb_set = true;
   return MS_OK;
@@ -201,7 +182,7 @@ int ms_thetab_boundary_enforce(ms_ctx* c) {
   if (int rc = tbb_geom_run(c, nullptr, false, 0.0, false)) return rc;
   if (int rc = tbb_apply_run(c, 0, c->tf[1].tilts, nullptr, false)) return rc;
   // the tilt-dependent energies held belong to the tilts before the projection
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   return MS_OK;
 }
 
@@ -269,13 +250,8 @@ int ms_thetab_boundary_tables_host(int nv, const int32_t* iperm, int n_facets, c
   std::vector<int32_t> lib((size_t)n_rows, 0);
   {
     std::vector<uint8_t> seen((size_t)nv, 0);
-    for (int i = 0; i < n_rows; ++i) {
-      const int32_t r = rows[i];
-      if (r < 0 || r >= nv) return fail(nullptr, MS_ERR_INVALID, "ms_thetab_boundary_tables_host: ring row out of range");
-      if (seen[(size_t)r]) return fail(nullptr, MS_ERR_INVALID, "ms_thetab_boundary_tables_host: a ring row is listed twice");
-      seen[(size_t)r] = 1;
-      lib[(size_t)i] = iperm[r];
-    }
+    if (int rc = ring_rows(nullptr, "ms_thetab_boundary_tables_host", "ring", "a ring", nv, iperm, n_rows, rows, seen, lib.data()))
+      return rc;
   }
   std::vector<int32_t> t3(3 * (size_t)n_facets, -1);
   for (int f = 0; f < n_facets; ++f) {

@@ -955,7 +955,7 @@ int ms_set_leaflet_tilts(ms_ctx* c, int leaflet, const double* tilts, const uint
     HIPCHK(c, hipStreamSynchronize(S(c)));
     HIPCHK(c, hipMemcpy(c->d_vflags, c->h_vflags.data(), c->h_vflags.size(), hipMemcpyHostToDevice));
   }
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   c->sh_carry_valid = c->sh_grad_valid = false;
   return ext_to_patch(c, tilts, f.tilts, 3);
 }
@@ -981,7 +981,7 @@ int ms_set_leaflet_bending(ms_ctx* c, int leaflet, const double* kappa, const do
   HIPCHK(c, hipMemcpy(f.kappa, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(f.c0, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice));
   c->carry.factors_valid = false;
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.bt_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate_with_bt();
   return MS_OK;
 }
 
@@ -1004,7 +1004,7 @@ int ms_set_leaflet_disk_target(ms_ctx* c, int leaflet, const uint8_t* disk_rows,
   HIPCHK(c, hipMemcpy(f.disk, m.data(), m.size(), hipMemcpyHostToDevice));
   f.dt = *p;
   for (int k = 0; k < 3; ++k) f.dt.normal[k] = p->normal[k] / nn;  // tilt_disk_target_in.py:73-77
-  c->carry.carry_valid = c->carry.grad_valid = c->carry.maxg2_valid = false;
+  c->carry.invalidate();
   return MS_OK;
 }
 

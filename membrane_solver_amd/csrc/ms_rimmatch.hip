@@ -6,9 +6,8 @@
 // The rings are re-ordered by angle from the positions handed to EVERY evaluation (geometry/plane_ops.py:73-103:
 // np.argsort of atan2(rel . v, rel . u), the position NOT projected first), and rim and outer entries are paired BY INDEX
 // after the ordering -- so, unlike in ms_thetab.hip, where atan2's branch cut starts a ring matters.  k_rsm_geom orders
-// the two or three rings one after another with that file's rank-by-counting (rank_i = #{j : (angle_j, j) < (angle_i, i)},
-// a strict total order on doubles, ties broken by the row's number in its table; the LDS arrays are reused per ring), then
-// forms the rim table, the pairing and the disk table.  With unequal counts the outer positions are interpolated at the
+// the two or three rings one after another by the rank-by-counting of ms_ring_dev.h (the LDS arrays are reused per ring),
+// then forms the rim table, the pairing and the disk table.  With unequal counts the outer positions are interpolated at the
 // rim's arc-length parameters (:190-229): the segment lengths are formed in parallel into LDS and ONE thread takes their
 // running sum in order, as np.cumsum does (n - 1 dependent LDS adds: about 0.15 ms for a ring of 4096 at 80 cycles an
 // add; the pass runs once per set of positions).  That reproduces the reference's unnormalised knots bit for bit, not
@@ -25,7 +24,7 @@
 // thread's.  Every sum is fixed-order (thread t takes items t, t + 256, ... in order, then a halving tree in LDS;
 // ms_stream_dev.h): a run is bitwise reproducible in both modes of ms_set_deterministic.  While a relaxation runs the
 // positions are frozen: the geometry pass runs once and every evaluation only applies it.
-#include "ms_stream_dev.h"
+#include "ms_ring_dev.h"
 
 namespace ms {
 namespace {
@@ -42,12 +41,6 @@ struct RsmShared {
 __device__ __forceinline__ double dot_n(const RsmArgs& a, const P3& p) {
   return (p.x - a.center[0]) * a.normal[0] + (p.y - a.center[1]) * a.normal[1] + (p.z - a.center[2]) * a.normal[2];
 }
-// p - center without its component along the normal (:450-451)
-__device__ __forceinline__ P3 rsm_in_plane(const RsmArgs& a, const P3& p) {
-  const double rx = p.x - a.center[0], ry = p.y - a.center[1], rz = p.z - a.center[2];
-  const double rn = rx * a.normal[0] + ry * a.normal[1] + rz * a.normal[2];
-  return P3{rx - rn * a.normal[0], ry - rn * a.normal[1], rz - rn * a.normal[2]};
-}
 
 // rows[0 .. n) in the order of their angles about the center -> orow; every thread of the workgroup calls it
 __device__ void rsm_order(const RsmArgs& a, const int32_t* rows, int n, int32_t* orow, RsmShared& sh) {
@@ -59,19 +52,9 @@ __device__ void rsm_order(const RsmArgs& a, const int32_t* rows, int n, int32_t*
     const double px = rx * a.u[0] + ry * a.u[1] + rz * a.u[2];
     const double py = rx * a.v[0] + ry * a.v[1] + rz * a.v[2];
     sh.key[i] = atan2(py, px);
-    sh.ord[i] = i;  // (every slot holds a row of the ring even if a non-finite angle breaks the ranks below)
+    sh.ord[i] = i;
   }
-  __syncthreads();
-  for (int i = t; i < n; i += LB) {
-    const double ki = sh.key[i];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-      const double kj = sh.key[j];
-      rank += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
-    }
-    sh.ord[rank] = i;  // (rank < n: at most n - 1 rows come before row i)
-  }
-  __syncthreads();
+  ring_rank(sh.key, sh.ord, n);
   for (int q = t; q < n; q += LB) orow[q] = rows[sh.ord[q]];
   __syncthreads();  // (orow is read by the whole workgroup from here on; key / ord are free again)
 }
@@ -102,11 +85,9 @@ __device__ double rsm_arc_params(const RsmArgs& a, const int32_t* orow, int n, R
   return total;
 }
 
-// 1/2 (|p_next - p| + |p - p_prev|) on the ordered closed ring (:178-187)
+// the arc-length weight on the ordered closed ring (:178-187)
 __device__ __forceinline__ double rsm_arc_weight(const RsmArgs& a, const int32_t* orow, int n, int q, const P3& p) {
-  const P3 pp = row_at(a, orow[q == 0 ? n - 1 : q - 1]);
-  const P3 pn = row_at(a, orow[q + 1 == n ? 0 : q + 1]);
-  return 0.5 * (len3(pn.x - p.x, pn.y - p.y, pn.z - p.z) + len3(p.x - pp.x, p.y - pp.y, p.z - pp.z));
+  return ring_arc_weight(a, n, q, p, [orow](int s) { return orow[s]; });
 }
 
 __global__ __launch_bounds__(LB) void k_rsm_geom(RsmArgs a) {
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(LB) void k_rsm_geom(RsmArgs a) {
     // :523-547 the disk rows' r_hat and, for the mean variant, their arc-length weights
     for (int q = t; q < nd; q += LB) {
       const P3 p = row_at(a, a.orow_disk[q]);
-      const P3 r = rsm_in_plane(a, p);
+      const P3 r = ring_in_plane(a, p);
       const double rl = len3(r.x, r.y, r.z);
       const bool good = rl > 1e-12;
       const double wd = good ? rsm_arc_weight(a, a.orow_disk, nd, q, p) : 0.0;
@@ -148,7 +129,7 @@ __global__ __launch_bounds__(LB) void k_rsm_geom(RsmArgs a) {
   double n_valid = 0.0;
   for (int q = t; q < nr; q += LB) {
     const P3 p = row_at(a, a.orow_rim[q]);
-    const P3 r = rsm_in_plane(a, p);
+    const P3 r = ring_in_plane(a, p);  // (:450-451)
     const double rl = len3(r.x, r.y, r.z);
     const bool good = rl > 1e-12;
     int i0 = q, i1 = q;
@@ -180,7 +161,7 @@ __global__ __launch_bounds__(LB) void k_rsm_geom(RsmArgs a) {
     }
     // :481-492
     const double h_rim = dot_n(a, p), h_out = dot_n(a, po);
-    const P3 ro = rsm_in_plane(a, po);
+    const P3 ro = ring_in_plane(a, po);
     const double dr = len3(ro.x, ro.y, ro.z) - rl;
     const double ph = fabs(dr) > 1e-8 ? (h_out - h_rim) / dr : 0.0;
     const bool valid = fabs(dr) > 1e-8 && isfinite(ph) && good && paired;

@@ -2,11 +2,9 @@
 // the energy): the contact work of the inner leaflet's boundary mode theta_B on an inclusion's ring of vertices.
 //
 // The ring is re-ordered by angle from the positions it is handed at EVERY evaluation (_order_by_angle, :94-118:
-// np.argsort of atan2), so its table is not a CSR the host can build once: k_thetab_geom sorts.  One workgroup keeps
-// the rows' angles in LDS and ranks them by counting -- rank_i = #{j : (angle_j, j) < (angle_i, i)}, a strict total
-// order on doubles, ties broken by the row's number in the table -- which needs no padding to a power of two, handles
-// every n from 1 up and reads LDS as a broadcast (every lane the same j).  Only the cyclic order enters w, so where
-// atan2's branch cut starts the ring does not matter.  Then w_i = 1/2 (|p_next - p_i| + |p_i - p_prev|) on the full
+// np.argsort of atan2 of the in-plane projection), so its table is not a CSR the host can build once: k_thetab_geom
+// sorts, by the rank-by-counting of ms_ring_dev.h.  Only the cyclic order enters w, so where atan2's branch cut
+// starts the ring does not matter.  Then w_i = 1/2 (|p_next - p_i| + |p_i - p_prev|) on the full
 // ring (:121-130), the in-plane r of every row, the keep flag |r| > 1e-12 (:250-260: rows are dropped AFTER the weights
 // are formed), wsum and R_eff over the kept rows and the two "wsum <= 1e-12" returns as a flag.
 //
@@ -15,19 +13,12 @@
 // a relaxation runs the positions are frozen: the geometry pass runs once and every evaluation only applies it.
 // Every sum is fixed-order (thread t takes items t, t + 256, ... in order, then a halving tree in LDS;
 // ms_stream_dev.h): a run is bitwise reproducible in both modes of ms_set_deterministic.
-#include "ms_stream_dev.h"
+#include "ms_ring_dev.h"
 
 namespace ms {
 namespace {
 
 constexpr int TB_MAX = MS_THETAB_MAX_ROWS;
-
-// p - center without its component along the normal (:250-251, and :113-114 of the ordering)
-__device__ __forceinline__ P3 thetab_in_plane(const ThetabArgs& a, const P3& p) {
-  const double rx = p.x - a.center[0], ry = p.y - a.center[1], rz = p.z - a.center[2];
-  const double rn = rx * a.normal[0] + ry * a.normal[1] + rz * a.normal[2];
-  return P3{rx - rn * a.normal[0], ry - rn * a.normal[1], rz - rn * a.normal[2]};
-}
 
 __global__ __launch_bounds__(LB) void k_thetab_geom(ThetabArgs a) {
   __shared__ double key[TB_MAX];
@@ -36,31 +27,19 @@ __global__ __launch_bounds__(LB) void k_thetab_geom(ThetabArgs a) {
   const int n = a.n < TB_MAX ? a.n : TB_MAX;  // (the setter refuses a larger ring)
   const int t = threadIdx.x;
   for (int i = t; i < n; i += LB) {
-    const P3 r = thetab_in_plane(a, row_at(a, a.rows[i]));
+    const P3 r = ring_in_plane(a, row_at(a, a.rows[i]));  // (:113-114: the ordering takes the component along the normal out first)
     const double px = r.x * a.u[0] + r.y * a.u[1] + r.z * a.u[2];
     const double py = r.x * a.v[0] + r.y * a.v[1] + r.z * a.v[2];
     key[i] = atan2(py, px);
-    ord[i] = i;  // (every slot holds a row of the ring even if a non-finite angle breaks the ranks below)
+    ord[i] = i;
   }
-  __syncthreads();
-  for (int i = t; i < n; i += LB) {
-    const double ki = key[i];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-      const double kj = key[j];
-      rank += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
-    }
-    ord[rank] = i;  // (rank < n: at most n - 1 rows come before row i)
-  }
-  __syncthreads();
+  ring_rank(key, ord, n);
   double sw_all = 0.0, sw = 0.0, swr = 0.0, nk = 0.0;
   for (int q = t; q < n; q += LB) {
     const int i = ord[q];
     const P3 p = row_at(a, a.rows[i]);
-    const P3 pp = row_at(a, a.rows[ord[q == 0 ? n - 1 : q - 1]]);
-    const P3 pn = row_at(a, a.rows[ord[q + 1 == n ? 0 : q + 1]]);
-    const double w = 0.5 * (len3(pn.x - p.x, pn.y - p.y, pn.z - p.z) + len3(p.x - pp.x, p.y - pp.y, p.z - pp.z));
-    const P3 r = thetab_in_plane(a, p);
+    const double w = ring_arc_weight(a, n, q, p, [&](int s) { return a.rows[ord[s]]; });
+    const P3 r = ring_in_plane(a, p);  // (:250-251)
     const double rl = len3(r.x, r.y, r.z);
     const bool keep = rl > 1e-12;
     a.w[i] = w;

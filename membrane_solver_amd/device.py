@@ -32,6 +32,17 @@ def _pu8(a):
     return None if a is None else a.ctypes.data_as(L._U8)
 
 
+def _vec3(v):
+    return (ctypes.c_double * 3)(*map(float, v))
+
+
+def _i32_table(a):
+    """-> (rows as a flat contiguous int32 array, a pointer to them); a table that holds nothing hands the library a
+    one-element dummy: a non-NULL pointer (NULL clears a setter's tables)."""
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+    return a, (a if len(a) else np.zeros(1, np.int32)).ctypes.data_as(L._I32)
+
+
 @dataclass(slots=True)
 class StepResult:
     success: bool
@@ -169,16 +180,11 @@ class DeviceMesh:
         if tail is None:
             self._chk(fn(self._h, 0, None, None, None, *[0.0 for _ in extra]), entry)
             return
-        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
-        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
+        (t, pt), (h, ph) = _i32_table(tail), _i32_table(head)
         c = np.ascontiguousarray(np.asarray(col, dtype=np.float64).reshape(-1))
         if not (len(t) == len(h) == len(c)):
             raise ValueError(f"{entry[3:]}: tail, head and {what} must have the same length")
-        n = len(t)
-        if n == 0:  # (a non-NULL pointer: tables that hold no edge)
-            t = h = np.zeros(1, np.int32)
-            c = np.zeros(1)
-        self._chk(fn(self._h, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32), _pd(c), *extra), entry)
+        self._chk(fn(self._h, len(t), pt, ph, _pd(c if len(c) else np.zeros(1)), *extra), entry)
 
     def _edge_term_energy(self, entry) -> float:
         e = ctypes.c_double(0.0)
@@ -336,33 +342,31 @@ class DeviceMesh:
         if mask.shape != (self.nv,):
             raise ValueError("disk_rows must be a (nv,) mask or a list of rows")
         mask = np.ascontiguousarray(mask)
-        p = L.ms_disk_target_params(float(strength), float(theta_b), float(lam), (ctypes.c_double * 3)(*map(float, center)),
-                                    (ctypes.c_double * 3)(*map(float, normal)), float(radius or 0.0))
+        p = L.ms_disk_target_params(float(strength), float(theta_b), float(lam), _vec3(center), _vec3(normal),
+                                    float(radius or 0.0))
         self._chk(L.lib().ms_set_leaflet_disk_target(self._h, lf, mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                                      ctypes.byref(p)), "ms_set_leaflet_disk_target")
+
+    def _set_rim_source(self, entry, lead, tail, head, gamma, center, normal, follow):
+        """One setter of the rim tables (``lead``: the entry point's arguments in front of the edge count): external rows
+        with their gamma and the circle's frame, or no edges to clear the tables."""
+        fn = getattr(L.lib(), entry)
+        if tail is None:
+            self._chk(fn(self._h, *lead, 0, None, None, None, None), entry)
+            return
+        (t, pt), (h, ph) = _i32_table(tail), _i32_table(head)
+        g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
+        if not (len(t) == len(h) == len(g)):
+            raise ValueError(f"{entry[3:]}: tail, head and gamma must have the same length")
+        p = L.ms_rim_source_params(_vec3(center), _vec3(normal), 1 if follow else 0)
+        self._chk(fn(self._h, *lead, len(t), pt, ph, _pd(g if len(g) else np.zeros(1)), ctypes.byref(p)), entry)
 
     def set_leaflet_rim_source(self, leaflet: str, tail=None, head=None, gamma=None, *, center=(0.0, 0.0, 0.0),
                                normal=(0.0, 0.0, 1.0), follow: bool = False):
         """tilt_rim_source_in/out: the rim edges as external rows with their strength gamma, and the circle's frame
         (``follow``: the center is the mean of the rim rows of the evaluated positions); no edges clear the tables."""
         lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]
-        if tail is None:
-            self._chk(L.lib().ms_set_leaflet_rim_source(self._h, lf, 0, None, None, None, None),
-                      "ms_set_leaflet_rim_source")
-            return
-        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
-        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
-        g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
-        if not (len(t) == len(h) == len(g)):
-            raise ValueError("set_leaflet_rim_source: tail, head and gamma must have the same length")
-        n = len(t)
-        if n == 0:  # (a non-NULL pointer: tables that hold no edge)
-            t = h = np.zeros(1, np.int32)
-            g = np.zeros(1)
-        p = L.ms_rim_source_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)),
-                                   1 if follow else 0)
-        self._chk(L.lib().ms_set_leaflet_rim_source(self._h, lf, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32),
-                                                    _pd(g), ctypes.byref(p)), "ms_set_leaflet_rim_source")
+        self._set_rim_source("ms_set_leaflet_rim_source", (lf,), tail, head, gamma, center, normal, follow)
 
     def leaflet_rim_source_energy(self, leaflet: str) -> float:
         """The rim source's own energy as the last evaluation summed it (ms_get_leaflet_rim_source_energy)."""
@@ -383,22 +387,7 @@ class DeviceMesh:
                                normal=(0.0, 0.0, 1.0), follow: bool = False):
         """tilt_rim_source_bilayer: set_leaflet_rim_source's tables, kept once for both leaflet fields
         (ms_set_rim_source_bilayer); no edges clear them."""
-        if tail is None:
-            self._chk(L.lib().ms_set_rim_source_bilayer(self._h, 0, None, None, None, None), "ms_set_rim_source_bilayer")
-            return
-        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
-        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
-        g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64).reshape(-1))
-        if not (len(t) == len(h) == len(g)):
-            raise ValueError("set_rim_source_bilayer: tail, head and gamma must have the same length")
-        n = len(t)
-        if n == 0:  # (a non-NULL pointer: tables that hold no edge)
-            t = h = np.zeros(1, np.int32)
-            g = np.zeros(1)
-        p = L.ms_rim_source_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)),
-                                   1 if follow else 0)
-        self._chk(L.lib().ms_set_rim_source_bilayer(self._h, n, t.ctypes.data_as(L._I32), h.ctypes.data_as(L._I32),
-                                                    _pd(g), ctypes.byref(p)), "ms_set_rim_source_bilayer")
+        self._set_rim_source("ms_set_rim_source_bilayer", (), tail, head, gamma, center, normal, follow)
 
     def rim_source_bilayer_energy(self) -> float:
         """The bilayer rim source's own energy as the last evaluation summed it (ms_get_rim_source_bilayer_energy)."""
@@ -453,19 +442,15 @@ class DeviceMesh:
         if rows is None:
             self._chk(L.lib().ms_set_thetab_contact(self._h, 0, None, None), "ms_set_thetab_contact")
             return
-        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
-        n = len(r)
-        if n == 0:  # (a non-NULL pointer: a table that holds no row)
-            r = np.zeros(1, np.int32)
+        r, pr = _i32_table(rows)
         work = {"scalar": L.MS_THETAB_WORK_SCALAR, "field_linear": L.MS_THETAB_WORK_FIELD_LINEAR}
         penalty = {"off": 0, "legacy": 1}
         if work_mode not in work or penalty_mode not in penalty:  # (leaflet_common.thetab_contact_modes resolves the aliases)
             raise ValueError("set_thetab_contact: work_mode must be 'scalar' or 'field_linear' and penalty_mode 'off' or "
                              f"'legacy', not {work_mode!r} / {penalty_mode!r}")
-        p = L.ms_thetab_contact_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)),
-                                       float(k), float(gamma), work[work_mode], penalty[penalty_mode])
-        self._chk(L.lib().ms_set_thetab_contact(self._h, n, r.ctypes.data_as(L._I32), ctypes.byref(p)),
-                  "ms_set_thetab_contact")
+        p = L.ms_thetab_contact_params(_vec3(center), _vec3(normal), float(k), float(gamma), work[work_mode],
+                                       penalty[penalty_mode])
+        self._chk(L.lib().ms_set_thetab_contact(self._h, len(r), pr, ctypes.byref(p)), "ms_set_thetab_contact")
 
     def set_thetab_value(self, theta_b: float):
         """theta_B of the contact term (tilt_thetaB_value, ms_set_thetab_value)."""
@@ -505,13 +490,9 @@ class DeviceMesh:
         if rim is None:
             self._chk(L.lib().ms_clear_rim_match(self._h), "ms_clear_rim_match")
             return
-        tabs = [np.ascontiguousarray(np.asarray([] if t is None else t, dtype=np.int32).reshape(-1))
-                for t in (rim, outer, disk)]
-        ptr = [(t if len(t) else np.zeros(1, np.int32)).ctypes.data_as(L._I32) for t in tabs]
-        p = L.ms_rim_match_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)),
-                                  float(strength))
-        self._chk(L.lib().ms_set_rim_match(self._h, len(tabs[0]), ptr[0], len(tabs[1]), ptr[1], len(tabs[2]), ptr[2],
-                                           ctypes.byref(p)), "ms_set_rim_match")
+        (r, p_r), (o, p_o), (d, p_d) = (_i32_table([] if t is None else t) for t in (rim, outer, disk))
+        p = L.ms_rim_match_params(_vec3(center), _vec3(normal), float(strength))
+        self._chk(L.lib().ms_set_rim_match(self._h, len(r), p_r, len(o), p_o, len(d), p_d, ctypes.byref(p)), "ms_set_rim_match")
 
     def rim_match_energy(self) -> float:
         """The rim matching term's own energy as the last evaluation summed it (ms_get_rim_match_energy)."""
@@ -538,14 +519,10 @@ class DeviceMesh:
             self._chk(L.lib().ms_set_thetab_boundary(self._h, 0, None, None), "ms_set_thetab_boundary")
             self._thetab_boundary_rows = 0
             return
-        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
-        n = len(r)
-        if n == 0:  # (a non-NULL pointer: a table that holds no row)
-            r = np.zeros(1, np.int32)
-        p = L.ms_thetab_boundary_params((ctypes.c_double * 3)(*map(float, center)), (ctypes.c_double * 3)(*map(float, normal)))
-        self._chk(L.lib().ms_set_thetab_boundary(self._h, n, r.ctypes.data_as(L._I32), ctypes.byref(p)),
-                  "ms_set_thetab_boundary")
-        self._thetab_boundary_rows = n
+        r, pr = _i32_table(rows)
+        p = L.ms_thetab_boundary_params(_vec3(center), _vec3(normal))
+        self._chk(L.lib().ms_set_thetab_boundary(self._h, len(r), pr, ctypes.byref(p)), "ms_set_thetab_boundary")
+        self._thetab_boundary_rows = len(r)
 
     def set_tilt_projection(self, cadence: str = "per_step", interval: int = 1):
         """tilt_projection_cadence / tilt_projection_interval of the leaflet relaxation (ms_set_tilt_projection)."""
@@ -935,14 +912,10 @@ class DeviceMesh:
                                           0, None, None, None), "ms_set_pins")
             return
 
-        def i32(v):
-            return np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(-1)) if len(v) else np.zeros(1, np.int32)
-
         prm = np.ascontiguousarray(np.asarray(tables.params, dtype=np.float64).reshape(-1, 7))
-        arrs = [i32(tables.stage_kind), i32(tables.stage_param), i32(tables.stage_off), i32(tables.item_row),
-                i32(tables.item_arg), i32(tables.grad_row), i32(tables.grad_kind), i32(tables.grad_param),
-                i32(tables.avg_param), i32(tables.avg_off), i32(tables.avg_row)]
-        p = [a.ctypes.data_as(L._I32) for a in arrs]
+        arrs, p = zip(*[_i32_table(v) for v in (
+            tables.stage_kind, tables.stage_param, tables.stage_off, tables.item_row, tables.item_arg, tables.grad_row,
+            tables.grad_kind, tables.grad_param, tables.avg_param, tables.avg_off, tables.avg_row)])
         lane = L.MS_PIN_LANE_PROJECT if tables.lane == "project" else L.MS_PIN_LANE_SKIP
         self._chk(L.lib().ms_set_pins(self._h, prm.shape[0], prm.ctypes.data_as(L._D), len(tables.stage_kind),
                                       p[0], p[1], p[2], p[3], p[4], lane, len(tables.grad_row), p[5], p[6], p[7],
@@ -986,9 +959,7 @@ class DeviceMesh:
                 self._chk(L.lib().ms_set_perimeter(self._h, 0, None, None, None, None), "ms_set_perimeter")
             self._perimeter_key = None
             return
-        lo = np.ascontiguousarray(np.asarray(loop_off, dtype=np.int32).reshape(-1))
-        t = np.ascontiguousarray(np.asarray(tail, dtype=np.int32).reshape(-1))
-        h = np.ascontiguousarray(np.asarray(head, dtype=np.int32).reshape(-1))
+        (lo, p_lo), (t, p_t), (h, p_h) = _i32_table(loop_off), _i32_table(tail), _i32_table(head)
         tg = np.ascontiguousarray(np.asarray(target, dtype=np.float64).reshape(-1))
         if len(tg) != len(lo) - 1 or len(t) != len(h) or (len(lo) and int(lo[-1]) != len(t)):
             raise L.MembraneHipError("set_perimeter: loop_off, tail / head and target do not fit together")
@@ -996,8 +967,7 @@ class DeviceMesh:
         if key == self.__dict__.get("_perimeter_key"):
             return
         self._perimeter_key = None
-        i32 = lambda a: (a if len(a) else np.zeros(1, np.int32)).ctypes.data_as(L._I32)  # noqa: E731
-        self._chk(L.lib().ms_set_perimeter(self._h, len(lo) - 1, i32(lo), i32(t), i32(h), _pd(tg)), "ms_set_perimeter")
+        self._chk(L.lib().ms_set_perimeter(self._h, len(lo) - 1, p_lo, p_t, p_h, _pd(tg)), "ms_set_perimeter")
         self._perimeter_key = key
 
     @property

@@ -227,10 +227,18 @@ def test_device_layer_refusals_without_a_device():
         with pytest.raises(ValueError, match=why):
             DeviceMesh.set_tilt_projection(types.SimpleNamespace(), *bad)
     src = open(os.path.join(ROOT, "membrane_solver_amd", "csrc", "ms_api_thetab_bnd.inc")).read()
-    for text in ("is not sharded (single GPU only)", "ring row out of range", "a ring row is listed twice",
-                 "center and normal must be finite", "a non-zero plane normal is required", "interval must be >= 1",
+    for text in ("is not sharded (single GPU only)", "interval must be >= 1",
                  "cadence must be MS_TILT_PROJECTION_PER_STEP or MS_TILT_PROJECTION_PER_PASS"):
         assert text in src, text
+    # the ring's and the plane's refusals are worded once for every ring setter (ms_api_tables.inc); this one hands them
+    # its name and its nouns, which makes "ms_set_thetab_boundary: ring row out of range" and so on
+    shared = open(os.path.join(ROOT, "membrane_solver_amd", "csrc", "ms_api_tables.inc")).read()
+    for text in ('": " + noun + " row out of range"', '": " + a_noun + " row is listed twice"',
+                 '": center and normal must be finite"', '": a non-zero plane normal is required"'):
+        assert text in shared, text
+    assert 'const char* who = "ms_set_thetab_boundary";' in src
+    assert re.search(r'ring_rows\(c, who, "ring", "a ring", nv, c->til\.iperm\.data\(\), n_rows, rows, seen, lib\.data\(\)\)', src)
+    assert "plane_finite(c, who, p->center, p->normal)" in src and "plane_frame(c, who, p->normal, unit)" in src
     # an unknown constraint module
     with pytest.raises(L.MembraneHipError, match="outside the HIP hot path"):
         _minimizer(cons=(NAME, "pins"))
