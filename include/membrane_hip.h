@@ -38,6 +38,7 @@ extern "C" {
 #define MS_ERR_TILE_CAPACITY (-3) /* a vertex patch does not fit LDS / uint16  */
 #define MS_ERR_STATE (-4)         /* call order (e.g. gradient before energy)  */
 #define MS_ERR_NOMEM (-5)
+#define MS_ERR_UNSUPPORTED (-6)   /* a case the device path does not take       */
 
 /* energy-module bits (modules/energy/{surface,bending,volume}.py) */
 #define MS_MOD_SURFACE 1u
@@ -476,6 +477,18 @@ typedef struct ms_tilt_relax_params {
   int jacobi;        /* CG: "tilt_cg_preconditioner" == jacobi */
 } ms_tilt_relax_params;
 int ms_set_tilt_fixed(ms_ctx *ctx, const uint8_t *tilt_fixed /* nv or NULL */);
+/* Rows on which a leaflet is absent (modules/energy/leaflet_presence.py:34-122: the rows whose vertex preset is in
+ * leaflet_<l>_absent_presets), one byte per external row; NULL, or no byte set, clears the mask.  A facet with a corner
+ * on such a row is no part of the outer field (leaflet_present_triangle_mask, :158-170): tilt_out and
+ * tilt_smoothness_out skip it -- energy, shape-gradient and tilt-gradient rows -- and the outer leaflet's vertex areas
+ * of a relaxation (tilt_relaxation.py:681-697) and the k_t A_v part of its Jacobi diagonal are summed over the kept
+ * facets; the smoothness part of the diagonal and the normals keep every facet, as in the reference.  Every other
+ * module reads the field as before.  The rows go through the vertex permutation as ms_set_tilt_fixed's do, and the call
+ * invalidates what ms_set_leaflet_tilts invalidates.  While a mask is set the fused tilt lanes (the search / gradient
+ * passes of a relaxation, the one-tile fused evaluator, the one-launch energy pass) are not selected: the per-module
+ * kernels run, directly or replayed by the interpreter.  leaflet = MS_LEAFLET_IN, and a sharded context, return
+ * MS_ERR_UNSUPPORTED.  MS_MOD_BENDING_TILT_OUT does not read the mask: callers refuse it next to one. */
+int ms_set_leaflet_absent(ms_ctx *ctx, int leaflet, const uint8_t *absent /* nv or NULL */);
 /* gp["tilt_smoothness_rigidity"] of the tilt_smoothness module */
 int ms_set_tilt_smoothness(ms_ctx *ctx, double k_smooth);
 int ms_tilt_energy_and_gradient(ms_ctx *ctx, double *energy, double *tilt_grad);
@@ -506,6 +519,11 @@ typedef struct ms_leaflet_params {
 int ms_set_leaflet_tilts(ms_ctx *ctx, int leaflet, const double *tilts /* nv*3 */,
                          const uint8_t *tilt_fixed /* nv or NULL */, const ms_leaflet_params *params);
 int ms_get_leaflet_tilts(ms_ctx *ctx, int leaflet, double *tilts /* nv*3 */);
+/* Diagnostic, changes nothing: the frozen geometry the last ms_relax_leaflet_tilts left for this leaflet -- its
+ * barycentric vertex areas (under ms_set_leaflet_absent: over the kept facets) and the clamped inverse Jacobi diagonal
+ * (1 everywhere unless the relaxation ran preconditioned CG).  Either output may be NULL.  MS_ERR_STATE before the
+ * leaflet's first relaxation. */
+int ms_get_leaflet_relax_geometry(ms_ctx *ctx, int leaflet, double *vertex_areas /* nv */, double *minv /* nv */);
 /* tilt_disk_target_in / _out: E = 1/2 k int |t - theta(r) r_hat|^2 dA over the tagged disk rows, theta(r) =
  * theta_B I1(lambda r)/I1(lambda R) (30-term series, tilt_disk_target_in.py:148-157) or theta_B r/R when
  * |lambda| < 1e-12; r, r_hat in the plane through `center` with unit `normal`; R = radius, or the largest

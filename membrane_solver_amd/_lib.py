@@ -17,7 +17,7 @@ _CSRC = os.path.join(_PKG, "csrc")
 
 MS_OK = 0
 MS_ERR = {-1: "MS_ERR_INVALID", -2: "MS_ERR_HIP", -3: "MS_ERR_TILE_CAPACITY",
-          -4: "MS_ERR_STATE", -5: "MS_ERR_NOMEM"}
+          -4: "MS_ERR_STATE", -5: "MS_ERR_NOMEM", -6: "MS_ERR_UNSUPPORTED"}
 
 MS_MOD_SURFACE = 1
 MS_MOD_BENDING = 2
@@ -198,6 +198,8 @@ SIGNATURES = {
     "ms_angle_defects": (ctypes.c_int, [_P, _D]),
     "ms_curvature_fields": (ctypes.c_int, [_P, _D, _D, _D, _D]),
     "ms_set_tilt_fixed": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint8)]),
+    "ms_set_leaflet_absent": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8)]),
+    "ms_get_leaflet_relax_geometry": (ctypes.c_int, [_P, ctypes.c_int, _D, _D]),
     "ms_set_tilt_smoothness": (ctypes.c_int, [_P, ctypes.c_double]),
     "ms_set_deterministic": (ctypes.c_int, [_P, ctypes.c_int]),
     "ms_tilt_energy_and_gradient": (ctypes.c_int, [_P, _D, _D]),

@@ -15,6 +15,7 @@
 
 #include "ms_internal.h"
 #include "ms_table_blob.h"
+#include "ms_test_hooks.h"
 
 static void shard_comm_destroy(void* comm);  // (RCCL binding further down)
 

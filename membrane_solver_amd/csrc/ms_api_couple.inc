@@ -37,8 +37,10 @@ int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gr
   a.cell_mode = cell != CPL_CELL_AUTO ? cell : ((modules & (fo.mod_tilt | fo.mod_rs | fo.mod_rb_slot)) ? 1 : 2);
   a.wg_sums = dp;
   // a relaxation in progress: x is frozen and the mode-3 set-up launch left the barycentric vertex areas (the same
-  // doubles in either leaflet's array)
-  const double* va = fo.va ? fo.va : fi.va;
+  // doubles in either leaflet's array -- unless the outer leaflet carries an absence mask: its array then holds the kept
+  // facets' areas, and the coupling is not masked (tilt_coupling.py:160-203 takes every facet), so the inner leaflet's
+  // array is read; both fields are relaxed whenever this module is on)
+  const double* va = fo.absent_bit ? fi.va : (fo.va ? fo.va : fi.va);
   const bool frozen = c->relax_va_valid && !use_dir && !gradient_into_g && va && !c->cpl_force_tile;
   ProfScope ps(c, 6);
   if (frozen) {

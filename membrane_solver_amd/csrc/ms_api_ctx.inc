@@ -106,6 +106,8 @@ struct ms_ctx {
     double k_smooth = 0.0;     // smoothness rigidity of the energy
     double k_smooth_precond = 0.0;  // rigidity entering the Jacobi diagonal
     uint8_t fixed_bit = 0;     // vertex flag bit that clamps a row of this field
+    uint8_t absent_bit = 0;    // vertex flag bit of the rows this leaflet is absent on; 0 while no row carries it
+                               // (ms_set_leaflet_absent)
     uint32_t mod_tilt = 0, mod_smooth = 0, mod_bt = 0;  // module bits that read this field
     int s_etilt = 0, s_ets = 0, s_gn2 = 0, s_rz = 0, s_ebt = 0;  // reduction slots
     // leaflet bending_tilt: per-vertex (kappa, c0), the per-vertex record of the last energy pass

@@ -229,7 +229,7 @@ int active_fields(ms_ctx* c, uint32_t mods, TiltField* out[3]) {
 // planes of x (+ alpha d) and writes `dst`.
 int tilt_pass_f(ms_ctx* c, TiltField& f, int mode, bool use_dir, double alpha, const double* src = nullptr,
                 double* dst = nullptr, bool shape_gradient = true, bool lumped = false, double k_override = -1.0,
-                int slot_override = -1, bool tg_accumulate = false) {
+                int slot_override = -1, bool tg_accumulate = false, bool masked = true) {
   if (!f.tilts) return fail(c, MS_ERR_STATE, "tilt module active but its tilt field was never set (ms_set_tilts / ms_set_leaflet_tilts)");
   TiltArgs a;
   a.fields = nullptr;
@@ -252,6 +252,7 @@ int tilt_pass_f(ms_ctx* c, TiltField& f, int mode, bool use_dir, double alpha, c
   a.tg_accumulate = tg_accumulate ? 1 : 0;
   a.cons_tilt_grad = (a.consistent && c->tilt_module_form) ? 1 : 0;
   a.va_out = nullptr;
+  a.absent_bit = (masked && mode != 2) ? f.absent_bit : 0;  // (the magnitude module's facets; the projection reads none)
   {
     ProfScope ps(c, 4);
     HIPCHK(c, launch_tilt(a, mode, c->cap, c->til.max_ent, c->stream));
@@ -322,6 +323,7 @@ int ts_pass_f(ms_ctx* c, TiltField& f, int mode, bool use_dir, double alpha, con
   a.diag = diag;
   a.partials = c->d_partials;
   a.e_slot = f.s_ets;
+  a.absent_bit = mode == 2 ? 0 : f.absent_bit;  // (the Jacobi diagonal keeps every facet: preconditioners.py:121-140)
   {
     ProfScope ps(c, 11);
     HIPCHK(c, launch_ts(a, mode, c->cap, c->til.max_ent, c->stream));
@@ -387,7 +389,7 @@ int disk_target_pass(ms_ctx* c, TiltField& f, int mode, bool use_dir, double alp
     HIPCHK(c, launch_disk_target(a, frozen ? 3 : 1, c->stream));
   }
   return tilt_pass_f(c, f, mode, use_dir, alpha, f.diff, nullptr, shape_gradient, /*lumped=*/true, f.dt.strength,
-                     f.s_edt, tilt_gradient);
+                     f.s_edt, tilt_gradient, /*masked=*/false);  // (tilt_disk_target_in/out never read the absence mask)
 }
 constexpr uint32_t MASK_GRAD = (1u << MS_S_GGC) | (1u << MS_S_GCGC);
 constexpr uint32_t MASK_DIR = (1u << MS_S_GNORM2) | (1u << MS_S_GDOTD) | (1u << MS_S_MAXD2) | (1u << MS_S_MAXG2);
@@ -575,6 +577,7 @@ int tilt_energy_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bo
     // (a disk target keeps its own passes -- the difference field and the magnitude kernel on it -- next to this one)
     if (!(tilt_on || bt_on || ts_on)) continue;
     if (nf == 2 || !f.tilts) return MS_OK;
+    if (f.absent_bit && (tilt_on || ts_on)) return MS_OK;  // an absence mask: k_tilt<0> / k_tsmooth<0> honour it, this pass does not
     if (tilt_on && (f.consistent || (single && !(bt_on && f.k_tilt != 0.0)))) return MS_OK;
     TsearchField& o = a.f[nf++];
     o.tilts = use_dir ? f.trial : f.tilts;

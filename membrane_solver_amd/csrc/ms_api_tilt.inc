@@ -133,6 +133,8 @@ double tilt_energy_from_mailbox(const ms_ctx* c) { return tilt_energy_from(c, c-
 bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs* a, uint32_t* mask) {
   const uint32_t mods = c->params.modules;
   if (!c->tsearch_enable || nf < 1 || nf > 2 || !c->d_tn) return false;
+  for (int k = 0; k < nf; ++k)
+    if (fl[k]->absent_bit) return false;  // an absence mask: the launch-per-module passes honour it, k_tsearch / k_tgrad do not
   *mask = 0;
   for (int k = 0; k < nf; ++k) {
     TiltField& f = *fl[k];
@@ -323,7 +325,9 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
     return MS_OK;
   };
   // ---- leaflet fields, frozen surface, LDS-atomic contexts: the fused evaluator (ms_relax_fused.inc) ----------------
-  if (c->exec_fused && c->relax_va_valid && !c->deterministic && c->d_tn) {
+  bool absent = false;  // an absence mask: the fused evaluator does not honour it, the captured program's bodies do
+  for (int k = 0; k < nf; ++k) absent = absent || fl[k]->absent_bit != 0;
+  if (!absent && c->exec_fused && c->relax_va_valid && !c->deterministic && c->d_tn) {
     const uint32_t mods = c->params.modules;
     ExecRelaxFusedArgs a;
     memset(&a, 0, sizeof(a));
@@ -628,6 +632,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
       a.proj_out = f.trial;
       a.finish_minv = smooth_diag ? 0 : 1;
       a.fixed_bit = f.fixed_bit;
+      a.absent_bit = f.absent_bit;
       if (nf == 2 && k == 0) {  // both fields of the relaxation in this one launch (same normals, same vertex areas)
         TiltField& fb = *fl[1];
         const double ksb = jacobi_smooth_by_param ? fb.k_smooth_precond : fb.k_smooth;
@@ -638,6 +643,7 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
         a.k_tilt_b = (rp->solver == 1 && rp->jacobi) ? fb.k_tilt : 0.0;
         a.finish_minv_b = (rp->solver == 1 && rp->jacobi && ksb != 0.0) ? 0 : 1;
         a.fixed_bit_b = fb.fixed_bit;
+        a.absent_bit_b = fb.absent_bit;
       }
       if (!(nf == 2 && k == 1)) HIPCHK(c, launch_tilt(a, 3, c->cap, t.max_ent, c->stream));
       if (smooth_diag) {
@@ -960,6 +966,53 @@ int ms_set_leaflet_tilts(ms_ctx* c, int leaflet, const double* tilts, const uint
   return ext_to_patch(c, tilts, f.tilts, 3);
 }
 
+namespace {
+// flags[i] of library row i takes VF_ABSENT_OUT from absent[perm[i]] (NULL: from nobody) and keeps its other bits
+// -> 1 some flag changed | 2 some row carries the bit
+int absent_flags_apply(int nv, const int32_t* perm, const uint8_t* absent, uint8_t* flags) {
+  int r = 0;
+  for (int i = 0; i < nv; ++i) {
+    uint8_t fl = flags[i] & (uint8_t)~VF_ABSENT_OUT;
+    if (absent && absent[perm[i]]) fl |= VF_ABSENT_OUT;
+    if (fl & VF_ABSENT_OUT) r |= 2;
+    if (fl != flags[i]) r |= 1;
+    flags[i] = fl;
+  }
+  return r;
+}
+}  // namespace
+
+int ms_leaflet_absent_flags_host(int nv, const int32_t* perm, const uint8_t* absent, uint8_t* flags, int* state) {
+  if (nv < 0 || (nv > 0 && (!perm || !flags))) return fail(nullptr, MS_ERR_INVALID, "ms_leaflet_absent_flags_host: bad argument");
+  for (int i = 0; i < nv; ++i)
+    if (perm[i] < 0 || perm[i] >= nv) return fail(nullptr, MS_ERR_INVALID, "ms_leaflet_absent_flags_host: permutation out of range");
+  const int r = absent_flags_apply(nv, perm, absent, flags);
+  if (state) *state = r;
+  return MS_OK;
+}
+
+// Rows the outer leaflet is absent on (leaflet_presence.py:34-122), through the vertex permutation as ms_set_tilt_fixed
+// takes its flags; NULL clears.  No per-facet array: a facet is masked when one of its corners carries VF_ABSENT_OUT.
+int ms_set_leaflet_absent(ms_ctx* c, int leaflet, const uint8_t* absent) {
+  if (!c) return fail(c, MS_ERR_INVALID, "ms_set_leaflet_absent: NULL context");
+  if (leaflet == MS_LEAFLET_IN)
+    return fail(c, MS_ERR_UNSUPPORTED, "ms_set_leaflet_absent: an absent inner leaflet is outside the device path");
+  if (leaflet != MS_LEAFLET_OUT)
+    return fail(c, MS_ERR_INVALID, "ms_set_leaflet_absent: leaflet must be MS_LEAFLET_IN or MS_LEAFLET_OUT");
+  if (c->shard_count != 1) return fail(c, MS_ERR_UNSUPPORTED, "ms_set_leaflet_absent: tilt passes are single-shard only");
+  TiltField& f = c->tf[1 + leaflet];
+  const Tiling& t = c->til;
+  const int state = absent_flags_apply(t.nv, t.perm.data(), absent, c->h_vflags.data());
+  f.absent_bit = (state & 2) ? VF_ABSENT_OUT : 0;
+  if (state & 1) {
+    HIPCHK(c, hipStreamSynchronize(S(c)));
+    HIPCHK(c, hipMemcpy(c->d_vflags, c->h_vflags.data(), c->h_vflags.size(), hipMemcpyHostToDevice));
+  }
+  c->carry.invalidate_with_bt();
+  c->sh_carry_valid = c->sh_grad_valid = false;
+  return MS_OK;
+}
+
 int ms_set_leaflet_bending(ms_ctx* c, int leaflet, const double* kappa, const double* c0) {
   if (!c || !kappa || !c0) return fail(c, MS_ERR_INVALID, "ms_set_leaflet_bending: NULL argument");
   if (leaflet != MS_LEAFLET_IN && leaflet != MS_LEAFLET_OUT)
@@ -1012,6 +1065,17 @@ int ms_get_leaflet_tilts(ms_ctx* c, int leaflet, double* tilts) {
   if (!c || !tilts || (leaflet != MS_LEAFLET_IN && leaflet != MS_LEAFLET_OUT) || !c->tf[1 + leaflet].tilts)
     return fail(c, MS_ERR_INVALID, "ms_get_leaflet_tilts: bad leaflet / no tilts set");
   return patch_to_ext(c, c->tf[1 + leaflet].tilts, tilts, 3);
+}
+
+int ms_get_leaflet_relax_geometry(ms_ctx* c, int leaflet, double* vertex_areas, double* minv) {
+  if (!c || (leaflet != MS_LEAFLET_IN && leaflet != MS_LEAFLET_OUT))
+    return fail(c, MS_ERR_INVALID, "ms_get_leaflet_relax_geometry: bad leaflet");
+  const TiltField& f = c->tf[1 + leaflet];
+  if (!f.va || !f.minv) return fail(c, MS_ERR_STATE, "ms_get_leaflet_relax_geometry: this leaflet was never relaxed");
+  if (vertex_areas)
+    if (int rc = patch_to_ext(c, f.va, vertex_areas, 1)) return rc;
+  if (minv) return patch_to_ext(c, f.minv, minv, 1);
+  return MS_OK;
 }
 
 namespace {

@@ -64,6 +64,7 @@ constexpr uint8_t VF_BOUNDARY = 2;
 constexpr uint8_t VF_TILT_FIXED = 4;  // vertex.tilt_fixed (runtime/minimizer_helpers.py:49-75)
 constexpr uint8_t VF_TILT_FIXED_IN = 8;    // vertex.tilt_fixed_in  (minimizer.py:460-472)
 constexpr uint8_t VF_TILT_FIXED_OUT = 16;  // vertex.tilt_fixed_out (minimizer.py:474-486)
+constexpr uint8_t VF_ABSENT_OUT = 32;      // the outer leaflet is absent on this row (leaflet_presence.py:34-122)
 
 // LDS bank model of one lane order (lane_order_model): per aligned lane group and corner slot k, the number of "ways"
 // (serialised passes) of the instruction the group issues.
@@ -263,6 +264,12 @@ struct TiltArgs {
   double k_tilt_b = 0.0;
   int finish_minv_b = 0;
   int fixed_bit_b = 0;
+  // leaflet absence (leaflet_presence.py:158-170): a facet with a corner that carries this flag bit is no part of the
+  // field.  Modes 0 / 1: it adds no energy, no shape-gradient and no tilt-gradient rows (tilt_leaflet.py:77-167).  Mode
+  // 3: the field's vertex areas -- va_out and the diagonal -- skip it (tilt_relaxation.py:681-697); the normals do
+  // not.  0 = no mask: the flag bytes are not staged and nothing else changes.
+  int absent_bit = 0;
+  int absent_bit_b = 0;
 };
 
 struct DiskTargetArgs {   // tilt_disk_target_in.py:160-286
@@ -317,6 +324,8 @@ struct TsArgs {
   double* diag;            // mode 2: Jacobi diagonal 1/2 k_s sum (c_a + c_b) ADDED here
   double* partials;
   int e_slot;              // reduction slot of the energy partial (MS_S_ETS / _IN / _OUT)
+  int absent_bit = 0;      // modes 0 / 1: facets with a corner that carries this flag bit drop out with their weights
+                           // (tilt_smoothness_utils.py:57-68); 0 = no mask
 };
 
 // stream kernels (one workgroup of BLOCK threads per tile): their arguments as structs, so that the same device body
@@ -910,6 +919,8 @@ GradientInst gradient_instance(const GradientArgs& a);
 bool gradient_lean_instance(const GradientArgs& a);  // gradient_instance(a).lean
 // mode 0: energy partial (MS_S_ETILT); 1: energy + gradients; 2: project tilts to tangent
 size_t tilt_lds_bytes(int T, int cap, int max_ent, bool consistent = false, int mode = 1);
+// (a launch with an absence mask stages one flag byte per patch row behind the kernel's own LDS)
+inline size_t absent_lds_bytes(int cap) { return ((size_t)cap + 7) & ~(size_t)7; }
 hipError_t launch_tilt(const TiltArgs& a, int mode, int cap, int max_ent, hipStream_t s);
 // bending_tilt facet pass.  mode 0: energy (MS_S_EBT); 1: energy + back-prop factors;
 // 2: energy + tilt gradient

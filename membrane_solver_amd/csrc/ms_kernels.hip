@@ -1900,7 +1900,9 @@ hipError_t launch_gradient(const GradientArgs& a_in, int cap, int max_ent, hipSt
 //           t <- t - (t.n) n on the owned rows.
 // LDS: px[3][cap] | tq[cap] | stg[10][T] | red[16] | voff, vent (u16)
 // ---------------------------------------------------------------------------
-template <int MODE>
+// MASK 0: the launch carries no absence mask -- nothing of it is compiled in (the kernels of an unmasked launch);
+// MASK 2: the arguments decide at run time (masked launches, and the interpreter, which replays both kinds)
+template <int MODE, int MASK = 2>
 __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_ent, double* lds, int block_id) {
   const int T = a.m.T;
   double* px = lds;
@@ -1912,6 +1914,10 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
   double* red = stg + (MODE == 0 ? 0 : 10 * T);
   uint16_t* voff = reinterpret_cast<uint16_t*>(red + 16);
   uint16_t* vent = voff + (T + 2);
+  // leaflet absence (modes 0, 1, 3; uniform over the launch): one flag byte per patch row behind everything else
+  // (absent_lds_bytes), staged with the rows, halo rows included -- a facet is masked when a corner carries the bit
+  const int abit = MASK == 0 ? 0 : ((MODE == 0 || MODE == 1) ? a.absent_bit : (MODE == 3 ? (a.absent_bit | a.absent_bit_b) : 0));
+  uint8_t* lab = MODE == 0 ? reinterpret_cast<uint8_t*>(red + 16) : reinterpret_cast<uint8_t*>(vent + (max_ent + 8));
 
   const TileCtx t = tile_ctx(a.m, a.tile0 + xcd_tile(block_id, a.tile1 - a.tile0));
   const int tid = threadIdx.x;
@@ -1926,6 +1932,7 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
   {
     struct Row {
       double x0, x1, x2, t0, t1, t2;
+      uint8_t fl;
     };
     auto load_row = [&](int v) {
       Row r;
@@ -1945,6 +1952,7 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
       r.t0 = a.tilts[g];
       r.t1 = a.tilts[g + 1];
       r.t2 = a.tilts[g + 2];
+      r.fl = abit ? fl : 0;
       return r;
     };
     auto put_row = [&](const Row& r, int sl) {
@@ -1958,6 +1966,7 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
         tl[cap + sl] = r.t1;
         tl[2 * cap + sl] = r.t2;
       }
+      if (abit) lab[sl] = r.fl;
     };
     const bool own = tid < t.n_owned, has_h = tid < t.nh;
     int hv = 0;
@@ -1983,6 +1992,7 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
 
   double e_tilt = 0.0;
   double ax = 0, ay = 0, az = 0, aw = 0;  // vertex accumulators: gradient / normal (xyz), area (w)
+  double awm = 0;                          // mode 3 with an absence mask: the area over the kept facets
   int cur = 0, end = 0;
   if (MODE != 0 && tid < t.n_owned) {
     cur = voff[tid];
@@ -2005,6 +2015,8 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
       const V3 n = cross(e2, -e1);
       const double A2 = norm(n);
       double* s = stg + tid;
+      bool kept = true;  // (leaflet_present_triangle_mask: none of the three rows absent)
+      if (abit) kept = !((lab[tf.l0] | lab[tf.l1] | lab[tf.l2]) & abit);
       if (MODE == 5) {
         // compute_curvature_data (tilt_kernels.f90:133-181): cotans with area_doubled = max(|n|, 1e-12), the
         // integrated curvature vectors K_k and the mixed-Voronoi corner areas; angles as in MODE 4
@@ -2039,11 +2051,14 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
         s[0 * T] = n.x;
         s[1 * T] = n.y;
         s[2 * T] = n.z;
-        if (MODE == 3) s[9 * T] = (0.5 * A2) / 3.0;
+        if (MODE == 3) {
+          s[9 * T] = (0.5 * A2) / 3.0;
+          if (abit) s[8 * T] = kept ? (0.5 * A2) / 3.0 : 0.0;  // the masked field's thirds (tilt_relaxation.py:685-697)
+        }
       } else {
         V3 G0 = mk(0, 0, 0), G1 = mk(0, 0, 0), G2 = mk(0, 0, 0);
         double a3 = 0.0;
-        if (A2 >= 1.0e-12) {
+        if (A2 >= 1.0e-12 && kept) {
           const double area = 0.5 * A2;
           const double sq = (tq[tf.l0] + tq[tf.l1]) + tq[tf.l2];
           double coeff = 0.5 * a.k_tilt * (sq / 3.0);
@@ -2095,7 +2110,10 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
           ax += s[0];
           ay += s[T];
           az += s[2 * T];
-          if (MODE == 3) aw += s[9 * T];
+          if (MODE == 3) {
+            aw += s[9 * T];
+            if (abit) awm += s[8 * T];
+          }
         } else {
           const int k = ent & 3;
           ax += s[(3 * k) * T];
@@ -2195,15 +2213,18 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
       a.tilts_out[o] = nrm.x;
       a.tilts_out[o + 1] = nrm.y;
       a.tilts_out[o + 2] = nrm.z;
+      // (a masked field takes the kept facets' areas, in va_out and in the k_t A_v part of the diagonal -- the smoothness
+      // part of the diagonal is not masked, preconditioners.py:106-140; a row without a kept facet gets the clamp)
+      const double aw_a = (MASK != 0 && a.absent_bit) ? awm : aw, aw_b = (MASK != 0 && a.absent_bit_b) ? awm : aw;
       if (a.minv) {  // raw diagonal (k_tvec mode 3 clamps and inverts), or finished here
-        double dg = a.k_tilt * aw;
+        double dg = a.k_tilt * aw_a;
         if (a.finish_minv) {
           if (!(dg > 1.0e-12) || (a.m.vflags[t.v_lo + tid] & a.fixed_bit)) dg = 1.0;
           dg = 1.0 / dg;
         }
         a.minv[t.v_lo + tid] = dg;
       }
-      if (a.va_out) a.va_out[t.v_lo + tid] = aw;         // barycentric vertex area (mesh.py:671-730)
+      if (a.va_out) a.va_out[t.v_lo + tid] = aw_a;       // barycentric vertex area (mesh.py:671-730)
 #pragma unroll
       for (int k = 0; k < 2; ++k)
         if (a.fld_in[k] != nullptr) {  // (MODE 2's projection, expression for expression)
@@ -2221,14 +2242,14 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
       }
       // the second field of the relaxation: the same three outputs
       if (a.minv_b) {
-        double dg = a.k_tilt_b * aw;
+        double dg = a.k_tilt_b * aw_b;
         if (a.finish_minv_b) {
           if (!(dg > 1.0e-12) || (a.m.vflags[t.v_lo + tid] & a.fixed_bit_b)) dg = 1.0;
           dg = 1.0 / dg;
         }
         a.minv_b[t.v_lo + tid] = dg;
       }
-      if (a.va_out_b) a.va_out_b[t.v_lo + tid] = aw;
+      if (a.va_out_b) a.va_out_b[t.v_lo + tid] = aw_b;
       if (a.proj_out_b) {
         const V3 tb = mk(a.tilts_b[o], a.tilts_b[o + 1], a.tilts_b[o + 2]);
         const V3 r = tilt_trial_row(tb, tb, nrm, 0.0);
@@ -2246,10 +2267,10 @@ __device__ __forceinline__ void tilt_body(const TiltArgs& a, int cap, int max_en
   }
 }
 
-template <int MODE>
+template <int MODE, int MASK>
 __global__ __launch_bounds__(512) void k_tilt(TiltArgs a, int cap, int max_ent) {
   extern __shared__ double lds[];
-  tilt_body<MODE>(a, cap, max_ent, lds, (int)blockIdx.x);
+  tilt_body<MODE, MASK>(a, cap, max_ent, lds, (int)blockIdx.x);
 }
 
 size_t tilt_lds_bytes(int T, int cap, int max_ent, bool consistent, int mode) {
@@ -2261,10 +2282,15 @@ size_t tilt_lds_bytes(int T, int cap, int max_ent, bool consistent, int mode) {
 hipError_t launch_tilt(const TiltArgs& a, int mode, int cap, int max_ent, hipStream_t s) {
   const int nb = a.tile1 - a.tile0;
   if (nb <= 0) return hipSuccess;
-  const size_t lds = tilt_lds_bytes(a.m.T, cap, max_ent, (mode == 0 || mode == 1) && a.consistent, mode);
+  size_t lds = tilt_lds_bytes(a.m.T, cap, max_ent, (mode == 0 || mode == 1) && a.consistent, mode);
+  const bool masked = ((mode == 0 || mode == 1) && a.absent_bit) || (mode == 3 && (a.absent_bit | a.absent_bit_b));
+  if (masked) lds += absent_lds_bytes(cap);
   if (ExecRecorder* r = exec_find(s)) return r->push(CK_TILT, mode, cap, max_ent, nb, 0, lds, &a, sizeof(a), &a.m);
   return pick_int<0, 1, 2, 3, 4, 5>(mode, [&](auto M) {
-    return launch(k_tilt<decltype(M)::value>, nb, a.m.T, lds, s, a, cap, max_ent);
+    constexpr int MD = decltype(M)::value;
+    if constexpr (MD == 0 || MD == 1 || MD == 3)
+      if (masked) return launch(k_tilt<MD, 2>, nb, a.m.T, lds, s, a, cap, max_ent);
+    return launch(k_tilt<MD, 0>, nb, a.m.T, lds, s, a, cap, max_ent);
   });
 }
 
@@ -2535,7 +2561,12 @@ hipError_t launch_bt(const BtArgs& a, int mode, int cap, int max_ent, hipStream_
 //   MODE 2: Jacobi diagonal k_s/2 (c_a + c_b) per corner (runtime/preconditioners.py:42-57), ADDED
 // LDS: px[3][cap] | tl[3][cap] | stg[9][T] (red aliases it) | vent
 // ---------------------------------------------------------------------------
-template <int MODE>
+// (k_tsmooth's LDS bytes without the absence flags, which lie behind them)
+__host__ __device__ inline size_t ts_lds_bytes_dev(int T, int cap, int max_ent) {
+  return (6 * (size_t)cap + 9 * (size_t)T) * sizeof(double) + 2 * ((size_t)((max_ent + 3) & ~3)) + 64;
+}
+// (MASK as in tilt_body: 0 compiles the absence mask out, 2 reads the arguments)
+template <int MODE, int MASK = 2>
 __device__ __forceinline__ void ts_body(const TsArgs& a, int cap, int max_ent, double* lds, int block_id) {
   const int T = a.m.T;
   double* px = lds;
@@ -2543,6 +2574,10 @@ __device__ __forceinline__ void ts_body(const TsArgs& a, int cap, int max_ent, d
   double* stg = tl + 3 * cap;
   double* red = stg;
   uint16_t* vent = reinterpret_cast<uint16_t*>(stg + 9 * T);
+  // leaflet absence (modes 0 / 1; uniform over the launch): one flag byte per patch row behind everything else
+  // (absent_lds_bytes), staged with the rows, halo rows included
+  const int abit = (MODE == 2 || MASK == 0) ? 0 : a.absent_bit;
+  uint8_t* lab = reinterpret_cast<uint8_t*>(lds) + ts_lds_bytes_dev(T, cap, max_ent);
 
   const TileCtx t = tile_ctx(a.m, a.tile0 + xcd_tile(block_id, a.tile1 - a.tile0));
   const int tid = threadIdx.x;
@@ -2554,6 +2589,7 @@ __device__ __forceinline__ void ts_body(const TsArgs& a, int cap, int max_ent, d
     if (MODE != 0) csr_issue(cs, a.m, t, T, tid);
     struct Row {
       double x0, x1, x2, t0, t1, t2;
+      uint8_t fl;
     };
     auto load_row = [&](int v) {
       Row r;
@@ -2572,6 +2608,7 @@ __device__ __forceinline__ void ts_body(const TsArgs& a, int cap, int max_ent, d
       r.t0 = a.tilts[g];
       r.t1 = a.tilts[g + 1];
       r.t2 = a.tilts[g + 2];
+      r.fl = abit ? a.m.vflags[v] : 0;
       return r;
     };
     auto put_row = [&](const Row& r, int sl) {
@@ -2581,6 +2618,7 @@ __device__ __forceinline__ void ts_body(const TsArgs& a, int cap, int max_ent, d
       tl[sl] = r.t0;
       tl[cap + sl] = r.t1;
       tl[2 * cap + sl] = r.t2;
+      if (abit) lab[sl] = r.fl;
     };
     const bool has_h = tid < t.nh;
     int hv = 0;
@@ -2616,6 +2654,8 @@ __device__ __forceinline__ void ts_body(const TsArgs& a, int cap, int max_ent, d
       const double inv_ad = 1.0 / ad;
       const double c0 = dot(-e1, e2) * inv_ad, c1 = dot(-e2, e0) * inv_ad, c2 = dot(-e0, e1) * inv_ad;
       double* s = stg + tid;
+      // (tilt_smoothness_utils.py:57-68: a facet that touches an absent row drops out with its weights)
+      const bool kept = !abit || !((lab[tf.l0] | lab[tf.l1] | lab[tf.l2]) & abit);
       if (MODE == 2) {
         s[0 * T] = hk * (c1 + c2);
         s[1 * T] = hk * (c2 + c0);
@@ -2623,13 +2663,14 @@ __device__ __forceinline__ void ts_body(const TsArgs& a, int cap, int max_ent, d
       } else {
         const V3 t0 = lds_v3(tl, cap, tf.l0), t1 = lds_v3(tl, cap, tf.l1), t2 = lds_v3(tl, cap, tf.l2);
         const V3 d12 = t1 - t2, d20 = t2 - t0, d01 = t0 - t1;
-        if (tf.flags & TF_OWNER)
+        if ((tf.flags & TF_OWNER) && kept)
           e_ts += 0.25 * a.k_smooth * ((c0 * dot(d12, d12) + c1 * dot(d20, d20)) + c2 * dot(d01, d01));
         if (MODE == 1) {
           // g0 = k/2 (c1 (t0-t2) + c2 (t0-t1)), g1 = k/2 (c2 (t1-t0) + c0 (t1-t2)), g2 = k/2 (c0 (t2-t1) + c1 (t2-t0))
-          const V3 g0 = hk * (c2 * d01 - c1 * d20);
-          const V3 g1 = hk * (c0 * d12 - c2 * d01);
-          const V3 g2 = hk * (c1 * d20 - c0 * d12);
+          const double hm = kept ? hk : 0.0;
+          const V3 g0 = hm * (c2 * d01 - c1 * d20);
+          const V3 g1 = hm * (c0 * d12 - c2 * d01);
+          const V3 g2 = hm * (c1 * d20 - c0 * d12);
           s[0 * T] = g0.x; s[1 * T] = g0.y; s[2 * T] = g0.z;
           s[3 * T] = g1.x; s[4 * T] = g1.y; s[5 * T] = g1.z;
           s[6 * T] = g2.x; s[7 * T] = g2.y; s[8 * T] = g2.z;
@@ -2677,23 +2718,25 @@ __device__ __forceinline__ void ts_body(const TsArgs& a, int cap, int max_ent, d
   }
 }
 
-template <int MODE>
+template <int MODE, int MASK>
 __global__ __launch_bounds__(512) void k_tsmooth(TsArgs a, int cap, int max_ent) {
   extern __shared__ double lds[];
-  ts_body<MODE>(a, cap, max_ent, lds, (int)blockIdx.x);
+  ts_body<MODE, MASK>(a, cap, max_ent, lds, (int)blockIdx.x);
 }
 
-size_t ts_lds_bytes(int T, int cap, int max_ent) {
-  return (6 * (size_t)cap + 9 * (size_t)T) * sizeof(double) + 2 * ((size_t)((max_ent + 3) & ~3)) + 64;
-}
+size_t ts_lds_bytes(int T, int cap, int max_ent) { return ts_lds_bytes_dev(T, cap, max_ent); }
 
 hipError_t launch_ts(const TsArgs& a, int mode, int cap, int max_ent, hipStream_t s) {
   const int nb = a.tile1 - a.tile0;
   if (nb <= 0) return hipSuccess;
-  const size_t lds = ts_lds_bytes(a.m.T, cap, max_ent);
+  const bool masked = mode != 2 && a.absent_bit;
+  const size_t lds = ts_lds_bytes(a.m.T, cap, max_ent) + (masked ? absent_lds_bytes(cap) : 0);
   if (ExecRecorder* r = exec_find(s)) return r->push(CK_TS, mode, cap, max_ent, nb, 0, lds, &a, sizeof(a), &a.m);
   return pick_int<0, 1, 2>(mode, [&](auto M) {
-    return launch(k_tsmooth<decltype(M)::value>, nb, a.m.T, lds, s, a, cap, max_ent);
+    constexpr int MD = decltype(M)::value;
+    if constexpr (MD != 2)
+      if (masked) return launch(k_tsmooth<MD, 2>, nb, a.m.T, lds, s, a, cap, max_ent);
+    return launch(k_tsmooth<MD, 0>, nb, a.m.T, lds, s, a, cap, max_ent);
   });
 }
 

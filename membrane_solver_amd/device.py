@@ -322,6 +322,20 @@ class DeviceMesh:
                                  float(smoothness if precond_smoothness is None else precond_smoothness))
         self._chk(L.lib().ms_set_leaflet_tilts(self._h, lf, _pd(arr), ptr, ctypes.byref(lp)), "ms_set_leaflet_tilts")
 
+    def set_leaflet_absent(self, leaflet: str, absent=None):
+        """Rows the leaflet is absent on (leaflet_presence.py:34-122; None clears them): tilt_out and
+        tilt_smoothness_out skip every facet that touches one, a relaxation's outer vertex areas are the kept facets'.
+        Only the outer leaflet has a mask on the device (include/membrane_hip.h, ms_set_leaflet_absent)."""
+        lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]
+        if absent is None:
+            ptr = None
+        else:
+            arr = np.ascontiguousarray(np.asarray(absent, dtype=bool).astype(np.uint8))
+            if arr.shape != (self.nv,):
+                raise ValueError("absent must have shape (nv,)")
+            ptr = arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        self._chk(L.lib().ms_set_leaflet_absent(self._h, lf, ptr), "ms_set_leaflet_absent")
+
     def set_leaflet_bending(self, leaflet: str, kappa, c0):
         """Per-vertex (kappa, c0) of bending_tilt_in / bending_tilt_out."""
         lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]
@@ -590,6 +604,14 @@ class DeviceMesh:
         self._chk(L.lib().ms_relax_leaflet_tilts(self._h, ctypes.byref(rp), ctypes.byref(it), ctypes.byref(ev)),
                   "ms_relax_leaflet_tilts")
         return int(it.value), int(ev.value)
+
+    def leaflet_relax_geometry(self, leaflet: str):
+        """-> (vertex areas (nv,), clamped inverse Jacobi diagonal (nv,)) the last relax_leaflet_tilts left for this
+        leaflet (include/membrane_hip.h, ms_get_leaflet_relax_geometry)."""
+        lf = {"in": L.MS_LEAFLET_IN, "out": L.MS_LEAFLET_OUT}[leaflet]
+        va, minv = np.empty(self.nv, dtype=np.float64), np.empty(self.nv, dtype=np.float64)
+        self._chk(L.lib().ms_get_leaflet_relax_geometry(self._h, lf, _pd(va), _pd(minv)), "ms_get_leaflet_relax_geometry")
+        return va, minv
 
     def angle_defects(self) -> np.ndarray:
         """Per-vertex angle defects (integrated Gaussian curvature) at the current positions."""

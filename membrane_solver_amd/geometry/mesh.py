@@ -374,19 +374,34 @@ class HipMirror:
             self.dm.set_tilts(tilts, k_t)
             self._tilt_key = key
 
-    def upload_leaflets(self, params: dict):
-        """Mesh.tilts_in_view()/tilts_out_view(), the tilt_fixed_in/out flags and the per-leaflet module
-        parameters (``params[leaflet]`` = kwargs of DeviceMesh.set_leaflet_tilts)."""
+    def upload_leaflets(self, params: dict, absent_out=None):
+        """Mesh.tilts_in_view()/tilts_out_view(), the tilt_fixed_in/out flags, the per-leaflet module
+        parameters (``params[leaflet]`` = kwargs of DeviceMesh.set_leaflet_tilts) and the rows the outer leaflet is
+        absent on (``absent_out``: (nv,) bool or None, leaflet_common.absent_mask)."""
         for lf in ("in", "out"):
             view = getattr(self.mesh, f"tilts_{lf}_view", None)
             tilts = (np.zeros((len(self.mesh.vertex_ids), 3)) if view is None
                      else np.ascontiguousarray(view(), dtype=np.float64))
             mask = tilt_fixed_mask(self.mesh, f"tilt_fixed_{lf}")
+            absent = None
+            if lf == "out" and absent_out is not None and np.any(absent_out):
+                absent = np.asarray(absent_out, dtype=bool)
+            # (element 4 is the field's checksum: mark_device_leaflets_current rewrites it; the mask rides in element 3)
             key = (self._topo_key, getattr(self.mesh, "_tilts_version", None), tuple(sorted(params[lf].items())),
-                   mask.tobytes(), None if hasattr(self.mesh, "_tilts_version") else float(np.sum(tilts)))
+                   mask.tobytes() + (b"" if absent is None else b"|absent|" + absent.tobytes()),
+                   None if hasattr(self.mesh, "_tilts_version") else float(np.sum(tilts)))
             if key != self._leaflet_keys.get(lf):
                 self.dm.set_leaflet_tilts(lf, tilts, tilt_fixed=mask if mask.any() else None, **params[lf])
+                if lf == "out":
+                    self.set_absent_out(absent)
                 self._leaflet_keys[lf] = key
+
+    def set_absent_out(self, absent):
+        """The outer leaflet's absence mask ((nv,) bool with a row set, or None) on the current context; a mask of an
+        earlier configuration of this context is replaced or cleared, a context that never had one is left alone."""
+        if absent is not None or getattr(self, "_absent_set_on", None) is self.dm:
+            self.dm.set_leaflet_absent("out", absent)
+            self._absent_set_on = self.dm if absent is not None else None
 
     def mark_device_leaflets_current(self):
         for lf, key in list(self._leaflet_keys.items()):

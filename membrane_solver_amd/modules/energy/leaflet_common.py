@@ -45,8 +45,155 @@ def _get(param_resolver, global_params, key):
     return val
 
 
-def check_supported(global_params) -> None:
+def normalize_preset_list(raw) -> list:
+    """_normalize_preset_list (leaflet_presence.py:16-31): a string is one preset, a list / tuple / set its stripped,
+    non-empty items, anything else nothing."""
+    if raw is None:
+        return []
+    if isinstance(raw, str):
+        val = raw.strip()
+        return [val] if val else []
+    if isinstance(raw, (list, tuple, set)):
+        return [s for s in (str(item).strip() for item in raw if item is not None) if s]
+    return []
+
+
+def vertex_options_by_row(mesh) -> dict:
+    """{row: options} of the rows that carry options: vertex options of a reference Mesh, or ``vertex_options`` of an
+    array mesh (as tilt_thetaB_boundary_in.group_rows reads them)."""
+    verts = getattr(mesh, "vertices", None)
+    row_of = mesh.vertex_index_to_row
+    out = {}
+    if isinstance(verts, dict):
+        for vid in mesh.vertex_ids:
+            opts = getattr(verts[int(vid)], "options", None) or {}
+            row = row_of.get(int(vid))
+            if row is not None and opts:
+                out[int(row)] = opts
+    else:
+        nv = len(mesh.vertex_ids)
+        for row, opts in (getattr(mesh, "vertex_options", None) or {}).items():  # (keyed by row)
+            if opts and 0 <= int(row) < nv:
+                out[int(row)] = opts
+    return out
+
+
+def absent_mask(mesh, global_params, leaflet: str) -> np.ndarray:
+    """leaflet_absent_vertex_mask (leaflet_presence.py:34-122): (nv,) bool, True where the row's vertex option
+    ``preset`` is in ``leaflet_<leaflet>_absent_presets``.  (The rows the reference restores for
+    ``rim_slope_match_mode: physical_edge_staggered_v1`` are not: check_supported refuses that mode next to a mask.)"""
+    nv = len(mesh.vertex_ids)
+    mask = np.zeros(nv, dtype=bool)
+    lf = str(leaflet or "").strip().lower()
+    if lf not in {"in", "out"} or global_params is None:
+        return mask
+    presets = set(normalize_preset_list(global_params.get(f"leaflet_{lf}_absent_presets")))
+    if not presets:
+        return mask
+    for row, opts in vertex_options_by_row(mesh).items():
+        preset = opts.get("preset")
+        try:
+            if preset in presets:
+                mask[row] = True
+        except TypeError:  # (an unhashable preset is in no set)
+            pass
+    return mask
+
+
+def kept_facets(tri_rows, absent) -> np.ndarray:
+    """leaflet_present_triangle_mask (leaflet_presence.py:158-170): (nf,) bool, True where none of the three rows is
+    absent."""
+    if tri_rows is None or len(tri_rows) == 0:
+        return np.zeros(0, dtype=bool)
+    absent = np.asarray(absent, dtype=bool)
+    if absent.size == 0:
+        return np.ones(len(tri_rows), dtype=bool)
+    return ~np.any(absent[np.asarray(tri_rows)], axis=1)
+
+
+def validate_absence_topology(mesh, global_params) -> None:
+    """validate_leaflet_absence_topology (runtime/leaflet_validation.py:22-84): in ``leaflet_out_absence_mode: strict``
+    (the default) a triangle with absent and present rows raises ValueError; ``triangles`` (facet / facets / triangle)
+    accepts."""
+    mode = str(global_params.get("leaflet_out_absence_mode", "strict") or "strict").strip().lower()
+    if mode in {"triangles", "facet", "facets", "triangle"}:
+        return
+    tri, _f = mesh.triangle_row_cache()
+    if tri is None or len(tri) == 0:
+        return
+    absent = absent_mask(mesh, global_params, "out")
+    if not np.any(absent):
+        return
+    tri = np.asarray(tri)
+    tri_abs = absent[tri]
+    bad = np.any(tri_abs, axis=1) & np.any(~tri_abs, axis=1)
+    if not np.any(bad):
+        return
+    idxs = np.nonzero(bad)[0]
+    vopts = vertex_options_by_row(mesh)
+    examples = [{"tri_index": int(i), "rows": tuple(int(r) for r in tri[i]),
+                 "presets": tuple(str((vopts.get(int(r)) or {}).get("preset") or "") for r in tri[i])} for i in idxs[:5]]
+    raise ValueError("Leaflet absence topology invalid: outer leaflet marked absent on some presets but mesh contains "
+                     f"triangles that straddle absent/present vertices. bad_triangles={int(idxs.size)} examples={examples}")
+
+
+def _cached_absent_mask(mesh, gp) -> np.ndarray:
+    """absent_mask(mesh, gp, "out"), resolved once per topology and preset list and kept on the mesh (as the reference
+    keeps ``_leaflet_absent_mask_cache``): check_supported runs at every configuration and every plugin call.  Vertex
+    presets edited in place need ``clear_absent_cache(mesh)`` (Minimizer.refresh_modules calls it)."""
+    key = (getattr(mesh, "_vertex_ids_version", 0), getattr(mesh, "_topology_version", 0),
+           getattr(mesh, "_facet_loops_version", 0), len(mesh.vertex_ids),
+           tuple(sorted(normalize_preset_list(gp.get("leaflet_out_absent_presets")))))
+    hit = getattr(mesh, "_hip_absent_out_cache", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    mask = absent_mask(mesh, gp, "out")
+    mask.setflags(write=False)
+    try:
+        mesh._hip_absent_out_cache = (key, mask)
+    except AttributeError:  # (a mesh object that takes no new attribute: resolved every time)
+        pass
+    return mask
+
+
+def clear_absent_cache(mesh) -> None:
+    if getattr(mesh, "_hip_absent_out_cache", None) is not None:
+        mesh._hip_absent_out_cache = None
+
+
+def absent_out_rows(mesh, global_params):
+    """The outer leaflet's absence mask for the device ((nv,) bool with a row set) or None when no preset list is
+    given; everything about the two lists that the device path does not take is refused here."""
+    gp = global_params if global_params is not None else {}
+    raw_in = gp.get("leaflet_in_absent_presets")
+    if normalize_preset_list(raw_in):
+        raise L.MembraneHipError(f"leaflet tilt option leaflet_in_absent_presets={raw_in!r} is outside the HIP hot path "
+                                 "(an absent inner leaflet: the reference's relaxation keeps the unmasked inner areas "
+                                 "while its tilt_in module masks)")
+    raw = gp.get("leaflet_out_absent_presets")
+    if not normalize_preset_list(raw):
+        return None
+    absent = _cached_absent_mask(mesh, gp) if mesh is not None else np.zeros(0, dtype=bool)
+    if not np.any(absent):
+        raise L.MembraneHipError(f"leaflet tilt option leaflet_out_absent_presets={raw!r} selects no row of this mesh and "
+                                 "is outside the HIP hot path (a mesh that lost its vertex options would otherwise run a "
+                                 "full outer leaflet without a word)")
+    mode = str(gp.get("rim_slope_match_mode") or "").strip().lower()
+    if mode == "physical_edge_staggered_v1":
+        raise L.MembraneHipError("leaflet_out_absent_presets next to rim_slope_match_mode=physical_edge_staggered_v1 (the "
+                                 "continuation shell rows the reference keeps present) is outside the HIP hot path")
+    return absent
+
+
+_ABSENT_KEYS = ("leaflet_out_absent_presets", "leaflet_in_absent_presets")
+
+
+def check_supported(global_params, mesh=None) -> None:
+    """``mesh``: the mesh the options are read for -- without one a preset list can select no row and is refused."""
+    absent_out_rows(mesh, global_params)
     for key in _UNSUPPORTED_KEYS:
+        if key in _ABSENT_KEYS:
+            continue
         val = global_params.get(key) if global_params is not None else None
         if val in (None, False, 0, 0.0, "", "off", "none", [], ()):
             continue
@@ -516,7 +663,7 @@ def evaluate_rim_bilayer(mesh, global_params, param_resolver, *, positions, tilt
     coefficient rows ADDED into ``tilt_in_grad_arr`` and ``tilt_out_grad_arr`` (each optional).  No shape gradient: the
     caller's ``grad_arr`` is never touched.  The early returns keep the reference's order (:431-462): no group and no
     selected edge return 0.0 before the tilt shapes are looked at, a bad shape raises before gamma is."""
-    check_supported(global_params if global_params is not None else {})
+    check_supported(global_params if global_params is not None else {}, mesh)
     tri, _f = mesh.triangle_row_cache()
     if tri is None or len(tri) == 0:
         return 0.0
@@ -657,7 +804,7 @@ def thetab_contact_key(prm):
 
 def _thetab_upload(mesh, global_params, param_resolver, positions, tilts_in):
     """The contact term alone on caller arrays -> (DeviceMesh, mirror), or None where the term contributes nothing."""
-    check_supported(global_params if global_params is not None else {})
+    check_supported(global_params if global_params is not None else {}, mesh)
     if thetab_contact_group(param_resolver, global_params) is None:
         return None
     nv = len(mesh.vertex_ids)
@@ -1040,13 +1187,13 @@ def splay_twist_params(param_resolver, global_params):
     return k_splay, k_twist, mode
 
 
-def splay_twist_device_params(param_resolver, global_params):
+def splay_twist_device_params(param_resolver, global_params, mesh=None):
     """(k_splay, k_twist) for DeviceMesh.set_tilt_splay_twist, or None when the module contributes nothing (both moduli
     0: tilt_splay_twist_in.py:134-135).  Everything is resolved before that early return, as in the reference (:128-133):
     a bad mode or transport model raises with both moduli 0 as well.  The vertex_recovered divergence is not on the
     device path."""
     k_splay, k_twist, mode = splay_twist_params(param_resolver, global_params)
-    check_supported(global_params if global_params is not None else {})
+    check_supported(global_params if global_params is not None else {}, mesh)
     if k_splay == 0.0 and k_twist == 0.0:
         return None
     if mode != "native":
@@ -1058,7 +1205,7 @@ def splay_twist_device_params(param_resolver, global_params):
 def evaluate_splay_twist(mesh, global_params, param_resolver, *, positions, tilts_in, tilt_in_grad_arr) -> float:
     """tilt_splay_twist_in on caller arrays (H2D/D2H per call: the parity seam, not the hot loop): energy; tilt gradient
     ADDED into ``tilt_in_grad_arr`` (optional).  No shape gradient: the caller's ``grad_arr`` is never touched."""
-    prm = splay_twist_device_params(param_resolver, global_params)
+    prm = splay_twist_device_params(param_resolver, global_params, mesh)
     if prm is None:
         return 0.0
     tri, _f = mesh.triangle_row_cache()
@@ -1102,7 +1249,10 @@ def device_params(param_resolver, global_params, leaflet: str) -> dict:
 def evaluate(mesh, global_params, param_resolver, *, kind: str, leaflet: str, positions, tilts, grad_arr,
              tilt_grad_arr) -> float:
     """One leaflet module on caller arrays (H2D/D2H per call: the parity seam, not the hot loop)."""
-    check_supported(global_params)
+    check_supported(global_params, mesh)
+    absent = absent_out_rows(mesh, global_params)
+    if kind == "bt" and leaflet == "out" and absent is not None:
+        raise L.MembraneHipError(BT_OUT_ABSENT_MESSAGE)
     tri, _f = mesh.triangle_row_cache()
     if tri is None or len(tri) == 0:
         return 0.0
@@ -1121,6 +1271,8 @@ def evaluate(mesh, global_params, param_resolver, *, kind: str, leaflet: str, po
     dm.set_leaflet_tilts(leaflet, tilts, **params)
     dm.set_leaflet_tilts(other, np.zeros((nv, 3)), tilt_modulus=0.0, smoothness=0.0)
     mir._leaflet_keys = {}  # foreign arrays were uploaded
+    if leaflet == "out":
+        mir.set_absent_out(absent)  # (tilt_out and tilt_smoothness_out read it; a mask of an earlier call is cleared)
     if kind == "bt":
         check_bt_supported(global_params)
         dm.set_leaflet_bending(leaflet, *bending_params(mesh, global_params, leaflet))
@@ -1173,3 +1325,93 @@ def evaluate(mesh, global_params, param_resolver, *, kind: str, leaflet: str, po
         _e, gi, go = dm.leaflet_tilt_energy_and_gradient(want_gradient=True, module_form=(kind == "tilt"))
         tilt_grad_arr += gi if leaflet == "in" else go
     return E
+
+
+# --- leaflet absence: the masked modules restated in NumPy -------------------------------------------------------------
+BT_OUT_ABSENT_MESSAGE = ("bending_tilt_out next to a non-empty leaflet_out_absent_presets mask is outside the HIP hot "
+                         "path (the follow-up to the mask: masked normals and effective areas in the energy pass's "
+                         "per-vertex record and in the leaflet shape-gradient instance)")
+
+
+def _facet_geometry(positions, tri):
+    x = np.asarray(positions, dtype=np.float64)
+    tri = np.asarray(tri, dtype=np.int64).reshape(-1, 3)
+    v0, v1, v2 = x[tri[:, 0]], x[tri[:, 1]], x[tri[:, 2]]
+    n = np.cross(v1 - v0, v2 - v0)
+    return tri, v0, v1, v2, n, np.linalg.norm(n, axis=1)
+
+
+def masked_vertex_areas(positions, tri, absent=None) -> np.ndarray:
+    """Barycentric vertex areas over the kept facets (tilt_relaxation.py:31-45, :681-697): what a relaxation hands the
+    outer leaflet's magnitude term and the k_t A_v part of its Jacobi diagonal."""
+    tri, _v0, _v1, _v2, _n, nn = _facet_geometry(positions, tri)
+    out = np.zeros(len(np.asarray(positions)), dtype=np.float64)
+    if absent is not None and np.any(absent):
+        keep = kept_facets(tri, absent)
+        tri, nn = tri[keep], nn[keep]
+    a3 = (0.5 * nn) / 3.0
+    for k in range(3):
+        np.add.at(out, tri[:, k], a3)
+    return out
+
+
+def tilt_leaflet_numpy(positions, tri, tilts, *, k_tilt, mass_mode="lumped", absent=None):
+    """tilt_in / tilt_out (tilt_leaflet.py:41-169) on the facets kept by ``absent`` -> dict with E, grad (shape
+    gradient) and tilt_grad.  Host-side statement of what k_tilt sums under a mask; not on any hot path."""
+    tri, v0, v1, v2, n, nn = _facet_geometry(positions, tri)
+    t = np.asarray(tilts, dtype=np.float64)
+    nv = len(t)
+    out = {"E": 0.0, "grad": np.zeros((nv, 3)), "tilt_grad": np.zeros((nv, 3))}
+    if k_tilt == 0.0 or len(tri) == 0:
+        return out
+    keep = nn >= 1e-12
+    if absent is not None and np.any(absent):
+        keep &= kept_facets(tri, absent)
+    if not np.any(keep):
+        return out
+    tri, v0, v1, v2, n, nn = tri[keep], v0[keep], v1[keep], v2[keep], n[keep], nn[keep]
+    area = 0.5 * nn
+    t0, t1, t2 = t[tri[:, 0]], t[tri[:, 1]], t[tri[:, 2]]
+    dot = lambda a, b: np.einsum("ij,ij->i", a, b)  # noqa: E731
+    sq = dot(t0, t0) + dot(t1, t1) + dot(t2, t2)
+    if mass_mode == "consistent":
+        coeff = (k_tilt / 12.0) * (sq + dot(t0, t1) + dot(t1, t2) + dot(t2, t0))
+        f = (k_tilt * area / 12.0)[:, None]
+        rows = (f * (2.0 * t0 + t1 + t2), f * (2.0 * t1 + t2 + t0), f * (2.0 * t2 + t0 + t1))
+    else:
+        coeff = 0.5 * k_tilt * (sq / 3.0)
+        f = (k_tilt * area / 3.0)[:, None]
+        rows = (f * t0, f * t1, f * t2)
+    out["E"] = float(np.dot(coeff, area))
+    nh = n / nn[:, None]
+    shape = (0.5 * np.cross(nh, v2 - v1), 0.5 * np.cross(nh, v0 - v2), 0.5 * np.cross(nh, v1 - v0))
+    for k in range(3):
+        np.add.at(out["tilt_grad"], tri[:, k], rows[k])
+        np.add.at(out["grad"], tri[:, k], coeff[:, None] * shape[k])
+    return out
+
+
+def tilt_smoothness_numpy(positions, tri, tilts, *, k_smooth, absent=None):
+    """tilt_smoothness_in / _out (tilt_smoothness.py:84-198 with the weights of tilt_smoothness_utils.py:17-76): the
+    cotangent Dirichlet energy over the facets kept by ``absent`` -> dict with E and tilt_grad (no shape gradient)."""
+    tri, v0, v1, v2, _n, nn = _facet_geometry(positions, tri)
+    t = np.asarray(tilts, dtype=np.float64)
+    out = {"E": 0.0, "tilt_grad": np.zeros((len(t), 3))}
+    if k_smooth == 0.0 or len(tri) == 0:
+        return out
+    if absent is not None and np.any(absent):
+        keep = kept_facets(tri, absent)
+        tri, v0, v1, v2, nn = tri[keep], v0[keep], v1[keep], v2[keep], nn[keep]
+    if len(tri) == 0:
+        return out
+    dot = lambda a, b: np.einsum("ij,ij->i", a, b)  # noqa: E731
+    ad = np.maximum(nn, 1e-12)  # (compute_curvature_data: area_doubled clamped)
+    c0, c1, c2 = dot(v1 - v0, v2 - v0) / ad, dot(v2 - v1, v0 - v1) / ad, dot(v0 - v2, v1 - v2) / ad
+    t0, t1, t2 = t[tri[:, 0]], t[tri[:, 1]], t[tri[:, 2]]
+    d12, d20, d01 = t1 - t2, t2 - t0, t0 - t1
+    out["E"] = float(0.25 * k_smooth * np.sum(c0 * dot(d12, d12) + c1 * dot(d20, d20) + c2 * dot(d01, d01)))
+    hk = 0.5 * k_smooth
+    np.add.at(out["tilt_grad"], tri[:, 0], hk * (c2[:, None] * d01 - c1[:, None] * d20))
+    np.add.at(out["tilt_grad"], tri[:, 1], hk * (c0[:, None] * d12 - c2[:, None] * d01))
+    np.add.at(out["tilt_grad"], tri[:, 2], hk * (c1[:, None] * d20 - c0[:, None] * d12))
+    return out

@@ -254,6 +254,8 @@ class Minimizer:
                     _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
                 raise L.MembraneHipError(f"{edge_mod} together with tilt modules is outside the HIP hot path")
         self._line_key = None
+        self._absent_key = None
+        _lc.clear_absent_cache(self.mesh)
         self._edgepen_key = None
         self.constraint_modules = [self.constraint_manager.get_constraint(c)
                                    for c in self.constraint_module_names]
@@ -490,7 +492,7 @@ class Minimizer:
                 if coupling is not None:  # tilt_coupling.py:129-132: unknown or absent mode, or k_c == 0
                     mods |= _ENERGY_BITS[name]
             elif name == "tilt_splay_twist_in":
-                splay_twist = _lc.splay_twist_device_params(self.param_resolver, gp)
+                splay_twist = _lc.splay_twist_device_params(self.param_resolver, gp, self.mesh)
                 if splay_twist is not None:  # tilt_splay_twist_in.py:134-135: both moduli 0
                     mods |= _ENERGY_BITS[name]
             else:
@@ -581,10 +583,28 @@ class Minimizer:
         if (mods & _SINGLE_TILT_BITS) and (mods & _LEAFLET_BITS):
             raise L.MembraneHipError("single-field and leaflet tilt modules together are outside the HIP hot path")
         if mods & _LEAFLET_BITS:
-            _lc.check_supported(gp)
+            _lc.check_supported(gp, self.mesh)
             if gp.get("line_search_reduced_energy", False):
                 raise L.MembraneHipError("line_search_reduced_energy is outside the HIP hot path")
-            mir.upload_leaflets({lf: _lc.device_params(self.param_resolver, gp, lf) for lf in ("in", "out")})
+            # leaflet_out_absent_presets: the rows (leaflet_common keeps them on the mesh, once per topology and preset
+            # list; refresh_modules() after the vertex presets change); validate_leaflet_absence_topology once per such
+            # key; what does not read the mask yet is refused
+            absent = None
+            if _lc.normalize_preset_list(gp.get("leaflet_out_absent_presets")):
+                akey = (mir._topo_key, tuple(sorted(_lc.normalize_preset_list(gp.get("leaflet_out_absent_presets")))),
+                        str(gp.get("leaflet_out_absence_mode", "strict") or "strict").strip().lower())
+                if getattr(self, "_absent_key", None) != akey:
+                    _lc.validate_absence_topology(self.mesh, gp)
+                    self._absent_rows = _lc.absent_out_rows(self.mesh, gp)
+                    self._absent_key = akey
+                absent = self._absent_rows
+                if mods & L.MS_MOD_BENDING_TILT_OUT:
+                    raise L.MembraneHipError(_lc.BT_OUT_ABSENT_MESSAGE)
+            leaflet_params = {lf: _lc.device_params(self.param_resolver, gp, lf) for lf in ("in", "out")}
+            if absent is None:
+                mir.upload_leaflets(leaflet_params)  # (clears the mask of an earlier configuration)
+            else:
+                mir.upload_leaflets(leaflet_params, absent_out=absent)
             for lf, prm in disk_params.items():
                 key = (mir._topo_key, prm["disk_rows"].tobytes(), tuple((k, v) for k, v in prm.items() if k != "disk_rows"))
                 if mir._leaflet_keys.get("bend_disk_" + lf) != key:
