@@ -51,7 +51,7 @@ mesh-quality repair hook.
 from __future__ import annotations
 
 import logging
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -75,65 +75,122 @@ from .steppers.base import write_back_positions
 
 logger = logging.getLogger("membrane_solver")
 
-_ENERGY_BITS = {"surface": L.MS_MOD_SURFACE, "bending": L.MS_MOD_BENDING, "volume": L.MS_MOD_VOLUME_PENALTY,
-                "tilt": L.MS_MOD_TILT, "bending_tilt": L.MS_MOD_BENDING_TILT,
-                "tilt_smoothness": L.MS_MOD_TILT_SMOOTH,
-                "tilt_in": L.MS_MOD_TILT_IN, "tilt_out": L.MS_MOD_TILT_OUT,
-                "tilt_smoothness_in": L.MS_MOD_TILT_SMOOTH_IN, "tilt_smoothness_out": L.MS_MOD_TILT_SMOOTH_OUT,
-                "bending_tilt_in": L.MS_MOD_BENDING_TILT_IN, "bending_tilt_out": L.MS_MOD_BENDING_TILT_OUT,
-                "tilt_disk_target_in": L.MS_MOD_TILT_DISK_TARGET_IN,
-                "tilt_disk_target_out": L.MS_MOD_TILT_DISK_TARGET_OUT,
-                "body_area_penalty": L.MS_MOD_AREA_PENALTY, "line_tension": L.MS_MOD_LINE_TENSION,
-                "edge_length_penalty": L.MS_MOD_EDGE_LENGTH_PENALTY,
-                "tilt_rim_source_in": L.MS_MOD_TILT_RIM_SOURCE_IN, "tilt_rim_source_out": L.MS_MOD_TILT_RIM_SOURCE_OUT,
-                "tilt_coupling": L.MS_MOD_TILT_COUPLING, "tilt_splay_twist_in": L.MS_MOD_TILT_SPLAY_TWIST_IN,
-                "tilt_rim_source_bilayer": L.MS_MOD_TILT_RIM_SOURCE_BILAYER,
-                "tilt_thetaB_contact_in": L.MS_MOD_TILT_THETAB_CONTACT_IN,
-                # (the bit is set only with a non-zero strength and both rings: strength 0, as in most caveolin decks, and
-                # a missing group or ring stay a host-side constant 0.0; the bit is left out of _LEAFLET_BITS: the module is
-                # admitted only next to leaflet modules that are in it)
-                "rim_slope_match_out": L.MS_MOD_RIM_SLOPE_MATCH_OUT,
-                # host-side constant, no kernel: a topological constant on closed surfaces
-                "gaussian_curvature": 0}
-_ENERGY_SLOT = {"surface": 0, "bending": 1, "volume": 2, "tilt": 3, "bending_tilt": 1, "tilt_smoothness": 3,
-                "tilt_in": 3, "tilt_out": 3, "tilt_smoothness_in": 3, "tilt_smoothness_out": 3,
-                "bending_tilt_in": 1, "bending_tilt_out": 1, "tilt_disk_target_in": 3, "tilt_disk_target_out": 3,
-                "body_area_penalty": 2, "line_tension": 0, "edge_length_penalty": 0, "gaussian_curvature": None, "rim_slope_match_out": None,
-                # (their sums ride in the leaflet's tilt-magnitude slot of energies[3]; each reports its own energy)
-                "tilt_rim_source_in": None, "tilt_rim_source_out": None,
-                # (its sums ride in the outer leaflet's tilt-magnitude slot; it reports its own energy)
-                "tilt_coupling": None,
-                # (its sums ride in the inner leaflet's smoothness slot; it reports its own energy)
-                "tilt_splay_twist_in": None,
-                # (its sums ride in the outer leaflet's tilt-magnitude slot as well; it reports its own energy)
-                "tilt_rim_source_bilayer": None,
-                # (its sums ride in the inner leaflet's tilt-magnitude slot; it reports its own energy)
-                "tilt_thetaB_contact_in": None}
-_RIM_MODULES = ("tilt_rim_source_in", "tilt_rim_source_out")
-_RIM_BILAYER = "tilt_rim_source_bilayer"  # one table for both leaflet fields (DeviceMesh.set_rim_source_bilayer)
-_THETAB = "tilt_thetaB_contact_in"  # the ring's table of the context (DeviceMesh.set_thetab_contact)
-_RIM_MATCH = "rim_slope_match_out"  # the three rings' tables of the context (DeviceMesh.set_rim_match)
+_RIM_MATCH = "rim_slope_match_out"
 _EDGE_MODULES = ("line_tension", "edge_length_penalty")  # they share the lane behind the energy and the gradient pass
-_SINGLE_TILT_BITS = L.MS_MOD_TILT | L.MS_MOD_BENDING_TILT | L.MS_MOD_TILT_SMOOTH
-_LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
-_LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_TILT_SMOOTH_OUT
-                 | _LEAFLET_BT_BITS | L.MS_MOD_TILT_DISK_TARGET_IN | L.MS_MOD_TILT_DISK_TARGET_OUT
-                 | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING
-                 | L.MS_MOD_TILT_SPLAY_TWIST_IN | L.MS_MOD_TILT_RIM_SOURCE_BILAYER | L.MS_MOD_TILT_THETAB_CONTACT_IN)
+
+
+class _Module(NamedTuple):
+    """What the Minimizer knows of one energy module.  A new module adds its record here, the refusals that are its own
+    in Minimizer._check() and, where it has a table on the device, one keyed upload in Minimizer._apply()."""
+
+    bit: int                            # its bit of the module mask (0: a host-side constant, no kernel)
+    slot: Optional[int]                 # its entry of energies[]; None: it reports its own energy, or a host constant
+    scalar: Optional[int] = None        # its scalar slot, where it shares energies[3] / energies[1] with others
+    field: Optional[str] = None         # the tilt field(s) it reads and relaxes: "single", or the leaflets "in" / "out" / "both"
+    edges: bool = False                 # it selects edges: refused on a mesh without an edge table
+    # resolve(...) -> its parameters; falsy: switched off; absent: always on.  Called by ``reads``: "params" (param_resolver,
+    # global_params, *args) or "mesh" (mesh, the same), leaflet_common's forms; else (minimizer, mirror, device or None)
+    resolve: Optional[Callable] = None
+    reads: str = ""
+    args: tuple = ()
+    # a ride-along module: its sums ride in the scalar slots of ``hosts``, it reports its own energy and each host
+    # reports its slot without it.  (device) -> that energy; a tuple where the hosts' parts differ: (own, part per host)
+    energy: Optional[Callable] = None
+    hosts: Tuple[str, ...] = ()
+
+
+def _gp_nonzero(key):
+    return lambda mz, mir, dm: float(mz.global_params.get(key, 0.0) or 0.0) != 0.0
+
+
+def _gaussian_constant(mz, mir, dm):
+    from ..modules.energy import gaussian_curvature as _gc
+
+    mz._const_energy["gaussian_curvature"] = _gc.constant_energy(mz.mesh, mz.global_params)  # gaussian_curvature.py:117-134
+
+
+def _rim_match_gate(mz, mir, dm):
+    """rim_slope_match_out.py:380-382: strength 0 is 0.0 whatever else is set.  With a strength the module is on for now:
+    _check() resolves its tables once the other modules' bits are known; no group or ring puts it back to this constant."""
+    mz._const_energy[_RIM_MATCH] = 0.0
+    return _lc.rim_match_strength(mz.param_resolver, mz.global_params) != 0.0
+
+
+# The order counts: the refusal of an unknown module lists the names in it, and the ride-along energies are taken out of
+# their hosts in it (floating-point sums).
+_MODULES = {
+    "surface": _Module(L.MS_MOD_SURFACE, 0),
+    "bending": _Module(L.MS_MOD_BENDING, 1, L.MS_S_EBEND),
+    "volume": _Module(L.MS_MOD_VOLUME_PENALTY, 2,
+                      resolve=lambda mz, mir, dm: (mz.global_params.get("volume_constraint_mode", "lagrange") == "penalty"
+                                               and bool(getattr(mz.mesh, "bodies", None)))),
+    "tilt": _Module(L.MS_MOD_TILT, 3, L.MS_S_ETILT, "single", resolve=_gp_nonzero("tilt_rigidity")),  # tilt.py:110-112
+    "bending_tilt": _Module(L.MS_MOD_BENDING_TILT, 1, L.MS_S_EBT, "single"),
+    "tilt_smoothness": _Module(L.MS_MOD_TILT_SMOOTH, 3, L.MS_S_ETS, "single",
+                               resolve=_gp_nonzero("tilt_smoothness_rigidity")),  # tilt_smoothness.py:258-260
+    # tilt_leaflet.py:41-43, tilt_smoothness_leaflet.py:32-34: a zero modulus switches the module off
+    "tilt_in": _Module(L.MS_MOD_TILT_IN, 3, L.MS_S_ETILT_IN, "in", False, _lc.tilt_modulus, "params", ("in",)),
+    "tilt_out": _Module(L.MS_MOD_TILT_OUT, 3, L.MS_S_ETILT_OUT, "out", False, _lc.tilt_modulus, "params", ("out",)),
+    "tilt_smoothness_in": _Module(L.MS_MOD_TILT_SMOOTH_IN, 3, L.MS_S_ETS_IN, "in", False, _lc.smoothness_rigidity, "params", ("in",)),
+    "tilt_smoothness_out": _Module(L.MS_MOD_TILT_SMOOTH_OUT, 3, L.MS_S_ETS_OUT, "out", False, _lc.smoothness_rigidity, "params", ("out",)),
+    "bending_tilt_in": _Module(L.MS_MOD_BENDING_TILT_IN, 1, L.MS_S_EBT_IN, "in"),
+    "bending_tilt_out": _Module(L.MS_MOD_BENDING_TILT_OUT, 1, L.MS_S_EBT_OUT, "out"),
+    # tilt_disk_target_in.py:175-191: no group, no row, k or theta_B zero
+    "tilt_disk_target_in": _Module(L.MS_MOD_TILT_DISK_TARGET_IN, 3, L.MS_S_EDT_IN, "in", False, _lc.disk_target_params, "mesh", ("in",)),
+    "tilt_disk_target_out": _Module(L.MS_MOD_TILT_DISK_TARGET_OUT, 3, L.MS_S_EDT_OUT, "out", False, _lc.disk_target_params, "mesh", ("out",)),
+    "body_area_penalty": _Module(L.MS_MOD_AREA_PENALTY, 2,  # body_area_penalty.py:114-123
+                                 resolve=lambda mz, mir, dm: body_area_params(mz.mesh, mz.global_params, mz.param_resolver)),
+    # the edge modules resolve on the device, which _device() synchronises first for them: their tables go up and say
+    # whether any edge is charged (k != 0)
+    "line_tension": _Module(L.MS_MOD_LINE_TENSION, 0, edges=True,
+                            resolve=lambda mz, mir, dm: mz._upload_line(mir, dm)),
+    "edge_length_penalty": _Module(L.MS_MOD_EDGE_LENGTH_PENALTY, 0, edges=True,
+                                   resolve=lambda mz, mir, dm: mz._upload_edge_penalty(mir, dm)),
+    # tilt_rim_source_in.py:386-404: no group, no rim edge, every gamma 0; in the leaflet's tilt-magnitude slot
+    "tilt_rim_source_in": _Module(L.MS_MOD_TILT_RIM_SOURCE_IN, None, None, "in", True, _lc.rim_source_params, "mesh", ("in",),
+                                  lambda dm: dm.leaflet_rim_source_energy("in"), ("tilt_in",)),
+    "tilt_rim_source_out": _Module(L.MS_MOD_TILT_RIM_SOURCE_OUT, None, None, "out", True, _lc.rim_source_params, "mesh", ("out",),
+                                   lambda dm: dm.leaflet_rim_source_energy("out"), ("tilt_out",)),
+    # tilt_coupling.py:129-132: unknown or absent mode, or k_c == 0; in the outer leaflet's tilt-magnitude slot
+    "tilt_coupling": _Module(L.MS_MOD_TILT_COUPLING, None, None, "both", False, _lc.coupling_params, "params", (),
+                             lambda dm: dm.tilt_coupling_energy(), ("tilt_out",)),
+    # tilt_splay_twist_in.py:134-135: both moduli 0; in the inner leaflet's smoothness slot
+    "tilt_splay_twist_in": _Module(L.MS_MOD_TILT_SPLAY_TWIST_IN, None, None, "in", False,
+                                   lambda mz, mir, dm: _lc.splay_twist_device_params(mz.param_resolver, mz.global_params, mz.mesh),
+                                   "", (), lambda dm: dm.tilt_splay_twist_energy(), ("tilt_smoothness_in",)),
+    # tilt_rim_source_bilayer.py:431-462: one table for both leaflet fields; in the outer leaflet's tilt-magnitude slot
+    "tilt_rim_source_bilayer": _Module(L.MS_MOD_TILT_RIM_SOURCE_BILAYER, None, None, "both", True,
+                                       _lc.rim_source_params, "mesh", (None,),
+                                       lambda dm: dm.rim_source_bilayer_energy(), ("tilt_out",)),
+    # tilt_thetaB_contact_in.py:351-374: no group, no tagged row, k == gamma == 0; in the inner leaflet's tilt-magnitude slot
+    "tilt_thetaB_contact_in": _Module(L.MS_MOD_TILT_THETAB_CONTACT_IN, None, None, "in", False, _lc.thetab_contact_params,
+                                      "mesh", (), lambda dm: dm.thetab_contact_energy(), ("tilt_in",)),
+    # (no field of its own: the module is admitted only next to leaflet modules that relax the fields it couples; one part
+    # in each leaflet's tilt-magnitude slot)
+    _RIM_MATCH: _Module(L.MS_MOD_RIM_SLOPE_MATCH_OUT, None, resolve=_rim_match_gate,
+                        energy=lambda dm: dm.rim_match_energies(), hosts=("tilt_out", "tilt_in")),
+    # host-side constant, no kernel: a topological constant on closed surfaces
+    "gaussian_curvature": _Module(0, None, resolve=_gaussian_constant),
+}
+__doc__ += "\nEnergy modules on the device path: " + ", ".join(_MODULES) + ".\n"
+
+
+def _bits(*fields):
+    return sum(m.bit for m in _MODULES.values() if m.field in fields)  # (distinct bits: the sum is their union)
+
+
+_WALK = {n: (m.bit, m.resolve, m.reads, m.args) for n, m in _MODULES.items()}  # what Minimizer._resolve() reads, unpacked
+_ENERGY_BITS = {n: m.bit for n, m in _MODULES.items()}
+_ENERGY_SLOT = {n: m.slot for n, m in _MODULES.items()}
+_TILT_SCALAR = {n: m.scalar for n, m in _MODULES.items() if m.slot == 3}  # scalar slot of every module that shares energies[3]
+_BEND_SCALAR = {n: m.scalar for n, m in _MODULES.items() if m.slot == 1}
+_SINGLE_TILT_BITS = _bits("single")
+_LEAFLET_BITS = _bits("in", "out", "both")
 _TILT_BITS = _SINGLE_TILT_BITS | _LEAFLET_BITS
-# every module that reads the inner leaflet's field (a relaxation with one of them relaxes that field)
-_INNER_LEAFLET_BITS = (L.MS_MOD_TILT_IN | L.MS_MOD_TILT_SMOOTH_IN | L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_TILT_DISK_TARGET_IN
-                       | L.MS_MOD_TILT_RIM_SOURCE_IN | L.MS_MOD_TILT_COUPLING | L.MS_MOD_TILT_SPLAY_TWIST_IN
-                       | L.MS_MOD_TILT_RIM_SOURCE_BILAYER | L.MS_MOD_TILT_THETAB_CONTACT_IN)
-# the modules whose tilt gradient relaxes the outer leaflet's field / the inner one's (rim_slope_match_out couples to a
-# field that one of them must relax)
-_OUTER_RELAX_BITS = (L.MS_MOD_TILT_OUT | L.MS_MOD_TILT_SMOOTH_OUT | L.MS_MOD_BENDING_TILT_OUT | L.MS_MOD_TILT_DISK_TARGET_OUT
-                     | L.MS_MOD_TILT_RIM_SOURCE_OUT | L.MS_MOD_TILT_COUPLING | L.MS_MOD_TILT_RIM_SOURCE_BILAYER)
-# scalar slot of every module that shares energies[3]
-_TILT_SCALAR = {"tilt": L.MS_S_ETILT, "tilt_smoothness": L.MS_S_ETS, "tilt_in": L.MS_S_ETILT_IN,
-                "tilt_out": L.MS_S_ETILT_OUT, "tilt_smoothness_in": L.MS_S_ETS_IN,
-                "tilt_smoothness_out": L.MS_S_ETS_OUT, "tilt_disk_target_in": L.MS_S_EDT_IN,
-                "tilt_disk_target_out": L.MS_S_EDT_OUT}
+_INNER_LEAFLET_BITS = _bits("in", "both")  # every module that reads the inner leaflet's field (a relaxation with one relaxes it)
+_OUTER_RELAX_BITS = _bits("out", "both")   # the modules whose tilt gradient relaxes the outer leaflet's field
+_LEAFLET_BT_BITS = L.MS_MOD_BENDING_TILT_IN | L.MS_MOD_BENDING_TILT_OUT
+_BEND_BITS = L.MS_MOD_BENDING | L.MS_MOD_BENDING_TILT
 _PIN_MODULES = ("pin_to_plane", "pin_to_circle")
 _AREA_CONSTRAINTS = ("body_area", "global_area")  # the area lane: the row (body_area) and the enforcer on every trial
 # The reference's fixed_plane and perimeter write vertex.position without Mesh.increment_version(), and volume.py:109 /
@@ -144,8 +201,13 @@ _AREA_CONSTRAINTS = ("body_area", "global_area")  # the area lane: the row (body
 _STALE_CACHE = ("the reference evaluates that module's first pass at the positions cached before the enforce-only module "
                 "moved them (Mesh.positions_view is not invalidated), which the device path does not reproduce")
 _ENFORCE_ONLY = (_fplane.NAME, _perimeter.NAME)  # no KKT row: they only move the positions of a trial / an enforce context
-_BEND_SCALAR = {"bending": L.MS_S_EBEND, "bending_tilt": L.MS_S_EBT, "bending_tilt_in": L.MS_S_EBT_IN,
-                "bending_tilt_out": L.MS_S_EBT_OUT}
+
+
+def _keyed_upload(keys, slot, key, dm, setter, args=(), kwargs=None):
+    """Call the device's ``setter`` unless the table under ``slot`` of the mirror's ``keys`` went up with the same key."""
+    if keys.get(slot) != key:
+        getattr(dm, setter)(*args, **(kwargs or {}))
+        keys[slot] = key
 
 
 class GradientRows:
@@ -236,23 +298,22 @@ class Minimizer:
             # an edge module on a mesh built without edges stays refused: nothing could be tagged or given a target,
             # and the deck would run with that module's energy at zero
             # (the rim sources select edges as well: without an edge table nothing could be a rim edge)
-            no_edges = name in _EDGE_MODULES + _RIM_MODULES + (_RIM_BILAYER,) and not _line.has_edge_table(self.mesh)
-            if name not in _ENERGY_BITS or no_edges:
+            no_edges = name in _MODULES and _MODULES[name].edges and not _line.has_edge_table(self.mesh)
+            if name not in _MODULES or no_edges:
                 where = " on a mesh without an edge table (ArrayMesh(edges=, edge_options=))" if no_edges else ""
-                raise L.MembraneHipError(
-                    f"energy module {name!r}{where} is outside the HIP hot path (surface, bending, volume, tilt, "
-                    "bending_tilt, tilt_smoothness, tilt_in, tilt_out, tilt_smoothness_in, tilt_smoothness_out, "
-                    "bending_tilt_in, bending_tilt_out, tilt_disk_target_in, tilt_disk_target_out, "
-                    "body_area_penalty, line_tension, edge_length_penalty, tilt_rim_source_in, tilt_rim_source_out, "
-                    "tilt_rim_source_bilayer, tilt_thetaB_contact_in, rim_slope_match_out, "
-                    "tilt_coupling, tilt_splay_twist_in)")
+                raise L.MembraneHipError(f"energy module {name!r}{where} is outside the HIP hot path "
+                                         f"({', '.join(_MODULES)})")
         if "body_area_penalty" in self.energy_module_names and any(
-                _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):  # (not rim_slope_match_out: see _ENERGY_BITS)
+                _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):  # (not rim_slope_match_out: see its record)
             raise L.MembraneHipError("body_area_penalty together with tilt modules is outside the HIP hot path")
         for edge_mod in _EDGE_MODULES:
             if edge_mod in self.energy_module_names and any(
                     _ENERGY_BITS[n] & _TILT_BITS for n in self.energy_module_names):
                 raise L.MembraneHipError(f"{edge_mod} together with tilt modules is outside the HIP hot path")
+        listed = list(dict.fromkeys(self.energy_module_names))
+        self._edge_listed = any(n in _EDGE_MODULES for n in listed)  # (_device() then synchronises before it resolves)
+        self._disk_order, self._rim_order = ([n[len(pre):] for n in listed if n in (pre + "in", pre + "out")]
+                                             for pre in ("tilt_disk_target_", "tilt_rim_source_"))
         self._line_key = None
         self._absent_key = None
         _lc.clear_absent_cache(self.mesh)
@@ -416,92 +477,51 @@ class Minimizer:
 
     # -- device configuration --------------------------------------------------
     def _device(self):
-        gp = self.global_params
+        """-> (mirror, device) in this minimizer's configuration, in three steps: resolve every listed module's parameters
+        and the module mask, run every refusal that needs nothing from the device, then synchronise and upload."""
         mir = mirror_for(self.mesh, device=self.device, tile_vertices=self.tile_vertices)
-        area_con = self._area_constraint_params()  # (refused before anything is uploaded)
-        dm = mir.sync()
-        if self.deterministic is not None:
-            dm.set_deterministic(self.deterministic)
-        mods = 0
-        self._const_energy = {}
-        disk_params = {}
-        rim_params = {}
-        rim_bilayer = None
-        thetab = None
-        rim_match = False  # (then: rim_slope_match_out is listed with a non-zero strength; below: its tables, or None)
-        coupling = None
-        splay_twist = None
-        vol_mode = gp.get("volume_constraint_mode", "lagrange")
-        area_params = None
-        for name in self.energy_module_names:
-            if name == "volume":
-                if vol_mode == "penalty" and getattr(self.mesh, "bodies", None):
-                    mods |= L.MS_MOD_VOLUME_PENALTY
-            elif name == "body_area_penalty":
-                area_params = body_area_params(self.mesh, gp, self.param_resolver)
-                if area_params is not None:  # body_area_penalty.py:114-123
-                    mods |= L.MS_MOD_AREA_PENALTY
-            elif name == "line_tension":
-                if self._upload_line(mir, dm):  # line_tension.py:113-115: nothing tagged, nothing charged
-                    mods |= L.MS_MOD_LINE_TENSION
-            elif name == "edge_length_penalty":
-                if self._upload_edge_penalty(mir, dm):  # nothing charged, or k == 0 (the reference adds zeros)
-                    mods |= L.MS_MOD_EDGE_LENGTH_PENALTY
-            elif name == "tilt":
-                if float(gp.get("tilt_rigidity", 0.0) or 0.0) != 0.0:  # tilt.py:110-112
-                    mods |= L.MS_MOD_TILT
-            elif name == "tilt_smoothness":
-                if float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0) != 0.0:  # tilt_smoothness.py:258-260
-                    mods |= L.MS_MOD_TILT_SMOOTH
-            elif name in ("tilt_in", "tilt_out"):
-                if _lc.tilt_modulus(self.param_resolver, gp, name[5:]) != 0.0:  # tilt_leaflet.py:41-43
-                    mods |= _ENERGY_BITS[name]
-            elif name in ("tilt_smoothness_in", "tilt_smoothness_out"):
-                if _lc.smoothness_rigidity(self.param_resolver, gp, name[16:]) != 0.0:  # tilt_smoothness_leaflet.py:32-34
-                    mods |= _ENERGY_BITS[name]
-            elif name == "gaussian_curvature":
-                from ..modules.energy import gaussian_curvature as _gc
+        area_con = self._area_constraint_params()
+        dm = None
+        if self._edge_listed:  # an edge module resolves by uploading: synchronise first; else _apply() does, after the checks
+            dm = mir.sync()
+            if self.deterministic is not None:
+                dm.set_deterministic(self.deterministic)
+        mods, p = self._resolve(mir, dm)
+        return mir, self._apply(mir, dm, p, area_con, self._check(mir, mods, p, area_con))
 
-                self._const_energy[name] = _gc.constant_energy(self.mesh, gp)  # gaussian_curvature.py:117-134
-            elif name == _RIM_MATCH:
-                # rim_slope_match_out.py:380-382: strength 0 is 0.0 whatever else is set
-                rim_match = _lc.rim_match_strength(self.param_resolver, gp) != 0.0
-                self._const_energy[name] = 0.0
-            elif name in ("tilt_disk_target_in", "tilt_disk_target_out"):
-                prm = _lc.disk_target_params(self.mesh, self.param_resolver, gp, name[17:])
-                if prm is not None:  # tilt_disk_target_in.py:175-191
-                    mods |= _ENERGY_BITS[name]
-                    disk_params[name[17:]] = prm
-            elif name in _RIM_MODULES:
-                prm = _lc.rim_source_params(self.mesh, self.param_resolver, gp, name[16:])
-                if prm is not None:  # tilt_rim_source_in.py:386-404: no group, no rim edge, every gamma 0
-                    mods |= _ENERGY_BITS[name]
-                    rim_params[name[16:]] = prm
-            elif name == _RIM_BILAYER:
-                rim_bilayer = _lc.rim_source_params(self.mesh, self.param_resolver, gp, None)
-                if rim_bilayer is not None:  # tilt_rim_source_bilayer.py:431-462: no group, no rim edge, every gamma 0
-                    mods |= _ENERGY_BITS[name]
-            elif name == _THETAB:
-                # tilt_thetaB_contact_in.py:351-374: no group, no tagged row, k == gamma == 0 (refusals: a missing normal,
-                # a ring above the device's size, non-finite parameters)
-                thetab = _lc.thetab_contact_params(self.mesh, self.param_resolver, gp)
-                if thetab is not None:
-                    mods |= _ENERGY_BITS[name]
-            elif name == "tilt_coupling":
-                coupling = _lc.coupling_params(self.param_resolver, gp)
-                if coupling is not None:  # tilt_coupling.py:129-132: unknown or absent mode, or k_c == 0
-                    mods |= _ENERGY_BITS[name]
-            elif name == "tilt_splay_twist_in":
-                splay_twist = _lc.splay_twist_device_params(self.param_resolver, gp, self.mesh)
-                if splay_twist is not None:  # tilt_splay_twist_in.py:134-135: both moduli 0
-                    mods |= _ENERGY_BITS[name]
+    def _resolve(self, mir, dm):
+        """Walk the listed energy modules through the table -> (module mask, {name: parameters}) of the modules that are
+        switched on; the host-side constants go to ``_const_energy``."""
+        self._const_energy = {}
+        mesh, pr, gp = self.mesh, self.param_resolver, self.global_params
+        mods, p = 0, {}
+        for name in self.energy_module_names:
+            bit, resolve, reads, args = _WALK[name]
+            if resolve is None:
+                prm = True
+            elif reads == "params":
+                prm = resolve(pr, gp, *args)
+            elif reads == "mesh":
+                prm = resolve(mesh, pr, gp, *args)
             else:
-                mods |= _ENERGY_BITS[name]
-        if rim_bilayer is not None:  # (refused before anything is uploaded)
+                prm = resolve(self, mir, dm)
+            if prm:  # (None, False, a zero modulus: switched off)
+                mods |= bit
+                p[name] = prm
+        return mods, p
+
+    def _check(self, mir, mods, p, area_con):
+        """Every refusal that reads only names, parameters and the mesh, in one order, with what is resolved on the way
+        (the two modules admitted by the other modules' bits, the constraint bits, the bending model, the leaflets'
+        parameters) -> (module mask, bending model, gradient mode, volume stiffness, target volume, tilt_thetaB_boundary_in's
+        tables, (leaflet parameters, absent outer rows or None) or None).  Nothing here touches the device: no upload precedes a refusal."""
+        gp, names, cons = self.global_params, self.energy_module_names, self.constraint_module_names
+        rim_bilayer, thetab = p.get("tilt_rim_source_bilayer"), p.get("tilt_thetaB_contact_in")
+        if rim_bilayer is not None:
             if mods & _SINGLE_TILT_BITS:
                 raise L.MembraneHipError("tilt_rim_source_bilayer together with a single-field tilt module is outside "
                                          "the HIP hot path")
-            if rim_bilayer["follow"] and (self._pin_names or "volume" in self.constraint_module_names):
+            if rim_bilayer["follow"] and (self._pin_names or "volume" in cons):
                 raise L.MembraneHipError("tilt_rim_source_bilayer in follow mode (pin_to_circle_mode: fit) next to "
                                          "pin_to_plane / pin_to_circle or the volume constraint's enforcer on the line "
                                          "search is outside the HIP hot path")
@@ -509,31 +529,28 @@ class Minimizer:
                     and np.all(np.isfinite(rim_bilayer["normal"]))):
                 raise L.MembraneHipError("tilt_rim_source_bilayer: gamma, tilt_rim_source_center and the frame's normal "
                                          "must be finite")
-        if thetab is not None and mods & _SINGLE_TILT_BITS:  # (refused before anything is uploaded)
+        if thetab is not None and mods & _SINGLE_TILT_BITS:
             raise L.MembraneHipError("tilt_thetaB_contact_in together with a single-field tilt module is outside the "
                                      "HIP hot path")
         self._thetab_update = thetab is not None and thetab["penalty_mode"] == "legacy" and thetab["k"] > 0.0
-        rim_match = self._rim_match_params(mods) if rim_match else None  # (refused before anything is uploaded)
-        if rim_match is not None:
-            mods |= _ENERGY_BITS[_RIM_MATCH]
-            del self._const_energy[_RIM_MATCH]
-        tbb = self._thetab_boundary_params(mods)
+        if _RIM_MATCH in p:  # (a non-zero strength)
+            p[_RIM_MATCH] = self._rim_match_params(mods)
+            if p[_RIM_MATCH] is None:
+                del p[_RIM_MATCH]
+                mods &= ~_MODULES[_RIM_MATCH].bit
+            else:
+                del self._const_energy[_RIM_MATCH]
+        tbb = self._thetab_boundary_params(mods) if _tbb.NAME in cons else None
         self._tbb_active = tbb is not None
-        target = 0.0
+        vol_mode = gp.get("volume_constraint_mode", "lagrange")
+        target_volume = self._target_volume() if getattr(self.mesh, "bodies", None) else None
+        target = 0.0 if target_volume is None else target_volume
         stiffness = float(gp.get("volume_stiffness") or 0.0)
-        body = mir.body
-        if body is not None:
-            t = body.target_volume if body.target_volume is not None else (body.options or {}).get("target_volume")
-            if t is not None:
-                target = float(t)
         if mods & L.MS_MOD_VOLUME_PENALTY:
-            kv = body_penalty_params(self.mesh, gp, self.param_resolver)
-            stiffness, target = kv
-        if "volume" in self.constraint_module_names and vol_mode == "lagrange" and body is not None \
-                and self._target_volume() is not None:
+            stiffness, target = body_penalty_params(self.mesh, gp, self.param_resolver)
+        if "volume" in cons and vol_mode == "lagrange" and target_volume is not None:
             mods |= L.MS_CON_VOLUME
-        if body is not None and self._target_volume() is not None and vol_mode == "lagrange" \
-                and not gp.get("volume_projection_during_minimization", True):
+        if target_volume is not None and vol_mode == "lagrange" and not gp.get("volume_projection_during_minimization", True):
             mods |= L.MS_TRACK_VOLUME  # drift check of minimizer.py:1478-1513
         if area_con is not None and area_con[0] == L.MS_AREA_BODY:
             mods |= L.MS_CON_BODY_AREA  # its row takes part in the KKT projection (global_area has none)
@@ -543,55 +560,51 @@ class Minimizer:
             raise L.MembraneHipError("bending and bending_tilt together are outside the HIP hot path")
         if mods & L.MS_MOD_BENDING_TILT:
             model = "helfrich"  # bending_tilt.py:212-215
-        any_bend = mods & (L.MS_MOD_BENDING | L.MS_MOD_BENDING_TILT)
+        any_bend = mods & _BEND_BITS
         mode = bending_gradient_mode(gp) if any_bend else "analytic"
         if mode == "approx" and (mods & L.MS_MOD_BENDING_TILT) and np.any(_boundary(self.mesh)) \
-                and self.energy_module_names.index("bending_tilt") != len(self.energy_module_names) - 1:
+                and names.index("bending_tilt") != len(names) - 1:
             raise L.MembraneHipError(
                 "bending_gradient_mode=approx with modules listed AFTER bending_tilt on an open mesh is "
                 "not on the fused device path (bending_tilt.py:297-299 zeroes boundary rows of what was "
                 "accumulated so far); list bending_tilt last")
         for edge_mod in _EDGE_MODULES:
-            if mode == "approx" and (mods & _ENERGY_BITS[edge_mod]) and np.any(_boundary(self.mesh)):
+            if mode == "approx" and edge_mod in p and np.any(_boundary(self.mesh)):
                 # (bending.py:165-166 / bending_tilt.py:297-299 zero the boundary rows of what the modules listed before
                 # them accumulated; the device adds the edge modules' rows behind the whole gradient pass)
                 raise L.MembraneHipError(f"{edge_mod} with bending_gradient_mode=approx on an open mesh is outside the "
                                          "HIP hot path")
         if mode == "approx" and (mods & L.MS_MOD_BENDING):
-            order = self.energy_module_names
-            if order.index("bending") != len(order) - 1 and np.any(_boundary(self.mesh)):
+            if names.index("bending") != len(names) - 1 and np.any(_boundary(self.mesh)):
                 raise L.MembraneHipError(
                     "bending_gradient_mode=approx with energy modules listed AFTER bending on an "
                     "open mesh is not on the fused device path (bending.py:165-166 zeroes boundary "
                     "rows of what was accumulated so far); list bending last")
-        if mods & L.MS_MOD_SURFACE:
-            mir.upload_surface_tension()
-        if any_bend:
-            mir.upload_bending_params(gp, model)
-        if mods & L.MS_MOD_TILT_SPLAY_TWIST_IN:
+        if "tilt_splay_twist_in" in p:
             if mods & _SINGLE_TILT_BITS:
                 raise L.MembraneHipError("tilt_splay_twist_in together with a single-field tilt module is outside the "
                                          "HIP hot path")
             if self._pin_names:
                 raise L.MembraneHipError("tilt_splay_twist_in next to pin_to_plane / pin_to_circle is outside the HIP "
                                          "hot path")
-            if _fplane.NAME in self.constraint_module_names:
+            if _fplane.NAME in cons:
                 raise L.MembraneHipError("tilt_splay_twist_in next to fixed_plane is outside the HIP hot path")
-            if "volume" in self.constraint_module_names:
+            if "volume" in cons:
                 raise L.MembraneHipError("tilt_splay_twist_in next to the volume constraint's enforcer is outside the "
                                          "HIP hot path")
         if (mods & _SINGLE_TILT_BITS) and (mods & _LEAFLET_BITS):
             raise L.MembraneHipError("single-field and leaflet tilt modules together are outside the HIP hot path")
+        leaflet = None
         if mods & _LEAFLET_BITS:
             _lc.check_supported(gp, self.mesh)
             if gp.get("line_search_reduced_energy", False):
                 raise L.MembraneHipError("line_search_reduced_energy is outside the HIP hot path")
-            # leaflet_out_absent_presets: the rows (leaflet_common keeps them on the mesh, once per topology and preset
-            # list; refresh_modules() after the vertex presets change); validate_leaflet_absence_topology once per such
-            # key; what does not read the mask yet is refused
+            # leaflet_out_absent_presets: the rows and validate_leaflet_absence_topology once per topology (as the mirror
+            # keys it) and preset list (refresh_modules() after the vertex presets change); what cannot read the mask is refused
             absent = None
-            if _lc.normalize_preset_list(gp.get("leaflet_out_absent_presets")):
-                akey = (mir._topo_key, tuple(sorted(_lc.normalize_preset_list(gp.get("leaflet_out_absent_presets")))),
+            presets = gp.get("leaflet_out_absent_presets")
+            if presets and (presets := _lc.normalize_preset_list(presets)):
+                akey = (mir._topology_key(), tuple(sorted(presets)),
                         str(gp.get("leaflet_out_absence_mode", "strict") or "strict").strip().lower())
                 if getattr(self, "_absent_key", None) != akey:
                     _lc.validate_absence_topology(self.mesh, gp)
@@ -600,96 +613,97 @@ class Minimizer:
                 absent = self._absent_rows
                 if mods & L.MS_MOD_BENDING_TILT_OUT:
                     raise L.MembraneHipError(_lc.BT_OUT_ABSENT_MESSAGE)
-            leaflet_params = {lf: _lc.device_params(self.param_resolver, gp, lf) for lf in ("in", "out")}
-            if absent is None:
-                mir.upload_leaflets(leaflet_params)  # (clears the mask of an earlier configuration)
-            else:
-                mir.upload_leaflets(leaflet_params, absent_out=absent)
-            for lf, prm in disk_params.items():
-                key = (mir._topo_key, prm["disk_rows"].tobytes(), tuple((k, v) for k, v in prm.items() if k != "disk_rows"))
-                if mir._leaflet_keys.get("bend_disk_" + lf) != key:
-                    dm.set_leaflet_disk_target(lf, **prm)
-                    mir._leaflet_keys["bend_disk_" + lf] = key
-            for lf, prm in rim_params.items():  # keyed on topology, rim edges, gamma and frame
-                key = (mir._topo_key, _lc.rim_source_key(prm))
-                if mir._leaflet_keys.get("bend_rim_" + lf) != key:
-                    dm.set_leaflet_rim_source(lf, **prm)
-                    mir._leaflet_keys["bend_rim_" + lf] = key
-            if rim_bilayer is not None:  # keyed like the leaflets' tables
-                key = (mir._topo_key, _lc.rim_source_key(rim_bilayer))
-                if mir._leaflet_keys.get("bend_rim_bilayer") != key:
-                    dm.set_rim_source_bilayer(**rim_bilayer)
-                    mir._leaflet_keys["bend_rim_bilayer"] = key
-            if thetab is not None:  # keyed like the rim tables; theta_B goes with every configuration
-                key = (mir._topo_key, id(dm), _lc.thetab_contact_key(thetab))
-                if mir._leaflet_keys.get("bend_thetab") != key:
-                    dm.set_thetab_contact(**thetab)
-                    mir._leaflet_keys["bend_thetab"] = key
-                dm.set_thetab_value(_lc.thetab_value(gp))
-            if rim_match is not None:  # keyed like the pins: topology, context and parameters
-                key = (mir._topo_key, id(dm), _lc.rim_match_key(rim_match))
-                if mir._leaflet_keys.get("bend_rim_match") != key:
-                    dm.set_rim_match(**rim_match)
-                    mir._leaflet_keys["bend_rim_match"] = key
-            # tilt_thetaB_boundary_in: keyed like the other ring tables; theta_B and the relaxation's cadence go with every
-            # configuration; a table of an earlier configuration is cleared
-            key = None if tbb is None else (mir._topo_key, id(dm), _tbb.device_key(tbb))
-            old = mir._leaflet_keys.get("bend_tbb")
-            if old != key:
-                if tbb is not None:
-                    dm.set_thetab_boundary(**tbb)
-                elif old is not None and old[1] == id(dm):
-                    dm.set_thetab_boundary(None)
-                mir._leaflet_keys["bend_tbb"] = key
-            if tbb is not None:
-                dm.set_thetab_value(_lc.thetab_value(gp))
-                dm.set_tilt_projection(*_tbb.projection_schedule(gp))
-            if coupling is not None:  # keyed on modulus and sign ("bend_": not a tilt upload, mark_device_leaflets_current)
-                key = (id(dm), coupling)
-                if mir._leaflet_keys.get("bend_coupling") != key:
-                    dm.set_tilt_coupling(*coupling)
-                    mir._leaflet_keys["bend_coupling"] = key
-            if splay_twist is not None:  # keyed on the two moduli ("bend_": not a tilt upload)
-                key = (id(dm), splay_twist)
-                if mir._leaflet_keys.get("bend_splay_twist") != key:
-                    dm.set_tilt_splay_twist(*splay_twist)
-                    mir._leaflet_keys["bend_splay_twist"] = key
+            leaflet = ({lf: _lc.device_params(self.param_resolver, gp, lf) for lf in ("in", "out")}, absent)
             if mods & _LEAFLET_BT_BITS:
                 _lc.check_bt_supported(gp)
-                if mods & (L.MS_MOD_BENDING | L.MS_MOD_BENDING_TILT):
+                if mods & _BEND_BITS:
                     raise L.MembraneHipError("bending / bending_tilt together with bending_tilt_in/out is outside "
                                              "the HIP hot path")
-                for lf, bit in (("in", L.MS_MOD_BENDING_TILT_IN), ("out", L.MS_MOD_BENDING_TILT_OUT)):
-                    if mods & bit:
-                        kappa, c0 = _lc.bending_params(self.mesh, gp, lf)
-                        key = (mir._topo_key, kappa.tobytes(), c0.tobytes())
-                        if mir._leaflet_keys.get("bend_" + lf) != key:
-                            dm.set_leaflet_bending(lf, kappa, c0)
-                            mir._leaflet_keys["bend_" + lf] = key
-        if mods & (_SINGLE_TILT_BITS):
+        if mods & _SINGLE_TILT_BITS:
             if gp.get("line_search_reduced_energy", False):
                 raise L.MembraneHipError("line_search_reduced_energy (inner tilt relaxation inside every "
                                          "line-search trial, minimizer.py:568-608) is outside the HIP hot path")
             if str(gp.get("tilt_transport_model", "ambient_v1") or "ambient_v1").strip().lower() != "ambient_v1":
                 raise L.MembraneHipError("tilt_transport_model other than ambient_v1 is outside the HIP hot path")
-            mir.upload_tilts(gp)
-            mir.upload_tilt_fixed()
-            dm.set_tilt_smoothness(float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0))
-        if self._pin_names:
-            self._upload_pins(mir, dm, mods)
-        if _fplane.NAME in self.constraint_module_names:
-            if mods & _TILT_BITS and ((mods & L.MS_CON_VOLUME) or "volume" in self.constraint_module_names):
+        if _fplane.NAME in cons:
+            if mods & _TILT_BITS and ((mods & L.MS_CON_VOLUME) or "volume" in cons):
                 raise L.MembraneHipError("fixed_plane next to tilt modules together with the volume constraint is "
                                          "outside the HIP hot path")
             if rim_bilayer is not None and rim_bilayer["follow"]:  # (ms_step refuses the one-leaflet sources' follow mode)
                 raise L.MembraneHipError("tilt_rim_source_bilayer in follow mode (pin_to_circle_mode: fit) next to "
                                          "fixed_plane's enforcer on the line search is outside the HIP hot path")
+        return mods, model, mode, stiffness, target, tbb, leaflet
+
+    def _apply(self, mir, dm, p, area_con, checked):
+        """Synchronise the mirror and upload what _resolve() and _check() made: the per-module tables where their key
+        changed, what goes with every configuration, the constraints' tables, and set_params behind ``_configured_key``."""
+        mods, model, mode, stiffness, target, tbb, leaflet = checked
+        gp = self.global_params
+        if dm is None:
+            dm = mir.sync()
+            if self.deterministic is not None:
+                dm.set_deterministic(self.deterministic)
+        topo, keys = mir._topo_key, mir._leaflet_keys
+        if mods & L.MS_MOD_SURFACE:
+            mir.upload_surface_tension()
+        if mods & _BEND_BITS:
+            mir.upload_bending_params(gp, model)
+        if mods & _LEAFLET_BITS:
+            if leaflet[1] is None:
+                mir.upload_leaflets(leaflet[0])  # (clears the mask of an earlier configuration)
+            else:
+                mir.upload_leaflets(leaflet[0], absent_out=leaflet[1])
+            # the modules' tables ("bend_": no tilt upload, mark_device_leaflets_current leaves the key): keyed on topology
+            # and parameters, and on the context where the table is its own; the leaflets' in the modules' listed order
+            for lf in self._disk_order:
+                if (prm := p.get("tilt_disk_target_" + lf)) is not None:
+                    key = (topo, prm["disk_rows"].tobytes(), tuple([kv for kv in prm.items() if kv[0] != "disk_rows"]))
+                    _keyed_upload(keys, "bend_disk_" + lf, key, dm, "set_leaflet_disk_target", (lf,), prm)
+            for lf in self._rim_order:
+                if (prm := p.get("tilt_rim_source_" + lf)) is not None:
+                    _keyed_upload(keys, "bend_rim_" + lf, (topo, _lc.rim_source_key(prm)), dm, "set_leaflet_rim_source", (lf,), prm)
+            if (prm := p.get("tilt_rim_source_bilayer")) is not None:
+                _keyed_upload(keys, "bend_rim_bilayer", (topo, _lc.rim_source_key(prm)), dm, "set_rim_source_bilayer", (), prm)
+            if (prm := p.get("tilt_thetaB_contact_in")) is not None:  # (theta_B goes with every configuration)
+                _keyed_upload(keys, "bend_thetab", (topo, id(dm), _lc.thetab_contact_key(prm)), dm, "set_thetab_contact", (), prm)
+                dm.set_thetab_value(_lc.thetab_value(gp))
+            if (prm := p.get(_RIM_MATCH)) is not None:
+                _keyed_upload(keys, "bend_rim_match", (topo, id(dm), _lc.rim_match_key(prm)), dm, "set_rim_match", (), prm)
+            # tilt_thetaB_boundary_in: keyed like the other ring tables; theta_B and the relaxation's cadence go with every
+            # configuration; a table of an earlier configuration is cleared
+            key = None if tbb is None else (topo, id(dm), _tbb.device_key(tbb))
+            old = keys.get("bend_tbb")
+            if old != key:
+                if tbb is not None:
+                    dm.set_thetab_boundary(**tbb)
+                elif old is not None and old[1] == id(dm):
+                    dm.set_thetab_boundary(None)
+                keys["bend_tbb"] = key
+            if tbb is not None:
+                dm.set_thetab_value(_lc.thetab_value(gp))
+                dm.set_tilt_projection(*_tbb.projection_schedule(gp))
+            if (prm := p.get("tilt_coupling")) is not None:  # modulus and sign
+                _keyed_upload(keys, "bend_coupling", (id(dm), prm), dm, "set_tilt_coupling", prm)
+            if (prm := p.get("tilt_splay_twist_in")) is not None:  # the two moduli
+                _keyed_upload(keys, "bend_splay_twist", (id(dm), prm), dm, "set_tilt_splay_twist", prm)
+            for lf in ("in", "out"):
+                if "bending_tilt_" + lf in p:
+                    kappa, c0 = _lc.bending_params(self.mesh, gp, lf)
+                    _keyed_upload(keys, "bend_" + lf, (topo, kappa.tobytes(), c0.tobytes()), dm, "set_leaflet_bending",
+                                  (lf, kappa, c0))
+        if mods & _SINGLE_TILT_BITS:
+            mir.upload_tilts(gp)
+            mir.upload_tilt_fixed()
+            dm.set_tilt_smoothness(float(gp.get("tilt_smoothness_rigidity", 0.0) or 0.0))
+        if self._pin_names:
+            self._upload_pins(mir, dm, mods)
         self._upload_enforce_only(mir, dm)
         if area_con is not None or getattr(self, "_area_set_on", None) is dm:
             # (the constraint of an earlier configuration of this minimizer is replaced or cleared)
             if (None if area_con is None else area_con[:2]) != dm.area_constraint:
                 dm.set_area_constraint(*(area_con[:2] if area_con is not None else (L.MS_AREA_NONE, 0.0)))
             self._area_set_on = dm if area_con is not None else None
+        area_params = p.get("body_area_penalty")
         key = (mods, model, mode, stiffness, target, area_params, self._line_key, self._edgepen_key, id(dm))
         if key != self._configured_key:
             if area_params is not None:
@@ -699,7 +713,7 @@ class Minimizer:
                           bending_grad_mode=L.MS_GRAD_ANALYTIC if mode == "analytic" else L.MS_GRAD_APPROX,
                           volume_stiffness=stiffness, target_volume=target)
             self._configured_key = key
-        return mir, dm
+        return dm
 
     def _upload_line(self, mir, dm) -> bool:
         """Resolve the tagged edges and their gamma (modules/energy/line_tension.py) once per mesh topology and
@@ -850,46 +864,30 @@ class Minimizer:
                 out["edge_length_penalty"] = pen_e
             if "surface" in out:
                 out["surface"] = float(e[0]) - line_e - pen_e if dm.modules & L.MS_MOD_SURFACE else 0.0
-        # a rim source adds its sums into the leaflet's tilt-magnitude slot: it reports its own energy, and whoever reports
-        # energies[3] or that slot reports it without the rim source's part
-        rim_e = {lf: (dm.leaflet_rim_source_energy(lf) if dm.modules & _ENERGY_BITS["tilt_rim_source_" + lf] else 0.0)
-                 for lf in ("in", "out")}
-        for lf in ("in", "out"):
-            if "tilt_rim_source_" + lf in out:
-                out["tilt_rim_source_" + lf] = rim_e[lf]
-        # the coupling rides in the outer leaflet's slot in the same way
-        cpl_e = dm.tilt_coupling_energy() if dm.modules & L.MS_MOD_TILT_COUPLING else 0.0
-        if "tilt_coupling" in out:
-            out["tilt_coupling"] = cpl_e
-        # ... and so does the bilayer rim source
-        rb_e = dm.rim_source_bilayer_energy() if dm.modules & L.MS_MOD_TILT_RIM_SOURCE_BILAYER else 0.0
-        if _RIM_BILAYER in out:
-            out[_RIM_BILAYER] = rb_e
-        # ... and the theta_B contact term in the inner leaflet's slot
-        tb_e = dm.thetab_contact_energy() if dm.modules & L.MS_MOD_TILT_THETAB_CONTACT_IN else 0.0
-        if _THETAB in out:
-            out[_THETAB] = tb_e
-        # ... and the rim matching term, one part in each leaflet's slot
-        rm_e = dm.rim_match_energies() if dm.modules & L.MS_MOD_RIM_SLOPE_MATCH_OUT else (0.0, 0.0, 0.0)
-        if _RIM_MATCH in out and dm.modules & L.MS_MOD_RIM_SLOPE_MATCH_OUT:
-            out[_RIM_MATCH] = rm_e[0]
-        # the splay / twist term rides in the inner leaflet's smoothness slot in the same way
-        st_e = dm.tilt_splay_twist_energy() if dm.modules & L.MS_MOD_TILT_SPLAY_TWIST_IN else 0.0
-        if "tilt_splay_twist_in" in out:
-            out["tilt_splay_twist_in"] = st_e
+        # the ride-along modules: each reports its own energy, and whoever reports the slot its sums ride in, or
+        # energies[3], reports it without that part
+        own, parts = [], {}
+        for name, rec in _MODULES.items():
+            if rec.energy is None:
+                continue
+            v = rec.energy(dm) if dm.modules & rec.bit else 0.0
+            own.append(v[0] if isinstance(v, tuple) else v)
+            for k, host in enumerate(rec.hosts):
+                parts.setdefault(host, []).append(v[1 + k] if isinstance(v, tuple) else v)
+            if name in out and dm.modules & rec.bit:
+                out[name] = own[-1]
         for table in (_TILT_SCALAR, _BEND_SCALAR):
             sharing = [n for n in out if n in table]
             if len(sharing) > 1:  # they share one entry of the energy vector: split via the scalars
                 sc = dm.fetch_scalars()
                 for n in sharing:
                     out[n] = float(sc[table[n]]) if dm.modules & _ENERGY_BITS[n] else 0.0
-                    if n in ("tilt_in", "tilt_out") and dm.modules & _ENERGY_BITS[n]:
-                        out[n] -= rim_e[n[5:]] + ((cpl_e + rb_e + rm_e[1]) if n == "tilt_out" else (tb_e + rm_e[2]))
-                    if n == "tilt_smoothness_in" and dm.modules & _ENERGY_BITS[n]:
-                        out[n] -= st_e
-            elif len(sharing) == 1 and table is _TILT_SCALAR and (rim_e["in"] or rim_e["out"] or cpl_e or st_e or rb_e
-                                                                     or tb_e or rm_e[0]):
-                out[sharing[0]] = float(e[3]) - rim_e["in"] - rim_e["out"] - cpl_e - st_e - rb_e - tb_e - rm_e[0]
+                    if n in parts and dm.modules & _ENERGY_BITS[n]:
+                        out[n] -= parts[n][0] + sum(parts[n][1:])
+            elif len(sharing) == 1 and table is _TILT_SCALAR and any(own):
+                out[sharing[0]] = float(e[3])
+                for v in own:
+                    out[sharing[0]] -= v
         return out
 
     # -- constraint enforcement (minimizer.py:1103-1188) ---------------------------

@@ -23,6 +23,8 @@ from membrane_solver_amd.runtime.energy_manager import EnergyModuleManager
 from membrane_solver_amd.runtime.minimizer import Minimizer
 from membrane_solver_amd.runtime.steppers import GradientDescent
 
+from minimizer_stub import install_stub
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 TRAJ = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLD, "traj_*edgepen*.npz")))
@@ -338,12 +340,7 @@ def test_minimizer_refuses_approx_bending_gradient_on_an_open_mesh(monkeypatch):
     """bending.py:165-166 zeroes the boundary rows of what the modules listed before it accumulated; the device adds
     the penalty's rows behind the whole gradient pass, so the combination is refused (as it is for line_tension).  The
     device is stood in for: the refusal is taken before anything but the tables is handed to it."""
-    from membrane_solver_amd.runtime import minimizer as mzmod
-
-    uploads = []
-    dm = types.SimpleNamespace(nv=4, set_edge_length_penalty=lambda *a: uploads.append(a))
-    mir = types.SimpleNamespace(sync=lambda: dm, dm=dm, body=None, _topo_key=1)
-    monkeypatch.setattr(mzmod, "mirror_for", lambda *a, **k: mir)
+    dm, _mir = install_stub(monkeypatch)
     gp = {"bending_modulus": 1.0, "bending_gradient_mode": "approx"}
     eo = {0: {"target_length": 0.5}}
     open_mesh = ArrayMesh(P4, T4[:3], global_parameters=gp, edges=E4, edge_options=eo,
@@ -351,7 +348,9 @@ def test_minimizer_refuses_approx_bending_gradient_on_an_open_mesh(monkeypatch):
     mz = _minimizer(open_mesh, ["edge_length_penalty", "bending"])
     with pytest.raises(L.MembraneHipError, match="edge_length_penalty with bending_gradient_mode=approx on an open"):
         mz._device()
+    uploads = [c[1] for c in dm.calls if c[0] == "set_edge_length_penalty"]
     assert len(uploads) == 1 and len(uploads[0]) == 4  # (the edge was charged: the bit was on when it was refused)
+    assert not [c for c in dm.calls if c[0] not in ("sync", "set_edge_length_penalty")]  # (nothing but the tables)
     # nothing charged: the module's bit stays off and there is nothing to refuse on its account
     idle = ArrayMesh(P4, T4[:3], global_parameters=gp, edges=E4, edge_options={0: {"energy": "edge_length_penalty"}},
                      energy_modules=["edge_length_penalty", "bending"])
@@ -360,8 +359,7 @@ def test_minimizer_refuses_approx_bending_gradient_on_an_open_mesh(monkeypatch):
         mz._device()
     except L.MembraneHipError as exc:
         pytest.fail(f"refused with nothing charged: {exc}")
-    except AttributeError:
-        pass  # (past the refusals: the stand-in has no parameter setters)
+    assert dm.modules == L.MS_MOD_BENDING  # (past the refusals: the parameters were set, without the module's bit)
 
 
 class _FakeDevice:

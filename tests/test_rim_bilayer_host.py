@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from minimizer_stub import Refused, install_stub
 from membrane_solver_amd import _lib as L
 from membrane_solver_amd import meshgen
 from membrane_solver_amd.core.parameters import GlobalParameters, ParameterResolver
@@ -266,39 +267,9 @@ def test_minimizer_knows_the_module():
                       quiet=True)
 
 
-class _Refused(Exception):
-    pass
-
-
 def _no_device(monkeypatch):
     """The refusals come before anything is uploaded: any upload or set_params in these tests is an error."""
-    from membrane_solver_amd.geometry import mesh as gm
-
-    class FakeDM:
-        modules = 0
-
-        def set_deterministic(self, on):
-            pass
-
-        def __getattr__(self, name):
-            raise _Refused("device call " + name)
-
-    class FakeMirror:
-        body = None
-        _topo_key = 0
-        _leaflet_keys = {}
-        dm = FakeDM()
-
-        def sync(self, **kw):
-            return self.dm
-
-        def __getattr__(self, name):
-            raise _Refused("mirror call " + name)
-
-    from membrane_solver_amd.runtime import minimizer as mzr
-
-    monkeypatch.setattr(mzr, "mirror_for", lambda *a, **k: FakeMirror())
-    return gm
+    install_stub(monkeypatch, refuse=True)
 
 
 def test_minimizer_refusals_come_before_any_upload(monkeypatch):
@@ -318,7 +289,7 @@ def test_minimizer_refusals_come_before_any_upload(monkeypatch):
             mz._device()
     # without a refusal the next thing IS an upload (fixed mode next to pins is allowed)
     mz = _minimizer({G: "rim", S: 2.0}, _tag(rows, pin_to_circle_mode="fixed"), ["tilt_in", NAME])
-    with pytest.raises(_Refused):
+    with pytest.raises(Refused):
         mz._device()
 
 

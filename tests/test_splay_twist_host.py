@@ -23,6 +23,7 @@ from membrane_solver_amd.runtime.minimizer import Minimizer
 from membrane_solver_amd.runtime.steppers import GradientDescent
 
 from conftest import load_golden
+from minimizer_stub import install_stub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = load_golden("splay_twist_cases.npz")
@@ -278,32 +279,18 @@ def test_minimizer_knows_the_module():
     assert mzr._ENERGY_BITS["tilt_splay_twist_in"] == L.MS_MOD_TILT_SPLAY_TWIST_IN == BIT
     assert mzr._ENERGY_SLOT["tilt_splay_twist_in"] is None and BIT & mzr._LEAFLET_BITS and BIT & mzr._TILT_BITS
     _minimizer(ON, ["tilt_in", "tilt_splay_twist_in"])  # accepted by the wiring
-    # the refusal of an unknown module lists the module
-    assert '"tilt_coupling, tilt_splay_twist_in)")' in inspect.getsource(mzr.Minimizer.refresh_modules)
-
-
-class _Stub:
-    """a DeviceMesh that records what it is handed and refuses nothing"""
-
-    def __init__(self):
-        self.calls, self.modules = [], 0
-
-    def __getattr__(self, name):
-        def rec(*a, **k):
-            self.calls.append((name, a, k))
-            if name == "set_params":
-                self.modules = k["modules"]
-        return rec
+    # the refusal of an unknown module lists every module the path takes
+    plugin = types.SimpleNamespace(compute_energy_and_gradient_array=None)  # (a module some plugin could load)
+    mesh = ArrayMesh(P3, T3, global_parameters=dict(ON))
+    with pytest.raises(L.MembraneHipError, match="energy module 'no_such_module' is outside the HIP hot path") as exc:
+        Minimizer(mesh, mesh.global_parameters, GradientDescent(), types.SimpleNamespace(get_module=lambda name: plugin),
+                  ConstraintModuleManager([]), energy_modules=["tilt_in", "no_such_module"], constraint_modules=[], quiet=True)
+    listed = str(exc.value).split("(", 1)[1].rstrip(")").split(", ")
+    assert listed == list(mzr._ENERGY_BITS) and "tilt_splay_twist_in" in listed and "gaussian_curvature" in listed
 
 
 def _with_stub(monkeypatch, gp, energy, constraints=()):
-    from membrane_solver_amd.runtime import minimizer as mzmod
-
-    dm = _Stub()
-    mir = types.SimpleNamespace(sync=lambda: dm, dm=dm, body=None, _topo_key=1, _leaflet_keys={},
-                                upload_leaflets=lambda p: dm.calls.append(("upload_leaflets", (p,), {})),
-                                upload_surface_tension=lambda: None, upload_bending_params=lambda *a: None)
-    monkeypatch.setattr(mzmod, "mirror_for", lambda *a, **k: mir)
+    dm, mir = install_stub(monkeypatch)
     return _minimizer(gp, energy, constraints), dm, mir
 
 

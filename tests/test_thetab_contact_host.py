@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from minimizer_stub import Refused, install_stub
 from membrane_solver_amd import _lib as L
 from membrane_solver_amd import meshgen
 from membrane_solver_amd.core.parameters import GlobalParameters, ParameterResolver
@@ -309,36 +310,9 @@ def _minimizer(gp, vopts, mods, cons=()):
                      ConstraintModuleManager(list(cons)), quiet=True)
 
 
-class _Refused(Exception):
-    pass
-
-
 def _no_device(monkeypatch):
     """The refusals come before anything is uploaded: any upload or set_params in these tests is an error."""
-    from membrane_solver_amd.runtime import minimizer as mzr
-
-    class FakeDM:
-        modules = 0
-
-        def set_deterministic(self, on):
-            pass
-
-        def __getattr__(self, name):
-            raise _Refused("device call " + name)
-
-    class FakeMirror:
-        body = None
-        _topo_key = 0
-        _leaflet_keys = {}
-        dm = FakeDM()
-
-        def sync(self, **kw):
-            return self.dm
-
-        def __getattr__(self, name):
-            raise _Refused("mirror call " + name)
-
-    monkeypatch.setattr(mzr, "mirror_for", lambda *a, **k: FakeMirror())
+    install_stub(monkeypatch, refuse=True)
 
 
 def test_minimizer_knows_the_module_and_refuses_before_any_upload(monkeypatch):
@@ -362,7 +336,7 @@ def test_minimizer_knows_the_module_and_refuses_before_any_upload(monkeypatch):
     # accepted next to the pins and the volume constraint: the next thing IS an upload
     for cons in ((), ("pin_to_circle",), ("volume",)):
         mz = _minimizer(BASE, vo, ["tilt_in", NAME], cons)
-        with pytest.raises(_Refused):
+        with pytest.raises(Refused):
             mz._device()
 
 

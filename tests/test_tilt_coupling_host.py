@@ -22,6 +22,7 @@ from membrane_solver_amd.runtime.minimizer import Minimizer
 from membrane_solver_amd.runtime.steppers import GradientDescent
 
 from conftest import load_golden
+from minimizer_stub import install_stub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = load_golden("tilt_coupling_cases.npz")
@@ -172,28 +173,8 @@ def test_minimizer_knows_the_module():
     _minimizer(ON, ["tilt_in", "tilt_out", "tilt_coupling"])  # accepted by the wiring
 
 
-class _Stub:
-    """a DeviceMesh that records what it is handed and refuses nothing"""
-
-    def __init__(self):
-        self.calls, self.modules = [], 0
-
-    def __getattr__(self, name):
-        def rec(*a, **k):
-            self.calls.append((name, a, k))
-            if name == "set_params":
-                self.modules = k["modules"]
-        return rec
-
-
 def _with_stub(monkeypatch, gp, energy):
-    from membrane_solver_amd.runtime import minimizer as mzmod
-
-    dm = _Stub()
-    mir = types.SimpleNamespace(sync=lambda: dm, dm=dm, body=None, _topo_key=1, _leaflet_keys={},
-                                upload_leaflets=lambda p: dm.calls.append(("upload_leaflets", (p,), {})),
-                                upload_surface_tension=lambda: None, upload_bending_params=lambda *a: None)
-    monkeypatch.setattr(mzmod, "mirror_for", lambda *a, **k: mir)
+    dm, mir = install_stub(monkeypatch)
     return _minimizer(gp, energy), dm, mir
 
 
