@@ -187,19 +187,14 @@ int ms_create(ms_ctx** out, int device, int nv, int nf, const double* positions,
     f0.mod_bt = MS_MOD_BENDING_TILT; f0.s_ebt = MS_S_EBT;
     f1.mod_dt = MS_MOD_TILT_DISK_TARGET_IN; f1.s_edt = MS_S_EDT_IN; f1.s_dtr = MS_S_DTR_IN;
     f1.mod_rs = MS_MOD_TILT_RIM_SOURCE_IN;
-    f1.mod_cpl = MS_MOD_TILT_COUPLING;
-    f1.mod_rb = MS_MOD_TILT_RIM_SOURCE_BILAYER;
-    f1.mod_st = MS_MOD_TILT_SPLAY_TWIST_IN;
-    f1.mod_tb = MS_MOD_TILT_THETAB_CONTACT_IN;
+    f1.mod_addons = addon_readers(1, /*rsm_inner=*/false);  // (rim_slope_match_out's bit: ms_set_rim_match, with a disk ring)
     TiltField& f2 = c->tf[2];
     f2.fixed_bit = VF_TILT_FIXED_OUT; f2.mod_tilt = MS_MOD_TILT_OUT; f2.mod_smooth = MS_MOD_TILT_SMOOTH_OUT;
     f2.s_etilt = MS_S_ETILT_OUT; f2.s_ets = MS_S_ETS_OUT; f2.s_gn2 = MS_S_TGNORM2_OUT; f2.s_rz = MS_S_TRZ_OUT;
     f2.mod_bt = MS_MOD_BENDING_TILT_OUT; f2.s_ebt = MS_S_EBT_OUT; f2.div_sign = 1.0;
     f2.mod_dt = MS_MOD_TILT_DISK_TARGET_OUT; f2.s_edt = MS_S_EDT_OUT; f2.s_dtr = MS_S_DTR_OUT;
     f2.mod_rs = MS_MOD_TILT_RIM_SOURCE_OUT;
-    f2.mod_cpl = f2.mod_cpl_slot = MS_MOD_TILT_COUPLING;
-    f2.mod_rb = f2.mod_rb_slot = MS_MOD_TILT_RIM_SOURCE_BILAYER;
-    f2.mod_rsm = MS_MOD_RIM_SLOPE_MATCH_OUT;  // (the inner field's: ms_set_rim_match, with a disk ring)
+    f2.mod_addons = addon_readers(2, false);
   }
   if (const char* pe = getenv("MS_PAIR")) {
     c->pair_enable = atoi(pe) != 0;

@@ -1,11 +1,11 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit):
-// tilt_coupling -- its setter and getters, and the pass wired behind the rim source's: k_couple<0> / k_couple<1> on
+// tilt_coupling -- its setter and getters, and its pass (addon_passes runs it): k_couple<0> / k_couple<1> on
 // x (+ alpha d), k_couple_vec while a relaxation holds the positions frozen.  Neither kernel is recorded by the
 // one-tile interpreter: the pass flushes it first.  No host-side table: the kernels work from the tiling alone.
 namespace {
 
-int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gradient_into_g, bool tilt_gradients,
-                bool trial_tilts, int cell, double* g_out) {
+int couple_pass(ms_ctx* c, bool use_dir, double alpha, bool tilt_gradients, bool trial_tilts, double* g_out, CellMode cell) {
+  const bool gradient_into_g = g_out != nullptr;
   if (c->cpl_sign == 0 || !c->d_cpl)
     return fail(c, MS_ERR_STATE, "tilt_coupling active but ms_set_tilt_coupling was never called (or switched it off)");
   ms_ctx::TiltField &fi = c->tf[1], &fo = c->tf[2];
@@ -27,14 +27,13 @@ int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gr
   if (!a.t_in || !a.t_out) return fail(c, MS_ERR_STATE, "tilt_coupling: a leaflet has no trial tilt buffer");
   a.k_c = c->cpl_k;
   a.sign = (double)c->cpl_sign;
-  a.g = gradient_into_g ? (g_out ? g_out : c->buf[MS_BUF_G]) : nullptr;
+  a.g = g_out;
   a.tg_in = tilt_gradients ? fi.grad : nullptr;
   a.tg_out = tilt_gradients ? fo.grad : nullptr;
   a.va = nullptr;
   a.partials = c->d_partials;
   a.slot = fo.s_etilt;
-  // tilt_out, tilt_rim_source_out and tilt_rim_source_bilayer off: no pass before this one left anything in the slot's cells
-  a.cell_mode = cell != CPL_CELL_AUTO ? cell : ((modules & (fo.mod_tilt | fo.mod_rs | fo.mod_rb_slot)) ? 1 : 2);
+  a.cell_mode = kernel_cell_mode(cell);
   a.wg_sums = dp;
   // a relaxation in progress: x is frozen and the mode-3 set-up launch left the barycentric vertex areas (the same
   // doubles in either leaflet's array -- unless the outer leaflet carries an absence mask: its array then holds the kept

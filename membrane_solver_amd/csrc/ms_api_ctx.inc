@@ -134,29 +134,15 @@ struct ms_ctx {
     bool rs_coef_valid = false;    // rs.coef holds c of the frozen surface of a running relaxation
     double* rs_center = nullptr;   // (inside d_rim)
     long rs_launches[3] = {0, 0, 0};  // k_rim_frame, k_rim_coef, k_rim_apply
-    // tilt_coupling reads BOTH leaflet fields (mod_cpl on each); its energy rides in the outer leaflet's tilt-magnitude
-    // slot (mod_cpl_slot on that field only)
-    uint32_t mod_cpl = 0, mod_cpl_slot = 0;
-    // tilt_rim_source_bilayer reads BOTH leaflet fields as well (mod_rb on each) and rides in the same slot (mod_rb_slot
-    // on the outer field only); its tables are the context's (ms_ctx::rb), not a field's
-    uint32_t mod_rb = 0, mod_rb_slot = 0;
+    // the add-on modules that read this leaflet's field (ms_slot_writers.h: addon_readers; mod_rs among them).
+    // rim_slope_match_out reads the inner one only with a disk ring: ms_set_rim_match sets that field's bit only then
+    uint32_t mod_addons = 0;
     // every module bit that reads this leaflet field
-    // tilt_splay_twist_in reads the inner leaflet's field; its energy rides in that field's smoothness slot
-    uint32_t mod_st = 0;
-    // tilt_thetaB_contact_in reads the inner leaflet's field and rides in its tilt-magnitude slot behind the rim source;
-    // its tables are the context's (ms_ctx::tb)
-    uint32_t mod_tb = 0;
-    // rim_slope_match_out reads the outer leaflet's field and, with a disk ring, the inner one's (ms_set_rim_match sets
-    // the inner field's bit only then); each term rides in its leaflet's tilt-magnitude slot behind every other pass;
-    // its tables are the context's (ms_ctx::rsm)
-    uint32_t mod_rsm = 0;
-    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_rs | mod_cpl | mod_st | mod_rb | mod_tb | mod_rsm; }
-    // every module bit whose sums land in this field's tilt-magnitude slot (s_etilt)
-    uint32_t etilt_mods() const { return mod_tilt | mod_rs | mod_cpl_slot | mod_rb_slot; }
-    // ... and the theta_B contact term on top of them: what the readers of the slot ask
-    uint32_t etilt_all() const { return etilt_mods() | mod_tb | mod_rsm; }
-    // every module bit whose sums land in this field's smoothness slot (s_ets)
-    uint32_t ets_mods() const { return mod_smooth | mod_st; }
+    uint32_t mods() const { return mod_tilt | mod_smooth | mod_bt | mod_dt | mod_addons; }
+    // every module bit whose sums land in this field's tilt-magnitude / smoothness slot: its own module and the
+    // add-ons riding there (what the readers of the slot ask)
+    uint32_t etilt_mods() const { return mod_tilt | (mod_addons & slot_writers(s_etilt, true)); }
+    uint32_t ets_mods() const { return mod_smooth | (mod_addons & slot_writers(s_ets, true)); }
     bool any_free = true;     // some row of this field is not clamped (kept current by the flag setters)
     double* va = nullptr;      // relaxation: barycentric vertex areas of the frozen positions
   } tf[3];

@@ -25,42 +25,27 @@ struct EdgeTerm {
 extern const EdgeTerm kEdgeTerms[2];
 int edge_energy_run(ms_ctx* c, int term, bool use_dir, double alpha);
 int edge_grad_run(ms_ctx* c, int term, double* g, bool volrow);
-// tilt_rim_source_in/out: c . t of the rim rows at x (+ alpha d) into the field's tilt-magnitude partials (ms_api_rim.inc)
-int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const double* tilts, bool gradient);
-// tilt_coupling: 1/2 k_c |t_out + s t_in|^2 of x (+ alpha d) into the outer leaflet's tilt-magnitude partials, behind the
-// rim source's pass where both run (ms_api_couple.inc).  trial_tilts: the fields' `trial` rows; cell: CPL_CELL_*
-enum { CPL_CELL_AUTO = -1, CPL_CELL_LEAVE = 0, CPL_CELL_ADD = 1 };
-// tilt_rim_source_bilayer: c . (t_in + t_out) of the rim rows at x (+ alpha d) into the outer leaflet's tilt-magnitude
-// partials, behind tilt_rim_source_out's pass and ahead of the coupling's (ms_api_rim.inc).  trial_tilts: the fields'
-// `trial` rows; gradient: c added into both fields' grad; cell: RB_CELL_*
-enum { RB_CELL_AUTO = -1, RB_CELL_ADD = 0, RB_CELL_DEFINE = 1 };
-int rim_bilayer_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool trial_tilts, bool gradient,
-                     int cell = RB_CELL_AUTO);
-int couple_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool gradient_into_g, bool tilt_gradients,
-                bool trial_tilts, int cell = CPL_CELL_AUTO, double* g_out = nullptr);
-// tilt_thetaB_contact_in: the ring ordered on x (+ alpha d) and the contact energy of `tilts` (the inner leaflet's rows
-// belonging to those positions) into the inner leaflet's tilt-magnitude partials, behind tilt_rim_source_in's pass
-// (ms_api_thetab.inc).  tilt_grad: the rows' gradient added there, or nullptr; cell: TB_CELL_*
-enum { TB_CELL_AUTO = -1, TB_CELL_ADD = 0, TB_CELL_DEFINE = 1 };
-int thetab_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const double* tilts, double* tilt_grad,
-                int cell = TB_CELL_AUTO);
-// rim_slope_match_out: the rings ordered on x (+ alpha d) and both terms of `t_in` / `t_out` (the leaflets' rows belonging
-// to those positions) into cell 0 of the leaflets' tilt-magnitude partials, behind EVERY other pass that writes those
-// slots (ms_api_rimmatch.inc).  tilt_gradients: the rows added into both fields' grad; g_out: the shape gradient's rows
-// added there, or nullptr; cell: RSM_CELL_* (AUTO: defined where no module in front of it writes the slot)
-enum { RSM_CELL_AUTO = -1, RSM_CELL_ADD = 0, RSM_CELL_LEAVE = 2 };
-int rim_match_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool trial_tilts, bool tilt_gradients,
-                   double* g_out, int cell = RSM_CELL_AUTO);
+// The leaflet add-on passes of one evaluation, in the table's order (ms_slot_writers.h), each with the cell mode the
+// table gives it.  tilt_eval, phase_energy and phase_gradient call this once, behind their base passes: the slots'
+// base modules have written the cells, every pass that writes the fields' grad rows (tilt_eval) or G (phase_gradient)
+// has run.  Behind a gradient pass nothing runs without g_out.
+struct AddonCall {
+  Phase phase;
+  bool use_dir;         // at x + alpha d ...
+  double alpha;
+  bool trial_tilts;     // ... reading the fields' `trial` rows
+  bool tilt_gradients;  // dE/dt added into the fields' grad
+  double* g_out;        // the shape gradients' rows added there (phase_gradient), or nullptr
+};
+int addon_passes(ms_ctx* c, uint32_t modules, const AddonCall& k);  // (ms_api_addons.inc)
+// CellMode as the kernels' `cell_mode` fields take it: 0 left alone, 1 added to, 2 defined
+constexpr int kernel_cell_mode(CellMode m) { return m == CellMode::DEFINE ? 2 : (m == CellMode::ADD ? 1 : 0); }
 // tilt_thetaB_boundary_in (ms_api_thetab_bnd.inc): the ring's table on x (nullptr: the context's positions) or on
 // x + alpha d, kept while `frozen` holds; and k_tbb_apply<mode> on it (0 enforce in place, 1 P(enforce(t)) into out,
 // 2 project the gradient `field`).  Both return at once when no table with a row is set.
 int tbb_geom_run(ms_ctx* c, const double* x, bool use_dir, double alpha, bool frozen);
 int tbb_apply_run(ms_ctx* c, int mode, double* field, double* out, bool project);
 bool tbb_active(const ms_ctx* c);
-// tilt_splay_twist_in: 1/2 A_f (k_splay div^2 + k_twist curl_n^2) of x (+ alpha d) and `tilts` into the inner leaflet's
-// smoothness partials, behind the smoothness pass where both run (ms_api_splay.inc).  tilt_grad: dE/dt ADDED there, or
-// nullptr (energy only).  The cells are ADDED to when tilt_smoothness_in's pass defined them, DEFINED otherwise
-int splay_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const double* tilts, double* tilt_grad);
 inline int exec_flush(ms_ctx* c) {
   if (!c->exec_on) return MS_OK;
   const hipError_t e = c->exec.flush();
@@ -202,9 +187,10 @@ constexpr uint32_t MS_LEAFLET_DT = MS_MOD_TILT_DISK_TARGET_IN | MS_MOD_TILT_DISK
 // the rim sources: no slot of their own (MS_NSCAL is full) -- their sums ride in the leaflet's tilt-magnitude slot -- and no
 // shape gradient, so they are not in MS_TILT_SHAPE_MODS
 constexpr uint32_t MS_LEAFLET_RS = MS_MOD_TILT_RIM_SOURCE_IN | MS_MOD_TILT_RIM_SOURCE_OUT;
-// (tilt_rim_source_bilayer is NOT part of MS_LEAFLET_RS: that mask selects the per-field tables and passes; the lanes
-// that decline a rim source name both)
-constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_RS | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_THETAB_CONTACT_IN | MS_MOD_RIM_SLOPE_MATCH_OUT;
+// (tilt_rim_source_bilayer is NOT part of MS_LEAFLET_RS: that mask selects the per-field tables.)  Every module that rides
+// in another one's slot, these among them; the lanes that cannot carry one decline them all
+constexpr uint32_t MS_LEAFLET_ADDONS = addon_mask();  // (ms_slot_writers.h)
+constexpr uint32_t MS_LEAFLET_MODS = MS_MOD_TILT_IN | MS_MOD_TILT_OUT | MS_MOD_TILT_SMOOTH_IN | MS_MOD_TILT_SMOOTH_OUT | MS_LEAFLET_BT | MS_LEAFLET_DT | MS_LEAFLET_ADDONS;
 constexpr uint32_t MS_ANY_TILT_MODS = MS_TILT_MODS | MS_LEAFLET_MODS;
 // the edge modules: energy added into the MS_S_ESURF partials behind the energy pass, gradient into G behind K_C; they
 // share one lane of the step (one trial per launch, every Armijo decision the host's, the separate direction pass)
@@ -823,8 +809,9 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
   }
   for (int l = 1; l <= 2 && (modules & MS_LEAFLET_MODS); ++l) {  // leaflet fields, same protocol
     TiltField& f = c->tf[l];
-    // (the coupling alone is reason enough: its trial energy is taken with BOTH leaflets projected onto the trial surface)
-    if (!(modules & (f.mod_tilt | f.mod_smooth | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb | f.mod_tb | f.mod_rsm))) continue;
+    // (an add-on that reads the field is reason enough: the coupling's trial energy is taken with BOTH leaflets projected
+    // onto the trial surface; bending_tilt alone is not: its passes ran above)
+    if (!(modules & f.mods() & ~f.mod_bt)) continue;
     int rc = MS_OK;
     const double* tilts = f.tilts;
     if (use_dir) {
@@ -846,31 +833,9 @@ int phase_energy(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool w
     if (rc) return rc;
     if (!used) return fail(c, MS_ERR_STATE, "tilt energy pass: planned but not launched");
   }
-  // tilt_rim_source_in/out: c . t of the rim rows added into the leaflet's tilt-magnitude partials, behind whichever pass
-  // above wrote them (k_tilt, or the one launch of tilt_energy_pass); on a trial, with the tilts projected onto it
-  for (int l = 1; l <= 2 && (modules & MS_LEAFLET_RS); ++l) {
-    TiltField& f = c->tf[l];
-    if (!(modules & f.mod_rs)) continue;
-    if (int rc_r = rim_pass(c, f, use_dir, alpha, use_dir ? f.trial : f.tilts, false)) return rc_r;
-  }
-  // tilt_thetaB_contact_in: behind the inner leaflet's rim source; the ring is ordered on THIS evaluation's positions (its
-  // scalar work mode has no gradient, yet its energy moves with x through R_eff: every Armijo trial takes it again)
-  if (modules & c->tf[1].mod_tb)
-    if (int rc_t = thetab_pass(c, modules, use_dir, alpha, use_dir ? c->tf[1].trial : c->tf[1].tilts, nullptr)) return rc_t;
-  // tilt_rim_source_bilayer: behind the outer leaflet's own rim source, with both fields' trial tilts on a trial
-  if (modules & MS_MOD_TILT_RIM_SOURCE_BILAYER)
-    if (int rc_b = rim_bilayer_pass(c, modules, use_dir, alpha, /*trial_tilts=*/use_dir, false)) return rc_b;
-  // tilt_coupling: behind the rim sources of the outer leaflet (the order of the adds into a cell is fixed)
-  if (modules & MS_MOD_TILT_COUPLING)
-    if (int rc_c = couple_pass(c, modules, use_dir, alpha, false, false, /*trial_tilts=*/use_dir)) return rc_c;
-  // rim_slope_match_out: behind everything that writes the two leaflets' tilt-magnitude cells; the rings are ordered on
-  // THIS evaluation's positions (the reference takes the module once at x and once per trial put to the Armijo test)
-  if (modules & MS_MOD_RIM_SLOPE_MATCH_OUT)
-    if (int rc_m = rim_match_pass(c, modules, use_dir, alpha, /*trial_tilts=*/use_dir, false, nullptr)) return rc_m;
-  // tilt_splay_twist_in: behind the inner leaflet's smoothness pass (k_tsmooth<0> above, or the one launch of
-  // tilt_energy_pass), at x and at every trial with the tilts projected onto it
-  if (modules & c->tf[1].mod_st)
-    if (int rc_s = splay_pass(c, modules, use_dir, alpha, use_dir ? c->tf[1].trial : c->tf[1].tilts, nullptr)) return rc_s;
+  // the add-ons, behind whichever pass above wrote their slots' cells (k_tilt / k_tsmooth, or the one launch of
+  // tilt_energy_pass); on a trial with the tilts projected onto it, the rings ordered on THIS evaluation's positions
+  if (int rc_a = addon_passes(c, modules, {Phase::ENERGY, use_dir, alpha, /*trial_tilts=*/use_dir, false, nullptr})) return rc_a;
   if (reduce_now) {
     constexpr uint32_t core = (1u << MS_S_ESURF) | (1u << MS_S_VOL) | (1u << MS_S_EBEND) | (1u << MS_S_MINEDGE2) |
                               (1u << MS_S_GUARD);
@@ -1015,22 +980,6 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
       int rc = tilt_pass_f(c, f, 1, false, 0.0);
       if (rc) return rc;
       added_after = true;
-      // k_tilt<1> has written the slot's partials again (the energy fold of this evaluation may still be ahead:
-      // queue_energy_and_gradient): the rim source's sums go in once more, behind it
-      if (k > 0 && (modules & f.mod_rs)) {
-        rc = rim_pass(c, f, false, 0.0, f.tilts, false);
-        if (rc) return rc;
-      }
-      // ... and the theta_B contact term's, behind the inner leaflet's (k == 1)
-      if (k == 1 && (modules & f.mod_tb)) {
-        rc = thetab_pass(c, modules, false, 0.0, f.tilts, nullptr, TB_CELL_ADD);
-        if (rc) return rc;
-      }
-      // ... and the bilayer rim source's, behind the outer leaflet's (k == 2): the order of an energy pass's adds
-      if (k == 2 && (modules & f.mod_rb_slot)) {
-        rc = rim_bilayer_pass(c, modules, false, 0.0, false, false, RB_CELL_ADD);
-        if (rc) return rc;
-      }
     }
     if (k > 0 && (modules & f.mod_dt)) {
       int rc = disk_target_pass(c, f, 1, false, 0.0, f.tilts, true, false);
@@ -1038,23 +987,10 @@ int phase_gradient(ms_ctx* c, uint32_t modules_in, double* g_out, bool accumulat
       added_after = true;
     }
   }
-  // tilt_coupling: its shape gradient behind the loop's; its energy goes into the outer leaflet's cells once more when
-  // k_tilt<1> above has rewritten them (behind the rim source's re-add), and nowhere when nobody has
-  if ((modules & MS_MOD_TILT_COUPLING) && g_out) {
-    int rc = couple_pass(c, modules, false, 0.0, true, false, false,
-                         (modules & c->tf[2].mod_tilt) ? CPL_CELL_ADD : CPL_CELL_LEAVE, g_out);
-    if (rc) return rc;
-    added_after = true;
-  }
-  // rim_slope_match_out: its shape gradient behind the coupling's; each of its energies goes into its leaflet's cells once
-  // more when k_tilt<1> above has rewritten them (behind every re-add above), and nowhere when nobody has
-  if ((modules & MS_MOD_RIM_SLOPE_MATCH_OUT) && g_out) {
-    int rc = rim_match_pass(c, modules, false, 0.0, false, false, g_out, RSM_CELL_ADD);
-    if (rc) return rc;
-    added_after = true;
-  }
-  // tilt_splay_twist_in: no shape gradient to add, and no pass above rewrites the inner leaflet's smoothness cells
-  // (k_tsmooth has no shape gradient either): they still hold this evaluation's sums and are LEFT as they are
+  // the add-ons: where k_tilt<1> above has written a slot's partials again (the energy fold of this evaluation may still
+  // be ahead: queue_energy_and_gradient) their sums go in once more, and the ones with a shape gradient add it into g
+  if (int rc = addon_passes(c, modules, {Phase::GRADIENT, false, 0.0, false, false, g_out})) return rc;
+  added_after = added_after || (g_out && (modules & MS_LEAFLET_ADDONS & MS_TILT_SHAPE_MODS));
   // the gradient kernel's <g, gC> partials predate those additions: take them again of the complete gradient
   if (added_after && g_out && (modules & MS_CON_VOLUME))
     HIPCHK(c, launch_row_dot(c->tile0, c->tile1, c->til.nv, c->til.own, g_out, c->buf[MS_BUF_GC], c->d_partials,
@@ -1243,8 +1179,8 @@ void energies_from_mailbox(const ms_ctx* c, double e[4]) {
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e[3] += c->h_scal[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
-    if (c->params.modules & f.etilt_all()) e[3] += c->h_scal[f.s_etilt];  // (the rim source, the coupling and the theta_B contact term ride in this slot)
-    if (c->params.modules & f.ets_mods()) e[3] += c->h_scal[f.s_ets];  // (the splay / twist term rides in this slot)
+    if (c->params.modules & f.etilt_mods()) e[3] += c->h_scal[f.s_etilt];  // (the slot's add-ons ride in it)
+    if (c->params.modules & f.ets_mods()) e[3] += c->h_scal[f.s_ets];
     if (c->params.modules & f.mod_bt) e[1] += c->h_scal[f.s_ebt];
     if (c->params.modules & f.mod_dt) e[3] += c->h_scal[f.s_edt];
   }

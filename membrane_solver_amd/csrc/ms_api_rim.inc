@@ -1,8 +1,9 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit):
-// tilt_rim_source_in/out -- the rim tables (ms_set_leaflet_rim_source) and the pass next to the disk-target pass:
-// k_rim_frame (follow mode), k_rim_coef (once per relaxation) and k_rim_apply -- and tilt_rim_source_bilayer
-// (ms_set_rim_source_bilayer): the same tables kept once per context, k_rim_frame / k_rim_coef as they are and
-// k_rim_apply2 on both leaflet fields.  None of the four is recorded by the one-tile interpreter: the passes flush it first.
+// tilt_rim_source_in/out -- the rim tables (ms_set_leaflet_rim_source) and their pass: k_rim_frame (follow mode),
+// k_rim_coef (once per relaxation) and k_rim_apply -- and tilt_rim_source_bilayer (ms_set_rim_source_bilayer): the same
+// tables kept once per context, k_rim_frame / k_rim_coef as they are and k_rim_apply2 on both leaflet fields.
+// addon_passes runs both passes, never to leave the cells.  None of the four kernels is recorded by the one-tile
+// interpreter: the passes flush it first.
 namespace {
 
 constexpr EdgeTableMsgs kRimMsgs = {"ms_set_leaflet_rim_source: edge row out of range", "",
@@ -68,22 +69,23 @@ int rim_coefficients(ms_ctx* c, const RimState& st, RimArgs& a, bool use_dir) {
   return MS_OK;
 }
 
+// tables without an edge or a row: nothing to add; the cells nobody else defines hold 0
+int empty_table_cells(ms_ctx* c, int slot, CellMode cell) {
+  if (cell != CellMode::DEFINE) return MS_OK;
+  return zero_doubles(c, c->d_partials + (size_t)slot * c->til.n_tiles + c->tile0, sizeof(double) * (size_t)(c->tile1 - c->tile0));
+}
+
 // c . t of the rim rows at x (+ alpha d) into the field's tilt-magnitude partials; gradient: c added into f.grad
-int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const double* tilts, bool gradient) {
+int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const double* tilts, bool gradient, CellMode cell) {
   if (!f.rs_set)
     return fail(c, MS_ERR_STATE, "tilt_rim_source active but ms_set_leaflet_rim_source was never called");
   if (!tilts) return fail(c, MS_ERR_STATE, "tilt_rim_source active but its tilt field was never set (ms_set_leaflet_tilts)");
   if (gradient && !f.grad) return fail(c, MS_ERR_STATE, "tilt_rim_source: the field has no tilt gradient buffer");
-  if (f.rs.n_touch == 0) {  // tables without an edge: nothing to add; the cells nobody else defines hold 0
-    if (c->params.modules & f.mod_tilt) return MS_OK;
-    return zero_doubles(c, c->d_partials + (size_t)f.s_etilt * c->til.n_tiles + c->tile0,
-                        sizeof(double) * (size_t)(c->tile1 - c->tile0));
-  }
+  if (f.rs.n_touch == 0) return empty_table_cells(c, f.s_etilt, cell);
   if (int rc = exec_flush(c)) return rc;
   const RimState st = rim_state(f);
   RimArgs a = f.rs;
-  // tilt_<leaflet> off: no pass before this one left anything in the slot's cells
-  rim_fill(c, st, a, use_dir, alpha, f.s_etilt, !(c->params.modules & f.mod_tilt));
+  rim_fill(c, st, a, use_dir, alpha, f.s_etilt, cell == CellMode::DEFINE);
   a.tilts = tilts;
   a.tilt_grad = gradient ? f.grad : nullptr;
   ProfScope ps(c, 6);
@@ -94,9 +96,8 @@ int rim_pass(ms_ctx* c, ms_ctx::TiltField& f, bool use_dir, double alpha, const 
 }
 
 // tilt_rim_source_bilayer: c . (t_in + t_out) of the rim rows at x (+ alpha d) into the OUTER leaflet's tilt-magnitude
-// partials, behind tilt_out's and tilt_rim_source_out's passes and ahead of the coupling's; gradient: c added into both
-// fields' grad.  cell: RB_CELL_AUTO adds when a pass before this one wrote the cells and defines them when none did.
-int rim_bilayer_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool trial_tilts, bool gradient, int cell) {
+// partials; gradient: c added into both fields' grad
+int rim_bilayer_pass(ms_ctx* c, bool use_dir, double alpha, bool trial_tilts, bool gradient, CellMode cell) {
   if (!c->rb_set)
     return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer active but ms_set_rim_source_bilayer was never called");
   ms_ctx::TiltField &fi = c->tf[1], &fo = c->tf[2];
@@ -106,17 +107,11 @@ int rim_bilayer_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bo
     return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer active but a leaflet's tilt field was never set (ms_set_leaflet_tilts)");
   if (gradient && (!fi.grad || !fo.grad))
     return fail(c, MS_ERR_STATE, "tilt_rim_source_bilayer: a leaflet has no tilt gradient buffer");
-  const bool written = (modules & (fo.mod_tilt | fo.mod_rs)) != 0;
-  const bool define = cell == RB_CELL_AUTO ? !written : cell == RB_CELL_DEFINE;
-  if (c->rb.n_touch == 0) {  // tables without an edge: nothing to add; the cells nobody else defines hold 0
-    if (!define) return MS_OK;
-    return zero_doubles(c, c->d_partials + (size_t)fo.s_etilt * c->til.n_tiles + c->tile0,
-                        sizeof(double) * (size_t)(c->tile1 - c->tile0));
-  }
+  if (c->rb.n_touch == 0) return empty_table_cells(c, fo.s_etilt, cell);
   if (int rc = exec_flush(c)) return rc;
   const RimState st = rim_state(c);
   RimArgs a = c->rb;
-  rim_fill(c, st, a, use_dir, alpha, fo.s_etilt, define);
+  rim_fill(c, st, a, use_dir, alpha, fo.s_etilt, cell == CellMode::DEFINE);
   a.tilts = t_in;
   a.tilt_grad = gradient ? fi.grad : nullptr;
   ProfScope ps(c, 6);

@@ -1,12 +1,12 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit):
-// rim_slope_match_out -- the three rings' rows and frame (ms_set_rim_match), the pass behind every other pass that
-// writes the leaflets' tilt-magnitude cells: k_rsm_geom on the positions of the evaluation (once per relaxation, whose
-// positions are frozen) and k_rsm_apply.  Neither kernel is recorded by the one-tile interpreter: the pass flushes it
-// first.
+// rim_slope_match_out -- the three rings' rows and frame (ms_set_rim_match), its pass (addon_passes runs it, with a cell
+// mode per leaflet: define_out / define_in 1 define, 0 add, -1 leave): k_rsm_geom on the positions of the evaluation
+// (once per relaxation, whose positions are frozen) and k_rsm_apply.  Neither kernel is recorded by the one-tile
+// interpreter: the pass flushes it first.
 namespace {
 
-int rim_match_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool trial_tilts, bool tilt_gradients,
-                   double* g_out, int cell) {
+int rim_match_pass(ms_ctx* c, bool use_dir, double alpha, bool trial_tilts, bool tilt_gradients, double* g_out,
+                   CellMode cell_out, CellMode cell_in) {
   if (!c->rsm_set)
     return fail(c, MS_ERR_STATE, "rim_slope_match_out active but ms_set_rim_match was never called (or ms_clear_rim_match dropped its tables)");
   ms_ctx::TiltField &fi = c->tf[1], &fo = c->tf[2];
@@ -33,18 +33,9 @@ int rim_match_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, bool
   a.n_cells = c->tile1 - c->tile0;
   a.slot_out = fo.s_etilt;
   a.slot_in = fi.s_etilt;
-  if (cell == RSM_CELL_AUTO) {
-    // the modules in front of this one that leave something in the slot's cells; none: this pass defines them
-    a.define_out = (modules & (fo.mod_tilt | fo.mod_rs | fo.mod_rb_slot | fo.mod_cpl_slot)) ? 0 : 1;
-    a.define_in = !inner ? -1 : ((modules & (fi.mod_tilt | fi.mod_rs | fi.mod_tb)) ? 0 : 1);
-  } else if (cell == RSM_CELL_ADD) {
-    // behind a gradient pass: only k_tilt<1> rewrites a leaflet's cells; where it did not run they still hold this
-    // evaluation's sums
-    a.define_out = (modules & fo.mod_tilt) ? 0 : -1;
-    a.define_in = (inner && (modules & fi.mod_tilt)) ? 0 : -1;
-  } else {
-    a.define_out = a.define_in = -1;
-  }
+  auto define = [](CellMode m) { return m == CellMode::DEFINE ? 1 : (m == CellMode::ADD ? 0 : -1); };
+  a.define_out = define(cell_out);
+  a.define_in = define(cell_in);  // (LEAVE without a disk ring)
   ProfScope ps(c, 6);
   // a relaxation in progress: x is frozen, its first evaluation orders the rings and the others reuse the tables
   const bool frozen = c->tb_relax && !use_dir;
@@ -62,7 +53,7 @@ int rim_match_drop(ms_ctx* c) {
   if (int rc = drop_table(c, c->d_rsm)) return rc;
   c->rsm = RsmArgs{};
   c->rsm_set = c->rsm_geom_valid = false;
-  c->tf[1].mod_rsm = 0;
+  c->tf[1].mod_addons = addon_readers(1, /*rsm_inner=*/false);
   c->carry.invalidate();  // (the energies held are the old term's)
   return MS_OK;
 }
@@ -149,7 +140,7 @@ int ms_set_rim_match(ms_ctx* c, int n_rim, const int32_t* rim, int n_outer, cons
     a.u[k] = u[k];
     a.v[k] = v[k];
   }
-  c->tf[1].mod_rsm = n_disk > 0 ? MS_MOD_RIM_SLOPE_MATCH_OUT : 0;  // (the inner leaflet is read only with a disk ring)
+  c->tf[1].mod_addons = addon_readers(1, /*rsm_inner=*/n_disk > 0);  // (the inner leaflet is read only with a disk ring)
   c->rsm_set = true;
   return MS_OK;
 }

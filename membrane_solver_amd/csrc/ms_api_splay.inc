@@ -1,10 +1,10 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit):
-// tilt_splay_twist_in -- its setter and getters, and the pass wired behind the inner leaflet's smoothness pass:
+// tilt_splay_twist_in -- its setter and getters, and its pass (addon_passes runs it):
 // k_splay<0> / k_splay<1> on x (+ alpha d).  Neither kernel is recorded by the one-tile interpreter: the pass flushes
 // it first.  No host-side table: the kernels work from the tiling alone.
 namespace {
 
-int splay_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const double* tilts, double* tilt_grad) {
+int splay_pass(ms_ctx* c, bool use_dir, double alpha, const double* tilts, double* tilt_grad, CellMode cell) {
   ms_ctx::TiltField& f = c->tf[1];
   if (!c->st_set || !c->d_st)
     return fail(c, MS_ERR_STATE, "tilt_splay_twist_in active but ms_set_tilt_splay_twist was never called");
@@ -24,8 +24,7 @@ int splay_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const do
   a.tilt_grad = tilt_grad;
   a.partials = c->d_partials;
   a.slot = f.s_ets;
-  // tilt_smoothness_in off: no pass before this one left anything in the slot's cells
-  a.cell_mode = (modules & f.mod_smooth) ? 1 : 2;
+  a.cell_mode = kernel_cell_mode(cell);
   a.wg_sums = static_cast<double*>(c->d_st);
   const int mode = tilt_grad ? 1 : 0;
   ProfScope ps(c, 11);

@@ -1,8 +1,8 @@
 // libmembrane_hip.so host side, part of ms_api.cpp (included there, in this order: one translation unit):
-// tilt_thetaB_contact_in -- the ring's rows and frame (ms_set_thetab_contact), theta_B (ms_set_thetab_value), the pass
-// behind the inner leaflet's rim source: k_thetab_geom on the positions of the evaluation (once per relaxation, whose
-// positions are frozen) and k_thetab_apply; and the scalar update.  Neither kernel is recorded by the one-tile
-// interpreter: the pass flushes it first.
+// tilt_thetaB_contact_in -- the ring's rows and frame (ms_set_thetab_contact), theta_B (ms_set_thetab_value), its pass
+// (addon_passes runs it, never to leave the cells): k_thetab_geom on the positions of the evaluation (once per
+// relaxation, whose positions are frozen) and k_thetab_apply; and the scalar update.  Neither kernel is recorded by the
+// one-tile interpreter: the pass flushes it first.
 namespace {
 
 // the positions, the tilt rows and where the energy goes
@@ -21,23 +21,16 @@ void thetab_fill(ms_ctx* c, ThetabArgs& a, bool use_dir, double alpha, const dou
   a.slot = c->tf[1].s_etilt;
 }
 
-int thetab_pass(ms_ctx* c, uint32_t modules, bool use_dir, double alpha, const double* tilts, double* tilt_grad, int cell) {
+int thetab_pass(ms_ctx* c, bool use_dir, double alpha, const double* tilts, double* tilt_grad, CellMode cell) {
   if (!c->tb_set)
     return fail(c, MS_ERR_STATE, "tilt_thetaB_contact_in active but ms_set_thetab_contact was never called");
-  ms_ctx::TiltField& f = c->tf[1];
   if (!tilts)
     return fail(c, MS_ERR_STATE, "tilt_thetaB_contact_in active but the inner leaflet's tilt field was never set (ms_set_leaflet_tilts)");
-  // tilt_in and tilt_rim_source_in off: no pass before this one left anything in the slot's cells
-  const bool define = cell == TB_CELL_AUTO ? !(modules & (f.mod_tilt | f.mod_rs)) : cell == TB_CELL_DEFINE;
-  if (c->tb.n == 0) {  // a table without a row: nothing to add; the cells nobody else defines hold 0
-    if (!define) return MS_OK;
-    return zero_doubles(c, c->d_partials + (size_t)f.s_etilt * c->til.n_tiles + c->tile0,
-                        sizeof(double) * (size_t)(c->tile1 - c->tile0));
-  }
+  if (c->tb.n == 0) return empty_table_cells(c, c->tf[1].s_etilt, cell);
   if (int rc = exec_flush(c)) return rc;
   ThetabArgs a = c->tb;
   thetab_fill(c, a, use_dir, alpha, tilts, tilt_grad);
-  a.define = define ? 1 : 0;
+  a.define = cell == CellMode::DEFINE ? 1 : 0;
   ProfScope ps(c, 6);
   // a relaxation in progress: x is frozen, its first evaluation orders the ring and the others reuse the table
   const bool frozen = c->tb_relax && !use_dir;

@@ -39,6 +39,8 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
   for (int l = 1; l <= 2; ++l) {
     TiltField& f = c->tf[l];
     if (!(mods & f.mods())) continue;
+    if (mods & f.etilt_mods()) mask |= 1u << f.s_etilt;  // (the slot's own module or an add-on riding there)
+    if (mods & f.ets_mods()) mask |= 1u << f.s_ets;
     const double* tilts = trial ? f.trial : f.tilts;
     if ((mods & f.mod_tilt) && c->relax_va_valid && f.va) {
       // positions frozen, vertex areas at hand: the reference's own form of this evaluation, one streaming pass
@@ -46,13 +48,11 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
       HIPCHK(c, launch_tvec(4, c->tile0, c->tile1, c->til.nv, c->til.own, c->d_vflags, f.grad, f.va, f.dir, tilts,
                             nullptr, nullptr, nullptr, f.k_tilt, gradient ? 1 : 0, c->d_partials, c->til.n_tiles,
                             c->stream, f.fixed_bit, f.s_etilt, f.s_rz));
-      mask |= 1u << f.s_etilt;
     } else if (mods & f.mod_tilt) {
       // (module form -- ms_leaflet_tilt_energy_and_gradient_ex: the field's own mass mode, tilt gradient included)
       rc = tilt_pass_f(c, f, gradient ? 1 : 0, false, 0.0, tilts, nullptr, /*shape_gradient=*/false,
                        /*lumped=*/!c->tilt_module_form);
       if (rc) return rc;
-      mask |= 1u << f.s_etilt;
     } else if (gradient) {
       if (int rz = zero_doubles(c, f.grad, b3)) return rz;
     }
@@ -69,47 +69,11 @@ int tilt_eval(ms_ctx* c, bool trial, bool gradient) {
     if (mods & f.mod_smooth) {
       rc = ts_pass_f(c, f, gradient ? 1 : 0, false, 0.0, tilts);
       if (rc) return rc;
-      mask |= 1u << f.s_ets;
-    }
-    if (mods & f.mod_st) {
-      // behind the smoothness pass (its partials) and every pass above that adds into f.grad
-      rc = splay_pass(c, mods, false, 0.0, tilts, gradient ? f.grad : nullptr);
-      if (rc) return rc;
-      mask |= 1u << f.s_ets;
-    }
-    if (mods & f.mod_rs) {
-      // behind the magnitude pass (its partials, its rows of f.grad) and every other pass that adds into f.grad
-      rc = rim_pass(c, f, false, 0.0, tilts, gradient);
-      if (rc) return rc;
-      mask |= 1u << f.s_etilt;
-    }
-    if (mods & f.mod_tb) {
-      // behind the rim source's pass: the same cells, the same rows of f.grad
-      rc = thetab_pass(c, mods, false, 0.0, tilts, gradient ? f.grad : nullptr);
-      if (rc) return rc;
-      mask |= 1u << f.s_etilt;
     }
   }
-  if (mods & MS_MOD_TILT_RIM_SOURCE_BILAYER) {
-    // behind both leaflets' blocks (their magnitude passes have written both grads, the outer one's its cells): c into
-    // both tilt gradients, c . (t_in + t_out) into the outer leaflet's magnitude partials
-    rc = rim_bilayer_pass(c, mods, false, 0.0, trial, gradient);
-    if (rc) return rc;
-    mask |= 1u << c->tf[2].s_etilt;
-  }
-  if (mods & MS_MOD_TILT_COUPLING) {
-    // behind both leaflets' passes: it adds into both tilt gradients and into the outer leaflet's magnitude partials
-    rc = couple_pass(c, mods, false, 0.0, false, gradient, trial);
-    if (rc) return rc;
-    mask |= 1u << c->tf[2].s_etilt;
-  }
-  if (mods & MS_MOD_RIM_SLOPE_MATCH_OUT) {
-    // behind every pass above: it adds into both tilt gradients and into cell 0 of both leaflets' magnitude partials
-    rc = rim_match_pass(c, mods, false, 0.0, trial, gradient, nullptr);
-    if (rc) return rc;
-    mask |= 1u << c->tf[2].s_etilt;
-    if (mods & c->tf[1].mod_rsm) mask |= 1u << c->tf[1].s_etilt;
-  }
+  // the add-ons, behind both leaflets' blocks: the base passes have written the slots' cells and both fields' grad rows
+  rc = addon_passes(c, mods, {Phase::TILT_EVAL, false, 0.0, trial, gradient, nullptr});
+  if (rc) return rc;
   return mask ? reduce_slots(c, mask) : MS_OK;
 }
 double tilt_energy_from(const ms_ctx* c, const double* hs) {
@@ -119,8 +83,8 @@ double tilt_energy_from(const ms_ctx* c, const double* hs) {
   if (c->params.modules & MS_MOD_TILT_SMOOTH) e += hs[MS_S_ETS];
   for (int l = 1; l <= 2; ++l) {
     const TiltField& f = c->tf[l];
-    if (c->params.modules & f.etilt_all()) e += hs[f.s_etilt];  // (tilt magnitude + rim source + coupling + theta_B contact)
-    if (c->params.modules & f.ets_mods()) e += hs[f.s_ets];  // (smoothness + splay / twist)
+    if (c->params.modules & f.etilt_mods()) e += hs[f.s_etilt];  // (the slot's add-ons ride in it)
+    if (c->params.modules & f.ets_mods()) e += hs[f.s_ets];
     if (c->params.modules & f.mod_bt) e += hs[f.s_ebt];
     if (c->params.modules & f.mod_dt) e += hs[f.s_edt];
   }
@@ -133,6 +97,10 @@ double tilt_energy_from_mailbox(const ms_ctx* c) { return tilt_energy_from(c, c-
 bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs* a, uint32_t* mask) {
   const uint32_t mods = c->params.modules;
   if (!c->tsearch_enable || nf < 1 || nf > 2 || !c->d_tn) return false;
+  // the add-ons keep their own passes.  (Whichever fields are relaxed: the leaflets are relaxed as a pair -- every field
+  // an active module reads, leaflet_ready -- so a field the add-on reads is always among them, and ms_relax_tilts
+  // refuses leaflet modules next to the single field)
+  if (mods & MS_LEAFLET_ADDONS) return false;
   for (int k = 0; k < nf; ++k)
     if (fl[k]->absent_bit) return false;  // an absence mask: the launch-per-module passes honour it, k_tsearch / k_tgrad do not
   *mask = 0;
@@ -143,10 +111,7 @@ bool tsearch_plan(ms_ctx* c, TiltField** fl, int nf, bool along_dir, TsearchArgs
     const bool tilt_on = single ? (mods & MS_MOD_TILT) != 0 : (mods & f.mod_tilt) != 0;
     const bool bt_on = single ? (mods & MS_MOD_BENDING_TILT) != 0 : (mods & f.mod_bt) != 0;
     const bool ts_on = single ? (mods & MS_MOD_TILT_SMOOTH) != 0 : (mods & f.mod_smooth) != 0;
-    // (the disk target, the rim sources, the coupling and the splay / twist term keep their own passes)
-    if (!single && (mods & (f.mod_rb | f.mod_dt | f.mod_rs | f.mod_cpl | f.mod_st))) return false;
-    if (!single && (mods & f.mod_tb)) return false;  // (and so does the theta_B contact term)
-    if (mods & MS_MOD_RIM_SLOPE_MATCH_OUT) return false;  // (... and the rim matching term, whichever fields are relaxed)
+    if (!single && (mods & f.mod_dt)) return false;  // (so does the disk target)
     o.tilts = f.tilts;
     o.src = along_dir ? f.dir : f.grad;
     o.bt_vert = nullptr;
@@ -363,7 +328,8 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
       q.has_ts = (mods & f.mod_smooth) ? 1 : 0;
       q.has_dt = (mods & f.mod_dt) ? 1 : 0;
       q.fixed_bit = f.fixed_bit;
-      ok = ok && !(mods & (f.mod_tb | f.mod_rsm | f.mod_rs | f.mod_cpl | f.mod_st | f.mod_rb)) && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
+      // (no add-on is on here: relax_fields keeps this program for module sets without one)
+      ok = ok && f.minv && (!q.has_tilt || f.va) && (!q.has_bt || (f.bt_vert && f.kappa)) &&
            (!q.has_dt || (f.dt_target && f.disk && f.dt_target_valid));
     }
     const size_t need = relax_fused_lds_bytes(c->cap, t.max_ent, t.max_tile_facets);
@@ -482,7 +448,7 @@ int relax_program(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int
     if (mods & MS_MOD_TILT_SMOOTH) head.e_slot[n++] = MS_S_ETS;
     for (int l = 1; l <= 2; ++l) {
       const TiltField& f = c->tf[l];
-      if (mods & f.etilt_all()) head.e_slot[n++] = f.s_etilt;
+      if (mods & f.etilt_mods()) head.e_slot[n++] = f.s_etilt;
       if (mods & f.ets_mods()) head.e_slot[n++] = f.s_ets;
       if (mods & f.mod_bt) head.e_slot[n++] = f.s_ebt;
       if (mods & f.mod_dt) head.e_slot[n++] = f.s_edt;
@@ -814,8 +780,8 @@ int relax_fields(ms_ctx* c, const ms_tilt_relax_params* rp, TiltField** fl, int 
     if (r || used) return r;
     return search(along_dir, sign, E0, E_acc, accepted);
   };
-  // (the rim source's, the coupling's, the splay / twist term's and the theta_B contact term's kernels are not recorded)
-  if (!tbb_on && c->exec_on && c->exec_relax && !(mods & (MS_LEAFLET_RS | MS_MOD_TILT_RIM_SOURCE_BILAYER | MS_MOD_TILT_COUPLING | MS_MOD_TILT_SPLAY_TWIST_IN | MS_MOD_TILT_THETAB_CONTACT_IN | MS_MOD_RIM_SLOPE_MATCH_OUT))) {
+  // (the add-ons' kernels are not recorded)
+  if (!tbb_on && c->exec_on && c->exec_relax && !(mods & MS_LEAFLET_ADDONS)) {
     // one-tile context: the whole solve below as ONE launch (ms_internal.h: ExecRelaxHead)
     bool used = false;
     rc = relax_program(c, rp, fl, nf, norm_mask, &iters, &evals, &used);

@@ -381,17 +381,18 @@ def test_one_helper_uploads_both_kinds_of_tables():
     # (one allocation for both: the table builder's upload, called once, and no allocation of the file's own)
     assert rim.count("upload_table(") == 1 and rim.count("hipMalloc(") == 0
     assert len(re.findall(r"return rim_upload\(c, \"ms_set_", rim)) == 2
-    ctx = open(os.path.join(csrc, "ms_api_ctx.inc")).read()
-    assert re.search(r"uint32_t etilt_mods\(\) const \{ return mod_tilt \| mod_rs \| mod_cpl_slot \| mod_rb_slot; \}", ctx)
-    assert re.search(r"uint32_t mods\(\) const \{[^}]*mod_rb[^}]*\}", ctx)
-    tilt = open(os.path.join(csrc, "ms_api_tilt.inc")).read()
+    # the slot list: the module's row of the slot-writer table rides in the outer leaflet's tilt-magnitude slot, reads
+    # both fields (TiltField::mods() of either) and has no shape gradient
+    import slot_writer_cases as sw
+
+    r = sw.row("MS_MOD_TILT_RIM_SOURCE_BILAYER")
+    assert r == {"bit": "MS_MOD_TILT_RIM_SOURCE_BILAYER", "slot": "MS_S_ETILT_OUT", "slot_disk": None,
+                 "reads": {"RD_IN", "RD_OUT"}, "base": False, "shape_grad": False}
+    assert sw.writers_in_front("MS_MOD_TILT_RIM_SOURCE_BILAYER", "MS_S_ETILT_OUT") == ["MS_MOD_TILT_OUT", "MS_MOD_TILT_RIM_SOURCE_OUT"]
+    # the coupling's cell rule counts it: tilt_out, tilt_rim_source_out and this module are the writers in front of it
+    assert sw.writers_in_front("MS_MOD_TILT_COUPLING", "MS_S_ETILT_OUT") == [
+        "MS_MOD_TILT_OUT", "MS_MOD_TILT_RIM_SOURCE_OUT", "MS_MOD_TILT_RIM_SOURCE_BILAYER"]
+    sw.assert_lanes_decline_every_addon("MS_MOD_TILT_RIM_SOURCE_BILAYER")  # tsearch_plan, the fused evaluator, the relaxation program
     phases = open(os.path.join(csrc, "ms_api_phases.inc")).read()
-    assert re.search(r"mods & \(f\.mod_rb \| f\.mod_dt [^)]*\)\)\) return false;", tilt)  # tsearch_plan
-    assert re.search(r"ok = ok && !\(mods & \([^)]*f\.mod_rb\)\)", tilt)  # the fused evaluator
-    assert re.search(r"exec_relax && !\(mods & \([^)]*MS_MOD_TILT_RIM_SOURCE_BILAYER", tilt)  # the relaxation program
-    m = re.search(r"constexpr uint32_t MS_LEAFLET_MODS = ([^;]*);", phases)
-    assert m and "MS_MOD_TILT_RIM_SOURCE_BILAYER" in m.group(1)
     m = re.search(r"constexpr uint32_t MS_TILT_SHAPE_MODS = ([^;]*);", phases)
     assert m and "MS_MOD_TILT_RIM_SOURCE_BILAYER" not in m.group(1)  # no shape gradient
-    cpl = open(os.path.join(csrc, "ms_api_couple.inc")).read()
-    assert "fo.mod_tilt | fo.mod_rs | fo.mod_rb_slot" in cpl

@@ -430,14 +430,17 @@ def test_one_list_says_what_lands_in_the_smoothness_slot():
     """TiltField::ets_mods() feeds every reader of the slot; the passes that cannot carry the term decline."""
     csrc = os.path.join(ROOT, "membrane_solver_amd", "csrc")
     ctx = open(os.path.join(csrc, "ms_api_ctx.inc")).read()
-    assert re.search(r"uint32_t ets_mods\(\) const \{ return mod_smooth \| mod_st; \}", ctx)
-    assert re.search(r"uint32_t mods\(\) const \{[^}]*mod_st[^}]*\}", ctx)
+    # the list is the slot-writer table's: the smoothness module and the add-ons whose row names the field's slot
+    import slot_writer_cases as sw
+
+    assert re.search(r"uint32_t ets_mods\(\) const \{ return mod_smooth \| \(mod_addons & slot_writers\(s_ets, true\)\); \}", ctx)
+    assert sw.row("MS_MOD_TILT_SPLAY_TWIST_IN") == {"bit": "MS_MOD_TILT_SPLAY_TWIST_IN", "slot": "MS_S_ETS_IN", "slot_disk": None,
+                                                    "reads": {"RD_IN"}, "base": False, "shape_grad": False}
+    assert sw.writers_in_front("MS_MOD_TILT_SPLAY_TWIST_IN", "MS_S_ETS_IN") == ["MS_MOD_TILT_SMOOTH_IN"]
     tilt = open(os.path.join(csrc, "ms_api_tilt.inc")).read()
     phases = open(os.path.join(csrc, "ms_api_phases.inc")).read()
     assert tilt.count("f.ets_mods()") >= 2 and phases.count("f.ets_mods()") >= 1
     assert not re.search(r"modules & f\.mod_smooth\) e(\[3\])? \+=", tilt + phases)  # no reader left on the old list
-    assert re.search(r"f\.mod_dt \| f\.mod_rs \| f\.mod_cpl \| f\.mod_st\)\)\) return false;", tilt)  # tsearch_plan
-    m = re.search(r"constexpr uint32_t MS_LEAFLET_MODS = ([^;]*);", phases)
-    assert m and "MS_MOD_TILT_SPLAY_TWIST_IN" in m.group(1)
+    sw.assert_lanes_decline_every_addon("MS_MOD_TILT_SPLAY_TWIST_IN")  # tsearch_plan among them
     m = re.search(r"constexpr uint32_t MS_TILT_SHAPE_MODS = ([^;]*);", phases)
     assert m and "MS_MOD_TILT_SPLAY_TWIST_IN" not in m.group(1)  # no shape gradient

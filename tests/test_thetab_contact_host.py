@@ -457,13 +457,14 @@ def test_c_abi_argument_checks_without_a_device():
 
 def test_the_passes_that_cannot_carry_the_term_decline():
     csrc = os.path.join(ROOT, "membrane_solver_amd", "csrc")
-    tilt = open(os.path.join(csrc, "ms_api_tilt.inc")).read()
     phases = open(os.path.join(csrc, "ms_api_phases.inc")).read()
-    assert re.search(r"if \(!single && \(mods & f\.mod_tb\)\) return false;", tilt)  # tsearch_plan (and tgrad_plan through it)
-    assert re.search(r"ok = ok && !\(mods & \(f\.mod_tb \|", tilt)  # the relaxation program
-    assert re.search(r"exec_relax && !\(mods & \([^)]*MS_MOD_TILT_THETAB_CONTACT_IN", tilt)  # the one-tile recorder
-    m = re.search(r"constexpr uint32_t MS_LEAFLET_MODS = ([^;]*);", phases)
-    assert m and "MS_MOD_TILT_THETAB_CONTACT_IN" in m.group(1)  # (the resident step declines every tilt module)
+    # the module is an add-on of the slot-writer table; tsearch_plan (and tgrad_plan through it), the relaxation program,
+    # the one-tile recorder and MS_LEAFLET_MODS (the resident step declines every tilt module) take the table's add-on mask
+    import slot_writer_cases as sw
+
+    assert sw.row("MS_MOD_TILT_THETAB_CONTACT_IN") == {"bit": "MS_MOD_TILT_THETAB_CONTACT_IN", "slot": "MS_S_ETILT_IN",
+                                                       "slot_disk": None, "reads": {"RD_IN"}, "base": False, "shape_grad": False}
+    sw.assert_lanes_decline_every_addon("MS_MOD_TILT_THETAB_CONTACT_IN")
     m = re.search(r"constexpr uint32_t MS_TILT_SHAPE_MODS = ([^;]*);", phases)
     assert m and "MS_MOD_TILT_THETAB_CONTACT_IN" not in m.group(1)  # no shape gradient
     kern = open(os.path.join(csrc, "ms_thetab.hip")).read()
